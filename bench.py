@@ -6,13 +6,20 @@ MI355X, batched HIP step() only (obs + state matrix + reward/done written every 
 actions = Philox(seed 9981) policy indices resident in HBM.
 
 A bench "step" = ONE ROLLOUT LAUNCH = ROLLOUT_T (128) environment steps of all envs of one GPU (tw_rollout,
-include/twoarmy.h): `--steps K --warmup W` runs W untimed launches and then times exactly K launches, so
-value = n_gpus * envs * 128 * K / wall.  The same K launches are bracketed by events on the launch stream and
-`roofline.achieved` comes from that one region (value x bytes-per-env-step == achieved up to the host's
-barrier/sync overhead, reported as roofline.wall_over_event).
+include/twoarmy.h): `--steps K --warmup W` runs >= 50 ms of clock warm-up launches (their env state is discarded),
+then W untimed launches, then times exactly K launches in one region, so value = n_gpus * envs * 128 * K / wall and
+ms_per_step = wall / K.  The same K launches are bracketed by events on the launch stream and `roofline.achieved`
+comes from that one region (value x bytes-per-env-step == achieved up to the host's barrier/sync overhead, reported
+as roofline.wall_over_event).
+
+A plain run does only that.  --full then also measures what the headline does not need: more timed regions and
+their spread (--regions), the kernel into freshly allocated slabs (--slab-check), the box's write-only fill ceiling
+and the CPU baseline (not with --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step computed
+(a fixed, seeded sample of the envs, float32 .npy files): the inputs depend only on the arguments, so two builds can
+be compared output for output.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--variant v6] [--view 17]
-                  [--mode rollout|step|ppo] [--no-cpu-baseline]
+                  [--mode rollout|step|ppo] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
 
 --gpus N > 1 without a torch.distributed environment: this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (before anything here touches the
@@ -40,6 +47,8 @@ ROLLOUT_T = 128
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 SEED = 9981                    # reference default, soa/train_ppo.py:25
 FWD_FLOP_PER_SAMPLE_PER_NET = 47.5e6
+DUMP_LIMIT_BYTES = 64 << 20                    # --dump-outputs: at most this much in all
+DUMP_SAMPLE_ENVS = 64                          # --dump-outputs: env columns written of a larger batch
 
 
 def algorithmic_bytes_per_env_step(view, rollout_t, matrix_bytes=289 * 4):
@@ -118,6 +127,46 @@ def cpu_baseline(variant, n_envs, view, seconds=10.0):
             "single_thread_value": steps1 / dt1, "host_cores_available": os.cpu_count()}
 
 
+def dump_env_sample(n_envs, k=DUMP_SAMPLE_ENVS):
+    """The env columns --dump-outputs writes: a fixed, seeded choice of k envs (sorted), every env when there are
+    no more than k."""
+    import numpy as np
+    if n_envs <= k:
+        return np.arange(n_envs)
+    return np.sort(np.random.default_rng(SEED).choice(n_envs, k, replace=False))
+
+
+def write_outputs(dump_dir, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float64 kept, everything else as float32; at most
+    DUMP_LIMIT_BYTES in all.  Returns the record of what was written for the result line."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+    return {"dir": dump_dir, "files": sorted(n + ".npy" for n in conv), "bytes": total}
+
+
+def dump_engine_outputs(dump_dir, out, n_envs, rollout):
+    """What the last timed launch handed its caller (obs, matrix, pos, reward, terminated, truncated: [T, N, ...] for a
+    rollout launch, [N, ...] for a step launch), restricted to the dump_env_sample() columns; env_ids names them."""
+    import torch
+    per_env = 4 * sum(t.numel() for t in out.values() if t is not None) // n_envs       # float32 bytes per env column
+    ids = dump_env_sample(n_envs, max(1, min(DUMP_SAMPLE_ENVS, (DUMP_LIMIT_BYTES - (1 << 20)) // per_env)))
+    idx = torch.as_tensor(ids, device=out["reward"].device)
+    arrays = {"env_ids": ids}
+    for name, t in out.items():
+        if t is not None:
+            arrays[name] = (t[:, idx] if rollout else t[idx]).float().cpu().numpy()
+    return write_outputs(dump_dir, arrays)
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -130,13 +179,19 @@ def build_parser():
     ap.add_argument("--mode", default="rollout", choices=["rollout", "step", "ppo"],
                     help="rollout: 128 env-steps per launch (headline); step: one tw_step launch per env-step; "
                          "ppo: rollout with the actor in the loop + PPO update, gradient all-reduce per optimiser step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what it does not need: rollout/step mode: more timed regions "
+                         "(--regions), the slab check (--slab-check), the box's fill ceiling and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32, a fixed "
+                         "seeded sample of the envs, <= 64 MB in all); the inputs are the same from run to run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--slab-check", type=int, default=3,
-                    help="rollout mode: time the kernel into this many freshly allocated engine slabs at set-up and report "
-                         "the values (evidence that placement no longer matters; nothing is selected); 1 = skip")
+                    help="--full, rollout mode: time the kernel into this many freshly allocated engine slabs after the timed "
+                         "region and report the values (evidence that placement no longer matters; nothing is selected); 1 = skip")
     ap.add_argument("--regions", type=int, default=0,
-                    help="rollout/step mode: number of timed regions of --steps launches each (0 = auto: >= 25 regions and about "
-                         "1 s of GPU time in total, at most 400); the median region is reported")
+                    help="--full, rollout/step mode: number of extra timed regions of --steps launches each (0 = auto: >= 25 "
+                         "regions and about 1 s of GPU time in total, at most 400); their spread and median are reported")
     ap.add_argument("--torch-outputs", action="store_true",
                     help="diagnostic: outputs from torch's caching allocator instead of the engine's slab")
     ap.add_argument("--matrix-codes", action="store_true",
@@ -350,22 +405,10 @@ def run_engine_mode(args, rank, world, dev, coll):
     # the engine's own Philox stream, HBM-resident; launches cycle over a fixed window of it
     n_act = min(W + K, 64) if rollout else W + K
     actions = eng.fill_actions(n_act * T).view(n_act, T, N)
-    slab_check_ms, slabs = None, None
     if args.torch_outputs or not rollout:
         out = eng.alloc_outputs(T if rollout else None, matrix_codes=args.matrix_codes, slab=False)
     else:
         out = eng.alloc_outputs(T, matrix_codes=args.matrix_codes)          # engine-owned slab (tw_alloc_outputs)
-        if args.slab_check > 1:
-            # untimed evidence, NOT a selection: the kernel time into a few more freshly allocated slabs; `out` (the
-            # first allocation) is what the timed region uses whatever these say.  The env state is restored.
-            state = eng.get_state()
-            slabs = [out] + [eng.alloc_outputs(T, matrix_codes=args.matrix_codes) for _ in range(args.slab_check - 1)]
-            for s_ in slabs:
-                eng.time_rollout(T, s_, actions=actions[0], iters=2)
-            slab_check_ms = [eng.time_rollout(T, s_, actions=actions[0], iters=4) for s_ in slabs]
-            eng.set_state(*state)
-            # the extra slabs stay allocated until the timed region is over: returning gigabytes of physical memory to
-            # the driver right before it was followed (once) by a timed region 21 % slower than the same slab's check
 
     def run(i_begin, n):
         for i in range(i_begin, i_begin + n):
@@ -374,36 +417,37 @@ def run_engine_mode(args, rank, world, dev, coll):
             else:
                 eng.step(actions[i % n_act, 0], out, autoreset=True, policy_idx=True)
 
-    run(0, W)
-    # clocks: at least ~50 ms of launches before the first timed region (a 4 ms region right after set-up ran 3-8 % off)
+    # clocks: at least ~50 ms of launches before the timed region (a 4 ms region right after set-up ran 3-8 % off).
+    # They start from the fresh env state and it is put back afterwards, so the W warm-up and K timed launches see
+    # the same inputs however many of these ran.
+    torch.cuda.synchronize()
+    state = eng.get_state()
     ew0, ew1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ew0.record()
     run(0, 8)
     ew1.record()
     torch.cuda.synchronize()
-    # every rank must run the same number of regions (each one has barriers): agree on the slowest rank's estimate
+    # every rank must run the same number of launches (barriers): agree on the slowest rank's estimate
     est_ms = max_over_ranks(max(ew0.elapsed_time(ew1) / 8.0, 1e-3), dev, world)
     warm_launches = 8 + int(50.0 / est_ms) + 1
     run(0, warm_launches - 8)
-    # R timed regions of exactly K launches each, every one bracketed by barrier + synchronize on both sides; the line
-    # reports the MEDIAN region (value, ms_per_step, roofline.kernel_ms) and the spread of all of them
-    R = args.regions if args.regions > 0 else auto_regions(K, est_ms)
-    wall_s, ev_ms_all = [], []
-    for r_ in range(R):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        sync_all(dev, world)
-        t0 = time.perf_counter()
-        e0.record()                 # torch's current stream == the stream handed to tw_rollout (engine._stream)
-        run(W + r_ * K, K)
-        e1.record()
-        sync_all(dev, world)
-        wall_s.append(time.perf_counter() - t0)
-        ev_ms_all.append(e0.elapsed_time(e1))
-    wall_s = max_over_ranks_vec(wall_s, dev, world)
-    order = sorted(range(R), key=lambda i: wall_s[i])
-    med = order[R // 2]
-    dt, ev_ms = wall_s[med], ev_ms_all[med]
-    del slabs
+    torch.cuda.synchronize()
+    eng.set_state(*state)
+    run(0, W)
+    # the headline: ONE timed region of exactly K launches (W .. W+K-1 of the action window), bracketed by barrier +
+    # synchronize on both sides; `value`, `ms_per_step` and `roofline.kernel_ms` all describe these K launches
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    sync_all(dev, world)
+    t0 = time.perf_counter()
+    e0.record()                     # torch's current stream == the stream handed to tw_rollout (engine._stream)
+    run(W, K)
+    e1.record()
+    sync_all(dev, world)
+    dt = max_over_ranks(time.perf_counter() - t0, dev, world)
+    ev_ms = e0.elapsed_time(e1)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_engine_outputs(args.dump_outputs, out, N, rollout)
 
     layout = getattr(out["matrix"], "_tw_layout", None)
     mine = "torch caching allocator" if layout is None else ("hipMalloc" if "hipMalloc" in layout else "2 MiB mapped chunks") + \
@@ -414,7 +458,7 @@ def run_engine_mode(args, rank, world, dev, coll):
     bytes_per_launch = bpe * N * T
     achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9
     traffic, traffic_src = (None, None) if args.matrix_codes or not rollout else traffic_from_profile(vname, N, T, V)
-    fill_gbs = fill_ceiling_gbs(dev)
+    full = run_engine_extras(args, eng, out, actions[0], run, W + K, K, T, est_ms, dev, world) if args.full else None
     if rank != 0:
         return None
     pipelined = rollout and os.environ.get("TW_PIPELINE", "1") != "0"
@@ -436,31 +480,69 @@ def run_engine_mode(args, rank, world, dev, coll):
                    "collective": coll,
                    "output_buffers": "torch caching allocator, two streams" if (args.torch_outputs or not rollout)
                                      else "engine slab (tw_alloc_outputs): %s" % getattr(out["matrix"], "_tw_layout", "?"),
-                   "slab_backing": backing,
-                   "slab_check_ms": None if slab_check_ms is None else {
-                       "what": "untimed set-up: kernel ms per launch into %d freshly allocated engine slabs; no selection, "
-                               "the first one is used by the timed region" % len(slab_check_ms),
-                       "ms": slab_check_ms,
-                       "spread": (max(slab_check_ms) - min(slab_check_ms)) / min(slab_check_ms)}},
+                   "slab_backing": backing},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "tw_pipe_kernel" if pipelined else "tw_rollout_kernel",
                      "kernel_ms": k_ms, "launches_timed": K, "timed_region": "the same K launches as `value` "
-                     "(events on the launch stream): the median of `regions` back-to-back regions of K launches",
-                     "regions": R, "gpu_ms_timed_total": sum(ev_ms_all), "clock_warm_launches": warm_launches,
-                     "kernel_ms_samples": {"min": min(ev_ms_all) / K, "median": sorted(ev_ms_all)[R // 2] / K,
-                                           "max": max(ev_ms_all) / K, "max_over_min": max(ev_ms_all) / min(ev_ms_all)},
-                     "region_wall_ms_samples": {"min": min(wall_s) * 1e3, "median": dt * 1e3, "max": max(wall_s) * 1e3},
-                     "wall_over_event": dt * 1e3 / ev_ms,
+                     "(events on the launch stream), one region after the warm-up",
+                     "clock_warm_launches": warm_launches, "wall_over_event": dt * 1e3 / ev_ms,
                      "algorithmic_bytes_per_env_step": bpe, "bytes_per_launch": bytes_per_launch,
                      "survey_bytes_per_env_step": 2690, "us_per_env_batch_step": k_ms * 1e3 / T,
-                     "launches_per_env_batch_step": 1.0 / T, "measured_fill_ceiling_GBs": fill_gbs,
-                     "frac_of_measured_fill_ceiling": achieved / fill_gbs},
+                     "launches_per_env_batch_step": 1.0 / T},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        res["outputs_dumped"] = dumped
+    if full is not None:
+        res["config"]["slab_check_ms"] = full.pop("slab_check_ms")
+        res["roofline"].update(full)
+        res["roofline"]["frac_of_measured_fill_ceiling"] = achieved / full["measured_fill_ceiling_GBs"]
+    if world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(variant, N, V)
     eng.close()
     return res
+
+
+def run_engine_extras(args, eng, out, actions0, run, i_next, K, T, est_ms, dev, world):
+    """--full, after the headline and its outputs: R more regions of K launches each (their spread and the median
+    region), the kernel time into freshly allocated engine slabs, the write-only fill ceiling of this box."""
+    import torch
+    R = args.regions if args.regions > 0 else auto_regions(K, est_ms)
+    wall_s, ev_ms_all = [], []
+    for r_ in range(R):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        sync_all(dev, world)
+        t0 = time.perf_counter()
+        e0.record()
+        run(i_next + r_ * K, K)
+        e1.record()
+        sync_all(dev, world)
+        wall_s.append(time.perf_counter() - t0)
+        ev_ms_all.append(e0.elapsed_time(e1))
+    wall_s = max_over_ranks_vec(wall_s, dev, world)
+    med = sorted(range(R), key=lambda i: wall_s[i])[R // 2]
+    slab_check_ms = None
+    if args.slab_check > 1 and not (args.torch_outputs or args.mode != "rollout"):
+        # evidence, NOT a selection: the kernel time into a few more freshly allocated slabs (env state restored)
+        state = eng.get_state()
+        slabs = [out] + [eng.alloc_outputs(T, matrix_codes=args.matrix_codes) for _ in range(args.slab_check - 1)]
+        for s_ in slabs:
+            eng.time_rollout(T, s_, actions=actions0, iters=2)
+        slab_check_ms = [eng.time_rollout(T, s_, actions=actions0, iters=4) for s_ in slabs]
+        eng.set_state(*state)
+        del slabs
+        slab_check_ms = {"what": "kernel ms per launch into %d freshly allocated engine slabs (after the timed "
+                                 "region); no selection, the first one is the one the timed region used" % len(slab_check_ms),
+                         "ms": slab_check_ms, "spread": (max(slab_check_ms) - min(slab_check_ms)) / min(slab_check_ms)}
+    return {"regions": R, "regions_what": "--full: %d more back-to-back regions of K launches after the timed one; "
+                                          "samples of those, and the env-steps/s of the median one" % R,
+            "regions_value_median": eng.num_envs * T * K * world / wall_s[med],
+            "gpu_ms_timed_total": sum(ev_ms_all),
+            "kernel_ms_samples": {"min": min(ev_ms_all) / K, "median": sorted(ev_ms_all)[R // 2] / K,
+                                  "max": max(ev_ms_all) / K, "max_over_min": max(ev_ms_all) / min(ev_ms_all)},
+            "region_wall_ms_samples": {"min": min(wall_s) * 1e3, "median": wall_s[med] * 1e3, "max": max(wall_s) * 1e3},
+            "measured_fill_ceiling_GBs": fill_ceiling_gbs(dev),
+            "slab_check_ms": slab_check_ms}
 
 
 def run_ppo_mode(args, rank, world, dev, coll):
@@ -530,6 +612,7 @@ def run_ppo_mode(args, rank, world, dev, coll):
         iteration(True)
     sync_all(dev, world)
     dt = max_over_ranks(time.perf_counter() - t0, dev, world)
+    dumped = dump_ppo_outputs(args.dump_outputs, tr, agent) if (args.dump_outputs and rank == 0) else None
     ar_exposed = bucket.exposed_ms() if bucket is not None else []
     n_reduces = bucket.n_reduces if bucket is not None else 0
     ar_alone = allreduce_alone_ms(bucket, dev) if bucket is not None else None
@@ -545,7 +628,7 @@ def run_ppo_mode(args, rank, world, dev, coll):
     flop_upd = FWD_FLOP_PER_SAMPLE_PER_NET * (target_rows + samples * args.k_epochs * 3 * 2)
     r, u = sum(roll_s) / K, sum(upd_s) / K
     nparam = sum(p.numel() for p in list(agent.actor.parameters()) + list(agent.critic.parameters()) if p.requires_grad)
-    return {
+    res = {
         "metric": "env-steps/sec", "value": world * S * K / dt, "unit": "env-steps/s", "n_gpus": world, "steps": K,
         "warmup": W, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32" if args.amp == "fp32" else "bf16", "data": "synthetic",
@@ -573,6 +656,24 @@ def run_ppo_mode(args, rank, world, dev, coll):
                      "target_forward_rows": target_rows,
                      "rollout_TFLOPs": S * FWD_FLOP_PER_SAMPLE_PER_NET / r / 1e12},
     }
+    if dumped is not None:
+        res["outputs_dumped"] = dumped
+    return res
+
+
+def dump_ppo_outputs(dump_dir, tr, agent):
+    """What the last timed PPO iteration handed back: its rollout's action, logp, reward, terminated, truncated [T, N]
+    (the dump_env_sample() columns, env_ids names them) and the updated actor / critic parameters, flattened."""
+    import torch
+    ids = dump_env_sample(tr.N)
+    idx = torch.as_tensor(ids, device=tr.reward.device)
+    arrays = {"env_ids": ids}
+    for name, t in (("action", tr.action), ("logp", tr.logp), ("reward", tr.reward), ("terminated", tr.term),
+                    ("truncated", tr.trunc)):
+        arrays[name] = t[:, idx].float().cpu().numpy()
+    for name, net in (("actor_params", agent.actor), ("critic_params", agent.critic)):
+        arrays[name] = torch.cat([p.detach().float().reshape(-1) for p in net.parameters()]).cpu().numpy()
+    return write_outputs(dump_dir, arrays)
 
 
 def run_rehearsal(args, rank, world, dev, coll):
@@ -633,7 +734,12 @@ def run_rehearsal(args, rank, world, dev, coll):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.rehearse and args.dump_outputs:
+        ap.error("--dump-outputs: a rehearsal computes nothing to compare")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)             # parent: nothing below runs here
     import torch.distributed as dist

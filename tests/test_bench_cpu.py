@@ -69,3 +69,79 @@ def test_cpu_baseline_leg_runs_the_oracle():
     r = bench.cpu_baseline(6, 256, 17, seconds=0.5)
     assert r["kind"] == "port" and r["unit"] == "env-steps/s" and r["value"] > 1e4 and r["single_thread_value"] > 1e4
     assert r["cores"] == bench.usable_cores()
+
+
+def test_plain_run_options():
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    a = bench.build_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_zero_steps_is_refused_before_anything_runs():
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], cwd=ROOT, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr and '"metric"' not in p.stdout
+
+
+def test_dump_sample_is_fixed_and_seeded():
+    import numpy as np
+    a, b = bench.dump_env_sample(4096), bench.dump_env_sample(4096)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_SAMPLE_ENVS == len(set(a.tolist()))
+    assert np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < 4096
+    assert np.array_equal(bench.dump_env_sample(10), np.arange(10))
+
+
+def test_write_outputs_float_files_and_size_limit(tmp_path):
+    import numpy as np
+    import pytest
+    rec = bench.write_outputs(str(tmp_path / "d"), {"obs": np.arange(6, dtype=np.uint8).reshape(2, 3),
+                                                    "ret": np.ones(3, np.float64)})
+    assert rec["files"] == ["obs.npy", "ret.npy"] and rec["bytes"] == 6 * 4 + 3 * 8
+    obs, ret = np.load(tmp_path / "d" / "obs.npy"), np.load(tmp_path / "d" / "ret.npy")
+    assert obs.dtype == np.float32 and np.array_equal(obs, np.arange(6).reshape(2, 3)) and ret.dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_dump_engine_outputs_takes_the_sampled_env_columns(tmp_path):
+    import numpy as np
+    import torch
+    T, N = 4, 300
+    g = torch.Generator().manual_seed(1)
+    out = {"obs": torch.randint(0, 255, (T, N, 17, 17, 3), dtype=torch.uint8, generator=g),
+           "matrix": torch.rand((T, N, 289), generator=g), "pos": torch.rand((T, N, 2), generator=g),
+           "reward": torch.rand((T, N), generator=g), "terminated": torch.randint(0, 2, (T, N), dtype=torch.uint8, generator=g),
+           "truncated": torch.randint(0, 2, (T, N), dtype=torch.uint8, generator=g)}
+    rec = bench.dump_engine_outputs(str(tmp_path), out, N, rollout=True)
+    ids = bench.dump_env_sample(N)
+    assert np.array_equal(np.load(tmp_path / "env_ids.npy"), ids.astype(np.float32))
+    for k, t in out.items():
+        got = np.load(tmp_path / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, t[:, torch.as_tensor(ids)].float().numpy()), k
+    assert rec["bytes"] == sum(np.load(tmp_path / f).nbytes for f in rec["files"])
+    # step launches hand back [N, ...]
+    rec = bench.dump_engine_outputs(str(tmp_path / "s"), {k: t[0] for k, t in out.items()}, N, rollout=False)
+    assert np.load(tmp_path / "s" / "obs.npy").shape == (len(ids), 17, 17, 3)
+
+
+def test_dump_ppo_outputs_rollout_columns_and_parameters(tmp_path):
+    import types
+    import numpy as np
+    import torch
+    T, N = 8, 100
+    tr = types.SimpleNamespace(N=N, action=torch.randint(0, 5, (T, N), dtype=torch.int32), logp=torch.rand(T, N),
+                               reward=torch.rand(T, N), term=torch.randint(0, 2, (T, N), dtype=torch.uint8),
+                               trunc=torch.randint(0, 2, (T, N), dtype=torch.uint8))
+    agent = types.SimpleNamespace(actor=torch.nn.Linear(3, 2), critic=torch.nn.Linear(3, 1))
+    rec = bench.dump_ppo_outputs(str(tmp_path), tr, agent)
+    ids = torch.as_tensor(bench.dump_env_sample(N))
+    assert np.array_equal(np.load(tmp_path / "reward.npy"), tr.reward[:, ids].numpy())
+    assert np.array_equal(np.load(tmp_path / "action.npy"), tr.action[:, ids].float().numpy())
+    actor = np.load(tmp_path / "actor_params.npy")
+    assert actor.shape == (3 * 2 + 2,) and np.array_equal(actor[:6], agent.actor.weight.detach().reshape(-1).numpy())
+    assert set(rec["files"]) == {"env_ids.npy", "action.npy", "logp.npy", "reward.npy", "terminated.npy", "truncated.npy",
+                                 "actor_params.npy", "critic_params.npy"}

@@ -1,14 +1,14 @@
 mkdir -p gpurun_out/final
 o=gpurun_out/final
-python bench.py --gpus 1 --steps 20 --warmup 5 > $o/bench_default.json 2> $o/err.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --torch-outputs > $o/bench_torch_two_streams.json 2>> $o/err.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --variant v4 > $o/bench_v4.json 2>> $o/err.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --view 7 > $o/bench_view7.json 2>> $o/err.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --matrix-codes > $o/bench_codes.json 2>> $o/err.log
-for n in 16384 2048 1024 512; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline --envs $n > $o/bench_envs$n.json 2>> $o/err.log; done
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --envs 1024 --variant v4 > $o/bench_envs1024_v4.json 2>> $o/err.log
-python bench.py --mode step --no-cpu-baseline > $o/bench_step_mode.json 2>> $o/err.log
-TW_SLAB_BACKING=0 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_slab_hipmalloc.json 2>> $o/err.log
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $o/bench_default.json 2> $o/err.log
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --torch-outputs > $o/bench_torch_two_streams.json 2>> $o/err.log
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --variant v4 > $o/bench_v4.json 2>> $o/err.log
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --view 7 > $o/bench_view7.json 2>> $o/err.log
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --matrix-codes > $o/bench_codes.json 2>> $o/err.log
+for n in 16384 2048 1024 512; do python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --envs $n > $o/bench_envs$n.json 2>> $o/err.log; done
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --envs 1024 --variant v4 > $o/bench_envs1024_v4.json 2>> $o/err.log
+python bench.py --full --mode step --no-cpu-baseline > $o/bench_step_mode.json 2>> $o/err.log
+TW_SLAB_BACKING=0 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_slab_hipmalloc.json 2>> $o/err.log
 python - <<'PY'
 import json,glob,os
 for f in sorted(glob.glob('gpurun_out/final/bench_*.json')):
