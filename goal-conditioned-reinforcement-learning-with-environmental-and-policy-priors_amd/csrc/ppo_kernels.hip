@@ -46,15 +46,18 @@ __global__ void ppo_sample_kernel(const float *__restrict__ probs, int B, const 
         philox4x32_10(k0, k1, c0, c1, c2, c3);
         u = (float)(c0 >> 8) * (1.0f / 16777216.0f);       // 24 random bits -> [0, 1)
     }
-    int a = A - 1;
+    // the rounded cumsum can end below u (up to 1 - 2^-24): then the last action with q > 0, never a zero-probability one
+    int a = A - 1, last = A - 1;
     float cum = 0.f, qa = 0.f;
     bool found = false;
 #pragma unroll
     for (int k = 0; k < A; ++k) {
         const float q = p[k] / sum;
         cum += q;
+        if (q > 0.f) last = k;
         if (!found && cum > u) { a = k; found = true; }
     }
+    if (!found) a = last;
 #pragma unroll
     for (int k = 0; k < A; ++k) if (k == a) qa = p[k] / sum;
     action[b] = a;
@@ -280,9 +283,11 @@ __global__ __launch_bounds__(256) void ppo_gae_kernel(const float *__restrict__ 
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const float d2 = __shfl_down(d, off), c2 = __shfl_down(c, off);
-                if (lane + off < 64) { d = fmaf(c, d2, d); c = c * c2; }
+                // c == 0 (lambda = 0 or a done) ends the segment: (0, d) absorbs whatever follows, and skipping the
+                // combine keeps 0 * inf / 0 * NaN of a later step out of it
+                if (lane + off < 64 && c != 0.f) { d = fmaf(c, d2, d); c = c * c2; }
             }
-            const float a = fmaf(c, carry[e], d);       // A of this row given the chunk above
+            const float a = c != 0.f ? fmaf(c, carry[e], d) : d;     // A of this row given the chunk above
             sd[lane][e] = a;
             const float a0 = __shfl(a, 0);
             if (lane == 0) carry[e] = a0;               // only this wave touches carry[e]

@@ -9,7 +9,8 @@
  *                  PPO.py:124-133  ratio-clip surrogate + entropy, SmoothL1      -> ppo_loss_fwd_bwd
  *   train_ppo.py:116-123  5-frame stack shift + store                            -> ppo_gather_stack
  * GAE(gamma, lambda) with done masks has no reference counterpart: it collapses to the
- * reference formula at lambda = 0, use_done_mask = 0 and is otherwise pinned by oracle/ppo_oracle.py only.
+ * reference formula at lambda = 0, use_done_mask = 0 and is otherwise pinned against a float64 statement of the
+ * formula (tests/test_ppo_kernels_edges_gpu.py).
  *
  * Conventions as in twoarmy.h: device pointers, caller-owned, `stream` = hipStream_t as void*,
  * asynchronous, 0 = ok / negative = TW_E_*.  All tensors fp32 unless noted; time-major [T][N].
@@ -25,10 +26,12 @@ extern "C" {
 
 /* torch.distributions.Categorical(probs=p) semantics: q = p / sum(p); logits = log(clamp(q, eps, 1-eps)),
  * eps = FLT_EPSILON; log_prob(a) = logits[a].  Sampling is inverse-CDF on q with a supplied uniform
- * u in [0,1): a = min{k : cumsum(q)[k] > u} (clamped to A-1).  uniforms == NULL -> u from
+ * u in [0,1): a = min{k : cumsum(q)[k] > u}, cumsum in fp32; where the rounded cumsum ends at or below u,
+ * a = the last k with q[k] > 0 (never an action of probability 0).  uniforms == NULL -> u from
  * Philox4x32-10(key = seed, counter = (lo32(row + offset), hi32(row + offset), 0, 'TWOS')),
  * u = (word0 >> 8) * 2^-24.
- *   probs float[B][A] (A <= 8), uniforms float[B]|NULL, action int32[B], logp float[B] */
+ *   probs float[B][A] (A in {2, 3, 4, 5, 7}; any other A returns TW_E_ARG), uniforms float[B]|NULL,
+ *   action int32[B], logp float[B] */
 int ppo_sample(const float *probs, int B, int A, const float *uniforms, uint64_t seed, uint64_t offset,
                int32_t *action, float *logp, void *stream);
 /* The same with the Philox row counter = row + offset + *offset_dev: a launch recorded in a HIP graph (the whole
@@ -37,7 +40,8 @@ int ppo_sample_dev(const float *probs, int B, int A, const float *uniforms, uint
                    const uint64_t *offset_dev, int32_t *action, float *logp, void *stream);
 
 /* delta_t = r_t + gamma * nv_t * cut_t - v_t;  A_t = delta_t + gamma*lambda*cut_t*A_{t+1} (A_T = 0);
- * cut_t = use_done_mask ? 1 - done_t : 1.  Outputs (each nullable): adv = A, target = r + gamma*nv*cut
+ * cut_t = use_done_mask ? 1 - done_t : 1.  Where gamma*lambda*cut_t = 0 (lambda = 0, or a done) A_t = delta_t
+ * exactly: a non-finite delta of a later step does not reach it.  Outputs (each nullable): adv = A, target = r + gamma*nv*cut
  * (the reference's target_v), ret = A + v.  Segmented reverse scan: one wavefront scans 64 time steps of
  * one env with 6 shuffle steps over affine maps; [T][N] tiles are transposed through LDS.
  *   reward, value, next_value float[T][N]; done uint8[T][N] (nullable when !use_done_mask) */

@@ -3,8 +3,8 @@
 TEST INFRASTRUCTURE ONLY (checker for <package>/csrc/ppo_kernels.hip).  Pinned against
 tests/golden/ppo.npz (log-probs, entropies and update losses recorded from the reference's own
 torch code).  GAE with lambda > 0 / done masks and advantage normalisation have no reference
-counterpart: for those this file is the only pin ("parity unpinned" beyond the
-lambda = 0 collapse, which equals PPO.py:113-114).
+counterpart: beyond the lambda = 0 collapse (= PPO.py:113-114) the kernels are pinned
+against float64 statements of the formulas in tests/test_ppo_kernels_edges_gpu.py, not against this file.
 """
 import numpy as np
 
@@ -26,13 +26,16 @@ def sample(probs, uniforms):
     q, logits, _ = categorical(probs)
     B, A = q.shape
     a = np.full(B, A - 1, np.int32)
+    last = np.full(B, A - 1, np.int32)                        # fallback: the last action with q > 0
     cum = np.zeros(B, F)
     found = np.zeros(B, bool)
     for k in range(A):
         cum = (cum + q[:, k]).astype(F)
+        last[q[:, k] > 0] = k
         hit = (~found) & (cum > np.asarray(uniforms, F))
         a[hit] = k
         found |= hit
+    a[~found] = last[~found]
     return a, logits[np.arange(B), a]
 
 
@@ -48,7 +51,9 @@ def gae(reward, value, next_value, done, gamma, lam, use_done_mask):
     nxt = np.zeros(N, F)
     coef = F(gamma) * F(lam)
     for t in range(T - 1, -1, -1):
-        nxt = (delta[t] + coef * cut[t] * nxt).astype(F)
+        c = coef * cut[t]
+        with np.errstate(invalid="ignore", over="ignore"):
+            nxt = np.where(c != 0, delta[t] + c * nxt, delta[t]).astype(F)   # c == 0: a later non-finite A stays out
         adv[t] = nxt
     return adv, target, (adv + v).astype(F)
 

@@ -60,3 +60,26 @@ def test_sample_inverse_cdf():
     a, logp = po.sample(probs, u)
     assert a.tolist() == [0, 0, 1, 2, 4, 4]
     np.testing.assert_allclose(logp, np.log(probs[np.arange(6), a]), rtol=1e-6)
+
+
+def test_sample_rounded_cumsum_below_u_never_picks_a_zero_probability_action():
+    """[0.37, 0.82, 0.10, 0, 0] normalises to an fp32 cumsum that ends below u = 1 - 2^-24 (the largest uniform of the
+    Philox path): the sample is the last action with q > 0, not A - 1 (Categorical(probs).sample() never draws
+    p = 0)."""
+    probs = np.array([[0.37, 0.82, 0.10, 0.0, 0.0],
+                      [0.0, 0.0, 0.37, 0.82, 0.10],
+                      [0.37, 0.0, 0.82, 0.0, 0.10]], np.float32)
+    u = np.full(3, 1.0 - 2.0 ** -24, np.float32)
+    q, _, _ = po.categorical(probs)
+    assert np.cumsum(q[0], dtype=np.float32)[-1] <= u[0]         # the case this test is about
+    a, logp = po.sample(probs, u)
+    assert a.tolist() == [2, 4, 4]
+    np.testing.assert_allclose(logp, np.log(q[np.arange(3), a]), rtol=1e-6)
+    # zeros at the start, middle and end, with u at 0 and at every fp32 cumsum boundary
+    for row in probs:
+        cum = np.cumsum(po.categorical(row[None])[0][0], dtype=np.float32)
+        us = np.concatenate([[0.0], cum[:-1], np.nextafter(cum[:-1], np.float32(0)), [1.0 - 2.0 ** -24]])
+        us = us.astype(np.float32)
+        us = us[us < 1]
+        a, _ = po.sample(np.repeat(row[None], len(us), 0), us)
+        assert np.all(row[a] > 0), (row, us, a)
