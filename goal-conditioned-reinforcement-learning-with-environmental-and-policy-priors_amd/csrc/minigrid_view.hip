@@ -13,8 +13,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "minigrid_view.h"
 #include "twoarmy.h"
@@ -170,9 +168,9 @@ __global__ __launch_bounds__(64) void mg_gen_obs_kernel(const uint8_t *__restric
 
 // Compile-time view sizes: lane = (env slot e, view column i) -- the same layout the ballot masks of process_vis use --
 // and the lane keeps its whole column (V cells) in registers: no per-element div / mod.
-// ROWS (the shipped mode): the plane bytes arrive row-wise as aligned dwords and are transposed through LDS (see the
-// block below); V = 7 occluded 56 -> 41 us, V = 17 see-through 251 -> 143 us on 262 144 random 17x17 worlds.
-// !ROWS (MG_VIEW_LOADS=cols, kept for A/B runs): every lane walks its column with one byte load per cell and plane, all
+// ROWS (every input of >= 64 plane bytes): the plane bytes arrive row-wise as aligned dwords and are transposed through
+// LDS (see the block below); V = 7 occluded 56 -> 41 us, V = 17 see-through 251 -> 143 us on 262 144 random 17x17 worlds.
+// !ROWS (inputs of fewer than 64 plane bytes): every lane walks its column with one byte load per cell and plane, all
 // requested up front.  Counters on that variant (rocprofv3 --pmc, V = 7): a wave lives ~35 k cycles for ~860
 // instructions and waits 73 % of that time -- not dependent round trips, as first assumed, but the L1 serving the same
 // lines over and over (V byte loads per line, ~130 KB of lines in flight per CU against 32 KB of L1).
@@ -442,9 +440,8 @@ extern "C" int mg_gen_obs(const uint8_t *type, const uint8_t *colour, const uint
                                colour, state, n_envs, width, height, agent_x, agent_y, agent_dir, carrying,            \
                                see_through_walls ? 1 : 0, image, image_pitch, vis_mask);                               \
     } while (0)
-    // row-wise aligned-dword loads (the default); MG_VIEW_LOADS=cols keeps the byte-per-cell column walk (A/B diagnostic)
-    static const bool cols_env = getenv("MG_VIEW_LOADS") && !strcmp(getenv("MG_VIEW_LOADS"), "cols");
-    const bool rows = !cols_env && (size_t)n_envs * width * height >= 64;
+    // row-wise aligned-dword loads; the byte-per-cell column walk for tiny inputs
+    const bool rows = (size_t)n_envs * width * height >= 64;
     switch (view_size) {                    // the usual odd sizes: lane-per-column kernel with the column in registers
     case 3: MG_LAUNCH_COLS(3); break;
     case 5: MG_LAUNCH_COLS(5); break;

@@ -32,7 +32,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -444,18 +443,6 @@ __device__ __forceinline__ void regen_env(uint32_t *env, int lane) {
     }
 }
 
-#ifdef TW_STAMP
-// Diagnostic build only (make stamp): phase cycle shares via s_memtime; never in the shipped library.
-__device__ unsigned long long g_stamp[64][8];
-__device__ unsigned long long g_stamp3[64][16][4];   // per wave, absolute s_memtime: kernel entry, loads issued, after the first barrier, first task drawn
-__device__ unsigned long long g_stamp2[64][16][3];   // per wave: tasks, poll cycles, work cycles
-#define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long _t; \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); \
-    st_acc[i] += _t - st_prev; st_prev = _t; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
-
 // ---------------------------------------------------------------- the rollout kernel
 // FAST = every output present, native 16-byte layouts, actions supplied, Philox draws: all the
 // wave-uniform "is this pointer null / is this layout aligned" branches fold away at compile time.
@@ -530,12 +517,7 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
     const size_t obs_step = (size_t)N * p.obs_pitch, mat_step = (size_t)N * p.mat_pitch;
     size_t idx = (size_t)n0 + lane;                         // [t][n] row of this lane's env
 
-#ifdef TW_STAMP
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) :: "memory");
-#endif
     for (int tt = 0; tt < p.T; ++tt, idx += N, obs_row += obs_step, mat_row += mat_step, matc_row += mat_step) {
-        STAMP(0);
 
         // ---- actions: one coalesced-per-env vector load every 64 steps, parked in LDS
         if (has_actions && (tt & 63) == 0) {
@@ -548,7 +530,6 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
             wave_sync();
         }
 
-        STAMP(1);
         // ================= LOGIC part 1 (lane-per-env): everything before gen_obs()
         int err = TW_ENV_OK, have_obs = 0, terminated = 0, truncated = 0, reward = R_STEP;
         uint32_t dw[4] = {0, 0, 0, 0};                      // draw block 0: gate, wall1, wall2, spawn
@@ -851,7 +832,6 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
             s.err = err;
         };
 
-        STAMP(2);
         // ---- wave-uniform path selection
         const bool cells2 = active && have_obs &&
                             ((!s.pone && (s.ax > 3 || s.ay < 14)) || (V4 && !s.patrol && s.ay <= 8) ||
@@ -879,9 +859,7 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
                     mq[e][1] = *reinterpret_cast<const uint4 *>(env + MAT_OFF + 4 * qb);
                 }
             }
-            STAMP(3);
             part2(std::false_type{});
-            STAMP(4);
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const bool valid_e = n0 + e < N;
@@ -948,7 +926,6 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
             }
         }
 
-        STAMP(5);
         // ================= auto-reset (soa/train_ppo.py:104): ballot of done envs, regenerate in place
         if (autoreset) {
             const unsigned long long dm = __ballot(done != 0);
@@ -963,10 +940,6 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
         }
     }
 
-#ifdef TW_STAMP
-    STAMP(6);
-    if (lane == 0 && blockIdx.x < 64) for (int i = 0; i < 8; ++i) g_stamp[blockIdx.x][i] = st_acc[i];
-#endif
     // ---- write state back
     wave_sync();
     if (lane < E) store_env(s, recs + lane * REC);
@@ -1027,41 +1000,24 @@ __global__ __launch_bounds__(64, (E == 1 ? 4 : 2)) void tw_rollout_kernel(Params
 // Anything outside normal play (illegal action, drifted balls, injected grids, ...) raises *p.abnormal;
 // the host always enqueues the sequential kernel behind this one, which re-runs the launch from the
 // untouched input state iff the flag is set (both write the `_out` state; the host swaps afterwards).
-#ifndef TW_PWAVES
-#define TW_PWAVES 16
-#endif
-#ifndef TW_WG_TARGET
-#define TW_WG_TARGET 256
-#endif
-constexpr int PWAVES = TW_PWAVES;   // waves per workgroup (wave e verifies env e of the group: PG <= PWAVES)
-constexpr int PG_MAX = PWAVES < 16 ? PWAVES : 16;   // envs per workgroup (template parameter PG = 16, 8, 4 or 2: small batches still fill the CUs)
-constexpr int PIPE_WG_TARGET = TW_WG_TARGET;        // envs per workgroup are chosen so that about this many workgroups exist
+constexpr int PWAVES = 16;            // waves per workgroup (wave e verifies env e of the group: PG <= PWAVES)
+constexpr int PG_MAX = 16;            // envs per workgroup (template parameter PG = 16, 8, 4 or 2: small batches still fill the CUs)
+constexpr int PIPE_WG_TARGET = 256;   // envs per workgroup are chosen so that about this many workgroups exist
 constexpr int PCH = 128;        // steps per ring chunk
 // env-steps one emission wave takes per draw from the task counter: a compile-time choice per frame layout.
 // Float frames: 1 -- the 16 waves of a workgroup then write 16 neighbouring rows of the same step at any time; with 8 (one
 // wave streaming 16 KB on its own) the same stores ran 5-17 % slower on every box tried, with 2 still 5 % slower, and a
 // store-only replica of the pattern (tools/store_pattern_probe.hip) drops from ~6.3 to ~4.3 TB/s: that layout is bound by
 // the store path, not by issue.  Code frames (TW_F_MATRIX_CODE, 1184-byte records) are issue-bound instead: 4 tasks per
-// draw save three of four counter / poll / index sequences (6 % per launch, tools/ab_variants.py with AB_CODES=1), and the
+// draw save three of four counter / poll / index sequences (6 % per launch, profiles/HISTORY.md), and the
 // code-frame instantiation of the kernel drops every float-matrix path at compile time.
-#ifdef TW_PGRP
-constexpr int PGRP_FLOAT = TW_PGRP, PGRP_CODE = TW_PGRP;      // diagnostic builds: one value for both layouts
-#else
 constexpr int PGRP_FLOAT = 1, PGRP_CODE = 4;
-#endif
 constexpr uint32_t REC_VALID = 0x80000000u;
 
 struct Dyn { int b0, pone, i1, i2, patrol, o1y0, o2x0; };
 // rare events of the logic loop (wall drop, patrol spawn, episode end): their code is laid out behind the loop so that the
 // common path falls through (a taken branch costs the lone logic wave an instruction-buffer refill)
-#ifdef LG_NOEXPECT
-#define LG_RARE(c) (c)
-#else
 #define LG_RARE(c) __builtin_expect(!!(c), 0)
-#endif
-#ifndef LG_UNROLL
-#define LG_UNROLL 1
-#endif
 // (x << K) | acc in ONE instruction; written as plain C the optimiser re-balances a chain of these into separate shifts
 // plus 3-input ORs (17 instead of 7 instructions for the record word)
 template <int K>
@@ -1167,11 +1123,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
     constexpr bool V4 = VARIANT == 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = p.n_envs;
-#ifdef TW_STAMP
-    unsigned long long pst_entry = 0, pst_lstart = 0, pst_lend = 0, pst_p1 = 0, pst_p2 = 0, pst_p3 = 0, pst_p4 = 0;
-#define PSTAMP0(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_entry) :: "memory");
-#endif
     // workgroups are dealt round-robin to the 8 XCDs: give each XCD one contiguous range of envs so that the
     // partially written lines of the [T][N] scalar outputs (reward / terminated / truncated / pos) merge in ONE L2
     const int n0 = ((gridDim.x & 7) == 0 ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x) * PG;
@@ -1210,10 +1161,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
             act_pre[k] = p.actions[(size_t)min(tl, len0 - 1) * N + min(n0 + e, N - 1)];
         }
     }
-#ifdef TW_STAMP
-    PSTAMP0(pst_p1);
-    if (lane == 0 && blockIdx.x < 64) { g_stamp3[blockIdx.x][wave][0] = pst_entry; g_stamp3[blockIdx.x][wave][1] = pst_p1; }
-#endif
     // ---- records of the block's envs; the image copies must have landed before anyone patches the image
     constexpr bool code_mode = CODE;                            // == (p.flags & TW_F_MATRIX_CODE) != 0: the host picks the instantiation
     uint8_t *img_bytes = reinterpret_cast<uint8_t *>(my_img);
@@ -1223,10 +1170,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
     __builtin_amdgcn_s_waitcnt(0x0f70);                           // vmcnt(0): LDS-direct loads retire through the vector-memory counter
     __syncthreads();
 
-#ifdef TW_STAMP
-    PSTAMP0(pst_p2);
-    if (lane == 0 && blockIdx.x < 64) g_stamp3[blockIdx.x][wave][2] = pst_p2;
-#endif
     // ---- wave e verifies env n0+e: scalar regime + planes == closed form (plane bytes: loaded above)
     {
         EnvS s;
@@ -1244,9 +1187,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
         if (__ballot(!ok) != 0ull && lane == 0) atomicOr(p.abnormal, 1);
     }
 
-#ifdef TW_STAMP
-    PSTAMP0(pst_p3);
-#endif
     // ---- emission constants of this lane.  Record layout (tw_alloc_outputs): the env-step's 2048-byte block is
     // written by exactly two full-wave stores of eight whole 128-byte lines each -- lanes 0..63 matrix floats 0..255,
     // then lanes 0..8 matrix floats 256..291 and lanes 9..63 the 55 image chunks.
@@ -1339,9 +1279,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
     }
     const bool policy_idx = (p.flags & TW_F_POLICY_IDX) != 0;
 
-#ifdef TW_STAMP
-    PSTAMP0(pst_p4);
-#endif
     for (int c0 = 0; c0 < p.T; c0 += PCH) {
         const int len = min(PCH, p.T - c0);
         // the chunk's actions go to LDS up front: the logic wave must never wait on vmcnt (on gfx950 a load
@@ -1379,15 +1316,8 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
             drw[i] = packed | ((raises ? 1u : 0u) << 10) | ((uint32_t)(dx + 32 * dy) << 16);
         }
         __syncthreads();
-#ifdef TW_STAMP
-        unsigned long long pst_l = 0, pst_poll = 0, pst_work = 0, pst_tasks = 0, pst_t0 = 0, pst_t1 = 0;
-#define PSTAMP(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
-#else
-#define PSTAMP(v) do { } while (0)
-#endif
         if (wave == 0) {
             // ================= LOGIC: the transition in closed form, one step per iteration
-            PSTAMP(pst_t0);
             __builtin_amdgcn_s_setprio(3);        // the serial chain must win issue arbitration on its SIMD
             // running LDS pointers (one add per step each); drw has one spare row, so the prefetch of step tl + 1 needs no clamp
             const uint32_t *drp = drw + (lane < PG ? lane : 0);
@@ -1399,7 +1329,7 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
             uint32_t pend = 0u, *pendp = rgp;
             // the whole loop sits inside the lane predicate: one exec set-up per chunk instead of an if / else per step
             if (lg_active)
-#pragma unroll LG_UNROLL
+#pragma unroll 1
             for (int tl = 0; tl < len; ++tl) {
                 const uint32_t dr = dr_next;
                 drp += PG;
@@ -1508,13 +1438,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
             }
             if (__ballot(bad) != 0ull && lane == 0) atomicOr(p.abnormal, 1);
             __builtin_amdgcn_s_setprio(0);
-            PSTAMP(pst_t1);
-#ifdef TW_STAMP
-            pst_l = pst_t1 - pst_t0;
-            if (c0 == 0) pst_lstart = pst_t0;
-            pst_lend = pst_t1;
-            if (lane == 0 && blockIdx.x < 64) g_stamp[blockIdx.x][0] = pst_l;
-#endif
         }
         // ================= EMIT: pull groups of PGRP (step, env) tasks
         const int ngroups = len * (PG / PGRP);
@@ -1528,16 +1451,11 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
             // the wave that draws a step's first group polls all PG records and writes the step's scalar outputs
             const int npoll = e0 == 0 ? PG : PGRP;
             uint32_t rv = REC_VALID;
-            PSTAMP(pst_t0);
             while (true) {
                 if (lane < npoll) rv = const_cast<volatile uint32_t *>(ring)[tl * PG + e0 + lane];
                 if (__ballot((rv & REC_VALID) == 0u) == 0ull) break;
                 __builtin_amdgcn_s_sleep(1);
             }
-            PSTAMP(pst_t1);
-#ifdef TW_STAMP
-            pst_poll += pst_t1 - pst_t0; pst_tasks += PGRP;
-#endif
             if (e0 == 0 && lane < PG && n0 + lane < N) {   // scalar outputs of the step's PG env-steps: one lane each, contiguous
                 const size_t srow = (size_t)(c0 + tl) * N + n0 + lane;
                 p.reward[srow] = reward_value((int)((rv >> 25) & 7u));
@@ -1556,10 +1474,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
                 uint8_t *obs_dst = obs_g + (size_t)j * p.obs_pitch;
                 float *mat_dst = mat_g + (size_t)j * p.mat_pitch;
                 uint8_t *matc_dst = reinterpret_cast<uint8_t *>(p.matrix) + (grow + j) * (size_t)p.mat_pitch;
-#ifdef TW_PIPE_NO_EMIT
-                if (ax == 99) p.obs[0] = (uint8_t)(ax + ay);
-                continue;
-#endif
                 // this lane's dynamic cell, decoded from the record with per-lane shift/mask constants
                 const int x = dc_xc + (int)((r >> dc_xsh) & dc_xmask);
                 const int y = dc_yc + (int)((r >> dc_ysh) & dc_ymask);
@@ -1632,19 +1546,7 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
                 }
                 wave_sync();
             }
-#ifdef TW_STAMP
-            PSTAMP(pst_t0);
-            pst_work += pst_t0 - pst_t1;
-#endif
         }
-#ifdef TW_STAMP
-        if (wave == 1 && lane == 0 && blockIdx.x < 64) {
-            g_stamp[blockIdx.x][1] = pst_poll; g_stamp[blockIdx.x][2] = pst_work; g_stamp[blockIdx.x][3] = pst_tasks;
-        }
-        if (lane == 0 && blockIdx.x < 64) {
-            g_stamp2[blockIdx.x][wave][0] = pst_tasks; g_stamp2[blockIdx.x][wave][1] = pst_poll; g_stamp2[blockIdx.x][wave][2] = pst_work;
-        }
-#endif
         __syncthreads();
         if (tid == 0) { ctrl[0] = 0; ctrl[1] = 0; }
         __syncthreads();
@@ -1688,19 +1590,6 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
             p.colour_out[gb + c] = (uint8_t)(v >> 8);
         }
     }
-#ifdef TW_STAMP
-    if (wave == 0) {
-        unsigned long long pst_exit;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pst_exit) :: "memory");
-        if (lane == 0 && blockIdx.x < 64) {
-            g_stamp[blockIdx.x][4] = pst_lstart - pst_entry;       // prologue: images, verification, staging
-            g_stamp[blockIdx.x][5] = pst_exit - pst_lend;          // from the logic wave's last record to the kernel's end
-            g_stamp[blockIdx.x][6] = pst_exit - pst_entry;         // whole kernel as wave 0 sees it
-            g_stamp2[blockIdx.x][0][0] = pst_p1 - pst_entry; g_stamp2[blockIdx.x][0][1] = pst_p2 - pst_p1;
-            g_stamp2[blockIdx.x][0][2] = pst_p3 - pst_p2; g_stamp2[blockIdx.x][1][0] = pst_p4 - pst_p3; g_stamp2[blockIdx.x][1][1] = pst_lstart - pst_p4;
-        }
-    }
-#endif
 }
 
 // ---------------------------------------------------------------- init / reset / obs-only kernels (wave per env)
@@ -1783,7 +1672,6 @@ struct tw_engine {
     int envs_per_wave;              // 0 = auto
     int pipeline;                   // 1 = use the pipelined kernel when eligible (TW_PIPELINE=0 disables)
     int *fb_count;                  // device counter: pipelined launches re-run by the sequential fallback
-    int slab_backing;               // how tw_alloc_outputs backs its slab (0 hipMalloc, 1 mapped 2 MiB granules, ...)
     uint32_t *pipe_tab;             // constant tables of the pipelined kernel (static image, per-lane emission constants)
 };
 
@@ -1915,11 +1803,7 @@ int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *
 #undef TW_PIPE_LAUNCH
     HIP_TRY(hipGetLastError());
     p.only_if_flagged = 1;
-#ifdef TW_DEBUG_NO_FALLBACK_LAUNCH
-    int rc = TW_OK;                              // diagnostic build only: what the flag-gated launch costs
-#else
-    int rc = launch_sequential(e, p, st);
-#endif
+    const int rc = launch_sequential(e, p, st);
     if (rc != TW_OK) return rc;
     uint8_t *t8; int32_t *t32;
     t8 = e->type; e->type = e->type2; e->type2 = t8;
@@ -1941,11 +1825,8 @@ int tw_create(tw_engine **out, int variant, int n_envs, int view_size, int devic
     if (!e) return TW_E_NOMEM;
     e->variant = variant; e->n_envs = n_envs; e->view = view_size; e->device = device_id;
     e->seed = seed; e->env_id0 = env_id0;
-    const char *epw = getenv("TW_ENVS_PER_WAVE");
-    e->envs_per_wave = epw ? atoi(epw) : 0;
     const char *pl = getenv("TW_PIPELINE");
     e->pipeline = pl ? atoi(pl) : 1;
-    e->slab_backing = 1;            // 2 MiB chunks created one by one, mapped in creation order (see slab_alloc)
     hipError_t rr[8];
     rr[0] = hipMalloc((void **)&e->type, (size_t)n_envs * NC);
     rr[1] = hipMalloc((void **)&e->colour, (size_t)n_envs * NC);
@@ -2099,27 +1980,14 @@ int tw_gen_obs(tw_engine *e, int view_size, uint8_t *obs, int obs_pitch, void *s
     return TW_OK;
 }
 
-#ifdef TW_STAMP
-int tw_debug_stamps2(unsigned long long *out3072) {
-    return hipMemcpyFromSymbol(out3072, HIP_SYMBOL(g_stamp2), sizeof(unsigned long long) * 3072) == hipSuccess ? 0 : -2;
-}
-int tw_debug_stamps3(unsigned long long *out4096) {
-    return hipMemcpyFromSymbol(out4096, HIP_SYMBOL(g_stamp3), sizeof(unsigned long long) * 4096) == hipSuccess ? 0 : -2;
-}
-int tw_debug_stamps(unsigned long long *out512) {
-    return hipMemcpyFromSymbol(out512, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 512) == hipSuccess ? 0 : -2;
-}
-#endif
-
 // ---------------------------------------------------------------- engine-owned output slab
 namespace {
 
 struct Slab {
     void *base = nullptr;
     size_t bytes = 0, chunk = 0;
-    int backing = 0;                                  // 0 hipMalloc, >0 mapped hipMemCreate granules
-    std::vector<hipMemGenericAllocationHandle_t> handles;
-    std::vector<size_t> slots;                        // handles[i] is mapped at base + slots[i] * chunk
+    int backing = 0;                                  // 0 hipMalloc, 1 mapped hipMemCreate chunks
+    std::vector<hipMemGenericAllocationHandle_t> handles;   // handles[i] is mapped at base + i * chunk
 };
 std::mutex g_slab_mu;
 std::map<void *, Slab> g_slabs;
@@ -2135,22 +2003,21 @@ int slab_release(Slab &s) {
         // hipMemAddressReserve served stale translations -- a rollout into the new slab lost ~10 % of its rows
         // (tools/dbg_fallback.py; leak / keep-range / free-range: fine / fine / corrupt).  The cost is virtual
         // address space only (about 1 GiB per released slab of the benchmark size, out of 128 TiB).
-        for (size_t i = 0; i < s.handles.size(); ++i) note(hipMemUnmap((char *)s.base + s.slots[i] * s.chunk, s.chunk));
+        for (size_t i = 0; i < s.handles.size(); ++i) note(hipMemUnmap((char *)s.base + i * s.chunk, s.chunk));
         for (auto h : s.handles) note(hipMemRelease(h));
     }
     s.base = nullptr;
     return first == hipSuccess ? TW_OK : hip_fail(first);
 }
 
-// backing: 0 hipMalloc; k > 0: the slab is a contiguous virtual range backed by separately created physical chunks
-// (hipMemCreate) of 2^(k-1) x 2 MiB each: 1 -> 2 MiB, 2 -> 4 MiB, 5 -> 32 MiB, ...; 99 -> one chunk for the slab.
-// Default 1.  Measured (tools/placement_probe2.py, 4096 x 128 record-layout rollout, 4 slabs each, ms per launch):
+// backing: 0 hipMalloc; 1 the slab is a contiguous virtual range backed by separately created physical 2 MiB chunks
+// (hipMemCreate), mapped in creation order.
+// Measured (profiles/r02_slab_backing_probe.log, 4096 x 128 record-layout rollout, 4 slabs each, ms per launch):
 // hipMalloc / one chunk / 32-256 MiB chunks 0.190-0.197; 2 MiB chunks mapped in creation order 0.178-0.189; the same
 // chunks mapped in reverse order 0.192-0.196 (= the contiguous case: the driver hands out physical memory top-down,
 // so reverse order IS physically ascending); shuffled 0.199-0.201.  Why a stream whose 2 MiB pages descend
 // physically absorbs these stores ~5 % faster than an ascending one is not understood; it is kept because it is
 // reproducible on every box tried and the fallback (hipMalloc) is what every other allocation gets anyway.
-// Diagnostic knob TW_SLAB_ORDER: 0 map the chunks in creation order, 1 in reverse order, 2 shuffled.
 int slab_alloc(int device, size_t bytes, int backing, Slab &s) {
     s.bytes = bytes; s.backing = backing; s.base = nullptr;
     if (backing == 0) {
@@ -2165,34 +2032,19 @@ int slab_alloc(int device, size_t bytes, int backing, Slab &s) {
     size_t gran = 0;
     HIP_TRY(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended));
     if (gran < ((size_t)2 << 20)) gran = (size_t)2 << 20;
-    size_t chunk = backing >= 99 ? bytes : ((size_t)2 << 20) << (backing - 1);
-    chunk = (chunk + gran - 1) / gran * gran;
+    const size_t chunk = (((size_t)2 << 20) + gran - 1) / gran * gran;
     s.bytes = (bytes + chunk - 1) / chunk * chunk;
     s.chunk = chunk;
     const size_t nchunks = s.bytes / chunk;
     hipError_t err = hipMemAddressReserve(&s.base, s.bytes, gran, nullptr, 0);
     if (err != hipSuccess) { s.base = nullptr; return hip_fail(err); }
-    const char *ord_s = getenv("TW_SLAB_ORDER");
-    const int order = ord_s ? atoi(ord_s) : 0;
-    std::vector<size_t> slot(nchunks);
-    for (size_t i = 0; i < nchunks; ++i) slot[i] = order == 1 ? nchunks - 1 - i : i;
-    if (order == 2) {
-        uint64_t r = 0x9E3779B97F4A7C15ull;
-        for (size_t i = nchunks; i > 1; --i) {
-            r = r * 6364136223846793005ull + 1442695040888963407ull;
-            std::swap(slot[i - 1], slot[(size_t)((r >> 33) % i)]);
-        }
-    }
-    std::vector<char> is_mapped(nchunks, 0);
     for (size_t i = 0; i < nchunks; ++i) {
         hipMemGenericAllocationHandle_t h;
         err = hipMemCreate(&h, chunk, &prop, 0);
         if (err != hipSuccess) break;
-        err = hipMemMap((char *)s.base + slot[i] * chunk, chunk, 0, h, 0);
+        err = hipMemMap((char *)s.base + i * chunk, chunk, 0, h, 0);
         if (err != hipSuccess) { (void)hipMemRelease(h); break; }
         s.handles.push_back(h);
-        s.slots.push_back(slot[i]);
-        is_mapped[slot[i]] = 1;
     }
     if (err == hipSuccess) {
         hipMemAccessDesc acc;
@@ -2202,10 +2054,9 @@ int slab_alloc(int device, size_t bytes, int backing, Slab &s) {
         err = hipMemSetAccess(s.base, s.bytes, &acc, 1);
     }
     if (err != hipSuccess) {
-        for (size_t i = 0; i < nchunks; ++i)
-            if (is_mapped[i]) (void)hipMemUnmap((char *)s.base + i * chunk, chunk);
+        for (size_t i = 0; i < s.handles.size(); ++i) (void)hipMemUnmap((char *)s.base + i * chunk, chunk);
         for (auto h : s.handles) (void)hipMemRelease(h);
-        s.handles.clear(); s.slots.clear();
+        s.handles.clear();
         // the range stays reserved, like in slab_release: a freed range that comes back from a later reserve is the
         // pattern that lost rows (the caller falls back to hipMalloc right after this)
         s.base = nullptr;
@@ -2234,10 +2085,8 @@ int tw_alloc_outputs(tw_engine *e, int T, int flags, tw_outputs *out) {
     const size_t sz[6] = {TN * rec_bytes, 0, TN * 8, TN * 4, TN, TN};
     size_t off[6], total = 0;
     for (int i = 0; i < 6; ++i) { off[i] = total; total += round_up(sz[i], A); }
-    // backing: mapped 2 MiB granules by default (TW_SLAB_BACKING=0..3 overrides); hipMalloc when the runtime refuses
-    const char *bk = getenv("TW_SLAB_BACKING");
-    int backing = bk ? atoi(bk) : e->slab_backing;
-    if (flags & TW_F_SLAB_HIPMALLOC) backing = 0;
+    // backing: mapped 2 MiB chunks; hipMalloc with TW_F_SLAB_HIPMALLOC or when the runtime refuses the mapping calls
+    int backing = (flags & TW_F_SLAB_HIPMALLOC) ? 0 : 1;
     Slab s;
     int rc = slab_alloc(e->device, total, backing, s);
     if (rc != TW_OK && backing != 0) { backing = 0; rc = slab_alloc(e->device, total, 0, s); }

@@ -115,7 +115,7 @@ int tw_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *draw
                int obs_pitch, float *state_matrix, int mat_pitch, float *pos, float *reward,
                uint8_t *terminated, uint8_t *truncated, int flags, void *stream);
 
-/* Envs per wavefront of the rollout kernel: 1, 2 or 4 (0 = auto from n_envs; also TW_ENVS_PER_WAVE). */
+/* Envs per wavefront of the rollout kernel: 1, 2 or 4 (0 = auto: 2 from 2048 envs up, 1 below; 4 only when set here). */
 int tw_set_envs_per_wave(tw_engine *e, int envs_per_wave);
 
 /* Rollouts of >= 8 steps with auto-reset, native layouts and Philox draws use the pipelined kernel
@@ -166,13 +166,14 @@ const char *tw_build_id(void);
  * bandwidth depend on where the driver happens to place them: 0.178 ... 0.230 ms per 4096 x 128 launch; the record
  * stream is 0.19-0.20 ms on every allocation.)
  *   pos float[T][N][2], reward float[T][N], terminated / truncated uint8[T][N]   (dense)
- * `backing`: how the slab is backed -- 1 (default) = 2 MiB physical chunks (hipMemCreate) mapped into one virtual range,
- * 0 = hipMalloc (also the fallback when the runtime refuses the mapping calls).  Pass the struct's members to tw_step /
- * tw_rollout.  tw_free_outputs returns the slab's physical memory (the struct is zeroed) but keeps a mapped slab's VIRTUAL
- * address range reserved for the life of the process -- slab_bytes of address space per released slab (about 1 GiB at
- * 4096 envs x 128 steps), nothing else: on ROCm 7.2 a range that went through hipMemAddressFree and was handed out again
- * by hipMemAddressReserve is read wrongly by hipMemcpy device -> host (tools/vmm_reuse_repro.hip).  Allocate output slabs
- * once and reuse them; a process that allocates and frees slabs in a loop only spends address space. */
+ * `backing`: how the slab is backed -- 1 (default) = 2 MiB physical chunks (hipMemCreate) mapped in creation order into
+ * one virtual range, 0 = hipMalloc (with TW_F_SLAB_HIPMALLOC, and the fallback when the runtime refuses the mapping
+ * calls).  Pass the struct's members to tw_step / tw_rollout.  tw_free_outputs returns the slab's physical memory (the
+ * struct is zeroed) but keeps a mapped slab's VIRTUAL address range reserved for the life of the process -- slab_bytes
+ * of address space per released slab (about 1 GiB at 4096 envs x 128 steps), nothing else: on ROCm 7.2 a range that
+ * went through hipMemAddressFree and was handed out again by hipMemAddressReserve is read wrongly by hipMemcpy
+ * device -> host (tools/vmm_reuse_repro.hip).  Allocate output slabs once and reuse them; a process that allocates and
+ * frees slabs in a loop only spends address space. */
 typedef struct tw_outputs {
     uint8_t *obs;
     void *matrix;
