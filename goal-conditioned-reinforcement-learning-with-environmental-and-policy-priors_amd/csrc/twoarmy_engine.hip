@@ -32,9 +32,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <map>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "twoarmy.h"
@@ -265,6 +267,68 @@ __device__ __forceinline__ bool move_group(uint32_t *env, int (&xs)[NB], int (&y
     return true;
 }
 
+// step_move += 1 (twoarmy_v6.py:88), its mod-6 / mod-4 phases and the draw counter; returns the row-8 balls' dx of this
+// step (:104-109)
+__device__ __forceinline__ int advance_counters(EnvS &s) {
+    s.t += 1;
+    s.step_move += 1;
+    s.m6 = s.m6 == 5 ? 0 : s.m6 + 1;
+    s.m4 = (s.m4 + 1) & 3;
+    return (s.m6 <= 1) ? 1 : (s.m6 <= 3 ? -1 : 0);
+}
+
+// Row-8 balls (:96-112): clear all three, then put each inside try/except.  When the balls are the adjacent triple
+// b0..b0+2 on row 8 and the moved triple stays inside the grid (always, in normal play) that is 4 branch-free cell writes.
+__device__ __forceinline__ void move_ball_triple(uint32_t *env, EnvS &s, int dxb) {
+    uint32_t *row8 = env + gpi(0, 8);          // row 8 of the x-major image: stride GPP per x
+    uint32_t *mrow8 = env + MAT_OFF + 8 * GS;
+    uint8_t *crow8 = mcb(env) + 8 * GS;
+    const int b0 = s.obx[0], nb = b0 + dxb;
+    const int cx = dxb > 0 ? b0 : b0 + 2;                 // the vacated cell (a ball cell when dxb == 0)
+    row8[cx * GPP] = dxb != 0 ? C_EMPTY : C_BALL;
+    mrow8[cx] = dxb != 0 ? M_FREE : M_BALL;
+    crow8[cx] = dxb != 0 ? 0 : 2;
+    row8[nb * GPP] = C_BALL; row8[(nb + 1) * GPP] = C_BALL; row8[(nb + 2) * GPP] = C_BALL;
+    mrow8[nb] = M_BALL; mrow8[nb + 1] = M_BALL; mrow8[nb + 2] = M_BALL;
+    crow8[nb] = 2; crow8[nb + 1] = 2; crow8[nb + 2] = 2;
+    s.obx[0] = nb; s.obx[1] = nb + 1; s.obx[2] = nb + 2;
+}
+
+// v4 patrols: the column (twoarmy_v4.py:115-144) or the square (:147-176) moves when its gate is open.  `gate` is the
+// step's gate draw.  Returns false when the reference raised (err set).
+__device__ __forceinline__ bool move_patrols(uint32_t *env, EnvS &s, uint32_t gate, int &err) {
+    bool alive = true;
+    if (s.upd_long) {
+        s.upd_horiz = 0;
+        bool go = (s.m4 == 2) || (s.m6 == 3) || (s.m6 == 0);
+        if (!go) go = (gate % 10u) == 6u;
+        if (go && s.patrol) {
+            if (s.up1) {
+                alive = move_group<3>(env, s.o1x, s.o1y, s.o1v, 0, -1, err);
+                if (alive && s.o1y[0] == 3) s.up1 = 0;
+            } else {
+                alive = move_group<3>(env, s.o1x, s.o1y, s.o1v, 0, 1, err);
+                if (alive && s.o1y[2] == 7) s.up1 = 1;
+            }
+        }
+    }
+    if (alive && s.upd_horiz) {
+        s.upd_long = 0;
+        bool go = (s.m6 != 1);
+        if (!go) go = (gate % 10u) == 6u;
+        if (go && s.patrol) {
+            if (s.right2) {
+                alive = move_group<4>(env, s.o2x, s.o2y, s.o2v, 1, 0, err);
+                if (alive && s.o2x[3] == 11) s.right2 = 0;
+            } else {
+                alive = move_group<4>(env, s.o2x, s.o2y, s.o2v, -1, 0, err);
+                if (alive && s.o2x[0] == 5) s.right2 = 1;
+            }
+        }
+    }
+    return alive;
+}
+
 __device__ __forceinline__ float reward_value(int code) {
     return code == R_STEP ? -0.01f : code == R_RISK ? -0.1f : code == R_HIT ? -0.9f : code == R_ROOM2 ? 0.2f : 0.9f;
 }
@@ -368,13 +432,8 @@ __device__ __forceinline__ ObsFast make_obs_fast(int chunk, int V) {
     return f;
 }
 
-__device__ __forceinline__ void emit_obs_fast(const uint32_t *env, int ax, int ay, const ObsFast &f, int lane,
-                                              uint8_t *dst) {
-    if (!f.active) return;
-    const char *base = reinterpret_cast<const char *>(env + gpi(ax, ay));
-    uint32_t c[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] = *reinterpret_cast<const uint32_t *>(base + f.rel4[k]);
+// the lane's six gathered cell codes -> its 16 output bytes: 144-bit stream w0..w4, funnel shift, agent / pad masks
+__device__ __forceinline__ uint4 pack_obs(const uint32_t (&c)[6], const ObsFast &f) {
     const uint32_t w0 = c[0] | (c[1] << 24);
     const uint32_t w1 = (c[1] >> 8) | (c[2] << 16);
     const uint32_t w2 = (c[2] >> 16) | (c[3] << 8);
@@ -385,24 +444,37 @@ __device__ __forceinline__ void emit_obs_fast(const uint32_t *env, int ax, int a
     o.y = (__builtin_amdgcn_alignbit(w2, w1, f.shift) & f.andm[1]) | f.orm[1];
     o.z = (__builtin_amdgcn_alignbit(w3, w2, f.shift) & f.andm[2]) | f.orm[2];
     o.w = (__builtin_amdgcn_alignbit(w4, w3, f.shift) & f.andm[3]) | f.orm[3];
-    *reinterpret_cast<uint4 *>(dst + 16 * f.chunk) = o;
+    return o;
+}
+
+__device__ __forceinline__ void emit_obs_fast(const uint32_t *env, int ax, int ay, const ObsFast &f, int lane,
+                                              uint8_t *dst) {
+    if (!f.active) return;
+    const char *base = reinterpret_cast<const char *>(env + gpi(ax, ay));
+    uint32_t c[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = *reinterpret_cast<const uint32_t *>(base + f.rel4[k]);
+    *reinterpret_cast<uint4 *>(dst + 16 * f.chunk) = pack_obs(c, f);
 }
 
 // ---------------------------------------------------------------- state matrix (env_buffer.py:300-318)
+// quad q of the float matrix image with the agent's cell (d = agent cell - 4q) patched to 0.3, as selects (no branch)
+__device__ __forceinline__ uint4 with_agent(uint4 v, int d) {
+    v.x = d == 0 ? M_AGENT : v.x;
+    v.y = d == 1 ? M_AGENT : v.y;
+    v.z = d == 2 ? M_AGENT : v.z;
+    v.w = d == 3 ? M_AGENT : v.w;
+    return v;
+}
+
 __device__ __forceinline__ void emit_matrix_fast(const uint32_t *env, int ax, int ay, int lane, float *dst) {
     const int ca = ay * GS + ax;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         const int q = lane + 64 * pass;
-        if (q < MAT_WORDS / 4) {
-            uint4 v = *reinterpret_cast<const uint4 *>(env + MAT_OFF + 4 * q);
-            const int d = ca - 4 * q;
-            v.x = d == 0 ? M_AGENT : v.x;
-            v.y = d == 1 ? M_AGENT : v.y;
-            v.z = d == 2 ? M_AGENT : v.z;
-            v.w = d == 3 ? M_AGENT : v.w;
-            *reinterpret_cast<uint4 *>(dst + 4 * q) = v;
-        }
+        if (q < MAT_WORDS / 4)
+            *reinterpret_cast<uint4 *>(dst + 4 * q) = with_agent(*reinterpret_cast<const uint4 *>(env + MAT_OFF + 4 * q),
+                                                                 ca - 4 * q);
     }
 }
 
@@ -560,56 +632,8 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
         const bool all_turbo = __ballot(active && !(mode_ok && legal)) == 0ull;
         if (all_turbo) {
             if (active) {
-                s.t += 1;
-                s.step_move += 1;                                 // twoarmy_v6.py:88
-                s.m6 = s.m6 == 5 ? 0 : s.m6 + 1;
-                s.m4 = (s.m4 + 1) & 3;
-                const int m6 = s.m6;
-                const int dxb = (m6 <= 1) ? 1 : (m6 <= 3 ? -1 : 0);   // :104-109
-                // row-8 balls (:96-112) as 4 branch-free cell writes
-                uint32_t *row8 = my_env + gpi(0, 8);      // row 8 of the x-major image: stride GPP per x
-                uint32_t *mrow8 = my_env + MAT_OFF + 8 * GS;
-                const int b0 = s.obx[0], nb = b0 + dxb;
-                const int cx = dxb > 0 ? b0 : b0 + 2;             // the vacated cell (a ball cell when dxb == 0)
-                uint8_t *crow8 = mcb(my_env) + 8 * GS;
-                row8[cx * GPP] = dxb != 0 ? C_EMPTY : C_BALL;
-                mrow8[cx] = dxb != 0 ? M_FREE : M_BALL;
-                crow8[cx] = dxb != 0 ? 0 : 2;
-                row8[nb * GPP] = C_BALL; row8[(nb + 1) * GPP] = C_BALL; row8[(nb + 2) * GPP] = C_BALL;
-                mrow8[nb] = M_BALL; mrow8[nb + 1] = M_BALL; mrow8[nb + 2] = M_BALL;
-                crow8[nb] = 2; crow8[nb + 1] = 2; crow8[nb + 2] = 2;
-                s.obx[0] = nb; s.obx[1] = nb + 1; s.obx[2] = nb + 2;
-                bool alive = true;
-                if (V4) {
-                    if (s.upd_long) {                             // twoarmy_v4.py:115-144
-                        s.upd_horiz = 0;
-                        bool go = (s.m4 == 2) || (m6 == 3) || (m6 == 0);
-                        if (!go) go = (dw[TW_S_GATE] % 10u) == 6u;
-                        if (go && s.patrol) {
-                            if (s.up1) {
-                                alive = move_group<3>(my_env, s.o1x, s.o1y, s.o1v, 0, -1, err);
-                                if (alive && s.o1y[0] == 3) s.up1 = 0;
-                            } else {
-                                alive = move_group<3>(my_env, s.o1x, s.o1y, s.o1v, 0, 1, err);
-                                if (alive && s.o1y[2] == 7) s.up1 = 1;
-                            }
-                        }
-                    }
-                    if (alive && s.upd_horiz) {                   // twoarmy_v4.py:147-176
-                        s.upd_long = 0;
-                        bool go = (m6 != 1);
-                        if (!go) go = (dw[TW_S_GATE] % 10u) == 6u;
-                        if (go && s.patrol) {
-                            if (s.right2) {
-                                alive = move_group<4>(my_env, s.o2x, s.o2y, s.o2v, 1, 0, err);
-                                if (alive && s.o2x[3] == 11) s.right2 = 0;
-                            } else {
-                                alive = move_group<4>(my_env, s.o2x, s.o2y, s.o2v, -1, 0, err);
-                                if (alive && s.o2x[0] == 5) s.right2 = 1;
-                            }
-                        }
-                    }
-                }
+                move_ball_triple(my_env, s, advance_counters(s));
+                const bool alive = !V4 || move_patrols(my_env, s, dw[TW_S_GATE], err);
                 if (alive) {
                     // MiniGridEnv.step (minigrid.py:1333-1441): dx/dy packed as 2-bit fields (value+1) per action
                     s.step_count += 1;
@@ -624,39 +648,20 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
                     truncated = s.step_count >= s.max_steps;      // :1436-1437
                     have_obs = 1;
                     // keep the invariants of the turbo step for the next one
-                    mode_ok = ((unsigned)(nb - 2) <= 10u) & ((unsigned)(s.ax - 1) <= 14u) & ((unsigned)(s.ay - 1) <= 14u);
+                    mode_ok = ((unsigned)(s.obx[0] - 2) <= 10u) & ((unsigned)(s.ax - 1) <= 14u) & ((unsigned)(s.ay - 1) <= 14u);
                 } else {
                     mode_ok = false;
                 }
             }
         } else if (active) {
             // GENERAL step: literal transition with every bounds check / raise of the reference
-            s.t += 1;
-            s.step_move += 1;                                     // :88
-            s.m6 = s.m6 == 5 ? 0 : s.m6 + 1;
-            s.m4 = (s.m4 + 1) & 3;
-            const int m6 = s.m6;
-            const int dxb = (m6 <= 1) ? 1 : (m6 <= 3 ? -1 : 0);   // :104-109
+            const int dxb = advance_counters(s);
             bool alive = true;
-            // ---- row-8 balls (:96-112): clear all three, then put each inside try/except.
-            // Fast path (always taken in normal play): the balls are the adjacent triple b..b+2 on row 8
-            // and the moved triple stays inside the grid -> 4 branch-free cell writes.
             const int b0 = s.obx[0];
             const bool balls_fast = (s.oby[0] == 8) & (s.oby[1] == 8) & (s.oby[2] == 8) & (s.obx[1] == b0 + 1) &
                                     (s.obx[2] == b0 + 2) & ((unsigned)(b0 + dxb - 1) <= 12u) & ((unsigned)(b0 - 1) <= 12u);
             if (balls_fast) {
-                uint32_t *row8 = my_env + gpi(0, 8);      // row 8 of the x-major image: stride GPP per x
-                uint32_t *mrow8 = my_env + MAT_OFF + 8 * GS;
-                const int nb = b0 + dxb;
-                const int cx = dxb > 0 ? b0 : b0 + 2;             // the vacated cell (a ball cell when dxb == 0)
-                uint8_t *crow8 = mcb(my_env) + 8 * GS;
-                row8[cx * GPP] = dxb != 0 ? C_EMPTY : C_BALL;
-                mrow8[cx] = dxb != 0 ? M_FREE : M_BALL;
-                crow8[cx] = dxb != 0 ? 0 : 2;
-                row8[nb * GPP] = C_BALL; row8[(nb + 1) * GPP] = C_BALL; row8[(nb + 2) * GPP] = C_BALL;
-                mrow8[nb] = M_BALL; mrow8[nb + 1] = M_BALL; mrow8[nb + 2] = M_BALL;
-                crow8[nb] = 2; crow8[nb + 1] = 2; crow8[nb + 2] = 2;
-                s.obx[0] = nb; s.obx[1] = nb + 1; s.obx[2] = nb + 2;
+                move_ball_triple(my_env, s, dxb);
             } else {
                 bool ok = true;
 #pragma unroll
@@ -671,36 +676,7 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
                     }
                 }
             }
-            if (V4 && alive) {
-                if (s.upd_long) {                                 // twoarmy_v4.py:115-144
-                    s.upd_horiz = 0;
-                    bool go = (s.m4 == 2) || (m6 == 3) || (m6 == 0);
-                    if (!go) go = (dw[TW_S_GATE] % 10u) == 6u;
-                    if (go && s.patrol) {
-                        if (s.up1) {
-                            alive = move_group<3>(my_env, s.o1x, s.o1y, s.o1v, 0, -1, err);
-                            if (alive && s.o1y[0] == 3) s.up1 = 0;
-                        } else {
-                            alive = move_group<3>(my_env, s.o1x, s.o1y, s.o1v, 0, 1, err);
-                            if (alive && s.o1y[2] == 7) s.up1 = 1;
-                        }
-                    }
-                }
-                if (alive && s.upd_horiz) {                       // twoarmy_v4.py:147-176
-                    s.upd_long = 0;
-                    bool go = (m6 != 1);
-                    if (!go) go = (dw[TW_S_GATE] % 10u) == 6u;
-                    if (go && s.patrol) {
-                        if (s.right2) {
-                            alive = move_group<4>(my_env, s.o2x, s.o2y, s.o2v, 1, 0, err);
-                            if (alive && s.o2x[3] == 11) s.right2 = 0;
-                        } else {
-                            alive = move_group<4>(my_env, s.o2x, s.o2y, s.o2v, -1, 0, err);
-                            if (alive && s.o2x[0] == 5) s.right2 = 1;
-                        }
-                    }
-                }
-            }
+            if (V4 && alive) alive = move_patrols(my_env, s, dw[TW_S_GATE], err);
             if (alive) {
                 // ---- MiniGridEnv.step (minigrid.py:1333-1441)
                 s.step_count += 1;
@@ -864,12 +840,10 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
             for (int e = 0; e < E; ++e) {
                 const bool valid_e = n0 + e < N;
                 if (has_obs) {
+                    // pack_obs written out: calling it costs <2,6,true> / <4,6,true> a VGPR, or <1,6,false> scratch
                     const uint32_t *c = oc[e];
-                    const uint32_t w0 = c[0] | (c[1] << 24);
-                    const uint32_t w1 = (c[1] >> 8) | (c[2] << 16);
-                    const uint32_t w2 = (c[2] >> 16) | (c[3] << 8);
-                    const uint32_t w3 = c[4] | (c[5] << 24);
-                    const uint32_t w4 = c[5] >> 8;
+                    const uint32_t w0 = c[0] | (c[1] << 24), w1 = (c[1] >> 8) | (c[2] << 16), w2 = (c[2] >> 16) | (c[3] << 8);
+                    const uint32_t w3 = c[4] | (c[5] << 24), w4 = c[5] >> 8;
                     uint4 o;
                     o.x = (__builtin_amdgcn_alignbit(w1, w0, of.shift) & of.andm[0]) | of.orm[0];
                     o.y = (__builtin_amdgcn_alignbit(w2, w1, of.shift) & of.andm[1]) | of.orm[1];
@@ -886,12 +860,7 @@ __device__ __forceinline__ void rollout_body(const Params &p, const int n0, cons
 #pragma unroll
                     for (int pass = 0; pass < 2; ++pass) {
                         const int q = pass == 0 ? lane : qb;
-                        uint4 v = mq[e][pass];
-                        const int d = ca - 4 * q;
-                        v.x = d == 0 ? M_AGENT : v.x;
-                        v.y = d == 1 ? M_AGENT : v.y;
-                        v.z = d == 2 ? M_AGENT : v.z;
-                        v.w = d == 3 ? M_AGENT : v.w;
+                        const uint4 v = with_agent(mq[e][pass], ca - 4 * q);
                         if (valid_e && (pass == 0 || lane < 9)) *reinterpret_cast<uint4 *>(dst + 4 * q) = v;
                     }
                 }
@@ -1504,6 +1473,7 @@ __global__ __launch_bounds__(64 * PWAVES, 16 / PWAVES) void tw_pipe_kernel(Param
                         m0 = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(my_img) + mat_lane_off);
                         m1 = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(my_img) + mat_laneb_off);
                     }
+                    // pack_obs written out: calling it changes this kernel's schedule (layouts 0 and 2)
                     const uint32_t w0 = c[0] | (c[1] << 24), w1 = (c[1] >> 8) | (c[2] << 16), w2 = (c[2] >> 16) | (c[3] << 8);
                     const uint32_t w3 = c[4] | (c[5] << 24), w4 = c[5] >> 8;
                     uint4 o;
@@ -1732,30 +1702,33 @@ bool params_fast(const tw_engine *e, const Params &p, bool allow_codes) {
            ((uintptr_t)p.matrix & 15u) == 0 && mat_ok;
 }
 
-template <int E>
-void launch_variant(const tw_engine *e, const Params &p, hipStream_t st) {
-    int grid = (e->n_envs + E - 1) / E;
-    if (p.only_if_flagged && grid > 256) grid = 256;        // grid-stride fallback launch (see tw_rollout_kernel)
-    const bool fast = params_fast(e, p, false);
-    if (e->variant == 4) {
-        if (fast) hipLaunchKernelGGL((tw_rollout_kernel<E, 4, true>), dim3(grid), dim3(64), 0, st, p);
-        else hipLaunchKernelGGL((tw_rollout_kernel<E, 4, false>), dim3(grid), dim3(64), 0, st, p);
-    } else {
-        if (fast) hipLaunchKernelGGL((tw_rollout_kernel<E, 6, true>), dim3(grid), dim3(64), 0, st, p);
-        else hipLaunchKernelGGL((tw_rollout_kernel<E, 6, false>), dim3(grid), dim3(64), 0, st, p);
-    }
+// Every instantiation a launch can pick, one table per kernel: E = 1, 2, 4 envs per wave, PG = 2, 4, 8, 16 envs per
+// workgroup.  tw_create sets the LDS attribute of every pipe kernel from the same table the launch indexes.
+using KernelFn = void (*)(Params);
+constexpr int log2i(int v) { return v > 1 ? 1 + log2i(v >> 1) : 0; }
+
+template <size_t... I>   // tw_rollout_kernel<E, VARIANT, FAST> at [log2 E][VARIANT == 6][FAST]
+constexpr std::array<KernelFn, sizeof...(I)> rollout_table(std::index_sequence<I...>) {
+    return {{&tw_rollout_kernel<1 << (I / 4), (I / 2) % 2 ? 6 : 4, (I % 2) != 0>...}};
 }
+constexpr auto ROLLOUT_KERNELS = rollout_table(std::make_index_sequence<12>{});
+
+template <size_t... I>   // tw_pipe_kernel<VARIANT, PG, LAYOUT> at [VARIANT == 6][LAYOUT][log2 PG - 1]
+constexpr std::array<KernelFn, sizeof...(I)> pipe_table(std::index_sequence<I...>) {
+    return {{&tw_pipe_kernel<I / 12 ? 6 : 4, 2 << (I % 4), (I / 4) % 3>...}};
+}
+constexpr auto PIPE_KERNELS = pipe_table(std::make_index_sequence<24>{});
 
 constexpr int PIPE_MIN_T = 8;
 constexpr size_t PIPE_LDS_BYTES = (size_t)(PWAVES * ENV_WORDS + PCH * PG_MAX + PG_MAX * REC + 4 + (PCH + 1) * PG_MAX) * 4;   // ~117 KB; drw has a spare row
 
 int launch_sequential(const tw_engine *e, const Params &p, hipStream_t st) {
-    switch (pick_envs_per_wave(e)) {
-    case 1: launch_variant<1>(e, p, st); break;
-    case 2: launch_variant<2>(e, p, st); break;
-    case 4: launch_variant<4>(e, p, st); break;
-    default: return TW_E_ARG;
-    }
+    const int E = pick_envs_per_wave(e);
+    if (E != 1 && E != 2 && E != 4) return TW_E_ARG;
+    int grid = (e->n_envs + E - 1) / E;
+    if (p.only_if_flagged && grid > 256) grid = 256;        // grid-stride fallback launch (see tw_rollout_kernel)
+    const KernelFn k = ROLLOUT_KERNELS[4 * log2i(E) + 2 * (e->variant == 6) + params_fast(e, p, false)];
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, st, p);
     HIP_TRY(hipGetLastError());
     return TW_OK;
 }
@@ -1788,19 +1761,9 @@ int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *
     // rounds, below ~2000 envs a second round would double the logic chain, which bounds the launch there).
     if (pg == 16 && (e->n_envs + 15) / 16 <= PIPE_WG_TARGET) pg = 8;
     const int grid = (e->n_envs + pg - 1) / pg;
-#define TW_PIPE_LAUNCH(VAR, PGV, LY) \
-    hipLaunchKernelGGL((tw_pipe_kernel<VAR, PGV, LY>), dim3(grid), dim3(64 * PWAVES), PIPE_LDS_BYTES, st, p)
-#define TW_PIPE_LAUNCH_PG(VAR, LY) do { \
-        if (pg == 16) TW_PIPE_LAUNCH(VAR, 16, LY); else if (pg == 8) TW_PIPE_LAUNCH(VAR, 8, LY); \
-        else if (pg == 4) TW_PIPE_LAUNCH(VAR, 4, LY); else TW_PIPE_LAUNCH(VAR, 2, LY); } while (0)
     const int layout = (flags & TW_F_MATRIX_CODE) ? 2 : (p.record ? 1 : 0);
-    if (e->variant == 4) {
-        if (layout == 2) TW_PIPE_LAUNCH_PG(4, 2); else if (layout == 1) TW_PIPE_LAUNCH_PG(4, 1); else TW_PIPE_LAUNCH_PG(4, 0);
-    } else {
-        if (layout == 2) TW_PIPE_LAUNCH_PG(6, 2); else if (layout == 1) TW_PIPE_LAUNCH_PG(6, 1); else TW_PIPE_LAUNCH_PG(6, 0);
-    }
-#undef TW_PIPE_LAUNCH_PG
-#undef TW_PIPE_LAUNCH
+    const KernelFn k = PIPE_KERNELS[12 * (e->variant == 6) + 4 * layout + log2i(pg) - 1];
+    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * PWAVES), PIPE_LDS_BYTES, st, p);
     HIP_TRY(hipGetLastError());
     p.only_if_flagged = 1;
     const int rc = launch_sequential(e, p, st);
@@ -1843,15 +1806,10 @@ int tw_create(tw_engine **out, int variant, int n_envs, int view_size, int devic
         e->fb_count = e->abnormal + 2;
         if (me != hipSuccess) { tw_destroy(e); return hip_fail(me); }
     }
-    {   // the pipelined kernel needs > 64 KB of dynamic LDS
-#define TW_PIPE_K(VAR, LY) reinterpret_cast<const void *>(&tw_pipe_kernel<VAR, 16, LY>), reinterpret_cast<const void *>(&tw_pipe_kernel<VAR, 8, LY>), \
-                           reinterpret_cast<const void *>(&tw_pipe_kernel<VAR, 4, LY>), reinterpret_cast<const void *>(&tw_pipe_kernel<VAR, 2, LY>)
-        const void *kernels[] = {TW_PIPE_K(4, 0), TW_PIPE_K(4, 1), TW_PIPE_K(4, 2), TW_PIPE_K(6, 0), TW_PIPE_K(6, 1), TW_PIPE_K(6, 2)};
-#undef TW_PIPE_K
-        for (const void *k : kernels)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS_BYTES) != hipSuccess)
-                e->pipeline = 0;
-    }
+    for (KernelFn k : PIPE_KERNELS)     // the pipelined kernel needs > 64 KB of dynamic LDS
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)PIPE_LDS_BYTES) != hipSuccess)
+            e->pipeline = 0;
     Params p = base_params(e);
     hipLaunchKernelGGL(tw_pipe_tables_kernel, dim3(1), dim3(64), 0, 0, e->pipe_tab, e->view);
     hipLaunchKernelGGL(tw_reset_kernel, dim3(n_envs), dim3(64), 0, 0, p, (const uint8_t *)nullptr, 0);

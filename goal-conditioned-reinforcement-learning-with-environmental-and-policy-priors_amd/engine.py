@@ -271,7 +271,8 @@ class TwoarmyEngine:
         lut = torch.tensor(MATRIX_CODE_VALUES, dtype=torch.float32, device=codes.device)
         return lut[codes.long()]
 
-    def _launch(self, fn, name, lead, T, actions, draws, out, flags):
+    def _out_args(self, lead, out, flags):
+        """(obs, obs_pitch, matrix, mat_pitch, pos, reward, terminated, truncated), flags: the output arguments of a launch."""
         V = self.view_size
         op, opitch = _pitched(out.get("obs"), lead, (V, V, 3), torch.uint8)
         mp, mpitch, flags = self._matrix_arg(out.get("matrix"), lead, flags)
@@ -279,9 +280,13 @@ class TwoarmyEngine:
                       ("truncated", torch.uint8)):
             t = out.get(k)
             assert t is None or (t.is_contiguous() and t.dtype == dt and tuple(t.shape[:len(lead)]) == lead), k
-        args = [self._h] + ([T] if T is not None else []) + [
-            _dense(actions, torch.int32), _ptr(draws), op, opitch, mp, mpitch, _ptr(out.get("pos")),
-            _ptr(out.get("reward")), _ptr(out.get("terminated")), _ptr(out.get("truncated")), flags, self._stream()]
+        return [op, opitch, mp, mpitch, _ptr(out.get("pos")), _ptr(out.get("reward")), _ptr(out.get("terminated")),
+                _ptr(out.get("truncated"))], flags
+
+    def _launch(self, fn, name, lead, T, actions, draws, out, flags):
+        outs, flags = self._out_args(lead, out, flags)
+        args = [self._h] + ([T] if T is not None else []) + [_dense(actions, torch.int32), _ptr(draws)] + outs + [
+            flags, self._stream()]
         _lib.check(fn(*args), name)
         return out
 
@@ -314,15 +319,10 @@ class TwoarmyEngine:
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""
         ms = C.c_float()
-        V = self.view_size
-        lead = (T, self.num_envs)
         flags = (TW_F_AUTORESET if autoreset else 0) | TW_F_POLICY_IDX
-        op, opitch = _pitched(out.get("obs"), lead, (V, V, 3), torch.uint8)
-        mp, mpitch, flags = self._matrix_arg(out.get("matrix"), lead, flags)
-        _lib.check(_lib.lib().tw_time_rollout(
-            self._h, T, _dense(actions, torch.int32), op, opitch, mp, mpitch,
-            _ptr(out.get("pos")), _ptr(out.get("reward")), _ptr(out.get("terminated")), _ptr(out.get("truncated")),
-            flags, iters, self._stream(), C.byref(ms)), "tw_time_rollout")
+        outs, flags = self._out_args((T, self.num_envs), out, flags)
+        _lib.check(_lib.lib().tw_time_rollout(self._h, T, _dense(actions, torch.int32), *outs, flags, iters,
+                                              self._stream(), C.byref(ms)), "tw_time_rollout")
         return ms.value
 
     # ------------------------------------------------------------------ state
