@@ -97,6 +97,10 @@ _SIGS.update({
     "ppo_decoder_frames": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "ppo_gather_stack_u8": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "ppo_age_scan": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "ppo_episode_scan": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ppo_episode_summary": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
+    "ppo_episode_summary_workspace": (C.c_int, [_i, _i]),
     "ppo_bias_relu_nhwc": (C.c_int, [_vp, _vp, _i64, _i, _vp]),
     "ppo_conv1_up4_bias_relu": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ppo_conv1_up4_bias_relu_c": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

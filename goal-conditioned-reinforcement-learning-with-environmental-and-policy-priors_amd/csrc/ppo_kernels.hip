@@ -586,6 +586,232 @@ __global__ void ppo_age_scan_kernel(const uint8_t *__restrict__ terminated, cons
     }
 }
 
+// ------------------------------------------------------------------ episode accounting
+// Per-episode return and length, carried across launches (train_ppo.py:124 `ep_reward += reward`, :136-141).  One lane
+// per env over coalesced rows; the float64 additions are one per step in step order, so the bits do not depend on how
+// a rollout is cut into launches.  The dependent chain is T adds per lane and costs nothing next to the loads, which
+// are issued EP_ROWS rows ahead of it: the rows of batch k + 1 are in flight while batch k is added up and stored.
+constexpr int EP_ROWS = 8;
+
+__global__ __launch_bounds__(64) void ppo_episode_scan_kernel(const float *__restrict__ reward,
+                                                              const uint8_t *__restrict__ terminated,
+                                                              const uint8_t *__restrict__ truncated, int T, int N,
+                                                              double *__restrict__ carry_return,
+                                                              int32_t *__restrict__ carry_length,
+                                                              double *__restrict__ ep_return,
+                                                              int32_t *__restrict__ ep_length) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;
+    double acc = carry_return[n];
+    int len = carry_length[n];
+    float r[EP_ROWS], rn[EP_ROWS];
+    uint32_t d[EP_ROWS], dn[EP_ROWS];
+#pragma unroll
+    for (int j = 0; j < EP_ROWS; ++j) {
+        const size_t i = (size_t)j * N + n;
+        r[j] = j < T ? reward[i] : 0.f;
+        d[j] = j < T ? (uint32_t)(terminated[i] | truncated[i]) : 0u;
+    }
+    for (int t0 = 0; t0 < T; t0 += EP_ROWS) {
+#pragma unroll
+        for (int j = 0; j < EP_ROWS; ++j) {                         // next batch: loads only, nothing waits on them yet
+            const int t = t0 + EP_ROWS + j;
+            const size_t i = (size_t)t * N + n;
+            rn[j] = t < T ? reward[i] : 0.f;
+            dn[j] = t < T ? (uint32_t)(terminated[i] | truncated[i]) : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < EP_ROWS; ++j) {
+            const int t = t0 + j;
+            if (t < T) {
+                const size_t i = (size_t)t * N + n;
+                acc += (double)r[j];
+                len += 1;
+                if (ep_return) ep_return[i] = acc;
+                if (ep_length) ep_length[i] = len;
+                if (d[j]) { acc = 0.0; len = 0; }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < EP_ROWS; ++j) { r[j] = rn[j]; d[j] = dn[j]; }
+    }
+    carry_return[n] = acc;
+    carry_length[n] = len;
+}
+
+// What one rollout's finished episodes looked like, and the reference's running score folded over them in row-major
+// (t, then n) order (train_ppo.py:140 `running_score = running_score * 0.99 + ep_reward * 0.01`).  A partial result is
+// EP_NV doubles (counts are integers far below 2^53, hence exact):
+//   0 a, 1 b        the fold of a run of steps as ONE affine map score -> score * a + b; a step that is not done is the
+//                   identity (1, 0); runs compose left to right: (a1, b1) then (a2, b2) = (a1 a2, b1 a2 + b2)
+//   2 episodes, 3 successes, 4 truncated-only, 5 sum return, 6 min return, 7 max return, 8 sum length, 9 max length
+//   10..16 action histogram, 17..22 reward histogram
+// Every thread walks a contiguous run of the row-major index range, lanes and waves are combined in index order, each
+// workgroup writes one partial, and one wavefront combines the partials in block order: a fixed grid and a fixed
+// order for a given (T, N), hence deterministic.
+constexpr int EP_NV = 24, EP_ACT = 10, EP_REW = 17, EP_MAX_ACTIONS = 7;
+constexpr int EP_BLOCK_ELEMS = 2048, EP_MAX_BLOCKS = 256;
+
+__device__ __forceinline__ void ep_identity(double (&v)[EP_NV]) {
+#pragma unroll
+    for (int k = 0; k < EP_NV; ++k) v[k] = 0.0;
+    v[0] = 1.0;
+    v[6] = (double)INFINITY;
+    v[7] = -(double)INFINITY;
+}
+
+// v <- v followed by w
+__device__ __forceinline__ void ep_combine(double (&v)[EP_NV], const double (&w)[EP_NV]) {
+    v[1] = v[1] * w[0] + w[1];
+    v[0] = v[0] * w[0];
+    v[6] = fmin(v[6], w[6]);
+    v[7] = fmax(v[7], w[7]);
+    v[9] = fmax(v[9], w[9]);
+#pragma unroll
+    for (int k = 2; k < EP_NV; ++k)
+        if (k != 6 && k != 7 && k != 9) v[k] += w[k];
+}
+
+// Ordered reduction over the 64 lanes of a wavefront: after step s a lane whose index is a multiple of 2s holds the
+// combination of lanes [lane, lane + 2s) in lane order; lane 0 ends with all 64 (the other lanes hold don't-cares).
+__device__ __forceinline__ void ep_wave_reduce(double (&v)[EP_NV]) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        double w[EP_NV];
+#pragma unroll
+        for (int k = 0; k < EP_NV; ++k) w[k] = __shfl_down(v[k], s, 64);
+        ep_combine(v, w);
+    }
+}
+
+__device__ __forceinline__ int ep_reward_bucket(float r) {
+    return r == -0.01f ? 0 : (r == -0.1f ? 1 : (r == -0.9f ? 2 : (r == 0.2f ? 3 : (r == 0.9f ? 4 : 5))));
+}
+
+__global__ __launch_bounds__(256) void ppo_episode_partial_kernel(const double *__restrict__ ep_return,
+                                                                  const int32_t *__restrict__ ep_length,
+                                                                  const uint8_t *__restrict__ terminated,
+                                                                  const uint8_t *__restrict__ truncated,
+                                                                  const float *__restrict__ reward,
+                                                                  const int32_t *__restrict__ action, int64_t M,
+                                                                  int64_t per_block, int per_thread, double keep,
+                                                                  double gain, double *__restrict__ ws) {
+    __shared__ double sh[4][EP_NV];
+    const int64_t block_lo = (int64_t)blockIdx.x * per_block;
+    const int64_t block_hi = block_lo + per_block < M ? block_lo + per_block : M;
+    int64_t lo = block_lo + (int64_t)threadIdx.x * per_thread;
+    int64_t hi = lo + per_thread;
+    if (hi > block_hi) hi = block_hi;
+    double a = 1.0, b = 0.0, sum_r = 0.0, min_r = (double)INFINITY, max_r = -(double)INFINITY;
+    long long sum_len = 0;
+    int episodes = 0, successes = 0, max_len = 0;
+    int ah[EP_MAX_ACTIONS], rh[6];
+#pragma unroll
+    for (int k = 0; k < EP_MAX_ACTIONS; ++k) ah[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rh[k] = 0;
+    for (int64_t i0 = lo; i0 < hi; i0 += EP_ROWS) {
+        float r[EP_ROWS];
+        uint32_t te[EP_ROWS], tr[EP_ROWS];
+        int ac[EP_ROWS];
+#pragma unroll
+        for (int j = 0; j < EP_ROWS; ++j) {                         // the batch's loads first, the fold after them
+            const int64_t i = i0 + j;
+            const bool in = i < hi;
+            r[j] = in ? reward[i] : 0.f;
+            te[j] = in ? (uint32_t)terminated[i] : 0u;
+            tr[j] = in ? (uint32_t)truncated[i] : 0u;
+            ac[j] = (in && action) ? action[i] : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < EP_ROWS; ++j) {
+            const int64_t i = i0 + j;
+            if (i < hi) {
+                const int bucket = ep_reward_bucket(r[j]);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) rh[k] += (bucket == k);
+#pragma unroll
+                for (int k = 0; k < EP_MAX_ACTIONS; ++k) ah[k] += (ac[j] == k);
+                if (te[j] | tr[j]) {                                 // an episode ends here: its return and length
+                    const double R = ep_return[i];
+                    const int L = ep_length[i];
+                    b = b * keep + R * gain;
+                    a = a * keep;
+                    episodes += 1;
+                    successes += te[j] ? 1 : 0;
+                    sum_r += R;
+                    min_r = fmin(min_r, R);
+                    max_r = fmax(max_r, R);
+                    sum_len += L;
+                    max_len = L > max_len ? L : max_len;
+                }
+            }
+        }
+    }
+    double v[EP_NV];
+    ep_identity(v);
+    v[0] = a; v[1] = b;
+    v[2] = (double)episodes; v[3] = (double)successes; v[4] = (double)(episodes - successes);
+    v[5] = sum_r; v[6] = min_r; v[7] = max_r; v[8] = (double)sum_len; v[9] = (double)max_len;
+#pragma unroll
+    for (int k = 0; k < EP_MAX_ACTIONS; ++k) v[EP_ACT + k] = (double)ah[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[EP_REW + k] = (double)rh[k];
+    ep_wave_reduce(v);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < EP_NV; ++k) sh[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {                                // waves in index order
+            double o[EP_NV];
+#pragma unroll
+            for (int k = 0; k < EP_NV; ++k) o[k] = sh[w][k];
+            ep_combine(v, o);
+        }
+#pragma unroll
+        for (int k = 0; k < EP_NV; ++k) ws[(size_t)blockIdx.x * EP_NV + k] = v[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void ppo_episode_finalize_kernel(const double *__restrict__ ws, int nblocks, int A,
+                                                                  double *__restrict__ score,
+                                                                  double *__restrict__ summary,
+                                                                  int64_t *__restrict__ action_hist,
+                                                                  int64_t *__restrict__ reward_hist) {
+    const int lane = threadIdx.x;
+    const int per_lane = (nblocks + 63) / 64;                        // nblocks <= EP_MAX_BLOCKS: at most 4 each
+    double v[EP_NV];
+    ep_identity(v);
+    for (int j = 0; j < per_lane; ++j) {                             // lane l: blocks [l * per_lane, (l + 1) * per_lane)
+        const int blk = lane * per_lane + j;
+        if (blk < nblocks) {
+            double o[EP_NV];
+#pragma unroll
+            for (int k = 0; k < EP_NV; ++k) o[k] = ws[(size_t)blk * EP_NV + k];
+            ep_combine(v, o);
+        }
+    }
+    ep_wave_reduce(v);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) summary[k] = v[2 + k];
+#pragma unroll
+        for (int k = 0; k < EP_MAX_ACTIONS; ++k)
+            if (action_hist && k < A) action_hist[k] = (int64_t)v[EP_ACT + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) reward_hist[k] = (int64_t)v[EP_REW + k];
+        if (score && v[2] > 0.0) *score = *score * v[0] + v[1];      // no finished episode: not written at all
+    }
+}
+
+__host__ int ep_summary_blocks(int64_t M) {
+    const int64_t want = (M + EP_BLOCK_ELEMS - 1) / EP_BLOCK_ELEMS;
+    return (int)(want < EP_MAX_BLOCKS ? want : EP_MAX_BLOCKS);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // World-model decoder, inference only (Net_Decoder, all_net.py:100-137): latent float[64][4][4] per frame ->
 //   ConvTranspose2d(64->16, k2, s2) + ReLU  -> a1[8][8][16]
@@ -851,6 +1077,40 @@ int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int3
     if (!terminated || !truncated || !age0 || !age || T <= 0 || N <= 0) return TW_E_ARG;
     hipLaunchKernelGGL(ppo_age_scan_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, terminated,
                        truncated, age0, T, N, age);
+    return check_launch();
+}
+
+int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
+                     double *carry_return, int32_t *carry_length, double *ep_return, int32_t *ep_length, void *stream) {
+    if (!reward || !terminated || !truncated || !carry_return || !carry_length || T <= 0 || N <= 0) return TW_E_ARG;
+    hipLaunchKernelGGL(ppo_episode_scan_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, reward, terminated,
+                       truncated, T, N, carry_return, carry_length, ep_return, ep_length);
+    return check_launch();
+}
+
+int ppo_episode_summary_workspace(int T, int N) {
+    if (T <= 0 || N <= 0) return TW_E_ARG;
+    return ep_summary_blocks((int64_t)T * N) * EP_NV;
+}
+
+int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const uint8_t *terminated,
+                        const uint8_t *truncated, const float *reward, const int32_t *action, int A, int T, int N,
+                        double keep, double gain, double *score, double *summary, int64_t *action_hist,
+                        int64_t *reward_hist, double *workspace, void *stream) {
+    if (!ep_return || !ep_length || !terminated || !truncated || !reward || !summary || !reward_hist || !workspace ||
+        T <= 0 || N <= 0)
+        return TW_E_ARG;
+    if (A != 2 && A != 3 && A != 4 && A != 5 && A != 7) return TW_E_ARG;      // the action counts ppo_sample accepts
+    const int64_t M = (int64_t)T * N;
+    if (M > ((int64_t)1 << 40)) return TW_E_ARG;                              // per-thread run length stays an int
+    const int nblocks = ep_summary_blocks(M);
+    const int64_t per_block = (M + nblocks - 1) / nblocks;
+    const int per_thread = (int)((per_block + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ppo_episode_partial_kernel, dim3(nblocks), dim3(256), 0, st, ep_return, ep_length, terminated,
+                       truncated, reward, action, M, per_block, per_thread, keep, gain, workspace);
+    hipLaunchKernelGGL(ppo_episode_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, nblocks, A, score, summary,
+                       action_hist, reward_hist);
     return check_launch();
 }
 

@@ -110,6 +110,56 @@ def age_scan(terminated, truncated, age0):
     return age
 
 
+def episode_scan(reward, terminated, truncated, carry_return, carry_length, want_steps=True, out=None):
+    """Per-episode return and length carried across calls (ppo_episode_scan, include/twoarmy_ppo.h; reference
+    soa/train_ppo.py:124 `ep_reward += reward`).  reward / terminated / truncated [T,N]; carry_return f64[N] and
+    carry_length i32[N] are updated IN PLACE.  Returns (ep_return f64[T,N], ep_length i32[T,N]), or (None, None) with
+    want_steps=False; out = (ep_return, ep_length) reuses buffers of the caller."""
+    T, N = reward.shape
+    assert terminated.shape == (T, N) and truncated.shape == (T, N) and carry_return.shape == (N,) and carry_length.shape == (N,)
+    ep_return = ep_length = None
+    if out is not None:
+        ep_return, ep_length = out
+        assert ep_return.shape == (T, N) and ep_length.shape == (T, N)
+    elif want_steps:
+        ep_return = torch.empty((T, N), dtype=torch.float64, device=reward.device)
+        ep_length = torch.empty((T, N), dtype=torch.int32, device=reward.device)
+    _lib.check(_lib.lib().ppo_episode_scan(_p(reward, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
+                                           T, N, _p(carry_return, torch.float64), _p(carry_length, torch.int32),
+                                           _p(ep_return, torch.float64), _p(ep_length, torch.int32), _stream(reward)),
+               "ppo_episode_scan")
+    return ep_return, ep_length
+
+
+def episode_summary_workspace(T, N):
+    n = _lib.lib().ppo_episode_summary_workspace(int(T), int(N))
+    _lib.check(min(n, 0), "ppo_episode_summary_workspace")
+    return n
+
+
+def episode_summary(ep_return, ep_length, terminated, truncated, reward, action=None, n_actions=5, keep=0.99, gain=0.01,
+                    score=None, summary=None, action_hist=None, reward_hist=None, workspace=None):
+    """What the episodes that finished in this rollout looked like, plus the reference's running score folded over them
+    in row-major order (ppo_episode_summary, include/twoarmy_ppo.h; soa/train_ppo.py:140).  score f64[1] is updated IN
+    PLACE (None: no fold).  Returns (summary f64[8], action_hist i64[A], reward_hist i64[6]); no host synchronisation."""
+    T, N = reward.shape
+    dev = reward.device
+    summary = torch.empty(8, dtype=torch.float64, device=dev) if summary is None else summary
+    action_hist = torch.empty(n_actions, dtype=torch.int64, device=dev) if action_hist is None else action_hist
+    reward_hist = torch.empty(6, dtype=torch.int64, device=dev) if reward_hist is None else reward_hist
+    need = episode_summary_workspace(T, N)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=dev)
+    assert workspace.numel() >= need and summary.numel() == 8 and action_hist.numel() == n_actions and reward_hist.numel() == 6
+    assert ep_return.shape == (T, N) and ep_length.shape == (T, N) and (action is None or action.shape == (T, N))
+    _lib.check(_lib.lib().ppo_episode_summary(
+        _p(ep_return, torch.float64), _p(ep_length, torch.int32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
+        _p(reward, torch.float32), _p(action, torch.int32), int(n_actions), T, N, float(keep), float(gain),
+        _p(score, torch.float64), _p(summary, torch.float64), _p(action_hist, torch.int64), _p(reward_hist, torch.int64),
+        _p(workspace, torch.float64), _stream(reward)), "ppo_episode_summary")
+    return summary, action_hist, reward_hist
+
+
 def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, env_id0=0, step0=0, max_goals=4, skip=0):
     """Hindsight relabelling of a time-major rollout (ppo_her_relabel_window, include/twoarmy_ppo.h; reference
     Buffer_gridworld.her_func, soa/env_buffer.py:101-143; skip = 4: pre_her_func / pre_f_her_func on the 9-frame window

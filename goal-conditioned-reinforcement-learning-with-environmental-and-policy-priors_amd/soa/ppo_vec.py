@@ -94,6 +94,7 @@ class VecPPOTrainer:
         self.max_steps = int(getattr(engine, "max_steps", 50))
         self._hist = collections.deque(maxlen=max(1, -(-(self.max_steps - 1) // self.T)))
         self.her_seed = int(getattr(engine, "seed", 9981))
+        self.episodes = None                  # EpisodeTracker, made by the first account_episodes()
         self.env_steps = 0
         self.episodes_done = 0
         self.return_sum = 0.0
@@ -406,6 +407,23 @@ class VecPPOTrainer:
         mean_ret = float(self.reward.sum()) / E
         k = 0.99 ** E
         return score * k + mean_ret * (1.0 - k)
+
+    def account_episodes(self):
+        """Account the rollout just collected (call after collect(), before carry_over()): per-episode returns and
+        lengths carried across rollout boundaries, the summary of the episodes that ended in it, and the reference's
+        running score folded over them one by one (train_ppo.py:140).  Two launches, no host synchronisation."""
+        if self.episodes is None:
+            from ..episode_stats import EpisodeTracker
+            self.episodes = EpisodeTracker(self.N, self.device, n_actions=5)
+        self.episodes.account(self.reward, self.term, self.trunc, self.action)
+
+    def episode_stats(self):
+        """EpisodeTracker.read() of the last accounted rollout plus mean_neg_logp = -mean log pi(a|s) of its actions."""
+        if self.episodes is None:
+            raise RuntimeError("episode_stats() before account_episodes()")
+        out = self.episodes.read()
+        out["mean_neg_logp"] = float(-self.logp.mean())
+        return out
 
     def stats(self):
         done = (self.term | self.trunc) != 0

@@ -55,9 +55,22 @@ def build_parser():
     p.add_argument("--k_epochs_orientation", type=int, default=50, help="SoA: epochs of the orientation head per update")
     p.add_argument("--gae_lambda", type=float, default=0.0)
     p.add_argument("--normalize_adv", action="store_true")
+    p.add_argument("--score", default="rollout", choices=["rollout", "episode"],
+                   help="what drives the HER switch and the logged score: rollout = one EMA step per rollout with the "
+                        "rollout's reward sum over its finished episodes; episode = the reference's fold, one step per "
+                        "finished episode with that episode's return (train_ppo.py:140), kept on the device")
     p.add_argument("--predictor_file", default=None, help="checkpoint with model_encoder / model_decoder / "
                    "model_predictor (train_ppo_predictor.py:38,81-85); random-init world model when absent")
     return p
+
+
+def episode_fields(es):
+    """Tail of the log line: what the rollout's finished episodes looked like (VecPPOTrainer.episode_stats())."""
+    def f(x):
+        return "-" if x is None or x in (float("inf"), float("-inf")) else "%.4f" % x
+    return " ep_return mean/min/max %s/%s/%s ep_len mean %s actions [%s] rewards [%s]" % (
+        f(es["mean_return"]), f(es["min_return"]), f(es["max_return"]), f(es["mean_length"]),
+        " ".join(str(c) for c in es["action_hist"]), " ".join(str(c) for c in es["reward_hist"]))
 
 
 def main(argv=None, predictor=False, soa=False):
@@ -122,7 +135,13 @@ def main(argv=None, predictor=False, soa=False):
         her = trainer.her_switch(her, score)                  # train_ppo.py:128-131 of the reference
         if her and agent.gae_lambda == 0.0:
             trainer.relabel()
-        score = trainer.running_score(score)
+        trainer.account_episodes()
+        es = None
+        if args.score == "episode":
+            es = trainer.episode_stats()
+            score = es["score"]
+        else:
+            score = trainer.running_score(score)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         n_her = 0 if trainer.her is None else int(trainer.her["t"].numel())
@@ -130,12 +149,13 @@ def main(argv=None, predictor=False, soa=False):
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         st = trainer.stats()
+        es = trainer.episode_stats() if es is None else es
         trainer.carry_over()
         if rank == 0:
             print("update %d: rollout %.3fs (%.0f env-steps/s/rank) update %.3fs action_loss %.5f value_loss %.5f "
                   "episodes %d successes %d mean_r %.4f her_records %d score %.4f" % (u, t1 - t0, trainer.T * trainer.N / (t1 - t0), t2 - t1,
                                                             float(la), float(lv), st["episodes"], st["successes"],
-                                                            st["mean_reward"], n_her, score), flush=True)
+                                                            st["mean_reward"], n_her, score) + episode_fields(es), flush=True)
     engine.close()
     return trainer
 

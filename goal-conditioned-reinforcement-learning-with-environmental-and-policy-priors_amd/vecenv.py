@@ -10,6 +10,8 @@ tensor + info["_final_observation"] mask, no host sync).  `policy_actions=True` 
 policy's 5 indices (4 -> done) like Env_transact.env_action (reference soa/env_buffer.py:364-376).
 Extra per-step tensors the reference computes in Python are fused into the same launch:
 `env.state_matrix` [N,289] (matrix_env) and `env.agent_yx` [N,2] (data_env).
+`record_episode_statistics=True` adds info["episode"] = {"r": float64 [N], "l": int32 [N]} and the mask
+info["_episode"] like gym.vector's RecordEpisodeStatistics, accounted on the device (episode_stats.EpisodeTracker).
 """
 import torch
 
@@ -20,7 +22,7 @@ _IDS = {"MiniGrid-twoarmy-17x17-v4": 4, "MiniGrid-twoarmy-17x17-v6": 6, "v4": 4,
 
 class TwoarmyVecEnv:
     def __init__(self, env_id="MiniGrid-twoarmy-17x17-v6", num_envs=4096, agent_view_size=17, device=None,
-                 seed=9981, env_id0=0, policy_actions=True, autoreset=True):
+                 seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False):
         self.variant = _IDS[env_id]
         self.num_envs = int(num_envs)
         self.view_size = agent_view_size
@@ -34,9 +36,15 @@ class TwoarmyVecEnv:
         self.goal_yx = torch.tensor([2.0, 14.0], device=self.device).expand(self.num_envs, 2)
         self.single_observation_shape = (agent_view_size, agent_view_size, 3)
         self.single_action_n = 5 if policy_actions else 7
+        self.episode_tracker = None
+        if record_episode_statistics:
+            from .episode_stats import EpisodeTracker
+            self.episode_tracker = EpisodeTracker(self.num_envs, self.device, n_actions=self.single_action_n)
 
     def reset(self):
         self.engine.reset(obs=self._out["obs"])
+        if self.episode_tracker is not None:
+            self.episode_tracker.reset()
         return self._out["obs"]
 
     def step(self, actions):
@@ -50,6 +58,13 @@ class TwoarmyVecEnv:
             info["final_observation"] = obs
             info["_final_observation"] = done
             obs = torch.where(done.view(-1, 1, 1, 1), self._init_obs, obs)
+        if self.episode_tracker is not None:
+            # gym.vector's RecordEpisodeStatistics: return / length of the episodes ending at this step (dense tensors,
+            # valid where the mask is set; overwritten by the next step, like final_observation)
+            tr = self.episode_tracker
+            tr.account(o["reward"], o["terminated"], o["truncated"], a)
+            info["episode"] = {"r": tr.ep_return[0], "l": tr.ep_length[0]}
+            info["_episode"] = done
         return obs, o["reward"], o["terminated"].bool(), o["truncated"].bool(), info
 
     @property

@@ -8,6 +8,7 @@
  *                  PPO.py:115      (commented) adv = (adv - mean) / (std + 1e-8) -> ppo_adv_norm
  *                  PPO.py:124-133  ratio-clip surrogate + entropy, SmoothL1      -> ppo_loss_fwd_bwd
  *   train_ppo.py:116-123  5-frame stack shift + store                            -> ppo_gather_stack
+ *   train_ppo.py:124,136-141  ep_reward += reward; running_score fold per episode  -> ppo_episode_scan / _summary
  * GAE(gamma, lambda) with done masks has no reference counterpart: it collapses to the
  * reference formula at lambda = 0, use_done_mask = 0 and is otherwise pinned against a float64 statement of the
  * formula (tests/test_ppo_kernels_edges_gpu.py).
@@ -94,6 +95,38 @@ int ppo_gather_stack_u8(const uint8_t *frames, int frame_pitch, const float *pos
  *   done uint8[T][N] (terminated | truncated), age0 int32[N], age int32[T+1][N] */
 int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0, int T, int N,
                  int32_t *age, void *stream);
+
+/* Episode accounting on the device (replaces the host bookkeeping of train_ppo.py:124 `ep_reward += reward` and
+ * :136-141, where the finished episode's return is folded into running_score and reset).
+ *
+ * ppo_episode_scan: for every env n, in step order: acc = carry_return[n], len = carry_length[n]; for t = 0 .. T-1:
+ *   acc += (double)reward[t][n]; len += 1; ep_return[t][n] = acc; ep_length[t][n] = len; and where
+ *   terminated | truncated is set, acc = 0, len = 0 after the write.  The carries are written back at the end, so at
+ * a done step ep_return / ep_length are the return and length of the episode that ends there, wherever it began.
+ * The additions are float64, one per step, in step order: the result does not depend on how a rollout is cut into
+ * launches (T = 128 once and 128 launches of T = 1 give the same bits).
+ *   reward float[T][N]; terminated, truncated uint8[T][N]; carry_return double[N] in/out; carry_length int32[N] in/out;
+ *   ep_return double[T][N] | NULL; ep_length int32[T][N] | NULL */
+int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
+                     double *carry_return, int32_t *carry_length, double *ep_return, int32_t *ep_length, void *stream);
+
+/* What the episodes that finished in one rollout looked like, and the reference's running score over them:
+ *   summary double[8] = {episodes, successes (terminated), truncated-only, sum of returns, min return, max return,
+ *       sum of lengths, max length} over the done steps; with no finished episode min = +inf, max = -inf, the rest 0
+ *   action_hist int64[A] | NULL: steps with action == a (A in {2, 3, 4, 5, 7} as for ppo_sample; action == NULL: zeros)
+ *   reward_hist int64[6]: steps whose reward equals, as float32, -0.01, -0.1, -0.9, 0.2, 0.9; last bucket: anything else
+ *   score double[1] in/out | NULL: for every done step in row-major (t, then n) order
+ *       score = score * keep + ep_return[t][n] * gain        (train_ppo.py:140 with keep = 0.99, gain = 0.01;
+ *       the episodes of one time step are taken in ascending env index); not written when no episode finished.
+ * Deterministic: a grid fixed by (T, N), per-block partial results in `workspace`
+ * (ppo_episode_summary_workspace(T, N) doubles), one ordered final pass.  Counts, min and max are exact; the sums
+ * and the fold are evaluated as a tree in row-major order, so they agree with a sequential evaluation up to rounding.
+ *   ep_return double[T][N], ep_length int32[T][N] (ppo_episode_scan's outputs); action int32[T][N] | NULL */
+int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const uint8_t *terminated,
+                        const uint8_t *truncated, const float *reward, const int32_t *action, int A, int T, int N,
+                        double keep, double gain, double *score, double *summary, int64_t *action_hist,
+                        int64_t *reward_hist, double *workspace, void *stream);
+int ppo_episode_summary_workspace(int T, int N);
 
 /* Hindsight experience replay over one time-major rollout: replaces Buffer_gridworld.her_func
  * (soa/env_buffer.py:101-143, called from soa/train_ppo.py:128-134 at every episode end).  For every episode

@@ -68,6 +68,20 @@ term = (torch.rand(T, N, generator=g) < 0.01).to(torch.uint8).to(dev)
 trunc = (torch.rand(T, N, generator=g) < 0.02).to(torch.uint8).to(dev)
 age0 = torch.zeros(N, dtype=torch.int32, device=dev)
 report("ppo_age_scan", T * N * (1 + 1 + 4), timed(lambda: ppo_ops.age_scan(term, trunc, age0)))
+rw5 = torch.tensor([-0.01, -0.1, -0.9, 0.2, 0.9])[torch.randint(0, 5, (T, N), generator=g)].to(dev)
+act_tn = torch.randint(0, A, (T, N), generator=g, dtype=torch.int32).to(dev)
+carry_r, carry_l = torch.zeros(N, dtype=torch.float64, device=dev), torch.zeros(N, dtype=torch.int32, device=dev)
+ep_r, ep_l = ppo_ops.episode_scan(rw5, term, trunc, carry_r, carry_l)
+report("ppo_episode_scan (per-step outputs)", T * N * (4 + 1 + 1 + 8 + 4),
+       timed(lambda: ppo_ops.episode_scan(rw5, term, trunc, carry_r, carry_l, out=(ep_r, ep_l))), "latency-bound: one lane per env")
+ep_score = torch.zeros(1, dtype=torch.float64, device=dev)
+ep_out = (torch.empty(8, dtype=torch.float64, device=dev), torch.empty(A, dtype=torch.int64, device=dev),
+          torch.empty(6, dtype=torch.int64, device=dev),
+          torch.empty(ppo_ops.episode_summary_workspace(T, N), dtype=torch.float64, device=dev))
+n_done = int(((term | trunc) != 0).sum())
+report("ppo_episode_summary (partials + ordered final pass)", T * N * (4 + 1 + 1 + 4) + n_done * 12,
+       timed(lambda: ppo_ops.episode_summary(ep_r, ep_l, term, trunc, rw5, act_tn, A, 0.99, 0.01, ep_score, *ep_out)),
+       "two launches")
 p2 = torch.randint(1, 16, (T, N, 2), generator=g).float().to(dev)
 rw = torch.randn(T, N, generator=g).to(dev)
 report("ppo_her_relabel (count + scan + emit, one host sync)", T * N * (8 + 1 + 1 + 4) * 2,
