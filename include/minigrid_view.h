@@ -34,7 +34,12 @@ extern "C" {
  * first V*V*3 bytes of each row (image_pitch 0 = dense); vis_mask: uint8[N][V*V] indexed [i][j] (nullable).
  * The planes are read as 4-byte-aligned words: the words that hold the first and the last byte of a plane array are
  * read whole, i.e. up to 3 bytes before its start / after its end inside the same aligned word (always inside the
- * caller's allocation when that starts and ends on 4-byte boundaries, as hipMalloc / torch allocations do). */
+ * caller's allocation when that starts and ends on 4-byte boundaries, as hipMalloc / torch allocations do).  Those
+ * neighbour bytes never reach the image.  image and image_pitch need no alignment; only the first V*V*3 bytes of each
+ * image row are written.  Bad arguments (view_size outside 1..MG_MAX_VIEW, a size <= 0, 0 < image_pitch < V*V*3, a
+ * NULL non-nullable pointer) return TW_E_ARG before anything is launched.
+ * Pinned by tests/test_minigrid_view_edges_gpu.py: planes 1, 2 and 3 bytes off a word boundary at both ends inside
+ * 0xFF-filled buffers, image bases 0..3 with six pitches inside 0xA5-filled buffers, every nullable pointer NULL. */
 int mg_gen_obs(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width, int height,
                const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_dir, const uint8_t *carrying,
                int view_size, int see_through_walls, uint8_t *image, int image_pitch, uint8_t *vis_mask, void *stream);
@@ -49,7 +54,9 @@ int mg_gen_obs(const uint8_t *type, const uint8_t *colour, const uint8_t *state,
  * unreachable in the reference).
  *   error int32[N] (nullable): 0 ok, 1 AttributeError (action outside {0,1,2,3,6}), 2 AssertionError (Grid.get out
  *   of range); on an error the env keeps the mutation the reference had made (step_count) and reports reward 0,
- *   terminated = truncated = 0.  agent_x / agent_y / step_count are updated in place. */
+ *   terminated = truncated = 0.  agent_x / agent_y / step_count are updated in place.  max_steps <= 0, a size <= 0
+ *   or a NULL non-nullable pointer return TW_E_ARG before anything is launched.  The reward is pinned bit for bit
+ *   against the Python expression for every 0 <= step_count < max_steps <= 200 (same test file). */
 int mg_step(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height, const int32_t *action,
             int32_t *agent_x, int32_t *agent_y, const int32_t *agent_dir, int32_t *step_count, int max_steps,
             double *reward, uint8_t *terminated, uint8_t *truncated, int32_t *error, void *stream);

@@ -5,7 +5,7 @@ TEST INFRASTRUCTURE ONLY.  Imports /root/reference through oracle/ref_harness.py
 classes with scripted / seeded inputs and writes small .npz fixtures into tests/golden/.
 Only data (inputs + the reference's outputs) is written; no reference source text is stored.
 
-  python oracle/gen_golden.py [traces] [views] [her] [window_her] [ppo] [predictor] [predictor_update] [occlusion] [mgstep] [soa] [pretrain]     (default: all)
+  python oracle/gen_golden.py [traces] [views] [her] [window_her] [ppo] [predictor] [predictor_update] [occlusion] [occlusion_wide] [mgstep] [soa] [pretrain]     (default: all)
 
 The random draws of Twoarmy (np.random.choice calls in twoarmy_v{4,6}.py) are replaced by the
 engine's counter-based Philox words (oracle/philox.py) through ref_harness.patched_choice, so
@@ -880,6 +880,75 @@ def gen_occlusion():
     print("occlusion: %d cases -> %s (%.1f KB)" % (ncase, path_out, os.path.getsize(path_out) / 1024))
 
 
+def gen_occlusion_wide():
+    """The recipe of gen_occlusion at the view sizes it leaves out: 13, 15, 17 (the compiled sizes Twoarmy uses) and
+    21, 31 (runtime-V kernel), all four directions at every size, on worlds larger (40x40, 17x17) and much smaller
+    (3x3, 1x9) than the view, doors in all three states, with and without a carried object.  Grid() refuses worlds
+    narrower than 3 cells, so the 1x9 world is a Grid whose width / cell list are set after construction; everything
+    that is recorded (get_view_exts, slice, rotate_left, process_vis, encode) runs the reference's code unchanged."""
+    rh.setup()
+    import gym_minigrid.minigrid as mg
+    rs = np.random.RandomState(131517)
+    env = rh.make_env("v6").unwrapped
+    colors = list(mg.COLOR_TO_IDX.keys())
+
+    def rand_obj():
+        k = rs.randint(0, 100)
+        c = colors[rs.randint(len(colors))]
+        if k < 40:
+            return None
+        if k < 58:
+            return mg.Wall()
+        if k < 70:
+            st = rs.randint(3)
+            return mg.Door(c, is_open=(st == 0), is_locked=(st == 2))
+        if k < 76:
+            return mg.Key(c)
+        if k < 82:
+            return mg.Ball(c)
+        if k < 88:
+            return mg.Box(c)
+        if k < 92:
+            return mg.Goal()
+        if k < 96:
+            return mg.Lava()
+        return mg.Floor(c)
+
+    out = {}
+    ncase = 0
+    worlds = [(17, 17), (40, 40), (3, 3), (1, 9), (9, 13), (25, 6), (3, 3), (1, 9)]
+    for vi, V in enumerate([13, 15, 17, 21, 31]):
+        for k, (W, H) in enumerate(worlds):
+            grid = mg.Grid(max(W, 3), max(H, 3))
+            grid.width, grid.height, grid.grid = W, H, [None] * (W * H)
+            for j in range(H):
+                for i in range(W):
+                    grid.set(i, j, rand_obj())
+            env.grid = grid
+            env.width, env.height = W, H
+            ax, ay = int(rs.randint(W)), int(rs.randint(H))
+            env.agent_pos = (ax, ay)
+            env.agent_dir = (k + k // 4 + vi) % 4                     # k = 0..3: every direction at every view size
+            env.carrying = [mg.Key("blue"), mg.Ball("red"), mg.Box("yellow")][rs.randint(3)] if (k + vi) % 2 else None
+            env.agent_view_size = V
+            enc = grid.encode().astype(np.uint8)                      # [W][H][3] world planes
+            for st in (0, 1):
+                env.see_through_walls = bool(st)
+                obs = env.gen_obs()
+                _, vis = env.gen_obs_grid()
+                out["c%03d_img%d" % (ncase, st)] = obs["image"].astype(np.uint8)
+                out["c%03d_vis%d" % (ncase, st)] = vis.astype(np.uint8)
+            out["c%03d_grid" % ncase] = enc
+            carry = env.carrying.encode() if env.carrying is not None else (0, 0, 0)
+            out["c%03d_meta" % ncase] = np.array([W, H, ax, ay, env.agent_dir, V, int(env.carrying is not None)]
+                                                 + list(carry), np.int32)
+            ncase += 1
+    out["n_cases"] = np.int32(ncase)
+    path_out = os.path.join(GOLD, "occlusion_wide.npz")
+    np.savez_compressed(path_out, **out)
+    print("occlusion_wide: %d cases -> %s (%.1f KB)" % (ncase, path_out, os.path.getsize(path_out) / 1024))
+
+
 def gen_mgstep():
     """MiniGridEnv.step (the base-class transition, minigrid.py:1333-1441) on random worlds: absolute moves with the
     can_overlap rules of every object class, goal termination with _reward() (:1061), truncation, and the
@@ -936,7 +1005,7 @@ def gen_mgstep():
     print("mgstep: %d cases -> %s (%.1f KB)" % (ncase, path_out, os.path.getsize(path_out) / 1024))
 
 
-STAGES = {"traces": gen_traces, "views": gen_views, "ppo": gen_ppo, "her": gen_her, "window_her": gen_window_her, "predictor": gen_predictor, "predictor_update": gen_predictor_update, "occlusion": gen_occlusion, "mgstep": gen_mgstep, "soa": gen_soa, "pretrain": gen_pretrain}
+STAGES = {"traces": gen_traces, "views": gen_views, "ppo": gen_ppo, "her": gen_her, "window_her": gen_window_her, "predictor": gen_predictor, "predictor_update": gen_predictor_update, "occlusion": gen_occlusion, "occlusion_wide": gen_occlusion_wide, "mgstep": gen_mgstep, "soa": gen_soa, "pretrain": gen_pretrain}
 
 
 def main(argv):

@@ -5,8 +5,8 @@ import numpy as np
 import minigrid_view_oracle as mvo
 
 
-def load_cases(golden_dir):
-    z = np.load(golden_dir + "/occlusion.npz")
+def load_cases(golden_dir, name="occlusion.npz"):
+    z = np.load(golden_dir + "/" + name)
     for ci in range(int(z["n_cases"])):
         W, H, ax, ay, d, V, has_carry, ct, cc, cs = (int(v) for v in z["c%03d_meta" % ci])
         yield dict(ci=ci, W=W, H=H, ax=ax, ay=ay, dir=d, V=V, carrying=(ct, cc, cs) if has_carry else None,
@@ -25,6 +25,33 @@ def test_view_oracle_matches_reference(golden_dir):
         occluded += int((c["vis"][0] == 0).sum())
         n += 1
     assert n == 30 and occluded > 100          # the occlusion path is really exercised
+
+
+def test_view_oracle_matches_reference_wide(golden_dir):
+    """The same pin at the sizes occlusion.npz leaves out (tests/golden/occlusion_wide.npz, gen_golden.py stage
+    occlusion_wide): V = 13, 15, 17 (compiled kernels) and 21, 31 (runtime-V kernel), every direction at every size,
+    worlds larger and much smaller than the view (40x40, 3x3, 1x9), doors in all three states, with and without a
+    carried object -- and occluded cells at each of the five sizes."""
+    n, occluded, dirs, worlds, doors, carried = 0, {}, {}, set(), set(), set()
+    for c in load_cases(golden_dir, "occlusion_wide.npz"):
+        assert c["grid"].shape == (c["W"], c["H"], 3)
+        for st in (0, 1):
+            img, vis = mvo.gen_obs(c["grid"], c["ax"], c["ay"], c["dir"], c["V"], bool(st), c["carrying"])
+            assert img.shape == (c["V"], c["V"], 3)
+            assert np.array_equal(img, c["img"][st]), (c["ci"], st)
+            assert np.array_equal(vis.astype(np.uint8), c["vis"][st]), (c["ci"], st)
+        assert c["vis"][1].all() and c["vis"][0][c["V"] // 2, c["V"] - 1] == 1
+        occluded[c["V"]] = occluded.get(c["V"], 0) + int((c["vis"][0] == 0).sum())
+        dirs.setdefault(c["V"], set()).add(c["dir"])
+        worlds.add((c["W"], c["H"]))
+        seen = c["img"][1].reshape(-1, 3)                                   # the see-through image shows every window cell
+        doors |= {int(s) for t, _, s in seen if t == mvo.DOOR}
+        carried.add(c["carrying"] is not None)
+        n += 1
+    assert n == 40 and sorted(occluded) == [13, 15, 17, 21, 31]
+    assert all(occluded[V] > V * V for V in occluded), occluded            # more than one whole view of hidden cells per size
+    assert all(dirs[V] == {0, 1, 2, 3} for V in dirs)
+    assert {(3, 3), (1, 9), (40, 40)} <= worlds and doors == {0, 1, 2} and carried == {False, True}
 
 
 def load_step_cases(golden_dir):
