@@ -89,6 +89,13 @@ _SIGS.update({
     "ppo_gather_stack": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mg_gen_obs": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "mg_step": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    # include/minigrid_render.h
+    "mg_render_tile_index": (C.c_int, [_i, _i, _i, _i, _i]),
+    "mg_render_atlas_bytes": (_i64, [_i]),
+    "mg_render_constants": (C.c_int, [C.POINTER(C.c_double)]),
+    "mg_render_build_atlas": (C.c_int, [_i, _vp, _vp]),
+    "mg_render": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp]),
+    "mg_highlight_mask": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "ppo_her_relabel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
     "ppo_her_relabel_window": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _i, _vp,

@@ -316,6 +316,32 @@ class TwoarmyEngine:
         _lib.check(_lib.lib().tw_gen_obs(self._h, V, _ptr(obs), 0, self._stream()), "tw_gen_obs")
         return obs
 
+    def render(self, env_index=None, tile_size=17, highlight=False, out=None):
+        """RGB frames of MiniGridEnv.get_full_render, uint8[n, 17*ts, 17*ts, 3], drawn on the device straight from the
+        engine's planes and records (tw_state_ptrs) on the current stream: no host copy of the state.  env_index:
+        int32 device tensor of the envs to draw (None = all); highlight: brighten the agent's view_size x view_size
+        view as the reference's `highlight=True` does (Twoarmy sees through walls: the whole view)."""
+        from .minigrid_render import TileAtlas
+        lib = _lib.lib()
+        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(lib.tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
+        ts, N, S = int(tile_size), self.num_envs, 17
+        n = N if env_index is None else int(env_index.shape[0])
+        frame = out if out is not None else torch.empty((n, S * ts, S * ts, 3), dtype=torch.uint8, device=self.device)
+        assert frame.shape == (n, S * ts, S * ts, 3) and frame.dtype == torch.uint8 and frame.is_contiguous()
+        atlas = TileAtlas.get(ts, self.device)
+        ax, ay, ad = (C.c_void_p(rec.value + 4 * FIELDS[k]) for k in ("AX", "AY", "DIR"))
+        with torch.cuda.device(self.device):
+            hm = None
+            if highlight:
+                hm = torch.empty((N, TW_CELLS), dtype=torch.uint8, device=self.device)
+                _lib.check(lib.mg_highlight_mask(None, N, S, S, ax, ay, ad, TW_REC_WORDS, self.view_size, _ptr(hm),
+                                                 self._stream()), "mg_highlight_mask")
+            _lib.check(lib.mg_render(ty, co, None, N, S, S, ax, ay, ad, TW_REC_WORDS, _dense(env_index, torch.int32), n,
+                                     _ptr(hm) if hm is not None else None, _ptr(atlas.tiles), ts, _ptr(frame), 0, None,
+                                     self._stream()), "mg_render")
+        return frame
+
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""
         ms = C.c_float()

@@ -77,7 +77,7 @@ class MiniGridEnv:
     variant = 6
 
     def __init__(self, size=17, agent_pos=(3, 15), goal_pos=(14, 2), agent_view_size=17, max_steps=50, tile_size=32,
-                 device=None, seed=9981, env_id=0, **kwargs):
+                 device=None, seed=9981, env_id=0, highlight=False, render_mode=None, **kwargs):
         if size != 17 or tuple(agent_pos) != (3, 15) or tuple(goal_pos) != (14, 2) or max_steps != 50:
             raise NotImplementedError("the HIP engine implements the registered configuration: size=17, "
                                       "agent_pos=(3,15), goal_pos=(14,2), max_steps=50")
@@ -86,6 +86,8 @@ class MiniGridEnv:
         self.agent_view_size = agent_view_size
         self.see_through_walls = True
         self.tile_size = tile_size
+        self.highlight = highlight                     # minigrid.py:876: brighten the cells of the agent's view
+        self.render_mode = render_mode
         self.actions = MiniGridEnv.Actions
         self.action_space = _Space(n=len(self.actions))
         self.observation_space = {"image": _Space(shape=(agent_view_size, agent_view_size, 3))}
@@ -154,10 +156,19 @@ class MiniGridEnv:
         g, _ = self.gen_obs_grid()
         return {"image": g.encode(), "direction": self.agent_dir, "mission": self.mission}
 
-    def get_full_render(self, *a, **k):
-        """The reference renders 17x17 tiles per step and discards the image when server=True
-        (env_buffer.py:456-459); rendering is out of scope."""
-        return None
+    def get_full_render(self):
+        """uint8[H*tile_size, W*tile_size, 3]: the image of the reference's get_full_render (minigrid.py:1514-1563),
+        drawn on the device from the engine's state (TwoarmyEngine.render) and copied to the host."""
+        return self._eng.render(tile_size=self.tile_size, highlight=self.highlight)[0].cpu().numpy()
+
+    def get_render(self):
+        return self.get_full_render()
+
+    def render(self):
+        """rgb_array behaviour of the reference's render(); the matplotlib window (render_mode="human") is not built."""
+        if self.render_mode == "human":
+            raise NotImplementedError("render_mode='human' (the matplotlib window) is out of scope; render() returns the image")
+        return self.get_full_render()
 
     def close(self):
         self._eng.close()

@@ -4,7 +4,8 @@ vectorised HIP engine instead of one Python env.
   python -m twoarmy_amd.soa.train_ppo --env MiniGrid-twoarmy-17x17-v6 --num_envs 4096 --updates 10
   python -m torch.distributed.run --nproc-per-node 8 ... train_ppo.py --num_envs 8192      (envs sharded per rank)
 
-Reference-only flags that concerned rendering / absolute log paths are accepted and ignored.
+Reference-only flags that concerned the matplotlib window / absolute log paths are accepted and ignored;
+--dump_frames DIR --dump_envs K writes the rendered frames of the first K envs once per update (off by default).
 """
 import argparse
 import os
@@ -61,7 +62,23 @@ def build_parser():
                         "finished episode with that episode's return (train_ppo.py:140), kept on the device")
     p.add_argument("--predictor_file", default=None, help="checkpoint with model_encoder / model_decoder / "
                    "model_predictor (train_ppo_predictor.py:38,81-85); random-init world model when absent")
+    p.add_argument("--dump_frames", default=None, metavar="DIR",
+                   help="write the rendered RGB frames (the reference's get_full_render, drawn on the device) of the "
+                        "first --dump_envs envs after the last rollout step of every update to DIR/update_<u>_frames.npy, "
+                        "with the state they were drawn from in update_<u>_state.npz; off by default")
+    p.add_argument("--dump_envs", type=int, default=4)
     return p
+
+
+def dump_frames(engine, path, update, k, tile_size):
+    """Frames of the engine's first k envs as uint8[k, 17*ts, 17*ts, 3] and the planes / records behind them."""
+    os.makedirs(path, exist_ok=True)
+    k = max(1, min(int(k), engine.num_envs))
+    idx = torch.arange(k, dtype=torch.int32, device=engine.device)
+    frames = engine.render(env_index=idx, tile_size=tile_size).cpu().numpy()
+    ty, co, rec = engine.get_state()
+    np.save(os.path.join(path, "update_%d_frames.npy" % update), frames)
+    np.savez_compressed(os.path.join(path, "update_%d_state.npz" % update), type=ty[:k], colour=co[:k], records=rec[:k])
 
 
 def episode_fields(es):
@@ -148,6 +165,8 @@ def main(argv=None, predictor=False, soa=False):
         la, lv = trainer.update()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
+        if args.dump_frames and rank == 0:                      # outside both timed spans; the update leaves the envs alone
+            dump_frames(engine, args.dump_frames, u, args.dump_envs, args.tile_size)
         st = trainer.stats()
         es = trainer.episode_stats() if es is None else es
         trainer.carry_over()

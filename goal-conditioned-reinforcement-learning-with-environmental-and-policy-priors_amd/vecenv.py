@@ -10,6 +10,8 @@ tensor + info["_final_observation"] mask, no host sync).  `policy_actions=True` 
 policy's 5 indices (4 -> done) like Env_transact.env_action (reference soa/env_buffer.py:364-376).
 Extra per-step tensors the reference computes in Python are fused into the same launch:
 `env.state_matrix` [N,289] (matrix_env) and `env.agent_yx` [N,2] (data_env).
+`env.render(env_index=None)` draws the RGB frames of the reference's get_full_render on the device (tile_size and
+highlight are constructor arguments).
 `record_episode_statistics=True` adds info["episode"] = {"r": float64 [N], "l": int32 [N]} and the mask
 info["_episode"] like gym.vector's RecordEpisodeStatistics, accounted on the device (episode_stats.EpisodeTracker).
 """
@@ -22,10 +24,12 @@ _IDS = {"MiniGrid-twoarmy-17x17-v4": 4, "MiniGrid-twoarmy-17x17-v6": 6, "v4": 4,
 
 class TwoarmyVecEnv:
     def __init__(self, env_id="MiniGrid-twoarmy-17x17-v6", num_envs=4096, agent_view_size=17, device=None,
-                 seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False):
+                 seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False,
+                 tile_size=17, highlight=False):
         self.variant = _IDS[env_id]
         self.num_envs = int(num_envs)
         self.view_size = agent_view_size
+        self.tile_size, self.highlight = int(tile_size), bool(highlight)
         self.policy_actions, self.autoreset = policy_actions, autoreset
         self.engine = TwoarmyEngine(self.variant, num_envs, agent_view_size, device=device, seed=seed, env_id0=env_id0)
         self.device = self.engine.device
@@ -74,6 +78,15 @@ class TwoarmyVecEnv:
     @property
     def agent_yx(self):
         return self._out["pos"]
+
+    def render(self, env_index=None, out=None):
+        """uint8[n, 17*tile_size, 17*tile_size, 3] device tensor: the reference's get_full_render image of every env,
+        or of the envs listed in env_index (int tensor / sequence), drawn on the device from the current state."""
+        if env_index is not None:
+            env_index = torch.as_tensor(env_index).to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+            if env_index.numel() == 0:
+                return torch.empty((0, 17 * self.tile_size, 17 * self.tile_size, 3), dtype=torch.uint8, device=self.device)
+        return self.engine.render(env_index=env_index, tile_size=self.tile_size, highlight=self.highlight, out=out)
 
     def close(self):
         self.engine.close()
