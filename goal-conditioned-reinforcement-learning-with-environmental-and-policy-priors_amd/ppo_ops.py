@@ -160,6 +160,50 @@ def episode_summary(ep_return, ep_length, terminated, truncated, reward, action=
     return summary, action_hist, reward_hist
 
 
+def visit_carry_words(width, height, N):
+    n = _lib.lib().ppo_visit_carry_words(int(width), int(height), int(N))
+    _lib.check(min(n, 0), "ppo_visit_carry_words")
+    return n
+
+
+def visit_scan(pos, terminated, truncated, carry, width=17, height=17, want_steps=True, out=None):
+    """Which cells the running episode of every env has stood on, carried across calls (ppo_visit_scan,
+    include/twoarmy_ppo.h).  pos f32[T,N,2] (y, x) after each step; terminated / truncated u8[T,N]; carry
+    u32[visit_carry_words(width, height, N)] is updated IN PLACE (all-zero: nothing seen).  Returns (first_visit u8[T,N],
+    ep_cells i32[T,N]), or (None, None) with want_steps=False; out = (first_visit, ep_cells) reuses the caller's buffers."""
+    T, N = terminated.shape
+    assert pos.shape == (T, N, 2) and truncated.shape == (T, N) and carry.numel() == visit_carry_words(width, height, N)
+    first_visit = ep_cells = None
+    if out is not None:
+        first_visit, ep_cells = out
+        assert first_visit.shape == (T, N) and ep_cells.shape == (T, N)
+    elif want_steps:
+        first_visit = torch.empty((T, N), dtype=torch.uint8, device=pos.device)
+        ep_cells = torch.empty((T, N), dtype=torch.int32, device=pos.device)
+    _lib.check(_lib.lib().ppo_visit_scan(_p(pos, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
+                                         T, N, int(width), int(height), _p(carry, torch.int32), _p(first_visit, torch.uint8),
+                                         _p(ep_cells, torch.int32), _stream(pos)), "ppo_visit_scan")
+    return first_visit, ep_cells
+
+
+def visit_hist(pos, counts, width=17, height=17, mask=None, t_idx=None, n_idx=None):
+    """counts i64[width*height + 1] += visits per cell, last entry = positions outside the grid (ppo_visit_hist,
+    include/twoarmy_ppo.h; the reference's values_matrix[y, x] += 1, soa/img_proccess/heatmap.py:63).  pos f32[T,N,2];
+    dense over every (t, n) whose mask u8[T,N] is non-zero (mask None: all), or, with t_idx / n_idx i32[B], over those
+    records (hindsight records; out-of-range ones count as outside).  Returns counts; no host synchronisation."""
+    T, N = pos.shape[:2]
+    assert pos.shape == (T, N, 2) and counts.numel() == int(width) * int(height) + 1
+    assert (t_idx is None) == (n_idx is None) and (mask is None or mask.shape == (T, N))
+    B = 0 if t_idx is None else t_idx.numel()
+    assert t_idx is None or n_idx.numel() == B
+    if t_idx is not None and B == 0:
+        return counts
+    _lib.check(_lib.lib().ppo_visit_hist(_p(pos, torch.float32), T, N, _p(mask, torch.uint8), _p(t_idx, torch.int32),
+                                         _p(n_idx, torch.int32), B, int(width), int(height), _p(counts, torch.int64),
+                                         _stream(pos)), "ppo_visit_hist")
+    return counts
+
+
 def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, env_id0=0, step0=0, max_goals=4, skip=0):
     """Hindsight relabelling of a time-major rollout (ppo_her_relabel_window, include/twoarmy_ppo.h; reference
     Buffer_gridworld.her_func, soa/env_buffer.py:101-143; skip = 4: pre_her_func / pre_f_her_func on the 9-frame window

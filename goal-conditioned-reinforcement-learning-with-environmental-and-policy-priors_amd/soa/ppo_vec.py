@@ -95,6 +95,7 @@ class VecPPOTrainer:
         self._hist = collections.deque(maxlen=max(1, -(-(self.max_steps - 1) // self.T)))
         self.her_seed = int(getattr(engine, "seed", 9981))
         self.episodes = None                  # EpisodeTracker, made by the first account_episodes()
+        self.visits = None                    # VisitTracker, made by the first account_visits()
         self.env_steps = 0
         self.episodes_done = 0
         self.return_sum = 0.0
@@ -424,6 +425,22 @@ class VecPPOTrainer:
         out = self.episodes.read()
         out["mean_neg_logp"] = float(-self.logp.mean())
         return out
+
+    def account_visits(self, her=None):
+        """Count the cells of the rollout just collected (call after collect(), before carry_over(), outside the
+        rollout's graph capture): the reference's heatmap matrix over the after-step positions (heatmap.py:58-81), with
+        the hindsight records `her` (relabel()'s result) counted like its appended copies, and the distinct cells each
+        episode covered, carried across rollout boundaries.  No host synchronisation."""
+        if self.visits is None:
+            from ..visitation import VisitTracker
+            self.visits = VisitTracker(self.N, self.device, 17, 17)
+        self.visits.account(self.pos[4:4 + self.T], self.term, self.trunc, her)
+
+    def visit_stats(self):
+        """VisitTracker.read() of the last accounted rollout."""
+        if self.visits is None:
+            raise RuntimeError("visit_stats() before account_visits()")
+        return self.visits.read()
 
     def stats(self):
         done = (self.term | self.trunc) != 0

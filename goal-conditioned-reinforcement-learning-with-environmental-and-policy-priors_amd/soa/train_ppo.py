@@ -6,6 +6,8 @@ vectorised HIP engine instead of one Python env.
 
 Reference-only flags that concerned the matplotlib window / absolute log paths are accepted and ignored;
 --dump_frames DIR --dump_envs K writes the rendered frames of the first K envs once per update (off by default).
+--visit_dir DIR writes the reference's heatmap MATRIX (heatmap.py:58-81; not the picture) once per update, counted on
+the device, and --track_buffer_file DIR its track dump (heatmap.py:79) for the first --dump_envs envs.
 """
 import argparse
 import os
@@ -29,7 +31,9 @@ def build_parser():
     p.add_argument("--weight_decay", type=float, default=0.0001)
     p.add_argument("--lr_gamma", type=float, default=0.8)
     p.add_argument("--lr_step_size", type=int, default=200)
-    p.add_argument("--track_buffer_file", default=None)
+    p.add_argument("--track_buffer_file", default=None, metavar="DIR",
+                   help="write the after-step (y, x) positions of the first --dump_envs envs of every update to "
+                        "DIR/track_<update>.npy, float64 [T, k, 2] (the reference's track dump, heatmap.py:79); off by default")
     p.add_argument("--num_episodes", type=int, default=1000000)
     p.add_argument("--max_steps", type=int, default=50)
     p.add_argument("--log_dir", default=None)
@@ -67,6 +71,11 @@ def build_parser():
                         "first --dump_envs envs after the last rollout step of every update to DIR/update_<u>_frames.npy, "
                         "with the state they were drawn from in update_<u>_state.npz; off by default")
     p.add_argument("--dump_envs", type=int, default=4)
+    p.add_argument("--visit_dir", default=None, metavar="DIR",
+                   help="count the visited cells of every rollout on the device (the reference's heatmap matrix, "
+                        "heatmap.py:58-81, hindsight records included while relabelling is on) and write "
+                        "DIR/visits_<update>_rank<r>.npz with rollout, first_visit_map, terminal_map, cumulative [17, 17] "
+                        "and other; adds the cells covered per episode and the share of room 2 to the log line; off by default")
     return p
 
 
@@ -88,6 +97,31 @@ def episode_fields(es):
     return " ep_return mean/min/max %s/%s/%s ep_len mean %s actions [%s] rewards [%s]" % (
         f(es["mean_return"]), f(es["min_return"]), f(es["max_return"]), f(es["mean_length"]),
         " ".join(str(c) for c in es["action_hist"]), " ".join(str(c) for c in es["reward_hist"]))
+
+
+def visit_fields(vs):
+    """Tail of the log line with --visit_dir: distinct cells per finished episode (VecPPOTrainer.visit_stats()) and the
+    share of the rollout's records that lie in room 2 (y < 8, beyond the ball gap)."""
+    def f(x, fmt):
+        return "-" if x is None else fmt % x
+    records = int(vs["rollout"].sum()) + vs["other"]
+    room2 = float(vs["rollout"][:8].sum()) / records if records else None
+    return " cells mean/min/max %s/%s/%s room2 %s" % (f(vs["cells_mean"], "%.2f"), f(vs["cells_min"], "%d"),
+                                                     f(vs["cells_max"], "%d"), f(room2, "%.4f"))
+
+
+def dump_visits(vs, path, update, rank):
+    os.makedirs(path, exist_ok=True)
+    np.savez(os.path.join(path, "visits_%06d_rank%d.npz" % (update, rank)), rollout=vs["rollout"],
+             first_visit_map=vs["first_visit_map"], terminal_map=vs["terminal_map"], cumulative=vs["cumulative"],
+             other=np.int64(vs["other"]))
+
+
+def dump_track(trainer, path, update, k):
+    """After-step (y, x) of the first k envs over the rollout, float64 [T, k, 2] (heatmap.py:79 saves buffer['p'][:, 4])."""
+    os.makedirs(path, exist_ok=True)
+    k = max(1, min(int(k), trainer.N))
+    np.save(os.path.join(path, "track_%06d.npy" % update), trainer.pos[4:4 + trainer.T, :k].double().cpu().numpy())
 
 
 def main(argv=None, predictor=False, soa=False):
@@ -153,6 +187,8 @@ def main(argv=None, predictor=False, soa=False):
         if her and agent.gae_lambda == 0.0:
             trainer.relabel()
         trainer.account_episodes()
+        if args.visit_dir:
+            trainer.account_visits(trainer.her)
         es = None
         if args.score == "episode":
             es = trainer.episode_stats()
@@ -169,12 +205,19 @@ def main(argv=None, predictor=False, soa=False):
             dump_frames(engine, args.dump_frames, u, args.dump_envs, args.tile_size)
         st = trainer.stats()
         es = trainer.episode_stats() if es is None else es
+        tail = ""
+        if args.visit_dir:                                      # every rank writes its own file: counts are additive
+            vs = trainer.visit_stats()
+            dump_visits(vs, args.visit_dir, u, rank)
+            tail = visit_fields(vs)
+        if args.track_buffer_file and rank == 0:
+            dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()
         if rank == 0:
             print("update %d: rollout %.3fs (%.0f env-steps/s/rank) update %.3fs action_loss %.5f value_loss %.5f "
                   "episodes %d successes %d mean_r %.4f her_records %d score %.4f" % (u, t1 - t0, trainer.T * trainer.N / (t1 - t0), t2 - t1,
                                                             float(la), float(lv), st["episodes"], st["successes"],
-                                                            st["mean_reward"], n_her, score) + episode_fields(es), flush=True)
+                                                            st["mean_reward"], n_her, score) + episode_fields(es) + tail, flush=True)
     engine.close()
     return trainer
 

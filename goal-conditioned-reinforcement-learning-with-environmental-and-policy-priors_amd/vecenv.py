@@ -14,6 +14,9 @@ Extra per-step tensors the reference computes in Python are fused into the same 
 highlight are constructor arguments).
 `record_episode_statistics=True` adds info["episode"] = {"r": float64 [N], "l": int32 [N]} and the mask
 info["_episode"] like gym.vector's RecordEpisodeStatistics, accounted on the device (episode_stats.EpisodeTracker).
+`record_visitation=True` adds info["visitation"] = {"cells": int32 [N], "first_visit": bool [N]} -- the distinct cells the
+running episode has stood on and whether this step's cell is new to it -- with the mask info["_visitation"] = done (where
+it is set, "cells" is the finished episode's coverage), and `env.visit_tracker` (visitation.VisitTracker) with the maps.
 """
 import torch
 
@@ -25,7 +28,7 @@ _IDS = {"MiniGrid-twoarmy-17x17-v4": 4, "MiniGrid-twoarmy-17x17-v6": 6, "v4": 4,
 class TwoarmyVecEnv:
     def __init__(self, env_id="MiniGrid-twoarmy-17x17-v6", num_envs=4096, agent_view_size=17, device=None,
                  seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False,
-                 tile_size=17, highlight=False):
+                 tile_size=17, highlight=False, record_visitation=False):
         self.variant = _IDS[env_id]
         self.num_envs = int(num_envs)
         self.view_size = agent_view_size
@@ -44,11 +47,17 @@ class TwoarmyVecEnv:
         if record_episode_statistics:
             from .episode_stats import EpisodeTracker
             self.episode_tracker = EpisodeTracker(self.num_envs, self.device, n_actions=self.single_action_n)
+        self.visit_tracker = None
+        if record_visitation:
+            from .visitation import VisitTracker
+            self.visit_tracker = VisitTracker(self.num_envs, self.device, 17, 17)
 
     def reset(self):
         self.engine.reset(obs=self._out["obs"])
         if self.episode_tracker is not None:
             self.episode_tracker.reset()
+        if self.visit_tracker is not None:
+            self.visit_tracker.reset()
         return self._out["obs"]
 
     def step(self, actions):
@@ -69,6 +78,11 @@ class TwoarmyVecEnv:
             tr.account(o["reward"], o["terminated"], o["truncated"], a)
             info["episode"] = {"r": tr.ep_return[0], "l": tr.ep_length[0]}
             info["_episode"] = done
+        if self.visit_tracker is not None:
+            vt = self.visit_tracker
+            vt.account(o["pos"], o["terminated"], o["truncated"])
+            info["visitation"] = {"cells": vt.ep_cells[0], "first_visit": vt.first_visit[0].bool()}
+            info["_visitation"] = done
         return obs, o["reward"], o["terminated"].bool(), o["truncated"].bool(), info
 
     @property

@@ -128,6 +128,41 @@ int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const
                         int64_t *reward_hist, double *workspace, void *stream);
 int ppo_episode_summary_workspace(int T, int N);
 
+/* Visited cells on the device (<package>/csrc/visitation.hip): the visit-count matrix the reference builds for its heatmap
+ * after every PPO.update (soa/agent/PPO.py:161 -> soa/img_proccess/heatmap.py:58-81, `values_matrix[y, x] += 1` over
+ * the buffer's after-step positions) and the set of distinct cells an episode has stood on (the goal candidates of
+ * her_func, soa/env_buffer.py:138).  The pictures are not drawn.
+ *
+ * Cell of a position (y, x) = (pos[..][0], pos[..][1]): valid iff 0 <= y < height and 0 <= x < width as float comparisons
+ * (NaN and +-inf fail, -0.0 passes as 0); cell = (int)y * width + (int)x, row-major like values_matrix[y][x].  Every
+ * invalid position is counted in ONE extra bin, other = width * height, and never addresses anything else.
+ * 1 <= width, height <= 32.  pos and counts are 8-byte aligned.
+ *
+ * ppo_visit_scan: for every env n, in step order: seen = the set in `carry`; for t = 0 .. T-1:
+ *   first_visit[t][n] = cell valid and not in seen; seen += cell; ep_cells[t][n] = |seen|; and where
+ *   terminated | truncated is set, seen = {} after the write.  The carry is written back at the end.
+ * The set is empty at an episode's first step (the reset cell is not in it: the reference's buffer holds after-step
+ * positions only), so within one episode the steps with first_visit = 1 are the indices np.unique(episode_p, axis=0,
+ * return_index=True) returns, and at a done step ep_cells is the episode's coverage wherever it began.  The result
+ * does not depend on how the steps are cut into launches.
+ *   pos float[T][N][2]; terminated, truncated uint8[T][N]; first_visit uint8[T][N] | NULL; ep_cells int32[T][N] | NULL
+ *   carry uint32[ppo_visit_carry_words(width, height, N)] in/out, opaque, all-zero = nothing seen (bit c & 31 of word
+ *   [c >> 5][n] = cell c of env n: word-major over envs, so a wavefront's accesses are contiguous).
+ *
+ * ppo_visit_hist: counts int64[width * height + 1] += number of records per cell (last entry: other).
+ *   dense   (t_idx == NULL): every (t, n) with mask == NULL || mask[t][n] != 0;  mask uint8[T][N]
+ *   indexed (t_idx, n_idx int32[B]): the records (t_idx[b], n_idx[b]), e.g. the hindsight records of ppo_her_relabel;
+ *           a record outside [0, T) x [0, N) counts as other; B == 0 adds nothing.
+ * Integer adds only: exact, whatever the scheduling.
+ *
+ * Both return TW_E_ARG and launch nothing on NULL pos / counts / carry / terminated / truncated, width or height outside
+ * 1..32, negative T, N or B, one of t_idx / n_idx without the other; T * N == 0 returns 0 and launches nothing. */
+int ppo_visit_scan(const float *pos, const uint8_t *terminated, const uint8_t *truncated, int T, int N, int width,
+                   int height, uint32_t *carry, uint8_t *first_visit, int32_t *ep_cells, void *stream);
+int ppo_visit_carry_words(int width, int height, int N);
+int ppo_visit_hist(const float *pos, int T, int N, const uint8_t *mask, const int32_t *t_idx, const int32_t *n_idx, int B,
+                   int width, int height, int64_t *counts, void *stream);
+
 /* Hindsight experience replay over one time-major rollout: replaces Buffer_gridworld.her_func
  * (soa/env_buffer.py:101-143, called from soa/train_ppo.py:128-134 at every episode end).  For every episode
  * [s0, t1] that starts (age0[n] == 0 or the step after a done) and ends (terminated | truncated) inside the

@@ -86,3 +86,39 @@ p2 = torch.randint(1, 16, (T, N, 2), generator=g).float().to(dev)
 rw = torch.randn(T, N, generator=g).to(dev)
 report("ppo_her_relabel (count + scan + emit, one host sync)", T * N * (8 + 1 + 1 + 4) * 2,
        timed(lambda: ppo_ops.her_relabel(p2, term, trunc, age0, rw, seed=1), iters=5), "includes the record-count sync")
+
+# Visited cells (csrc/visitation.hip): the scan, the three dense histograms a VisitTracker.account() launches and an
+# indexed one over 100 000 hindsight records, on positions as concentrated as a rollout's (every env walks away from one
+# start cell and returns to it when its episode ends) and on uniformly spread ones; beside them the torch expression a
+# user would otherwise write for the plain matrix.
+W = H = 17
+walk = torch.zeros(T, N, 2)
+cur = torch.tensor([15.0, 1.0]).repeat(N, 1)
+moves = torch.tensor([[0.0, 0.0], [1.0, 0.0], [-1.0, 0.0], [0.0, 1.0], [0.0, -1.0]])
+ended = ((term | trunc) != 0).cpu()
+for t in range(T):
+    cur = (cur + moves[torch.randint(0, 5, (N,), generator=g)]).clamp_(1.0, 15.0)
+    walk[t] = cur
+    cur = torch.where(ended[t].view(-1, 1), torch.tensor([15.0, 1.0]), cur)
+done_tn = term | trunc
+her_t = torch.randint(0, T, (100000,), generator=g, dtype=torch.int32).to(dev)
+her_n = torch.randint(0, N, (100000,), generator=g, dtype=torch.int32).to(dev)
+for label, pv in (("rollout-like walks", walk.to(dev)), ("uniform cells", p2)):
+    v_carry = torch.zeros(ppo_ops.visit_carry_words(W, H, N), dtype=torch.int32, device=dev)
+    fv, ec = ppo_ops.visit_scan(pv, term, trunc, v_carry, W, H)
+    counts = torch.zeros(W * H + 1, dtype=torch.int64, device=dev)
+    report("ppo_visit_scan (%s)" % label, T * N * (8 + 1 + 1 + 1 + 4),
+           timed(lambda: ppo_ops.visit_scan(pv, term, trunc, v_carry, W, H, out=(fv, ec))), "latency-bound: one lane per env")
+    report("ppo_visit_hist dense (%s)" % label, T * N * 8, timed(lambda: ppo_ops.visit_hist(pv, counts, W, H)))
+    report("ppo_visit_hist dense, first-visit mask (%s)" % label, T * N * 1 + int(fv.sum()) * 8,
+           timed(lambda: ppo_ops.visit_hist(pv, counts, W, H, mask=fv)))
+    report("ppo_visit_hist dense, done mask (%s)" % label, T * N * 1 + n_done * 8,
+           timed(lambda: ppo_ops.visit_hist(pv, counts, W, H, mask=done_tn)))
+    report("ppo_visit_hist indexed, 100000 records (%s)" % label, 100000 * 16,
+           timed(lambda: ppo_ops.visit_hist(pv, counts, W, H, t_idx=her_t, n_idx=her_n)))
+    report("torch.bincount((y * 17 + x).long()) (%s)" % label, T * N * 8,
+           timed(lambda: torch.bincount((pv[..., 0] * 17 + pv[..., 1]).long().view(-1), minlength=289)),
+           "several torch kernels and a device-to-host sync inside bincount")
+    ref = torch.bincount((pv[..., 0] * 17 + pv[..., 1]).long().view(-1), minlength=289)
+    one = ppo_ops.visit_hist(pv, torch.zeros(W * H + 1, dtype=torch.int64, device=dev), W, H)
+    assert torch.equal(one[:289], ref) and int(one[289]) == 0
