@@ -111,6 +111,10 @@ _SIGS.update({
     "ppo_visit_scan": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ppo_visit_carry_words": (C.c_int, [_i, _i, _i]),
     "ppo_visit_hist": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ppo_bonus_table_words": (C.c_int, [_i, _i, _i, _i, _i, _i]),
+    "ppo_bonus_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i]),
+    "ppo_bonus_scan": (C.c_int, [_vp, _vp, _vp, C.c_long, C.c_long, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _vp]),
     "ppo_bias_relu_nhwc": (C.c_int, [_vp, _vp, _i64, _i, _vp]),
     "ppo_conv1_up4_bias_relu": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ppo_conv1_up4_bias_relu_c": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,289 @@
+// exploration_bonus.hip -- count-based exploration bonuses (C ABI in include/twoarmy_ppo.h).
+//
+// The reference's gym_minigrid/wrappers.py:34-102 keep a dict of visit counts and add 1/sqrt(count) to the reward:
+// StateBonus keyed by agent_pos, ActionBonus by (agent_pos, agent_dir, action).  The bonus of a step depends on how often
+// its key was seen BEFORE it, so the work is an ordered count, not a histogram:
+//   env scope     ppo_bonus_env_kernel: one wavefront per env; a chunk of steps has its keys in LDS, every step's rank
+//                 among the earlier equal keys of the chunk is counted there, the carried counts are gathered with
+//                 independent loads, and the last occurrence of a key stores the new count.  No atomics.
+//   shared scope  ppo_bonus_row_hist_kernel (per-row histogram of keys), ppo_bonus_key_scan_kernel (inclusive scan over
+//                 the rows per key, table += total), ppo_bonus_gather_kernel (count of (t, n) = table - total + prefix).
+// Only integer adds reach the tables: the counts are exact whatever the scheduling, and the bonus is a pure function
+// of the count.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "twoarmy.h"
+#include "twoarmy_ppo.h"
+#include "visit_cell.h"
+
+namespace {
+
+constexpr int BONUS_CHUNK = 256;                  // steps whose keys sit in LDS at once (env scope)
+constexpr int BONUS_PER_LANE = BONUS_CHUNK / 64;
+constexpr int BONUS_SLICE = 8192;                 // keys per LDS row histogram (shared scope); Twoarmy's 8093 fit in one
+constexpr int BONUS_THREADS = 256;
+constexpr int BONUS_MAX_ACTIONS = 8;
+
+struct BonusIn {
+    const float2 *pos;
+    const int32_t *action;
+    const int32_t *dir;
+    long dir_stride_t, dir_stride_n;
+    int T, N, width, height, n_actions;
+};
+
+__device__ __forceinline__ int bonus_keys(const BonusIn &in, int kind) {
+    const int cells = in.width * in.height;
+    return kind == 1 ? cells + 1 : cells * 4 * in.n_actions + 1;
+}
+
+// key of step (t, n): kind 1 = the cell, kind 2 = (cell * 4 + dir) * n_actions + action; anything invalid is the
+// table's last slot
+template <int KIND>
+__device__ __forceinline__ int bonus_key(const BonusIn &in, int t, int n) {
+    const size_t i = (size_t)t * in.N + n;
+    const float2 p = in.pos[i];
+    const int cells = in.width * in.height;
+    const int cell = visit_cell(p.x, p.y, in.width, in.height);
+    if (KIND == 1) return cell;
+    const int d = in.dir ? in.dir[(size_t)t * in.dir_stride_t + (size_t)n * in.dir_stride_n] : 0;
+    const int a = in.action[i];
+    const bool ok = cell < cells && d >= 0 && d < 4 && a >= 0 && a < in.n_actions;
+    return ok ? (cell * 4 + d) * in.n_actions + a : cells * 4 * in.n_actions;
+}
+
+// scale * (1 / sqrt(c)) in IEEE double, one rounding per operation (the product must not fuse into a later add)
+template <typename C>
+__device__ __forceinline__ double bonus_value(C count, double scale) {
+#pragma clang fp contract(off)
+    const double inv = 1.0 / sqrt((double)count);
+    return scale * inv;
+}
+
+__device__ __forceinline__ void bonus_write(size_t i, double bs, double ba, const float *reward, const uint8_t *keep,
+                                            float *bonus_state, float *bonus_action, float *reward_out) {
+#pragma clang fp contract(off)
+    if (bonus_state) bonus_state[i] = (float)bs;
+    if (bonus_action) bonus_action[i] = (float)ba;
+    if (reward_out) {
+        const float r = reward[i];
+        const double shaped = ((double)r + bs) + ba;              // ActionBonus(StateBonus(env)): state first
+        reward_out[i] = (keep && keep[i]) ? r : (float)shaped;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- env scope
+// One chunk of one env for one kind.  Lane l owns the steps u = j * 64 + l of the chunk.  b[j] receives the bonus.
+template <int KIND>
+__device__ __forceinline__ void bonus_env_chunk(const BonusIn &in, int n, int c0, int len, uint32_t *table, double scale,
+                                                int32_t *keys, double (&b)[BONUS_PER_LANE]) {
+    const int lane = threadIdx.x;
+    int k[BONUS_PER_LANE];
+    uint32_t carry[BONUS_PER_LANE];
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j) {
+        const int u = j * 64 + lane;
+        k[j] = -1;
+        carry[j] = 0u;
+        if (u < len) {
+            k[j] = bonus_key<KIND>(in, c0 + u, n);
+            keys[u] = k[j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j)                       // independent gathers: nothing waits on them yet
+        if (j * 64 + lane < len) carry[j] = table[k[j]];
+    int earlier[BONUS_PER_LANE] = {};
+    bool later[BONUS_PER_LANE] = {};
+    for (int v = 0; v < len; ++v) {
+        const int kv = keys[v];                                    // one address for the wavefront: a broadcast read
+#pragma unroll
+        for (int j = 0; j < BONUS_PER_LANE; ++j) {
+            const int u = j * 64 + lane;
+            const bool same = kv == k[j];
+            earlier[j] += (same && v < u) ? 1 : 0;
+            later[j] = later[j] || (same && v > u);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j) {
+        if (j * 64 + lane < len) {
+            const uint32_t count = carry[j] + (uint32_t)earlier[j] + 1u;
+            if (!later[j]) table[k[j]] = count;                    // the chunk's last occurrence of the key
+            b[j] = bonus_value(count, scale);
+        }
+    }
+    __syncthreads();                                               // keys[] is reused; the next chunk gathers what was stored
+}
+
+__global__ __launch_bounds__(64) void ppo_bonus_env_kernel(BonusIn in, const float *reward, const uint8_t *keep,
+                                                           int kind_mask, double scale, uint32_t *state_table,
+                                                           uint32_t *action_table, float *bonus_state,
+                                                           float *bonus_action, float *reward_out) {
+    __shared__ int32_t keys[BONUS_CHUNK];
+    const int lane = threadIdx.x;
+    const int n = blockIdx.x;
+    const size_t ks = (size_t)bonus_keys(in, 1), ka = (size_t)bonus_keys(in, 2);
+    for (int c0 = 0; c0 < in.T; c0 += BONUS_CHUNK) {
+        const int len = min(BONUS_CHUNK, in.T - c0);
+        double bs[BONUS_PER_LANE] = {}, ba[BONUS_PER_LANE] = {};
+        if (kind_mask & 1) bonus_env_chunk<1>(in, n, c0, len, state_table + (size_t)n * ks, scale, keys, bs);
+        if (kind_mask & 2) bonus_env_chunk<2>(in, n, c0, len, action_table + (size_t)n * ka, scale, keys, ba);
+#pragma unroll
+        for (int j = 0; j < BONUS_PER_LANE; ++j) {
+            const int u = j * 64 + lane;
+            if (u < len)
+                bonus_write((size_t)(c0 + u) * in.N + n, bs[j], ba[j], reward, keep, bonus_state, bonus_action, reward_out);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- shared scope
+// hist[t][k0 .. k0 + BONUS_SLICE) of row t = blockIdx.x and key slice blockIdx.y: the block owns that part of the row,
+// so it is written with plain stores and needs no clearing beforehand.
+template <int KIND>
+__global__ __launch_bounds__(BONUS_THREADS) void ppo_bonus_row_hist_kernel(BonusIn in, uint32_t *__restrict__ hist) {
+    __shared__ uint32_t part[BONUS_SLICE];
+    const int K = bonus_keys(in, KIND);
+    const int t = blockIdx.x;
+    const int k0 = blockIdx.y * BONUS_SLICE;
+    const int kn = min(BONUS_SLICE, K - k0);
+    for (int c = threadIdx.x; c < kn; c += BONUS_THREADS) part[c] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    // every lane of a wavefront runs the same number of rounds (visit_grouped_add's ballots need all of them)
+    for (int base = threadIdx.x - lane; base < in.N; base += BONUS_THREADS) {
+        const int n = base + lane;
+        bool pending = n < in.N;
+        int c = 0;
+        if (pending) {
+            c = bonus_key<KIND>(in, t, n) - k0;
+            pending = c >= 0 && c < kn;
+        }
+        visit_grouped_add(part, c, pending, lane);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < kn; c += BONUS_THREADS) hist[(size_t)t * K + k0 + c] = part[c];
+}
+
+// hist[t][k] <- hist[0][k] + ... + hist[t][k]; table[k] += hist[T-1][k].  One thread per key, coalesced rows.
+__global__ __launch_bounds__(BONUS_THREADS) void ppo_bonus_key_scan_kernel(uint32_t *__restrict__ hist, int T, int K,
+                                                                           int64_t *__restrict__ table) {
+    const int k = blockIdx.x * BONUS_THREADS + threadIdx.x;
+    if (k >= K) return;
+    uint32_t run = 0u;
+    for (int t = 0; t < T; ++t) {
+        run += hist[(size_t)t * K + k];
+        hist[(size_t)t * K + k] = run;
+    }
+    table[k] += (int64_t)run;
+}
+
+template <int KIND>
+__device__ __forceinline__ double bonus_shared_value(const BonusIn &in, int t, int n, const uint32_t *hist,
+                                                     const int64_t *table, double scale) {
+    const int K = bonus_keys(in, KIND);
+    const int k = bonus_key<KIND>(in, t, n);
+    // table already holds this launch's total: count = carry + rows 0 .. t
+    const int64_t count = table[k] - (int64_t)hist[(size_t)(in.T - 1) * K + k] + (int64_t)hist[(size_t)t * K + k];
+    return bonus_value(count, scale);
+}
+
+__global__ __launch_bounds__(BONUS_THREADS) void ppo_bonus_gather_kernel(BonusIn in, const float *reward,
+                                                                         const uint8_t *keep, int kind_mask, double scale,
+                                                                         const int64_t *state_table,
+                                                                         const int64_t *action_table,
+                                                                         const uint32_t *hist_state,
+                                                                         const uint32_t *hist_action, float *bonus_state,
+                                                                         float *bonus_action, float *reward_out) {
+    const int64_t i = (int64_t)blockIdx.x * BONUS_THREADS + threadIdx.x;
+    if (i >= (int64_t)in.T * in.N) return;
+    const int t = (int)(i / in.N), n = (int)(i % in.N);
+    const double bs = (kind_mask & 1) ? bonus_shared_value<1>(in, t, n, hist_state, state_table, scale) : 0.0;
+    const double ba = (kind_mask & 2) ? bonus_shared_value<2>(in, t, n, hist_action, action_table, scale) : 0.0;
+    bonus_write((size_t)i, bs, ba, reward, keep, bonus_state, bonus_action, reward_out);
+}
+
+int64_t bonus_keys_host(int kind, int width, int height, int n_actions) {
+    const int64_t cells = (int64_t)width * height;
+    return kind == 1 ? cells + 1 : cells * 4 * n_actions + 1;
+}
+
+bool bonus_geom_ok(int width, int height, int n_actions) {
+    return visit_grid_ok(width, height) && n_actions >= 1 && n_actions <= BONUS_MAX_ACTIONS;
+}
+
+int bonus_launched() { return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP; }
+
+}  // namespace
+
+extern "C" {
+
+int ppo_bonus_table_words(int kind, int scope, int width, int height, int n_actions, int N) {
+    if ((kind != 1 && kind != 2) || (scope != 0 && scope != 1) || !bonus_geom_ok(width, height, n_actions) || N < 0)
+        return TW_E_ARG;
+    const int64_t K = bonus_keys_host(kind, width, height, n_actions);
+    const int64_t words = scope == 0 ? K * N : 2 * K;
+    return words < ((int64_t)1 << 31) ? (int)words : TW_E_ARG;
+}
+
+int64_t ppo_bonus_workspace_bytes(int kind_mask, int scope, int T, int width, int height, int n_actions) {
+    if (kind_mask < 1 || kind_mask > 3 || (scope != 0 && scope != 1) || !bonus_geom_ok(width, height, n_actions) || T < 0)
+        return TW_E_ARG;
+    if (scope == 0) return 0;
+    int64_t K = 0;
+    if (kind_mask & 1) K += bonus_keys_host(1, width, height, n_actions);
+    if (kind_mask & 2) K += bonus_keys_host(2, width, height, n_actions);
+    return 4 * K * (int64_t)T;
+}
+
+int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, long dir_stride_t, long dir_stride_n,
+                   const float *reward, const uint8_t *keep, int T, int N, int width, int height, int n_actions,
+                   int kind_mask, int scope, double scale, void *state_table, void *action_table, float *bonus_state,
+                   float *bonus_action, float *reward_out, void *workspace, void *stream) {
+    if (!pos || ((uintptr_t)pos & 7u) || T < 0 || N < 0 || !bonus_geom_ok(width, height, n_actions)) return TW_E_ARG;
+    if (kind_mask < 1 || kind_mask > 3 || (scope != 0 && scope != 1)) return TW_E_ARG;
+    if ((kind_mask & 1) && (!state_table || ((uintptr_t)state_table & 7u))) return TW_E_ARG;
+    if ((kind_mask & 2) && (!action_table || ((uintptr_t)action_table & 7u) || !action)) return TW_E_ARG;
+    if (dir && (dir_stride_t < 0 || dir_stride_n < 0)) return TW_E_ARG;
+    if (reward_out && !reward) return TW_E_ARG;
+    if ((int64_t)T * N >= ((int64_t)1 << 31)) return TW_E_ARG;            // a row histogram's 32-bit prefix cannot wrap
+    for (int kind = 1; kind <= 2; ++kind)
+        if ((kind_mask & kind) && ppo_bonus_table_words(kind, scope, width, height, n_actions, N) < 0) return TW_E_ARG;
+    if (scope == 1 && (!workspace || ((uintptr_t)workspace & 3u))) return TW_E_ARG;
+    if (T == 0 || N == 0) return TW_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    const BonusIn in = {reinterpret_cast<const float2 *>(pos), action, dir, dir_stride_t, dir_stride_n, T, N, width, height,
+                        n_actions};
+    if (scope == 0) {
+        hipLaunchKernelGGL(ppo_bonus_env_kernel, dim3(N), dim3(64), 0, s, in, reward, keep, kind_mask, scale,
+                           (uint32_t *)state_table, (uint32_t *)action_table, bonus_state, bonus_action, reward_out);
+        return bonus_launched();
+    }
+    const int Ks = (int)bonus_keys_host(1, width, height, n_actions), Ka = (int)bonus_keys_host(2, width, height, n_actions);
+    uint32_t *hist_state = (uint32_t *)workspace;
+    uint32_t *hist_action = hist_state + ((kind_mask & 1) ? (size_t)T * Ks : 0);
+    if (kind_mask & 1) {
+        hipLaunchKernelGGL(ppo_bonus_row_hist_kernel<1>, dim3(T, (Ks + BONUS_SLICE - 1) / BONUS_SLICE), dim3(BONUS_THREADS),
+                           0, s, in, hist_state);
+        hipLaunchKernelGGL(ppo_bonus_key_scan_kernel, dim3((Ks + BONUS_THREADS - 1) / BONUS_THREADS), dim3(BONUS_THREADS), 0,
+                           s, hist_state, T, Ks, (int64_t *)state_table);
+    }
+    if (kind_mask & 2) {
+        hipLaunchKernelGGL(ppo_bonus_row_hist_kernel<2>, dim3(T, (Ka + BONUS_SLICE - 1) / BONUS_SLICE), dim3(BONUS_THREADS),
+                           0, s, in, hist_action);
+        hipLaunchKernelGGL(ppo_bonus_key_scan_kernel, dim3((Ka + BONUS_THREADS - 1) / BONUS_THREADS), dim3(BONUS_THREADS), 0,
+                           s, hist_action, T, Ka, (int64_t *)action_table);
+    }
+    if (bonus_state || bonus_action || reward_out) {
+        const int64_t blocks = ((int64_t)T * N + BONUS_THREADS - 1) / BONUS_THREADS;
+        hipLaunchKernelGGL(ppo_bonus_gather_kernel, dim3((unsigned)blocks), dim3(BONUS_THREADS), 0, s, in, reward, keep,
+                           kind_mask, scale, (const int64_t *)state_table, (const int64_t *)action_table, hist_state,
+                           hist_action, bonus_state, bonus_action, reward_out);
+    }
+    return bonus_launched();
+}
+
+}  // extern "C"

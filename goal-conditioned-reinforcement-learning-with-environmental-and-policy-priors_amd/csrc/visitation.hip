@@ -12,19 +12,12 @@
 
 #include "twoarmy.h"
 #include "twoarmy_ppo.h"
+#include "visit_cell.h"
 
 namespace {
 
-constexpr int VISIT_MAX_SIDE = 32;
 constexpr int VISIT_MAX_WORDS = VISIT_MAX_SIDE * VISIT_MAX_SIDE / 32;        // bitmap words of the largest grid
 constexpr int VISIT_ROWS = 8;                                               // rows loaded ahead of the dependent chain
-
-// values_matrix[y][x] of heatmap.py:63, row-major; every position outside the grid (NaN and +-inf fail the float
-// comparisons) is the extra bin width * height.
-__device__ __forceinline__ int visit_cell(float y, float x, int width, int height) {
-    const bool ok = y >= 0.f && y < (float)height && x >= 0.f && x < (float)width;
-    return ok ? (int)y * width + (int)x : width * height;
-}
 
 // One lane per env over coalesced rows, like ppo_episode_scan.  The bitmap is indexed by a run-time cell number, so it
 // lives in LDS and not in registers (a register array indexed at run time becomes scratch): word w of lane l sits at
@@ -94,15 +87,12 @@ __global__ __launch_bounds__(64) void ppo_visit_scan_kernel(const float2 *__rest
 }
 
 // Positions are concentrated: on the step after a reset every env stands next to the same start cell, and a plain LDS
-// histogram would have 64 lanes adding to one address.  So a wavefront first groups equal cells: the lowest pending
-// lane broadcasts its cell, the lanes that hold the same cell are counted with one ballot, and the leader adds the
-// count once.  VISIT_GROUP_ROUNDS such rounds take the few crowded cells; whatever is still pending after them is
-// spread thinly and goes through plain LDS adds.  Blocks keep 32-bit partial histograms (a block sees < 2^31 elements)
+// histogram would have 64 lanes adding to one address.  So a wavefront first groups equal cells (visit_grouped_add,
+// visit_cell.h).  Blocks keep 32-bit partial histograms (a block sees < 2^31 elements)
 // and add their non-empty bins to the int64 counts at the end.
 constexpr int VISIT_HIST_THREADS = 256;
 constexpr int VISIT_HIST_PER_THREAD = 8;
 constexpr int VISIT_HIST_MAX_BLOCKS = 512;
-constexpr int VISIT_GROUP_ROUNDS = 4;
 
 __global__ __launch_bounds__(VISIT_HIST_THREADS) void ppo_visit_hist_kernel(
     const float2 *__restrict__ pos, int T, int N, const uint8_t *__restrict__ mask, const int32_t *__restrict__ t_idx,
@@ -132,27 +122,13 @@ __global__ __launch_bounds__(VISIT_HIST_THREADS) void ppo_visit_hist_kernel(
                 c = visit_cell(p.x, p.y, width, height);
             }
         }
-#pragma unroll
-        for (int r = 0; r < VISIT_GROUP_ROUNDS; ++r) {
-            const unsigned long long todo = __ballot(pending);
-            if (todo == 0ull) break;
-            const int leader = __ffsll(todo) - 1;
-            const int lc = __shfl(c, leader, 64);
-            const unsigned long long same = __ballot(pending && c == lc);
-            if (lane == leader) atomicAdd(&hist[lc], (uint32_t)__popcll(same));
-            if (c == lc) pending = false;
-        }
-        if (pending) atomicAdd(&hist[c], 1u);
+        visit_grouped_add(hist, c, pending, lane);
     }
     __syncthreads();
     for (int c = threadIdx.x; c <= cells; c += VISIT_HIST_THREADS) {
         const uint32_t v = hist[c];
         if (v) atomicAdd(&counts[c], (unsigned long long)v);
     }
-}
-
-bool visit_grid_ok(int width, int height) {
-    return width >= 1 && width <= VISIT_MAX_SIDE && height >= 1 && height <= VISIT_MAX_SIDE;
 }
 
 int visit_launched() { return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP; }

@@ -342,6 +342,23 @@ class TwoarmyEngine:
                                      self._stream()), "mg_render")
         return frame
 
+    def dir_ptr(self):
+        """(address, stride_t, stride_n) of the agents' directions in the engine's records (tw_state_ptrs), in int32
+        elements: one value per env, as ppo_ops.bonus_scan(dir_ptr=...) takes it.  After an auto-reset the record holds
+        the new episode's direction."""
+        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
+        return rec.value + 4 * FIELDS["DIR"], 0, TW_REC_WORDS
+
+    def dir_view(self):
+        """int32[N] strided device view of the same directions (no copy)."""
+        addr = self.dir_ptr()[0] - 4 * FIELDS["DIR"]
+        span = _DevSpan(self, addr, self.num_envs * TW_REC_WORDS * 4)
+        t = torch.as_tensor(span, device=self.device)
+        if t.data_ptr() != addr:
+            raise _lib.TwoarmyLibraryError("torch did not alias the engine's records")
+        return t.view(torch.int32).view(self.num_envs, TW_REC_WORDS)[:, FIELDS["DIR"]]
+
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""
         ms = C.c_float()

@@ -204,6 +204,60 @@ def visit_hist(pos, counts, width=17, height=17, mask=None, t_idx=None, n_idx=No
     return counts
 
 
+BONUS_KINDS = {"state": 1, "action": 2}
+BONUS_SCOPES = {"env": 0, "shared": 1}
+
+
+def bonus_table_words(kind, scope, width=17, height=17, n_actions=7, N=1):
+    """32-bit words of one count table (kind "state" / "action", scope "env" / "shared"; ppo_bonus_table_words)."""
+    n = _lib.lib().ppo_bonus_table_words(BONUS_KINDS[kind], BONUS_SCOPES[scope], int(width), int(height), int(n_actions),
+                                         int(N))
+    _lib.check(min(n, 0), "ppo_bonus_table_words")
+    return n
+
+
+def bonus_workspace_bytes(kind_mask, scope, T, width=17, height=17, n_actions=7):
+    n = _lib.lib().ppo_bonus_workspace_bytes(int(kind_mask), BONUS_SCOPES[scope], int(T), int(width), int(height),
+                                             int(n_actions))
+    _lib.check(min(n, 0), "ppo_bonus_workspace_bytes")
+    return n
+
+
+def bonus_scan(pos, action, reward, state_table=None, action_table=None, scope="env", scale=1.0, width=17, height=17,
+               n_actions=7, keep=None, dir=None, dir_ptr=None, bonus_state=None, bonus_action=None, reward_out=None,
+               workspace=None):
+    """Count-based exploration bonuses of one rollout (ppo_bonus_scan, include/twoarmy_ppo.h; the reference's StateBonus /
+    ActionBonus, gym_minigrid/wrappers.py:34-102).  pos f32[T,N,2] (y, x) after each step, action i32[T,N], reward
+    f32[T,N]; the tables given (i32 words, bonus_table_words; updated IN PLACE) select the kinds.  dir: i32[T,N] or [N]
+    (one direction per env), or dir_ptr = (address, stride_t, stride_n) of directions that live elsewhere on the device
+    (the engine's records); neither: direction 0.  keep u8[T,N]: steps whose reward passes through unshaped.  Writes the
+    outputs given (bonus_state / bonus_action / reward_out f32[T,N]; reward_out may be reward); no host synchronisation."""
+    T, N = pos.shape[:2]
+    assert pos.shape == (T, N, 2)
+    for t in (action, reward, keep, bonus_state, bonus_action, reward_out):
+        assert t is None or t.shape == (T, N)
+    mask = (1 if state_table is not None else 0) | (2 if action_table is not None else 0)
+    dp, st, sn = None, 0, 0
+    if dir is not None:
+        assert dir.shape in ((T, N), (N,))
+        dp, st, sn = _p(dir, torch.int32), (N if dir.dim() == 2 else 0), 1
+    elif dir_ptr is not None:
+        dp, st, sn = C.c_void_p(int(dir_ptr[0])), int(dir_ptr[1]), int(dir_ptr[2])
+    if BONUS_SCOPES[scope] == 1:
+        need = bonus_workspace_bytes(mask, scope, T, width, height, n_actions)
+        if workspace is None:
+            workspace = torch.empty(max(1, need // 4), dtype=torch.int32, device=pos.device)
+        assert workspace.numel() * 4 >= need
+    for kind, tab in (("state", state_table), ("action", action_table)):
+        assert tab is None or tab.numel() == bonus_table_words(kind, scope, width, height, n_actions, N)
+    _lib.check(_lib.lib().ppo_bonus_scan(
+        _p(pos, torch.float32), _p(action, torch.int32), dp, st, sn, _p(reward, torch.float32), _p(keep, torch.uint8), T, N,
+        int(width), int(height), int(n_actions), mask, BONUS_SCOPES[scope], float(scale), _p(state_table, torch.int32),
+        _p(action_table, torch.int32), _p(bonus_state, torch.float32), _p(bonus_action, torch.float32),
+        _p(reward_out, torch.float32), _p(workspace, torch.int32), _stream(pos)), "ppo_bonus_scan")
+    return reward_out
+
+
 def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, env_id0=0, step0=0, max_goals=4, skip=0):
     """Hindsight relabelling of a time-major rollout (ppo_her_relabel_window, include/twoarmy_ppo.h; reference
     Buffer_gridworld.her_func, soa/env_buffer.py:101-143; skip = 4: pre_her_func / pre_f_her_func on the 9-frame window

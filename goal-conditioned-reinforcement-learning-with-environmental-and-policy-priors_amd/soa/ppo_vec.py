@@ -96,6 +96,9 @@ class VecPPOTrainer:
         self.her_seed = int(getattr(engine, "seed", 9981))
         self.episodes = None                  # EpisodeTracker, made by the first account_episodes()
         self.visits = None                    # VisitTracker, made by the first account_visits()
+        self.bonus = None                     # BonusTracker, made by enable_bonus()
+        self.reward_train = self.reward       # what targets and hindsight records use: the shaped reward when a bonus is on
+        self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
         self.env_steps = 0
         self.episodes_done = 0
         self.return_sum = 0.0
@@ -139,6 +142,8 @@ class VecPPOTrainer:
                 a, logp = self.agent.act_batch(s4, p4, self.goal, None, offset_dev=offset_dev, offset_add=t * N)
             self.action[t], self.logp[t] = a, logp
             self.engine.step(a, step_out[t], autoreset=True, policy_idx=True)
+            if self.dir is not None:
+                self.dir[t].copy_(self._dir_now)
             torch.where((self.term[t] | self.trunc[t]) != 0, self._zero_age, self.age[t] + 1, out=self.age[t + 1])
         self._pred_valid = self.cache_predictions
 
@@ -182,7 +187,7 @@ class VecPPOTrainer:
         """Make the last 4 frames the history of the next rollout (and keep what hindsight relabelling needs of
         this one: episodes that end in the next rollout start here)."""
         T = self.T
-        self._hist.append((self.pos[4:4 + T].clone(), self.term.clone(), self.trunc.clone(), self.reward.clone(),
+        self._hist.append((self.pos[4:4 + T].clone(), self.term.clone(), self.trunc.clone(), self.reward_train.clone(),
                            self.age[0].clone()))
         self.frames_buf[:4] = self.frames_buf[T:T + 4].clone()
         self.pos[:4] = self.pos[T:T + 4].clone()
@@ -220,7 +225,7 @@ class VecPPOTrainer:
         start = self.env_steps // N - T                       # global step index of this rollout's first step
         if not self._hist or choices is not None:
             self.her = ppo_ops.her_relabel(self.pos[4:4 + T], self.term, self.trunc, self.age[0].contiguous(),
-                                           self.reward, choices, seed=self.her_seed, env_id0=self.engine.env_id0,
+                                           self.reward_train, choices, seed=self.her_seed, env_id0=self.engine.env_id0,
                                            step0=start, max_goals=max_goals, skip=skip)
             return self.her
         hist = list(self._hist)
@@ -228,7 +233,7 @@ class VecPPOTrainer:
         h = ppo_ops.her_relabel(torch.cat([x[0] for x in hist] + [self.pos[4:4 + T]]),
                                 torch.cat([x[1] for x in hist] + [self.term]),
                                 torch.cat([x[2] for x in hist] + [self.trunc]), hist[0][4],
-                                torch.cat([x[3] for x in hist] + [self.reward]), None,
+                                torch.cat([x[3] for x in hist] + [self.reward_train]), None,
                                 seed=self.her_seed, env_id0=self.engine.env_id0, step0=start - back, max_goals=max_goals,
                                 skip=skip)
         keep = h["t"] >= back
@@ -309,7 +314,7 @@ class VecPPOTrainer:
         done = (self.term | self.trunc).contiguous()
         goal = self.sample_goal(idx // N, idx % N, self.goal1.expand(total, 2), done.view(-1))
         v, nv = self._values_rollout(goal, done) if self.reuse_next_values else self._values(idx // N, idx % N, goal)
-        adv, target, ret = ppo_ops.gae(self.reward, v.view(T, N), nv.view(T, N), done, gamma=self.agent.gamma,
+        adv, target, ret = ppo_ops.gae(self.reward_train, v.view(T, N), nv.view(T, N), done, gamma=self.agent.gamma,
                                        lam=self.agent.gae_lambda, use_done_mask=self.agent.use_done_mask)
         critic_target = target if self.agent.gae_lambda == 0.0 else ret
         adv, critic_target = adv.view(-1), critic_target.view(-1)
@@ -424,6 +429,44 @@ class VecPPOTrainer:
             raise RuntimeError("episode_stats() before account_episodes()")
         out = self.episodes.read()
         out["mean_neg_logp"] = float(-self.logp.mean())
+        return out
+
+    # ------------------------------------------------------------------ exploration bonuses
+    def enable_bonus(self, kinds=("state",), scope="shared", scale=1.0):
+        """Shape the training reward with the reference's count-based bonuses (gym_minigrid/wrappers.py:34-102):
+        shape_rewards() then fills `reward_train`, which compute_targets(), relabel() and carry_over() use, while
+        `reward` -- and with it account_episodes(), running_score(), stats() and the HER switch -- stays extrinsic.
+        The action bonus keys on the env's action (policy index 4 is env action 6) and on the agent's direction after
+        the step, copied out of the engine's records once per step."""
+        from ..exploration import BonusTracker
+        self.bonus = BonusTracker(self.N, self.device, kinds, scope, scale, 17, 17, 7)
+        self.reward_train = torch.zeros_like(self.reward)
+        if "action" in self.bonus.kinds:
+            self.dir = torch.zeros((self.T, self.N), dtype=torch.int32, device=self.device)
+            self._dir_now = self.engine.dir_view()
+            self._graph = None
+        return self.bonus
+
+    def env_actions(self):
+        """The rollout's actions as the env saw them (Env_transact.env_action: policy index 4 -> actions.done = 6)."""
+        return torch.where(self.action == 4, 6, self.action).to(torch.int32)
+
+    def shape_rewards(self):
+        """reward_train <- reward + bonuses of the rollout just collected (call after collect(), before relabel());
+        terminated steps are counted but keep their reward, as under the reference's Env_transact.step.  One
+        ppo_bonus_scan call, no host synchronisation.  Without enable_bonus(): reward_train is reward, nothing runs."""
+        if self.bonus is not None:
+            self.bonus.account(self.pos[4:4 + self.T], self.env_actions(), self.reward, self.term, dir=self.dir,
+                               out=self.reward_train)
+        return self.reward_train
+
+    def bonus_stats(self):
+        """BonusTracker.read() plus the mean bonus per kind over the last shaped rollout and their sum, "mean"."""
+        if self.bonus is None:
+            raise RuntimeError("bonus_stats() before enable_bonus()")
+        out = self.bonus.read()
+        out["mean_by_kind"] = {k: float(b.mean()) for k, b in self.bonus.bonus.items()}
+        out["mean"] = sum(out["mean_by_kind"].values())
         return out
 
     def account_visits(self, her=None):

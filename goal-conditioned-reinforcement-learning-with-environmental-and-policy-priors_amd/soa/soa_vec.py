@@ -54,6 +54,8 @@ class VecSoATrainer(VecPPOTrainer):
             out = {"obs": None, "matrix": self.frames[t + 4], "pos": self.pos[t + 4], "reward": self.reward[t],
                    "terminated": self.term[t], "truncated": self.trunc[t]}
             self.engine.step(a, out, autoreset=True, policy_idx=True)
+            if self.dir is not None:
+                self.dir[t].copy_(self._dir_now)
             done = (self.term[t] | self.trunc[t]) != 0
             self.age[t + 1] = torch.where(done, torch.zeros_like(self.age[t]), self.age[t] + 1)
         self.pending_future = self.future[T].clone()

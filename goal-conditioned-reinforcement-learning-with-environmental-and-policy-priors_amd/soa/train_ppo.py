@@ -8,6 +8,8 @@ Reference-only flags that concerned the matplotlib window / absolute log paths a
 --dump_frames DIR --dump_envs K writes the rendered frames of the first K envs once per update (off by default).
 --visit_dir DIR writes the reference's heatmap MATRIX (heatmap.py:58-81; not the picture) once per update, counted on
 the device, and --track_buffer_file DIR its track dump (heatmap.py:79) for the first --dump_envs envs.
+--bonus {state,action,both} shapes the training reward with the reference's count-based exploration bonuses
+(gym_minigrid/wrappers.py:34-102), counted on the device; off by default.
 """
 import argparse
 import os
@@ -76,7 +78,26 @@ def build_parser():
                         "heatmap.py:58-81, hindsight records included while relabelling is on) and write "
                         "DIR/visits_<update>_rank<r>.npz with rollout, first_visit_map, terminal_map, cumulative [17, 17] "
                         "and other; adds the cells covered per episode and the share of room 2 to the log line; off by default")
+    p.add_argument("--bonus", default="none", choices=["none", "state", "action", "both"],
+                   help="count-based exploration bonus added to the TRAINING reward on the device: the reference's "
+                        "StateBonus (1/sqrt N(cell)), ActionBonus (1/sqrt N(cell, dir, action)) or both "
+                        "(gym_minigrid/wrappers.py:34-102); scores, episode returns and the HER switch stay extrinsic")
+    p.add_argument("--bonus_scope", default="shared", choices=["env", "shared"],
+                   help="env: one count table per env (N copies of the reference's wrapper); shared: one table for all envs "
+                        "of a rank, a time step counted as simultaneous.  With several ranks every rank keeps its own tables")
+    p.add_argument("--bonus_scale", type=float, default=1.0,
+                   help="factor on the bonus; 1.0 is the reference's value and dwarfs the task's rewards of -0.01 ... 0.9")
+    p.add_argument("--bonus_dir", default=None, metavar="DIR",
+                   help="with --bonus: write DIR/bonus_<update>_rank<r>.npz with the count maps (state [17, 17], action "
+                        "[4, 7, 17, 17], summed over the rank's envs) once per update; off by default")
     return p
+
+
+def dump_bonus(bs, path, update, rank):
+    os.makedirs(path, exist_ok=True)
+    maps = {k: bs[k] for k in ("state", "action") if k in bs}
+    maps.update({"other_" + k: np.int64(v) for k, v in bs["other"].items()})
+    np.savez(os.path.join(path, "bonus_%06d_rank%d.npz" % (update, rank)), **maps)
 
 
 def dump_frames(engine, path, update, k, tile_size):
@@ -178,11 +199,16 @@ def main(argv=None, predictor=False, soa=False):
     trainer = Trainer(agent, engine, args.rollout_steps, args.minibatch, frame_codes=args.frame_codes)
     trainer.use_graph = (not predictor and not soa) and (args.graph_rollout == "on" or
                                                          (args.graph_rollout == "auto" and hi - lo <= 512))
+    if args.bonus != "none":
+        trainer.enable_bonus(("state", "action") if args.bonus == "both" else (args.bonus,), args.bonus_scope,
+                             args.bonus_scale)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
         t0 = time.perf_counter()
         trainer.collect()
+        if args.bonus != "none":
+            trainer.shape_rewards()
         her = trainer.her_switch(her, score)                  # train_ppo.py:128-131 of the reference
         if her and agent.gae_lambda == 0.0:
             trainer.relabel()
@@ -210,6 +236,11 @@ def main(argv=None, predictor=False, soa=False):
             vs = trainer.visit_stats()
             dump_visits(vs, args.visit_dir, u, rank)
             tail = visit_fields(vs)
+        if args.bonus != "none":                                # behind every other field; every rank has its own counts
+            bs = trainer.bonus_stats()
+            if args.bonus_dir:
+                dump_bonus(bs, args.bonus_dir, u, rank)
+            tail += " bonus mean %.4f" % bs["mean"]
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

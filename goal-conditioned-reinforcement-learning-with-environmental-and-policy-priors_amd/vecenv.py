@@ -17,6 +17,10 @@ info["_episode"] like gym.vector's RecordEpisodeStatistics, accounted on the dev
 `record_visitation=True` adds info["visitation"] = {"cells": int32 [N], "first_visit": bool [N]} -- the distinct cells the
 running episode has stood on and whether this step's cell is new to it -- with the mask info["_visitation"] = done (where
 it is set, "cells" is the finished episode's coverage), and `env.visit_tracker` (visitation.VisitTracker) with the maps.
+`state_bonus=True` / `action_bonus=True` make step() return the reward shaped by the reference's StateBonus / ActionBonus
+wrappers (gym_minigrid/wrappers.py:34-102; `bonus_scope` "env" = one wrapper per env, "shared" = one count table for all
+envs; `bonus_scale` 1.0 = the reference), counted on the device by `env.bonus_tracker` (exploration.BonusTracker);
+info["reward_extrinsic"] keeps the env's own reward.  Episode statistics stay extrinsic.
 """
 import torch
 
@@ -28,7 +32,8 @@ _IDS = {"MiniGrid-twoarmy-17x17-v4": 4, "MiniGrid-twoarmy-17x17-v6": 6, "v4": 4,
 class TwoarmyVecEnv:
     def __init__(self, env_id="MiniGrid-twoarmy-17x17-v6", num_envs=4096, agent_view_size=17, device=None,
                  seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False,
-                 tile_size=17, highlight=False, record_visitation=False):
+                 tile_size=17, highlight=False, record_visitation=False, state_bonus=False, action_bonus=False,
+                 bonus_scope="env", bonus_scale=1.0):
         self.variant = _IDS[env_id]
         self.num_envs = int(num_envs)
         self.view_size = agent_view_size
@@ -51,6 +56,13 @@ class TwoarmyVecEnv:
         if record_visitation:
             from .visitation import VisitTracker
             self.visit_tracker = VisitTracker(self.num_envs, self.device, 17, 17)
+
+        self.bonus_tracker = None
+        if state_bonus or action_bonus:
+            from .exploration import BonusTracker
+            kinds = (("state",) if state_bonus else ()) + (("action",) if action_bonus else ())
+            self.bonus_tracker = BonusTracker(self.num_envs, self.device, kinds, bonus_scope, bonus_scale, 17, 17, 7)
+            self._shaped = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
 
     def reset(self):
         self.engine.reset(obs=self._out["obs"])
@@ -83,7 +95,14 @@ class TwoarmyVecEnv:
             vt.account(o["pos"], o["terminated"], o["truncated"])
             info["visitation"] = {"cells": vt.ep_cells[0], "first_visit": vt.first_visit[0].bool()}
             info["_visitation"] = done
-        return obs, o["reward"], o["terminated"].bool(), o["truncated"].bool(), info
+        reward = o["reward"]
+        if self.bonus_tracker is not None:
+            # the wrappers see the env's action (policy index 4 is actions.done = 6) and the direction in the records
+            env_a = torch.where(a == 4, 6, a).to(torch.int32) if self.policy_actions else a
+            reward = self.bonus_tracker.account(o["pos"], env_a, o["reward"], dir_ptr=self.engine.dir_ptr(),
+                                                out=self._shaped)
+            info["reward_extrinsic"] = o["reward"]
+        return obs, reward, o["terminated"].bool(), o["truncated"].bool(), info
 
     @property
     def state_matrix(self):

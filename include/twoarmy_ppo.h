@@ -163,6 +163,52 @@ int ppo_visit_carry_words(int width, int height, int N);
 int ppo_visit_hist(const float *pos, int T, int N, const uint8_t *mask, const int32_t *t_idx, const int32_t *n_idx, int B,
                    int width, int height, int64_t *counts, void *stream);
 
+/* Count-based exploration bonuses on the device (<package>/csrc/exploration_bonus.hip): the reference's StateBonus and
+ * ActionBonus wrappers (gym_minigrid/wrappers.py:69-102 and :34-66), `reward += 1 / math.sqrt(count)` with a count per
+ * agent_pos / per (agent_pos, agent_dir, action) that outlives reset().
+ *
+ * Keys.  state (kind 1): the cell of the after-step position exactly as ppo_visit_scan takes it (same device function);
+ * K = width * height + 1.  action (kind 2): (cell * 4 + dir) * n_actions + action with dir in 0..3 and action in
+ * [0, n_actions), 1 <= n_actions <= 8; K = width * height * 4 * n_actions + 1.  A step with an invalid cell, dir or
+ * action counts in the table's LAST slot (`other`), takes its bonus from that slot's count and addresses nothing else.
+ *
+ * Scopes.  env (0): one table per env = N independent copies of the wrapper; for every env in step order
+ * c = ++count[n][key].  shared (1): one table for all envs, a time step being simultaneous:
+ * c(t, n) = carry[key] + #{(t', n') : t' <= t, key(t', n') = key}, so all envs on one key in row t get the same bonus,
+ * which already includes the whole row; at N = 1 this is the env scope.  Counts are never cleared by an episode end.  In
+ * both scopes the result does not depend on how the steps are cut into launches.
+ *
+ * Arithmetic, IEEE double, one rounding per operation: b = scale * (1.0 / sqrt((double)c)); bonus_*[t][n] = (float)b;
+ * reward_out[t][n] = (float)(((double)reward[t][n] + b_state) + b_action)  (ActionBonus(StateBonus(env)); a kind that is
+ * off contributes 0.0), except where keep[t][n] != 0: there the counts still advance and reward_out = reward (the
+ * reference's Env_transact.step overwrites the reward of a terminated step above the wrappers, env_buffer.py:448-450).
+ *
+ * Tables, opaque except that all-zero = nothing counted; ppo_bonus_table_words(kind, scope, ...) 32-bit words each,
+ * 8-byte aligned:
+ *   env     uint32[N][K], env-major: an env's K counts are contiguous (1.2 KB state / 32 KB action for Twoarmy: 133 MB of
+ *           action counts at 4096 envs), because the wavefront that owns the env gathers and stores within that one span
+ *   shared  int64[K]
+ * so count of (cell, dir, action) = table[(n *) K + key] as laid out above; the last entry of a (per-env) table is other.
+ * env scope: one wavefront per env, the keys of up to 256 steps in LDS, a step's count = carried count + its rank among
+ * the earlier equal keys of the chunk + 1, the chunk's last occurrence of a key stores the new count; no atomics.  An
+ * env's column of the time-major pos / action / reward is read with stride N (adjacent envs share the cache lines).
+ * shared scope: a histogram per row in `workspace` (uint32[T][K] per kind, ppo_bonus_workspace_bytes; 4 MB for Twoarmy's
+ * action keys at T = 128), an inclusive scan over t per key that also updates the table, then a gather pass.
+ *
+ *   pos float[T][N][2] (8-byte aligned); action int32[T][N] (kind 2 only); dir int32, element (t, n) at
+ *   dir[t * dir_stride_t + n * dir_stride_n] (NULL: direction 0; stride_t = 0: one value per env, e.g. the engine's records);
+ *   reward float[T][N] | NULL (needed for reward_out); keep uint8[T][N] | NULL; kind_mask 1 state, 2 action, 3 both;
+ *   bonus_state, bonus_action, reward_out float[T][N], each | NULL; reward_out may alias reward.
+ * TW_E_ARG and nothing launched: NULL or misaligned pos, a missing table / action / workspace that the kinds and the scope
+ * need, reward_out without reward, width or height outside 1..32, n_actions outside 1..8, kind_mask outside 1..3, scope
+ * outside 0..1, negative T, N or dir strides, T * N >= 2^31.  T * N == 0 returns 0 and launches nothing. */
+int ppo_bonus_table_words(int kind, int scope, int width, int height, int n_actions, int N);
+int64_t ppo_bonus_workspace_bytes(int kind_mask, int scope, int T, int width, int height, int n_actions);
+int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, long dir_stride_t, long dir_stride_n,
+                   const float *reward, const uint8_t *keep, int T, int N, int width, int height, int n_actions,
+                   int kind_mask, int scope, double scale, void *state_table, void *action_table, float *bonus_state,
+                   float *bonus_action, float *reward_out, void *workspace, void *stream);
+
 /* Hindsight experience replay over one time-major rollout: replaces Buffer_gridworld.her_func
  * (soa/env_buffer.py:101-143, called from soa/train_ppo.py:128-134 at every episode end).  For every episode
  * [s0, t1] that starts (age0[n] == 0 or the step after a done) and ends (terminated | truncated) inside the

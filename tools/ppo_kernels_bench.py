@@ -122,3 +122,19 @@ for label, pv in (("rollout-like walks", walk.to(dev)), ("uniform cells", p2)):
     ref = torch.bincount((pv[..., 0] * 17 + pv[..., 1]).long().view(-1), minlength=289)
     one = ppo_ops.visit_hist(pv, torch.zeros(W * H + 1, dtype=torch.int64, device=dev), W, H)
     assert torch.equal(one[:289], ref) and int(one[289]) == 0
+
+# Exploration bonuses (csrc/exploration_bonus.hip): one BonusTracker.account() of a 4096 x 128 rollout per kind mask and
+# scope, on the same two kinds of positions; ppo_episode_scan and ppo_visit_scan above are the yardsticks.
+from twoarmy_amd.exploration import BonusTracker  # noqa: E402
+act7 = torch.randint(0, 7, (T, N), generator=g, dtype=torch.int32).to(dev)
+dir_tn = torch.randint(0, 4, (T, N), generator=g, dtype=torch.int32).to(dev)
+shaped = torch.empty_like(rw5)
+for label, pv in (("rollout-like walks", walk.to(dev)), ("uniform cells", p2)):
+    for scope in ("env", "shared"):
+        for kinds in (("state",), ("action",), ("state", "action")):
+            bt = BonusTracker(N, dev, kinds, scope, 1.0, W, H, 7)
+            moved = T * N * (8 + 4 + 4 + 4 * len(kinds)) + (T * N * 8 if "action" in kinds else 0)
+            report("ppo_bonus_scan %s, %s scope (%s)" % ("+".join(kinds), scope, label), moved,
+                   timed(lambda: bt.account(pv, act7, rw5, term, dir=dir_tn, out=shaped)),
+                   "one wavefront per env" if scope == "env" else "row histograms + key scan + gather")
+            del bt
