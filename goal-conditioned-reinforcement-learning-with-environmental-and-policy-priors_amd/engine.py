@@ -350,6 +350,26 @@ class TwoarmyEngine:
         _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
         return rec.value + 4 * FIELDS["DIR"], 0, TW_REC_WORDS
 
+    def agent_ptrs(self):
+        """(address of TW_AX, of TW_AY, of TW_DIR, stride in int32 elements) in the engine's records: the `agent_ptrs`
+        argument of minigrid_obs.full_obs / goal_direction, which then read the agent where it lives."""
+        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
+        return tuple(rec.value + 4 * FIELDS[k] for k in ("AX", "AY", "DIR")) + (TW_REC_WORDS,)
+
+    def plane_views(self):
+        """(type, colour) uint8[N, 289] device views of the engine's own planes (tw_state_ptrs; no copy): cell (x, y)
+        at y*17 + x.  They show the state of the moment a kernel reads them."""
+        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
+        out = []
+        for p in (ty, co):
+            t = torch.as_tensor(_DevSpan(self, p.value, self.num_envs * TW_CELLS), device=self.device)
+            if t.data_ptr() != p.value:
+                raise _lib.TwoarmyLibraryError("torch did not alias the engine's planes")
+            out.append(t.view(self.num_envs, TW_CELLS))
+        return tuple(out)
+
     def dir_view(self):
         """int32[N] strided device view of the same directions (no copy)."""
         addr = self.dir_ptr()[0] - 4 * FIELDS["DIR"]

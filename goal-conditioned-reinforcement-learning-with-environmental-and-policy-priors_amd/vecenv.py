@@ -21,6 +21,15 @@ it is set, "cells" is the finished episode's coverage), and `env.visit_tracker` 
 wrappers (gym_minigrid/wrappers.py:34-102; `bonus_scope` "env" = one wrapper per env, "shared" = one count table for all
 envs; `bonus_scale` 1.0 = the reference), counted on the device by `env.bonus_tracker` (exploration.BonusTracker);
 info["reward_extrinsic"] keeps the env's own reward.  Episode statistics stay extrinsic.
+`observation=` selects what reset() / step() return first and what info["final_observation"] holds (minigrid_obs, the
+reference's observation wrappers, gym_minigrid/wrappers.py): "image" (default) the egocentric view uint8[N, V, V, 3];
+"onehot" its one-hot uint8[N, V, V, 21]; "flat" float32[N, V*V*3 + 96*28], the image and the one-hot mission string;
+"full" the whole grid with the agent stamped in, uint8[N, 17, 17, 3]; "symbolic" int32[N, 17, 17, 3] = (x, y, idx).
+`goal_direction="slope" | "angle"` adds info["goal_direction"] float64[N] (DirectionObsWrapper) for the state `obs`
+shows, and info["final_goal_direction"] under auto-reset.  "onehot" and "flat" are passes over the engine's image;
+"full", "symbolic" and the goal direction read the engine's state after the step, so with autoreset=True the env steps
+without the in-kernel reset, emits the final observation, resets the finished envs (engine.reset(mask=done)) and emits
+again; everything else the env returns is what the default env returns.
 """
 import torch
 
@@ -33,7 +42,7 @@ class TwoarmyVecEnv:
     def __init__(self, env_id="MiniGrid-twoarmy-17x17-v6", num_envs=4096, agent_view_size=17, device=None,
                  seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False,
                  tile_size=17, highlight=False, record_visitation=False, state_bonus=False, action_bonus=False,
-                 bonus_scope="env", bonus_scale=1.0):
+                 bonus_scope="env", bonus_scale=1.0, observation="image", goal_direction=None):
         self.variant = _IDS[env_id]
         self.num_envs = int(num_envs)
         self.view_size = agent_view_size
@@ -48,6 +57,36 @@ class TwoarmyVecEnv:
         self.goal_yx = torch.tensor([2.0, 14.0], device=self.device).expand(self.num_envs, 2)
         self.single_observation_shape = (agent_view_size, agent_view_size, 3)
         self.single_action_n = 5 if policy_actions else 7
+        V = agent_view_size
+        if observation not in ("image", "onehot", "full", "symbolic", "flat"):
+            raise ValueError("observation must be image, onehot, full, symbolic or flat, not %r" % (observation,))
+        if goal_direction not in (None, "slope", "angle"):
+            raise ValueError("goal_direction must be None, slope or angle, not %r" % (goal_direction,))
+        self.observation, self.goal_direction = observation, goal_direction
+        # the kinds read from the engine's state (not from its image) take the reset out of the step kernel
+        self._state_obs = observation in ("full", "symbolic") or goal_direction is not None
+        self._goal_index = self._angle_table = self._state_src = None
+        if observation != "image" or goal_direction is not None:
+            from . import minigrid_obs
+            self._mo = minigrid_obs
+            N, d = self.num_envs, self.device
+            if observation == "onehot":
+                self.single_observation_shape = (V, V, minigrid_obs.ONEHOT_BITS)
+                self._obs_buf = [torch.empty((N, V, V, minigrid_obs.ONEHOT_BITS), dtype=torch.uint8, device=d) for _ in range(2)]
+                self._init_kind = minigrid_obs.onehot(self._init_obs)
+            elif observation == "flat":
+                self._tail = torch.from_numpy(minigrid_obs.mission_tail("get to the green goal square")).to(d)
+                self.single_observation_shape = (V * V * 3 + self._tail.numel(),)
+                self._obs_buf = [torch.empty((N,) + self.single_observation_shape, dtype=torch.float32, device=d) for _ in range(2)]
+                self._init_kind = minigrid_obs.flat_obs(self._init_obs, self._tail)
+            elif observation in ("full", "symbolic"):
+                self.single_observation_shape = (17, 17, 3)
+                dt = torch.uint8 if observation == "full" else torch.int32
+                self._obs_buf = [torch.empty((N, 17, 17, 3), dtype=dt, device=d) for _ in range(2)]
+            if goal_direction is not None:
+                self._dir_buf = [torch.empty(N, dtype=torch.float64, device=d) for _ in range(2)]
+                if goal_direction == "angle":
+                    self._angle_table = minigrid_obs.angle_table(17, 17, d)
         self.episode_tracker = None
         if record_episode_statistics:
             from .episode_stats import EpisodeTracker
@@ -70,16 +109,64 @@ class TwoarmyVecEnv:
             self.episode_tracker.reset()
         if self.visit_tracker is not None:
             self.visit_tracker.reset()
-        return self._out["obs"]
+        if self.goal_direction is not None and self._goal_index is None:
+            self._goal_index = self._mo.goal_index(self._state()[0], 17, 17)                   # once: goal_position is cached
+        return self._emit(self._out["obs"], 0)
+
+    # ------------------------------------------------------------------ observation kinds (minigrid_obs)
+    def _emit(self, image, slot):
+        """The chosen observation of the engine's image / current state, into buffer `slot` (0 = returned, 1 = final)."""
+        kind = self.observation
+        if kind == "image":
+            return image
+        mo, out = self._mo, self._obs_buf[slot]
+        if kind == "onehot":
+            return mo.onehot(image, out=out)
+        if kind == "flat":
+            return mo.flat_obs(image, self._tail, out=out)
+        ty, co, agent = self._state()
+        if kind == "full":
+            return mo.full_obs(ty, co, None, 17, 17, agent_ptrs=agent, out=out)
+        return mo.symbolic_obs(ty, 17, 17, out=out)
+
+    def _state(self):
+        """(type plane, colour plane, agent_ptrs) of the engine: views and addresses that hold for the engine's life."""
+        if self._state_src is None:
+            self._state_src = self.engine.plane_views() + (self.engine.agent_ptrs(),)
+        return self._state_src
+
+    def _emit_direction(self, slot):
+        if self._goal_index is None:                     # once, as DirectionObsWrapper caches goal_position
+            self._goal_index = self._mo.goal_index(self._state()[0], 17, 17)
+        return self._mo.goal_direction(self._goal_index, 17, 17, agent_ptrs=self._state()[2],
+                                       mode=self.goal_direction, table=self._angle_table, out=self._dir_buf[slot])
 
     def step(self, actions):
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()
         o = self._out
-        self.engine.step(a, o, autoreset=self.autoreset, policy_idx=self.policy_actions)
+        self.engine.step(a, o, autoreset=self.autoreset and not self._state_obs, policy_idx=self.policy_actions)
         done = (o["terminated"] | o["truncated"]).bool()
         info = {}
         obs = o["obs"]
-        if self.autoreset:
+        if self._state_obs:
+            # the state after the step is the observation's source: final observation, reset of the finished envs, again
+            if self.autoreset:
+                info["final_observation"] = self._emit(obs, 1)
+                info["_final_observation"] = done
+                if self.goal_direction is not None:
+                    info["final_goal_direction"] = self._emit_direction(1)
+                self.engine.reset(mask=o["terminated"] | o["truncated"])
+                obs = torch.where(done.view(-1, 1, 1, 1), self._init_obs, obs)
+            obs = self._emit(obs, 0)
+            if self.goal_direction is not None:
+                info["goal_direction"] = self._emit_direction(0)
+        elif self.observation != "image":
+            obs = self._emit(obs, 1 if self.autoreset else 0)
+            if self.autoreset:
+                info["final_observation"] = obs
+                info["_final_observation"] = done
+                obs = torch.where(done.view((-1,) + (1,) * (obs.dim() - 1)), self._init_kind, obs)
+        elif self.autoreset:
             info["final_observation"] = obs
             info["_final_observation"] = done
             obs = torch.where(done.view(-1, 1, 1, 1), self._init_obs, obs)

@@ -4,6 +4,10 @@ Prints one JSON line per configuration: views/s and the HBM roofline fraction fo
 (window cells of three planes read + image and mask written).
 
   python tools/view_bench.py [--envs 262144] [--size 17] [--iters 20]
+  python tools/view_bench.py --obs [--obs_envs 4096]      the observation wrappers (minigrid_obs) instead: every kind at
+                                                          view sizes 17 and 7, each beside a torch composition of the
+                                                          same result and the fill_ rate of a buffer of its size; median
+                                                          and range of --repeats windows of --obs_iters launches
 """
 import argparse
 import json
@@ -18,8 +22,97 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=262144)
 ap.add_argument("--size", type=int, default=17)
 ap.add_argument("--iters", type=int, default=20)
+ap.add_argument("--obs", action="store_true")
+ap.add_argument("--obs_envs", type=int, default=4096)
+ap.add_argument("--obs_iters", type=int, default=200)
+ap.add_argument("--repeats", type=int, default=9)
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
+
+
+def obs_rows():
+    """One JSON line per (kind, view size, implementation)."""
+    import statistics
+    import torch.nn.functional as F
+    from twoarmy_amd import minigrid_obs as mo
+    N, S = a.obs_envs, 17
+    g = torch.Generator(device="cpu").manual_seed(2)
+    ty = torch.tensor([1, 1, 1, 1, 1, 2, 2, 6, 8], dtype=torch.uint8)[torch.randint(0, 9, (N, S * S), generator=g)].to(dev)
+    co = torch.randint(0, 6, (N, S * S), generator=g, dtype=torch.uint8).to(dev)
+    ax, ay, ad = (torch.randint(0, hi, (N,), generator=g, dtype=torch.int32).to(dev) for hi in (S, S, 4))
+    tail = torch.from_numpy(mo.mission_tail("get to the green goal square")).to(dev)
+    env_idx = torch.arange(N, device=dev)
+
+    def window(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.obs_iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.obs_iters * 1e3                         # us per call
+
+    def row(kind, V, impl, fn, out_bytes, check=None):
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        us = sorted(window(fn) for _ in range(a.repeats))
+        med = statistics.median(us)
+        print(json.dumps({"kind": kind, "view": V, "impl": impl, "envs": N, "out_MB": out_bytes / 1e6, "us_median": med,
+                          "us_min": us[0], "us_max": us[-1], "store_GBs": out_bytes / med / 1e3, "equal": check}), flush=True)
+
+    for V in (17, 7):
+        img = torch.stack([ty[:, :V * V], co[:, :V * V], torch.zeros_like(ty[:, :V * V])], -1).view(N, V, V, 3).contiguous()
+        long = img.long()
+        oh = torch.empty((N, V, V, 21), dtype=torch.uint8, device=dev)
+        comp = lambda: torch.cat([F.one_hot(long[..., 0], 12), F.one_hot(long[..., 1], 6), F.one_hot(long[..., 2], 3)], -1).to(torch.uint8)  # noqa: E731
+        mo.onehot(img, out=oh)
+        row("onehot", V, "mg_obs_onehot", lambda: mo.onehot(img, out=oh), oh.numel(), bool(torch.equal(oh, comp())))
+        row("onehot", V, "torch one_hot+cat", comp, oh.numel())
+        row("onehot", V, "torch fill_", lambda: oh.fill_(1), oh.numel())
+        fl = torch.empty((N, V * V * 3 + tail.numel()), dtype=torch.float32, device=dev)
+        compf = lambda: torch.cat([img.view(N, -1).float(), tail.expand(N, -1)], 1)                            # noqa: E731
+        mo.flat_obs(img, tail, out=fl)
+        row("flat", V, "mg_obs_flat", lambda: mo.flat_obs(img, tail, out=fl), fl.numel() * 4, bool(torch.equal(fl, compf())))
+        row("flat", V, "torch float+cat", compf, fl.numel() * 4)
+        row("flat", V, "torch fill_", lambda: fl.fill_(1), fl.numel() * 4)
+    full = torch.empty((N, S, S, 3), dtype=torch.uint8, device=dev)
+    stamp = torch.stack([torch.full_like(ad, 10), torch.zeros_like(ad), ad], -1).to(torch.uint8)
+
+    def compfull():
+        e = ty.view(N, S, S) <= 1
+        o = torch.stack([torch.where(e, 1, ty.view(N, S, S)), torch.where(e, 0, co.view(N, S, S)), torch.zeros_like(e, dtype=torch.uint8)],
+                        -1).permute(0, 2, 1, 3).contiguous()
+        o[env_idx, ax.long(), ay.long()] = stamp
+        return o
+    mo.full_obs(ty, co, None, S, S, ax, ay, ad, out=full)
+    row("full", S, "mg_obs_full", lambda: mo.full_obs(ty, co, None, S, S, ax, ay, ad, out=full), full.numel(),
+        bool(torch.equal(full, compfull())))
+    row("full", S, "torch where+permute+stamp", compfull, full.numel())
+    sym = torch.empty((N, S, S, 3), dtype=torch.int32, device=dev)
+    xs, ys = torch.meshgrid(torch.arange(S, device=dev, dtype=torch.int32), torch.arange(S, device=dev, dtype=torch.int32), indexing="ij")
+
+    def compsym():
+        t = ty.view(N, S, S).int()
+        return torch.stack([xs.expand(N, S, S), ys.expand(N, S, S), torch.where(t <= 1, -1, t)], -1)
+    mo.symbolic_obs(ty, S, S, out=sym)
+    row("symbolic", S, "mg_obs_symbolic", lambda: mo.symbolic_obs(ty, S, S, out=sym), sym.numel() * 4, bool(torch.equal(sym, compsym())))
+    row("symbolic", S, "torch where+stack", compsym, sym.numel() * 4)
+    ty[:, 2 * S + 14] = 8
+    k = mo.goal_index(ty, S, S)
+    tab = mo.angle_table(S, S, dev)
+    gd = torch.empty(N, dtype=torch.float64, device=dev)
+    row("goal_index", S, "mg_obs_goal_index", lambda: mo.goal_index(ty, S, S), 4 * N)
+    for mode in ("slope", "angle"):
+        row("goal_direction " + mode, S, "mg_obs_goal_direction",
+            lambda: mo.goal_direction(k, S, S, ax, ay, mode=mode, table=tab, out=gd), 8 * N)
+    row("goal_direction slope", S, "torch div", lambda: (14 - ay).double() / (2 - ax).double(), 8 * N)
+    row("goal_direction angle", S, "torch div+atan", lambda: torch.atan((14 - ay).double() / (2 - ax).double()), 8 * N)
+
+
+if a.obs:
+    obs_rows()
+    sys.exit(0)
 N, W = a.envs, a.size
 g = torch.Generator(device="cpu").manual_seed(1)
 ty = torch.tensor([1, 1, 1, 1, 1, 2, 2, 4, 5, 6, 8], dtype=torch.uint8)[torch.randint(0, 11, (N, W * W), generator=g)].to(dev)
