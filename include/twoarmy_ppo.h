@@ -86,7 +86,8 @@ int ppo_gather_stack(const float *frames, int frame_pitch, const float *pos_fram
 
 /* Same, for frames stored as uint8 codes (tw_step/tw_rollout with TW_F_MATRIX_CODE, twoarmy.h): frame_pitch in
  * bytes, each code expanded to its matrix_env value {0: 0.9, 1: -0.9, 2: -0.5, 3: 0.3}; init_frame stays float[289].
- * BASELINE config 5 ("reduced-precision frames"): the stored rollout is 4x smaller and the expansion is exact. */
+ * BASELINE config 5 ("reduced-precision frames"): the stored rollout is 4x smaller and the expansion is exact.
+ * Only the codes 0..3 are defined; what a larger byte expands to is unspecified. */
 int ppo_gather_stack_u8(const uint8_t *frames, int frame_pitch, const float *pos_frames, int N,
                         const int32_t *k_idx, const int32_t *n_idx, const int32_t *age, const float *init_frame,
                         const float *init_pos, int B, float *out, float *pos_out, void *stream);
@@ -228,7 +229,9 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
  *       perm[j + word_j % (U - j)]  (max_goals <= 4).
  * Two passes: offsets == NULL -> only counts[n] (records produced by env n) is written; then, with
  * offsets = exclusive prefix sum of counts (int64[N]), the records are written at offsets[n] ....
- *   pos float[T][N][2] (achieved (y,x) after each step), reward float[T][N], age0 int32[N] (episode age at t=0) */
+ *   pos float[T][N][2] (achieved (y,x) after each step), reward float[T][N], age0 int32[N] (episode age at t=0)
+ * Positions must be finite (+0.0 and -0.0 are one position, as for np.unique); the records of an episode that holds a NaN
+ * or an infinity are unspecified. */
 int ppo_her_relabel(const float *pos, const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0,
                     const float *reward, const int32_t *choices, uint64_t seed, uint32_t env_id0, uint32_t step0, int T,
                     int N, int max_goals, const int64_t *offsets, int32_t *counts, int32_t *out_t, int32_t *out_n,

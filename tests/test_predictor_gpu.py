@@ -136,7 +136,7 @@ def test_lstm_cell_kernel_vs_torch():
     pre-activations (saturated gates) and a batch that does not fill the last workgroup."""
     from twoarmy_amd import ppo_ops
     torch.manual_seed(8)
-    for B, H, scale in ((3, 1024, 1.0), (2048, 1024, 4.0), (77, 64, 30.0)):
+    for B, H, scale in ((3, 1024, 1.0), (2048, 1024, 4.0), (77, 64, 30.0), (1, 4, 1.0), (513, 4, 1.0)):
         gates = torch.randn(B, 4 * H, device=DEV) * scale
         c0 = torch.randn(B, H, device=DEV)
         i, f, g, o = gates.double().chunk(4, dim=1)
@@ -160,6 +160,57 @@ def test_lstm_cell_kernel_vs_torch():
         c4 = c0.clone()
         h4 = ppo_ops.lstm_cell_((xin[:, 2] + bias).contiguous(), c4)
         assert float((h3 - h4).abs().max()) < 2e-6 and float((c3 - c4).abs().max()) < 2e-6 * max(1.0, float(c4.abs().max()))
+    # pre-activations at and far beyond saturation (exp(88) is the last finite fp32 power, exp(104) and exp(1e4) are not),
+    # each magnitude in each gate with either sign, the other gates random: finite, and float64's value
+    H, mags = 8, (88.0, 104.0, 1e4)
+    rows = [(q, s * m) for q in range(4) for m in mags for s in (1.0, -1.0)]
+    gates = torch.randn(len(rows) + len(mags), 4 * H, device=DEV)
+    for r, (q, v) in enumerate(rows):
+        gates[r, q * H:(q + 1) * H] = v
+    for r, m in enumerate(mags, len(rows)):                  # f saturates high, i saturates low: the cell keeps its state
+        gates[r, 0:H], gates[r, H:2 * H] = -m, m
+    c0 = torch.randn(gates.shape[0], H, device=DEV)
+    c0 = torch.where(c0 < 0, c0 - 0.1, c0 + 0.1)             # |c| >= 0.1: sigmoid(-88) = 6e-39 is far below half an ulp of it
+    i, f, g, o = gates.double().chunk(4, dim=1)
+    c_want = torch.sigmoid(f) * c0.double() + torch.sigmoid(i) * torch.tanh(g)
+    h_want = torch.sigmoid(o) * torch.tanh(c_want)
+    c = c0.clone()
+    h = ppo_ops.lstm_cell_(gates, c)
+    assert torch.isfinite(h).all() and torch.isfinite(c).all()
+    assert float((c.double() - c_want).abs().max()) < 2e-6 * max(1.0, float(c_want.abs().max()))
+    assert float((h.double() - h_want).abs().max()) < 2e-6
+    assert torch.equal(c[len(rows):], c0[len(rows):])
+    # the same rows with the saturating value split over GEMM result, input projection and bias (each term finite)
+    c2 = c0.clone()
+    h2 = ppo_ops.lstm_cell_((gates * 0.5).contiguous(), c2, (gates * 0.25).contiguous(), None)
+    c3 = c0.clone()
+    h3 = ppo_ops.lstm_cell_((gates * 0.75).contiguous(), c3)
+    assert torch.equal(h2, h3) and torch.equal(c2, c3)       # 0.5 x + 0.25 x == 0.75 x exactly in binary floating point
+
+
+def test_lstm_cell_rejections_launch_nothing():
+    """H % 4, no pre-activations at all, pointers off 16-byte alignment by one float, a row pitch shorter than a row or
+    no multiple of 4 floats, an empty batch: TW_E_ARG on the host, c and h untouched."""
+    import ctypes as C
+    from twoarmy_amd import _lib, ppo_ops
+    lib = _lib.lib()
+    B, H = 5, 8
+    store = {k: torch.full((B * 4 * H + 8,), 0.5, device=DEV) for k in ("ga", "gb", "bias", "c", "h")}
+
+    def call(B_=B, H_=H, ldb=4 * H, off=(), null=()):
+        p = {k: (None if k in null else C.c_void_p(v.data_ptr() + (4 if k in off else 0))) for k, v in store.items()}
+        rc = lib.ppo_lstm_cell(p["ga"], p["gb"], ldb, p["bias"], p["c"], p["h"], B_, H_, ppo_ops._stream(store["c"]))
+        torch.cuda.synchronize()
+        return rc
+
+    bad = [dict(H_=6), dict(H_=0), dict(null=("ga", "gb")), dict(null=("c",)), dict(null=("h",)), dict(B_=0), dict(B_=-1),
+           dict(ldb=4 * H - 4), dict(ldb=4 * H + 2)]
+    bad += [dict(off=(k,)) for k in ("c", "h", "gb", "bias", "ga")]
+    for kw in bad:
+        assert call(**kw) == -1, kw
+        assert all(bool((v == 0.5).all()) for v in store.values()), kw
+    assert call() == 0 and call(null=("gb",)) == 0 and call(null=("ga", "bias")) == 0 and call(ldb=4 * H + 4, B_=4) == 0
+    assert not bool((store["h"][:B * H] == 0.5).all()) and bool((store["h"][B * H:] == 0.5).all())
 
 
 def test_fused_encoder_path_equals_the_module_path():
