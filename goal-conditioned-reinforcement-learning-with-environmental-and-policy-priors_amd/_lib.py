@@ -95,6 +95,8 @@ _SIGS.update({
     "mg_render_constants": (C.c_int, [C.POINTER(C.c_double)]),
     "mg_render_build_atlas": (C.c_int, [_i, _vp, _vp]),
     "mg_render": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp]),
+    "mg_render_pov": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _vp,
+                                _vp]),
     "mg_highlight_mask": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     # include/minigrid_obs.h
     "mg_obs_onehot": (C.c_int, [_vp, _i64, _i, _i, _vp, _i64, _vp, _vp]),

@@ -4,7 +4,9 @@
  *   mg_render_atlas_kernel   one workgroup per atlas tile: 3 x 3 supersampled rasterisation in float64, in the
  *                            operation order of the reference's rendering.py / Grid.render_tile, so that the bytes
  *                            are the reference's.  Runs once per tile size.
- *   mg_render_kernel         the frame: a gather of atlas bytes selected by the world planes.  The body of every
+ *   mg_render_kernel<Cells>  the frame: a gather of atlas bytes selected by the cells the frame shows -- the world's
+ *                            (mg_world_cells, mg_render) or the agent's rotated, wall-padded view (mg_view_cells,
+ *                            mg_render_pov); the gather itself is written once.  The body of every
  *                            frame leaves as aligned 16-byte stores, its two ends byte by byte.  Its byte budget is
  *                            that of a store stream; measured, the gather's index arithmetic and unaligned fetches
  *                            bound it well below the store rate.
@@ -22,6 +24,7 @@
 #include "minigrid_render.h"
 #include "minigrid_view.h"
 #include "twoarmy.h"
+#include "view_map.h"
 
 #pragma clang fp contract(off)
 
@@ -181,15 +184,95 @@ __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_atlas_kernel(int 
 }
 
 /* ------------------------------------------------------------------------------------------------ frame */
+struct mg_cell { int type, colour, state, agent, highlight; };     /* agent: direction, -1 = the agent is not here */
+
+/* The two pictures a frame can show.  A cell source is built per output frame and answers "what does cell
+ * cy * W + cx of this frame's W x H cells hold"; the gather below is written against that question alone. */
+
+/* Grid.render of the world itself (mg_render): frame cell = world cell. */
+struct mg_world_cells {
+    struct args {
+        const uint8_t *type, *colour, *state, *highlight;
+        const int32_t *agent_x, *agent_y, *agent_dir;
+        int astride;
+    };
+    const uint8_t *ty, *co, *st, *hm;
+    int acell, ad;
+    __device__ mg_world_cells(const args &a, int e, int W, int H)
+    {
+        const int HW = W * H;
+        ty = a.type + (int64_t)e * HW;
+        co = a.colour + (int64_t)e * HW;
+        st = a.state ? a.state + (int64_t)e * HW : nullptr;
+        hm = a.highlight ? a.highlight + (int64_t)e * HW : nullptr;
+        const int ax = a.agent_x[(int64_t)e * a.astride], ay = a.agent_y[(int64_t)e * a.astride];
+        ad = a.agent_dir[(int64_t)e * a.astride] & 3;
+        acell = (ax >= 0 && ax < W && ay >= 0 && ay < H) ? ay * W + ax : -1;
+    }
+    __device__ mg_cell at(int cell) const
+    {
+        return {ty[cell], co[cell], st ? st[cell] : 0, cell == acell ? ad : -1, hm ? hm[cell] != 0 : 0};
+    }
+};
+
+/* get_pov_render (mg_render_pov): the V x V frame cell (i, j) is the world cell gen_obs_grid puts there (view_map.h),
+ * a grey wall outside the world; the highlight is the view's visibility mask, and a cell the mask hides is drawn
+ * empty (process_vis clears it in the grid it is handed, minigrid.py:827-830); the agent's own cell (V / 2, V - 1)
+ * holds the carried object, placed after process_vis, under the triangle of direction 3. */
+struct mg_view_cells {
+    struct args {
+        const uint8_t *type, *colour, *state, *carrying, *vis_mask;
+        const int32_t *agent_x, *agent_y, *agent_dir;
+        int astride, width, height;
+    };
+    const uint8_t *ty, *co, *st, *vm;
+    int W, H, V, topx, topy, rot;
+    mg_cell carried;
+    __device__ mg_view_cells(const args &a, int e, int v, int)
+    {
+        W = a.width; H = a.height; V = v;
+        const int HW = W * H;
+        ty = a.type + (int64_t)e * HW;
+        co = a.colour + (int64_t)e * HW;
+        st = a.state ? a.state + (int64_t)e * HW : nullptr;
+        vm = a.vis_mask ? a.vis_mask + (int64_t)e * V * V : nullptr;
+        const int dir = a.agent_dir[(int64_t)e * a.astride] & 3;
+        mg_view_top(a.agent_x[(int64_t)e * a.astride], a.agent_y[(int64_t)e * a.astride], dir, V, topx, topy);
+        rot = (dir + 1) & 3;
+        const uint8_t *c = a.carrying ? a.carrying + (int64_t)e * 3 : nullptr;
+        carried = (c && c[0] != 0) ? mg_cell{c[0], c[1], c[2], 3, 0} : mg_cell{1, 0, 0, 3, 0};
+    }
+    __device__ mg_cell at(int cell) const
+    {
+        const int j = cell / V, i = cell - j * V;           /* once per cell and workgroup, not per byte */
+        const int lit = vm ? vm[i * V + j] != 0 : 1;
+        mg_cell q = {2, 5, 0, -1, 0};                       /* Grid.slice: outside the world -> Wall() */
+        if (i == V / 2 && j == V - 1) {
+            q = carried;
+        } else if (!lit) {
+            q.type = 1; q.colour = 0;
+        } else {
+            int si, sj;
+            mg_view_to_slice(rot, V, i, j, si, sj);
+            const int x = topx + si, y = topy + sj;
+            if (x >= 0 && x < W && y >= 0 && y < H) {
+                const int o = y * W + x;
+                q.type = ty[o]; q.colour = co[o]; q.state = st ? st[o] : 0;
+            }
+        }
+        q.highlight = lit;
+        return q;
+    }
+};
+
 /* Workgroup b of frame o owns the 16-byte-aligned chunks [b * MG_RENDER_CHUNKS, (b + 1) * MG_RENDER_CHUNKS) of the
  * frame, counted from the aligned address at or below the frame's first byte.  It first resolves the cells of the
  * tile rows its span touches into atlas tile indices (LDS), then every lane builds whole chunks: a chunk walks the
  * frame's bytes as (tile row j, pixel row r, tile column i, byte k of the tile's run of tile_size * 3 bytes), fetching
- * four source bytes at a time while they stay inside one run. */
+ * four source bytes at a time while they stay inside one run.  W x H are the frame's cells; what they show is Cells'. */
+template <class Cells>
 __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_kernel(
-    const uint8_t *__restrict__ type, const uint8_t *__restrict__ colour, const uint8_t *__restrict__ state, int N, int W,
-    int H, const int32_t *__restrict__ agent_x, const int32_t *__restrict__ agent_y, const int32_t *__restrict__ agent_dir,
-    int astride, const int32_t *__restrict__ env_index, const uint8_t *__restrict__ highlight,
+    typename Cells::args src_args, int N, int W, int H, const int32_t *__restrict__ env_index,
     const uint8_t *__restrict__ atlas, int ts, uint8_t *__restrict__ frame, int64_t pitch, int32_t *__restrict__ error,
     int blocks_per_frame)
 {
@@ -213,22 +296,20 @@ __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_kernel(
     const int c1 = min(c0 + MG_RENDER_CHUNKS, total);
     const int p_lo = max(0, 16 * c0 - s), p_hi = min(F, 16 * c1 - s);          /* frame bytes of this workgroup */
     const int j0 = p_lo / B, j1 = (p_hi - 1) / B;
-    const uint8_t *ty = type + (int64_t)e * HW, *co = colour + (int64_t)e * HW;
-    const uint8_t *st = state ? state + (int64_t)e * HW : nullptr, *hm = highlight ? highlight + (int64_t)e * HW : nullptr;
-    const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride], ad = agent_dir[(int64_t)e * astride];
-    const int acell = (ax >= 0 && ax < W && ay >= 0 && ay < H) ? ay * W + ax : -1;
+    const Cells src(src_args, e, W, H);
 
     for (int t = tid; t < (j1 - j0 + 1) * W; t += MG_RENDER_THREADS) {
-        const int cell = j0 * W + t;
-        const int ag = cell == acell ? (ad & 3) : -1, hl = hm ? hm[cell] != 0 : 0;
-        int idx = mg_tile_index(ty[cell], co[cell], st ? st[cell] : 0, ag, hl);
-        if (idx < 0) idx = mg_tile_index(1, 0, 0, ag, hl);
+        const mg_cell q = src.at(j0 * W + t);
+        int idx = mg_tile_index(q.type, q.colour, q.state, q.agent, q.highlight);
+        if (idx < 0) idx = mg_tile_index(1, 0, 0, q.agent, q.highlight);
         tidx[t] = (uint16_t)idx;
     }
-    if (b == 0 && error) {                                  /* uniform per workgroup: one workgroup scans the world */
+    if (b == 0 && error) {                                  /* uniform per workgroup: one workgroup scans the frame's cells */
         int bad = 0;
-        for (int cell = tid; cell < HW; cell += MG_RENDER_THREADS)
-            bad |= mg_tile_index(ty[cell], co[cell], 0, -1, 0) < 0;
+        for (int cell = tid; cell < HW; cell += MG_RENDER_THREADS) {
+            const mg_cell q = src.at(cell);
+            bad |= mg_tile_index(q.type, q.colour, 0, -1, 0) < 0;
+        }
         if (__ballot(bad) != 0 && (tid & 63) == 0) wave_bad[tid >> 6] = 1;
     }
     __syncthreads();
@@ -245,8 +326,8 @@ __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_kernel(
 #pragma unroll
             for (int d = 0; d < 4; d++) {
                 if (k + 4 <= run) {
-                    const uint8_t *src = atlas + (int)tidx[j * W + i] * tileB + r * run + k;
-                    __builtin_memcpy(&w[d], src, 4);
+                    const uint8_t *src_b = atlas + (int)tidx[j * W + i] * tileB + r * run + k;
+                    __builtin_memcpy(&w[d], src_b, 4);
                     k += 4;
                     if (k == run) { k = 0; if (++i == W) { i = 0; if (++r == ts) { r = 0; j++; } } }
                 } else {
@@ -342,14 +423,13 @@ extern "C" int mg_render_build_atlas(int tile_size, uint8_t *atlas, void *stream
     return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
 }
 
-extern "C" int mg_render(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
-                         int height, const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_dir,
-                         int agent_stride, const int32_t *env_index, int n_out, const uint8_t *highlight,
-                         const uint8_t *atlas, int tile_size, uint8_t *frame, int64_t frame_pitch, int32_t *error,
-                         void *stream)
+/* The frame-side argument rules and launch geometry of both entry points: n_out frames of width x height cells. */
+template <class Cells>
+static int mg_launch_frames(const typename Cells::args &src, int n_envs, int width, int height, const int32_t *env_index,
+                            int n_out, const uint8_t *atlas, int tile_size, uint8_t *frame, int64_t frame_pitch,
+                            int32_t *error, void *stream)
 {
-    if (!type || !colour || !agent_x || !agent_y || !agent_dir || !atlas || !frame) return TW_E_ARG;
-    if (n_envs <= 0 || width <= 0 || height <= 0 || n_out <= 0 || agent_stride <= 0) return TW_E_ARG;
+    if (!atlas || !frame || n_envs <= 0 || width <= 0 || height <= 0 || n_out <= 0) return TW_E_ARG;
     if (tile_size < 1 || tile_size > MG_RENDER_MAX_TILE) return TW_E_ARG;
     if (!env_index && n_out > n_envs) return TW_E_ARG;
     const int64_t band = (int64_t)width * tile_size * tile_size * 3, fbytes = band * height;
@@ -363,10 +443,37 @@ extern "C" int mg_render(const uint8_t *type, const uint8_t *colour, const uint8
     if (bands > height) bands = height;
     const int64_t lds = bands * width * (int64_t)sizeof(uint16_t);
     if (lds > 48 * 1024) return TW_E_ARG;
-    hipLaunchKernelGGL(mg_render_kernel, dim3((unsigned)(bpf * n_out)), dim3(MG_RENDER_THREADS), (size_t)lds,
-                       (hipStream_t)stream, type, colour, state, n_envs, width, height, agent_x, agent_y, agent_dir,
-                       agent_stride, env_index, highlight, atlas, tile_size, frame, pitch, error, (int)bpf);
+    hipLaunchKernelGGL(mg_render_kernel<Cells>, dim3((unsigned)(bpf * n_out)), dim3(MG_RENDER_THREADS), (size_t)lds,
+                       (hipStream_t)stream, src, n_envs, width, height, env_index, atlas, tile_size, frame, pitch, error,
+                       (int)bpf);
     return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
+}
+
+extern "C" int mg_render(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
+                         int height, const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_dir,
+                         int agent_stride, const int32_t *env_index, int n_out, const uint8_t *highlight,
+                         const uint8_t *atlas, int tile_size, uint8_t *frame, int64_t frame_pitch, int32_t *error,
+                         void *stream)
+{
+    if (!type || !colour || !agent_x || !agent_y || !agent_dir || agent_stride <= 0) return TW_E_ARG;
+    const mg_world_cells::args src = {type, colour, state, highlight, agent_x, agent_y, agent_dir, agent_stride};
+    return mg_launch_frames<mg_world_cells>(src, n_envs, width, height, env_index, n_out, atlas, tile_size, frame,
+                                            frame_pitch, error, stream);
+}
+
+extern "C" int mg_render_pov(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
+                             int height, const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_dir,
+                             int agent_stride, const uint8_t *carrying, const int32_t *env_index, int n_out,
+                             const uint8_t *vis_mask, int view_size, const uint8_t *atlas, int tile_size, uint8_t *frame,
+                             int64_t frame_pitch, int32_t *error, void *stream)
+{
+    if (!type || !colour || !agent_x || !agent_y || !agent_dir || agent_stride <= 0) return TW_E_ARG;
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 31)) return TW_E_ARG;
+    if (view_size < 1 || view_size > MG_MAX_VIEW) return TW_E_ARG;
+    const mg_view_cells::args src = {type, colour, state, carrying, vis_mask, agent_x, agent_y, agent_dir, agent_stride,
+                                     width, height};
+    return mg_launch_frames<mg_view_cells>(src, n_envs, view_size, view_size, env_index, n_out, atlas, tile_size, frame,
+                                           frame_pitch, error, stream);
 }
 
 extern "C" int mg_highlight_mask(const uint8_t *vis_mask, int n_envs, int width, int height, const int32_t *agent_x,

@@ -16,6 +16,7 @@
 
 #include "minigrid_view.h"
 #include "twoarmy.h"
+#include "view_map.h"
 
 namespace {
 
@@ -83,9 +84,10 @@ __global__ __launch_bounds__(64) void mg_gen_obs_kernel(const uint8_t *__restric
     if (lane < ne) {
         const int n = n0 + lane;
         const int ax = agent_x[n], ay = agent_y[n], dir = agent_dir[n] & 3;
-        // get_view_exts (minigrid.py:1262-1293)
-        topx[lane] = dir == 0 ? ax : (dir == 2 ? ax - V + 1 : ax - half);
-        topy[lane] = dir == 1 ? ay : (dir == 3 ? ay - V + 1 : ay - half);
+        int tx, ty;
+        mg_view_top(ax, ay, dir, V, tx, ty);                                // get_view_exts (minigrid.py:1262-1293)
+        topx[lane] = tx;
+        topy[lane] = ty;
         rot[lane] = (dir + 1) & 3;                                          // number of rotate_left applications mod 4
         uint32_t c = EMPTY_CELL;
         if (carrying && carrying[(size_t)n * 3] != 0)
@@ -98,10 +100,8 @@ __global__ __launch_bounds__(64) void mg_gen_obs_kernel(const uint8_t *__restric
     for (int c = lane; c < ne * VV; c += 64) {
         const int e = c / VV, cc = c - e * VV;
         const int j = cc / V, i = cc - j * V;
-        const int k = rot[e];
-        // rotate_left maps old (a, b) -> new (b, V-1-a); inverted k times: view (i, j) <- slice (si, sj)
-        const int si = k == 0 ? i : (k == 1 ? V - 1 - j : (k == 2 ? V - 1 - i : j));
-        const int sj = k == 0 ? j : (k == 1 ? i : (k == 2 ? V - 1 - j : V - 1 - i));
+        int si, sj;
+        mg_view_to_slice(rot[e], V, i, j, si, sj);
         const int x = topx[e] + si, y = topy[e] + sj;
         uint32_t cell = WALL_CELL;                                          // Grid.slice: outside the world -> Wall()
         if (x >= 0 && x < W && y >= 0 && y < H) {
@@ -218,8 +218,8 @@ __global__ __launch_bounds__(64) void mg_gen_obs_cols_kernel(const uint8_t *__re
         constexpr int ND = ((V - 1) >> 2) + 2;                             // aligned dwords covering V bytes at any alignment
         __shared__ uint32_t win[E * VV];
         const int r = li, lec = le < E ? le : E - 1;
-        const int topx = dir[0] == 0 ? ax[0] : (dir[0] == 2 ? ax[0] - V + 1 : ax[0] - half);
-        const int topy = dir[0] == 1 ? ay[0] : (dir[0] == 3 ? ay[0] - V + 1 : ay[0] - half);
+        int topx, topy;
+        mg_view_top(ax[0], ay[0], dir[0], V, topx, topy);
         const int y = topy + r, yc = min(max(y, 0), H - 1);
         const bool yin = y >= 0 && y < H;
         const intptr_t o0 = (intptr_t)n[0] * W * H + (intptr_t)yc * W + topx;      // window-row byte 0, relative to the plane
@@ -266,8 +266,8 @@ __global__ __launch_bounds__(64) void mg_gen_obs_cols_kernel(const uint8_t *__re
 #pragma unroll
     for (int g = 0; g < (ROWS ? 0 : G); ++g) {
         // get_view_exts (minigrid.py:1262-1293) and the number of rotate_left applications
-        const int topx = dir[g] == 0 ? ax[g] : (dir[g] == 2 ? ax[g] - V + 1 : ax[g] - half);
-        const int topy = dir[g] == 1 ? ay[g] : (dir[g] == 3 ? ay[g] - V + 1 : ay[g] - half);
+        int topx, topy;
+        mg_view_top(ax[g], ay[g], dir[g], V, topx, topy);
         const int k = (dir[g] + 1) & 3;
         // view (i, j) <- slice (si, sj): rotate_left maps old (a, b) -> new (b, V-1-a), inverted k times.  For this lane i
         // is fixed, so (x, y) walks a straight line in the world as j grows: start + j * step.

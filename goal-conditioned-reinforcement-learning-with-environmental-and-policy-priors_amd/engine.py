@@ -342,6 +342,26 @@ class TwoarmyEngine:
                                      self._stream()), "mg_render")
         return frame
 
+    def render_pov(self, env_index=None, tile_size=17, view_size=None, out=None):
+        """RGB frames of MiniGridEnv.get_pov_render, uint8[n, V*ts, V*ts, 3] (V = view_size, default the engine's):
+        the agent's view with the agent at the bottom centre pointing up, every cell highlighted (Twoarmy sees through
+        walls and carries nothing).  Drawn like render(): from the engine's planes and records, on the current stream."""
+        from .minigrid_render import TileAtlas
+        lib = _lib.lib()
+        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(lib.tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
+        ts, N, S, V = int(tile_size), self.num_envs, 17, int(view_size or self.view_size)
+        n = N if env_index is None else int(env_index.shape[0])
+        frame = out if out is not None else torch.empty((n, V * ts, V * ts, 3), dtype=torch.uint8, device=self.device)
+        assert frame.shape == (n, V * ts, V * ts, 3) and frame.dtype == torch.uint8 and frame.is_contiguous()
+        atlas = TileAtlas.get(ts, self.device)
+        ax, ay, ad = (C.c_void_p(rec.value + 4 * FIELDS[k]) for k in ("AX", "AY", "DIR"))
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mg_render_pov(ty, co, None, N, S, S, ax, ay, ad, TW_REC_WORDS, None,
+                                         _dense(env_index, torch.int32), n, None, V, _ptr(atlas.tiles), ts, _ptr(frame), 0,
+                                         None, self._stream()), "mg_render_pov")
+        return frame
+
     def dir_ptr(self):
         """(address, stride_t, stride_n) of the agents' directions in the engine's records (tw_state_ptrs), in int32
         elements: one value per env, as ppo_ops.bonus_scan(dir_ptr=...) takes it.  After an auto-reset the record holds

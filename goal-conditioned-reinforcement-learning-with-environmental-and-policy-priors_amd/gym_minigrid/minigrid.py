@@ -77,7 +77,7 @@ class MiniGridEnv:
     variant = 6
 
     def __init__(self, size=17, agent_pos=(3, 15), goal_pos=(14, 2), agent_view_size=17, max_steps=50, tile_size=32,
-                 device=None, seed=9981, env_id=0, highlight=False, render_mode=None, **kwargs):
+                 device=None, seed=9981, env_id=0, highlight=False, render_mode=None, agent_pov=False, **kwargs):
         if size != 17 or tuple(agent_pos) != (3, 15) or tuple(goal_pos) != (14, 2) or max_steps != 50:
             raise NotImplementedError("the HIP engine implements the registered configuration: size=17, "
                                       "agent_pos=(3,15), goal_pos=(14,2), max_steps=50")
@@ -87,6 +87,7 @@ class MiniGridEnv:
         self.see_through_walls = True
         self.tile_size = tile_size
         self.highlight = highlight                     # minigrid.py:876: brighten the cells of the agent's view
+        self.agent_pov = agent_pov                     # minigrid.py:878: get_render() / render() draw the agent's view
         self.render_mode = render_mode
         self.actions = MiniGridEnv.Actions
         self.action_space = _Space(n=len(self.actions))
@@ -161,14 +162,19 @@ class MiniGridEnv:
         drawn on the device from the engine's state (TwoarmyEngine.render) and copied to the host."""
         return self._eng.render(tile_size=self.tile_size, highlight=self.highlight)[0].cpu().numpy()
 
+    def get_pov_render(self):
+        """uint8[V*tile_size, V*tile_size, 3]: the image of the reference's get_pov_render (minigrid.py:1498-1512), the
+        agent's view drawn on the device (TwoarmyEngine.render_pov) and copied to the host."""
+        return self._eng.render_pov(tile_size=self.tile_size, view_size=self.agent_view_size)[0].cpu().numpy()
+
     def get_render(self):
-        return self.get_full_render()
+        return self.get_pov_render() if self.agent_pov else self.get_full_render()
 
     def render(self):
         """rgb_array behaviour of the reference's render(); the matplotlib window (render_mode="human") is not built."""
         if self.render_mode == "human":
             raise NotImplementedError("render_mode='human' (the matplotlib window) is out of scope; render() returns the image")
-        return self.get_full_render()
+        return self.get_render()
 
     def close(self):
         self._eng.close()

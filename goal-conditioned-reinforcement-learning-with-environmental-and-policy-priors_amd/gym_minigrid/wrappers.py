@@ -10,8 +10,10 @@ facade's engine state and return what the reference classes return, quirks inclu
 flat cell list (the transposed world), DirectionObsWrapper's goal_position = (k // height, k % width), its reset() without
 kwargs that returns the observation without goal_direction, and its goal_position cached for the wrapper's life.
 ReseedWrapper (:13-31) is host code.  Thousands of envs take all of these through TwoarmyVecEnv(agent_view_size=...,
-state_bonus=..., action_bonus=..., observation=..., goal_direction=...) or train_ppo --bonus.  Out of scope: the pixel
-wrappers RGBImgObsWrapper / RGBImgPartialObsWrapper and DictObservationSpaceWrapper."""
+state_bonus=..., action_bonus=..., observation=..., goal_direction=...) or train_ppo --bonus.  The pixel wrappers
+RGBImgObsWrapper (:157-186) and RGBImgPartialObsWrapper (:189-217) return the device renderer's frames
+(csrc/minigrid_render.hip); as in the reference their tile_size sizes only the declared space, the picture is drawn by
+the env's get_full_render / get_pov_render with the env's own tile_size.  Out of scope: DictObservationSpaceWrapper."""
 import numpy as np
 import torch
 
@@ -165,6 +167,36 @@ class OneHotPartialObsWrapper(_ObservationWrapper):
         if int(err[0]):
             raise IndexError("one-hot index out of bounds for axis 2 with size 21")
         return {**obs, "image": out[0].cpu().numpy()}
+
+
+class RGBImgObsWrapper(_ObservationWrapper):
+    """wrappers.py:157-186: obs["image"] = get_full_render().  The wrapper keeps tile_size and highlight = True for
+    itself; gym.Wrapper forwards get_full_render to the env, which draws with its own tile_size and highlight, so the
+    declared shape (width * tile_size, height * tile_size, 3) is the image's only when the two tile sizes agree."""
+
+    def __init__(self, env, tile_size=8):
+        super().__init__(env)
+        self.highlight = True
+        self.tile_size = tile_size
+        self.observation_space["image"] = _Space(shape=(self.env.width * tile_size, self.env.height * tile_size, 3))
+
+    def observation(self, obs):
+        return {**obs, "image": self.get_full_render()}
+
+
+class RGBImgPartialObsWrapper(_ObservationWrapper):
+    """wrappers.py:189-217: obs["image"] = get_pov_render(), drawn by the env with its own tile_size (see above);
+    sets unwrapped.agent_pov, so the env's render() shows the agent's view from then on."""
+
+    def __init__(self, env, tile_size=8):
+        super().__init__(env)
+        self.unwrapped.agent_pov = True
+        self.tile_size = tile_size
+        shape = env.observation_space["image"].shape
+        self.observation_space["image"] = _Space(shape=(shape[0] * tile_size, shape[1] * tile_size, 3))
+
+    def observation(self, obs):
+        return {**obs, "image": self.get_pov_render()}
 
 
 class FullyObsWrapper(_ObservationWrapper):

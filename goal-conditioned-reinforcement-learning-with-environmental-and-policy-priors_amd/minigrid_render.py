@@ -1,7 +1,7 @@
-"""Torch front end of the device renderer (include/minigrid_render.h): MiniGridEnv.get_full_render of the reference
-(gym_minigrid/minigrid.py:662-747, 1514-1563 and rendering.py) for N worlds kept as structure-of-arrays planes on the
-GPU, byte for byte.  A tile atlas is rasterised once per (device, tile size); a frame is then a gather from it.
-No CPU fallback."""
+"""Torch front end of the device renderer (include/minigrid_render.h): MiniGridEnv.get_full_render and get_pov_render
+of the reference (gym_minigrid/minigrid.py:662-747, 1498-1563 and rendering.py) for N worlds kept as
+structure-of-arrays planes on the GPU, byte for byte.  A tile atlas is rasterised once per (device, tile size); a frame
+is then a gather from it.  No CPU fallback."""
 import ctypes as C
 
 import torch
@@ -92,6 +92,39 @@ def render(type_plane, colour_plane, state_plane, width, height, agent_x, agent_
             _ap(agent_x, agent_stride), _ap(agent_y, agent_stride), _ap(agent_dir, agent_stride), int(agent_stride),
             _p(env_index, torch.int32), n, _p(highlight, torch.uint8), _p(atlas.tiles, torch.uint8), ts,
             _p(frame, torch.uint8), 0, _p(error, torch.int32), _stream(dev)), "mg_render")
+    return frame
+
+
+def render_pov(type_plane, colour_plane, state_plane, width, height, agent_x, agent_y, agent_dir, view_size, tile_size,
+               carrying=None, vis_mask=None, env_index=None, out=None, error=None, agent_stride=1, see_through_walls=True):
+    """-> uint8[n, V*ts, V*ts, 3], the frames of get_pov_render: the agent's V x V view drawn unmasked, the carried
+    object (carrying uint8[N, 3], None = nothing) under the agent, the cells of vis_mask (uint8[N, V, V] from gen_obs)
+    highlighted.  vis_mask None: every cell, or with see_through_walls=False the mask of one mg_gen_obs launch (dense
+    agent arrays only).  The other arguments as in render; error also counts the carried object."""
+    N = type_plane.shape[0]
+    W, H, V, ts = int(width), int(height), int(view_size), int(tile_size)
+    assert type_plane.shape == (N, W * H) and colour_plane.shape == (N, W * H)
+    dev = type_plane.device
+    n = N if env_index is None else env_index.shape[0]
+    frame = out if out is not None else torch.empty((n, V * ts, V * ts, 3), dtype=torch.uint8, device=dev)
+    assert frame.shape == (n, V * ts, V * ts, 3)
+    assert carrying is None or carrying.shape == (N, 3)
+    if agent_stride == 1:
+        assert agent_x.numel() >= N and agent_y.numel() >= N and agent_dir.numel() >= N
+    atlas = TileAtlas.get(ts, dev)
+    with torch.cuda.device(dev):
+        if vis_mask is None and not see_through_walls:
+            from . import minigrid_view
+            assert agent_stride == 1, "mg_gen_obs reads dense agent arrays"
+            vis_mask = minigrid_view.gen_obs(type_plane, colour_plane, state_plane, W, H, agent_x, agent_y, agent_dir, V,
+                                             see_through_walls=False, carrying=carrying)[1]
+        assert vis_mask is None or vis_mask.shape == (N, V, V)
+        _lib.check(_lib.lib().mg_render_pov(
+            _p(type_plane, torch.uint8), _p(colour_plane, torch.uint8), _p(state_plane, torch.uint8), N, W, H,
+            _ap(agent_x, agent_stride), _ap(agent_y, agent_stride), _ap(agent_dir, agent_stride), int(agent_stride),
+            _p(carrying, torch.uint8), _p(env_index, torch.int32), n, _p(vis_mask, torch.uint8), V,
+            _p(atlas.tiles, torch.uint8), ts, _p(frame, torch.uint8), 0, _p(error, torch.int32), _stream(dev)),
+            "mg_render_pov")
     return frame
 
 

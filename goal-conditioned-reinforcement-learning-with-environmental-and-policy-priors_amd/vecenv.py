@@ -11,7 +11,7 @@ policy's 5 indices (4 -> done) like Env_transact.env_action (reference soa/env_b
 Extra per-step tensors the reference computes in Python are fused into the same launch:
 `env.state_matrix` [N,289] (matrix_env) and `env.agent_yx` [N,2] (data_env).
 `env.render(env_index=None)` draws the RGB frames of the reference's get_full_render on the device (tile_size and
-highlight are constructor arguments).
+highlight are constructor arguments), `env.render_pov(env_index=None)` those of get_pov_render (the agent's view).
 `record_episode_statistics=True` adds info["episode"] = {"r": float64 [N], "l": int32 [N]} and the mask
 info["_episode"] like gym.vector's RecordEpisodeStatistics, accounted on the device (episode_stats.EpisodeTracker).
 `record_visitation=True` adds info["visitation"] = {"cells": int32 [N], "first_visit": bool [N]} -- the distinct cells the
@@ -24,10 +24,12 @@ info["reward_extrinsic"] keeps the env's own reward.  Episode statistics stay ex
 `observation=` selects what reset() / step() return first and what info["final_observation"] holds (minigrid_obs, the
 reference's observation wrappers, gym_minigrid/wrappers.py): "image" (default) the egocentric view uint8[N, V, V, 3];
 "onehot" its one-hot uint8[N, V, V, 21]; "flat" float32[N, V*V*3 + 96*28], the image and the one-hot mission string;
-"full" the whole grid with the agent stamped in, uint8[N, 17, 17, 3]; "symbolic" int32[N, 17, 17, 3] = (x, y, idx).
+"full" the whole grid with the agent stamped in, uint8[N, 17, 17, 3]; "symbolic" int32[N, 17, 17, 3] = (x, y, idx);
+"rgb" the pixels of render(), uint8[N, 17*tile_size, 17*tile_size, 3] (RGBImgObsWrapper); "rgb_partial" the pixels of
+render_pov(), uint8[N, V*tile_size, V*tile_size, 3] (RGBImgPartialObsWrapper).
 `goal_direction="slope" | "angle"` adds info["goal_direction"] float64[N] (DirectionObsWrapper) for the state `obs`
 shows, and info["final_goal_direction"] under auto-reset.  "onehot" and "flat" are passes over the engine's image;
-"full", "symbolic" and the goal direction read the engine's state after the step, so with autoreset=True the env steps
+"full", "symbolic", "rgb", "rgb_partial" and the goal direction read the engine's state after the step, so with autoreset=True the env steps
 without the in-kernel reset, emits the final observation, resets the finished envs (engine.reset(mask=done)) and emits
 again; everything else the env returns is what the default env returns.
 """
@@ -58,13 +60,14 @@ class TwoarmyVecEnv:
         self.single_observation_shape = (agent_view_size, agent_view_size, 3)
         self.single_action_n = 5 if policy_actions else 7
         V = agent_view_size
-        if observation not in ("image", "onehot", "full", "symbolic", "flat"):
-            raise ValueError("observation must be image, onehot, full, symbolic or flat, not %r" % (observation,))
+        if observation not in ("image", "onehot", "full", "symbolic", "flat", "rgb", "rgb_partial"):
+            raise ValueError("observation must be image, onehot, full, symbolic, flat, rgb or rgb_partial, not %r"
+                             % (observation,))
         if goal_direction not in (None, "slope", "angle"):
             raise ValueError("goal_direction must be None, slope or angle, not %r" % (goal_direction,))
         self.observation, self.goal_direction = observation, goal_direction
         # the kinds read from the engine's state (not from its image) take the reset out of the step kernel
-        self._state_obs = observation in ("full", "symbolic") or goal_direction is not None
+        self._state_obs = observation in ("full", "symbolic", "rgb", "rgb_partial") or goal_direction is not None
         self._goal_index = self._angle_table = self._state_src = None
         if observation != "image" or goal_direction is not None:
             from . import minigrid_obs
@@ -83,6 +86,10 @@ class TwoarmyVecEnv:
                 self.single_observation_shape = (17, 17, 3)
                 dt = torch.uint8 if observation == "full" else torch.int32
                 self._obs_buf = [torch.empty((N, 17, 17, 3), dtype=dt, device=d) for _ in range(2)]
+            elif observation in ("rgb", "rgb_partial"):
+                side = (17 if observation == "rgb" else V) * self.tile_size
+                self.single_observation_shape = (side, side, 3)
+                self._obs_buf = [torch.empty((N, side, side, 3), dtype=torch.uint8, device=d) for _ in range(2)]
             if goal_direction is not None:
                 self._dir_buf = [torch.empty(N, dtype=torch.float64, device=d) for _ in range(2)]
                 if goal_direction == "angle":
@@ -124,6 +131,10 @@ class TwoarmyVecEnv:
             return mo.onehot(image, out=out)
         if kind == "flat":
             return mo.flat_obs(image, self._tail, out=out)
+        if kind == "rgb":
+            return self.render(out=out)
+        if kind == "rgb_partial":
+            return self.render_pov(out=out)
         ty, co, agent = self._state()
         if kind == "full":
             return mo.full_obs(ty, co, None, 17, 17, agent_ptrs=agent, out=out)
@@ -207,6 +218,16 @@ class TwoarmyVecEnv:
             if env_index.numel() == 0:
                 return torch.empty((0, 17 * self.tile_size, 17 * self.tile_size, 3), dtype=torch.uint8, device=self.device)
         return self.engine.render(env_index=env_index, tile_size=self.tile_size, highlight=self.highlight, out=out)
+
+    def render_pov(self, env_index=None, out=None):
+        """uint8[n, V*tile_size, V*tile_size, 3] device tensor: the reference's get_pov_render image (the agent's view,
+        V = agent_view_size) of every env, or of the envs listed in env_index, drawn on the device from the current state."""
+        if env_index is not None:
+            env_index = torch.as_tensor(env_index).to(device=self.device, dtype=torch.int32).contiguous().view(-1)
+            if env_index.numel() == 0:
+                side = self.view_size * self.tile_size
+                return torch.empty((0, side, side, 3), dtype=torch.uint8, device=self.device)
+        return self.engine.render_pov(env_index=env_index, tile_size=self.tile_size, out=out)
 
     def close(self):
         self.engine.close()

@@ -1,20 +1,23 @@
 /*
  * minigrid_render.h -- C ABI of the device renderer (libtwoarmy_hip.so, <package>/csrc/minigrid_render.hip): the
- * RGB frame of MiniGridEnv.get_full_render for N worlds resident in HBM, byte for byte what the reference draws.
+ * RGB frames of MiniGridEnv.get_full_render and get_pov_render for N worlds resident in HBM, byte for byte what the
+ * reference draws.
  *
  * Replaces (paths relative to the reference root)
  *   gym_minigrid/rendering.py          fill_coords, point_in_rect / circle / triangle, rotate_fn, highlight_img,
  *                                      downsample (3 x 3 supersampling)
  *   Grid.render_tile                   gym_minigrid/minigrid.py:662-710
  *   Grid.render                        :712-747
+ *   MiniGridEnv.get_pov_render         :1498-1512 (mg_render_pov)
  *   MiniGridEnv.get_full_render        :1514-1563 (the highlight loop :1521-1553 is mg_highlight_mask)
  *   WorldObj.render of Wall, Floor, Door (open / closed / locked), Key, Ball, Box, Goal   :357-551
  *
  * Two stages.  mg_render_build_atlas rasterises every drawable tile once per tile size, in float64 and in the
  * reference's operation order (grid lines, object, agent triangle, highlight blend at sample resolution, the
  * two-stage mean of the downsample, truncating cast); the agent's tile is the object under the agent with the triangle
- * rasterised over it BEFORE the downsample, so the atlas holds every object with every agent direction.  mg_render is
- * then a pure gather: frame bytes <- atlas bytes, selected by the world planes.
+ * rasterised over it BEFORE the downsample, so the atlas holds every object with every agent direction.  mg_render and
+ * mg_render_pov are then pure gathers, one kernel instantiated twice: frame bytes <- atlas bytes, selected by the world
+ * planes, or by the agent's rotated view of them.
  *
  * Atlas layout: MG_RENDER_TILES tiles of [tile_size][tile_size][3] bytes; tile index
  *   ((kind * 6 + colour) * 5 + (agent_dir + 1)) * 2 + highlight          agent_dir -1 = no agent
@@ -23,8 +26,7 @@
  *         a door whose state is neither 0 (open) nor 2 (locked) is closed, other types ignore the state.
  *
  * Not drawn (out of scope): lava (type 9; its point_in_line mixes float32 and float64 through np.dot and
- * np.linalg.norm), type codes 10, 11 and above, colour codes above 5; get_pov_render (it draws the unmasked view grid,
- * which mg_gen_obs does not emit); the matplotlib window and render_mode="human"; the image wrappers.
+ * np.linalg.norm), type codes 10, 11 and above, colour codes above 5; the matplotlib window and render_mode="human".
  *
  * Conventions as in minigrid_view.h / twoarmy.h: device pointers, caller-owned, `stream` = hipStream_t as void*,
  * asynchronous, 0 = ok / negative = TW_E_*; TW_E_ARG is returned before anything is launched.
@@ -81,6 +83,30 @@ int mg_render(const uint8_t *type, const uint8_t *colour, const uint8_t *state, 
               const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_dir, int agent_stride,
               const int32_t *env_index, int n_out, const uint8_t *highlight, const uint8_t *atlas, int tile_size,
               uint8_t *frame, int64_t frame_pitch, int32_t *error, void *stream);
+
+/* get_pov_render for n_out frames: Grid.render of the V x V grid gen_obs_grid returns, V = view_size.
+ *   type, colour, state, agent_*, agent_stride, env_index, atlas, error: as in mg_render, except that ANY agent position
+ *                         is valid (Grid.slice pads the window with walls) and agent_dir is taken modulo 4 as mg_gen_obs
+ *                         takes it
+ *   view cell (i, j)      shows the world cell mg_gen_obs puts there (get_view_exts, agent_dir + 1 rotate_left calls); a
+ *                         world cell outside the world is a grey wall (2, 5, 0).  The agent's own cell (V / 2, V - 1)
+ *                         shows the carried object under the agent triangle of direction 3, whatever the mask says
+ *                         there.  Every other cell the mask hides is drawn as an empty, unlit tile: process_vis clears
+ *                         such cells in the grid gen_obs_grid returns (minigrid.py:827-830), so the reference's picture
+ *                         does not show them.
+ *   carrying              uint8[n_envs][3] = WorldObj.encode() of the carried object, type 0 = nothing (nullable)
+ *   vis_mask              uint8[n_envs][V*V] indexed [i][j] as mg_gen_obs emits it: cell (i, j) is highlighted iff
+ *                         non-zero; NULL = every cell (see_through_walls)
+ *   frame                 uint8[n_out][frame_pitch]: the [V*tile_size][V*tile_size][3] image, view cell (i, j) at pixel
+ *                         rows j*tile_size.. and pixel columns i*tile_size.., in the first V*V*tile_size^2*3 bytes of
+ *                         each row; alignment and the bytes written as in mg_render
+ *   error                 1: a view cell the mask does not hide (the carried object included) is one this renderer does
+ *                         not draw; 2 as in mg_render
+ * TW_E_ARG as in mg_render, and for view_size outside 1..MG_MAX_VIEW. */
+int mg_render_pov(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width, int height,
+                  const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_dir, int agent_stride,
+                  const uint8_t *carrying, const int32_t *env_index, int n_out, const uint8_t *vis_mask, int view_size,
+                  const uint8_t *atlas, int tile_size, uint8_t *frame, int64_t frame_pitch, int32_t *error, void *stream);
 
 /* The highlight loop of get_full_render (minigrid.py:1521-1553): view-space vis_mask uint8[n_envs][V*V] indexed [i][j]
  * as mg_gen_obs emits it (NULL = every view cell visible, Twoarmy's see_through_walls) -> world-space

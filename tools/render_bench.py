@@ -5,6 +5,7 @@ the algorithmic bytes (frame written + two planes and the agent read) and that a
 of the same device taken in the same process (the yardstick of bench.py --full).
 
   python tools/render_bench.py [--envs 4096] [--iters 20]
+  python tools/render_bench.py --pov           # mg_render_pov instead: the agents' 7 x 7 views at tile size 8
 """
 import argparse
 import json
@@ -20,6 +21,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--pov", action="store_true", help="time mg_render_pov (view size 7, tile size 8) instead of mg_render")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
 
@@ -44,6 +46,19 @@ def main():
     eng.rollout(64, out, actions=eng.fill_actions(64))
     g = torch.Generator(device="cpu").manual_seed(1)
     some = torch.randperm(a.envs, generator=g)[:16].to(dev, torch.int32)
+    if a.pov:
+        V, ts = 7, 8
+        for idx in (None, some):
+            n = a.envs if idx is None else idx.numel()
+            frames = torch.empty((n, V * ts, V * ts, 3), dtype=torch.uint8, device=dev)
+            s = timed(lambda: eng.render_pov(env_index=idx, tile_size=ts, view_size=V, out=frames))
+            nbytes = n * (V * V * ts * ts * 3 + 2 * V * V + 12)          # frame written + the view's cells of two planes + agent
+            print(json.dumps({"kernel": "mg_render_pov", "envs": a.envs, "frames": n, "view_size": V, "tile_size": ts,
+                              "ms": s * 1e3, "frames_per_s": n / s, "algorithmic_GBs": nbytes / s / 1e9,
+                              "frac_of_fill": nbytes / s / fill, "frac_of_8TBs": nbytes / s / 8e12}), flush=True)
+            del frames
+        eng.close()
+        return
     for ts, idx, highlight in ((17, None, False), (17, None, True), (17, some, False), (32, None, False), (8, None, False)):
         n = a.envs if idx is None else idx.numel()
         frames = torch.empty((n, 17 * ts, 17 * ts, 3), dtype=torch.uint8, device=dev)
