@@ -12,14 +12,14 @@
  *   mg_obs_goal_index_kernel one wave per env: ballot over 64 cells at a time, first set bit.
  *   mg_obs_goal_direction_kernel   one lane per env; the slope is one IEEE double division, the angle a table entry.
  *
- * Every chunked kernel counts its chunks from the 16-byte-aligned address at or below the first byte of the row (of
- * the whole array for the dense symbolic grid): a chunk that lies inside the row is one aligned 16-byte store, the
- * first and last chunk store only their own elements one by one.
+ * Every chunked kernel stores its rows (the whole array for the dense symbolic grid) by the rule of row_store.h:
+ * aligned 16-byte chunks inside the row, the elements of its first and last chunk one by one.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "minigrid_obs.h"
+#include "row_store.h"
 #include "twoarmy.h"
 
 #define MG_OBS_THREADS 256
@@ -54,23 +54,18 @@ __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_onehot_kernel(const uin
     if (g >= (int64_t)N * cpr) return;
     const int e = (int)(g / cpr), c = (int)(g - (int64_t)e * cpr);
     uint8_t *ob = out + (int64_t)e * opitch;
-    const int s = (int)((uintptr_t)ob & 15), F = n_cells * MG_OBS_ONEHOT_BITS;
-    const int p = 16 * c - s;                               /* ob + p is 16-byte aligned; p > -16 */
-    if (p >= F) return;
+    const int F = n_cells * MG_OBS_ONEHOT_BITS, lo = mg_row_chunk(mg_row_misalign(ob, 16), F, c, 16).lo;
+    if (lo >= F) return;
     const uint8_t *img = image + (int64_t)e * ipitch;
-    const int lo = max(p, 0), hi = min(p + 16, F);
     const int cell0 = lo / MG_OBS_ONEHOT_BITS, k0 = lo - cell0 * MG_OBS_ONEHOT_BITS;
     int bad = 0;
     uint64_t m = (uint64_t)mg_obs_cell_mask(img, cell0, n_cells, &bad) |
                  (uint64_t)mg_obs_cell_mask(img, cell0 + 1, n_cells, &bad) << MG_OBS_ONEHOT_BITS;
     m >>= k0;                                               /* bit j = byte lo + j; k0 + 16 <= 37 < 42 */
-    if (p >= 0 && p + 16 <= F) {
+    mg_row_store(ob, F, c, [&](int) {
         const uint32_t w = (uint32_t)m;
-        *reinterpret_cast<uint4 *>(ob + p) = make_uint4(mg_obs_spread4(w), mg_obs_spread4(w >> 4), mg_obs_spread4(w >> 8),
-                                                        mg_obs_spread4(w >> 12));
-    } else {                                                /* the row's first / last chunk: only its own bytes */
-        for (int q = lo; q < hi; q++) ob[q] = (uint8_t)((m >> (q - lo)) & 1u);
-    }
+        return make_uint4(mg_obs_spread4(w), mg_obs_spread4(w >> 4), mg_obs_spread4(w >> 8), mg_obs_spread4(w >> 12));
+    }, [&](int q) { return (uint8_t)((m >> (q - lo)) & 1u); });
     if (bad && error) error[e] = 1;                         /* zeroed on the stream before the launch */
 }
 
@@ -84,12 +79,10 @@ __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_full_kernel(
     const int tid = threadIdx.x;
     const int e = blockIdx.x / bpe, b = blockIdx.x - e * bpe;
     uint8_t *ob = out + (int64_t)e * pitch;
-    const int s = (int)((uintptr_t)ob & 15), HW = W * H, F = HW * 3;
-    const int total = (s + F + 15) >> 4;
-    const int c0 = b * MG_OBS_FULL_CHUNKS, c1 = min(c0 + MG_OBS_FULL_CHUNKS, total);
-    if (c0 >= c1) return;                                   /* uniform per workgroup; workgroup 0 always has chunks */
-    const int p_lo = max(0, 16 * c0 - s), p_hi = min(F, 16 * c1 - s);             /* output bytes of this workgroup */
-    const int cell_lo = p_lo / 3, cell_hi = (p_hi - 1) / 3;                       /* x-major cells x * H + y, inclusive */
+    const int HW = W * H, F = HW * 3;
+    const mg_row_span_t<int> g = mg_row_span(mg_row_misalign(ob, 16), F, b, MG_OBS_FULL_CHUNKS, 16);
+    if (g.c0 >= g.c1) return;                               /* uniform per workgroup; workgroup 0 always has chunks */
+    const int cell_lo = g.p_lo / 3, cell_hi = (g.p_hi - 1) / 3;                   /* x-major cells x * H + y, inclusive */
     const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride], ad = agent_dir[(int64_t)e * astride];
     const bool inside = ax >= 0 && ax < W && ay >= 0 && ay < H;
     const int acell = inside ? ax * H + ay : -1;
@@ -106,40 +99,18 @@ __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_full_kernel(
     if (b == 0 && tid == 0 && error) error[e] = inside ? 0 : 2;
     __syncthreads();
     const int off = -3 * cell_lo;                           /* cells[off + p] = output byte p, p_lo <= p < p_hi */
-    for (int c = c0 + tid; c < c1; c += MG_OBS_THREADS) {
-        const int p = 16 * c - s;
-        if (p >= 0 && p + 16 <= F) {
+    for (int c = g.c0 + tid; c < g.c1; c += MG_OBS_THREADS)
+        mg_row_store(ob, F, c, [&](int p) {
             uint32_t w[4];
 #pragma unroll
             for (int d = 0; d < 4; d++)
                 w[d] = (uint32_t)cells[off + p + 4 * d] | (uint32_t)cells[off + p + 4 * d + 1] << 8 |
                        (uint32_t)cells[off + p + 4 * d + 2] << 16 | (uint32_t)cells[off + p + 4 * d + 3] << 24;
-            *reinterpret_cast<uint4 *>(ob + p) = make_uint4(w[0], w[1], w[2], w[3]);
-        } else {
-            for (int q = max(p, 0); q < min(p + 16, F); q++) ob[q] = cells[off + q];
-        }
-    }
+            return make_uint4(w[0], w[1], w[2], w[3]);
+        }, [&](int q) { return cells[off + q]; });
 }
 
 /* ------------------------------------------------------------------------------------------------ symbolic, flat */
-/* Chunk c of `total` 4-byte values at `base` (4-byte aligned), counted from the aligned address at or below it:
- * value i comes from gen(i). */
-template <typename V, typename G>
-__device__ static inline void mg_obs_store4(V *base, int64_t total, int64_t c, G gen)
-{
-    const int s = (int)(((uintptr_t)base >> 2) & 3);
-    const int64_t p = 4 * c - s;
-    if (p >= total) return;
-    if (p >= 0 && p + 4 <= total) {
-        union { V v[4]; uint4 u; } w;
-#pragma unroll
-        for (int d = 0; d < 4; d++) w.v[d] = gen(p + d);
-        *reinterpret_cast<uint4 *>(base + p) = w.u;
-    } else {
-        for (int64_t q = p < 0 ? 0 : p; q < (p + 4 < total ? p + 4 : total); q++) base[q] = gen(q);
-    }
-}
-
 __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_symbolic_kernel(const uint8_t *__restrict__ type, int W, int H,
                                                                          int32_t *__restrict__ out, int64_t total,
                                                                          int64_t chunks)
@@ -147,7 +118,7 @@ __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_symbolic_kernel(const u
     const int64_t c = (int64_t)blockIdx.x * MG_OBS_THREADS + threadIdx.x;
     if (c >= chunks) return;
     const int HW = W * H, R = HW * 3;
-    mg_obs_store4(out, total, c, [&](int64_t i) -> int32_t {
+    mg_row_store(out, total, c, [&](int64_t i) -> int32_t {
         const int64_t e = i / R;
         const int r = (int)(i - e * R), f = r / 3, k = r - 3 * f;
         if (k == 0) return f / H;
@@ -166,7 +137,7 @@ __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_flat_kernel(const uint8
     if (g >= (int64_t)N * cpr) return;
     const int e = (int)(g / cpr), c = (int)(g - (int64_t)e * cpr);
     const uint8_t *img = image + (int64_t)e * ipitch;
-    mg_obs_store4(out + (int64_t)e * opitch, (int64_t)n_img + n_tail, c, [&](int64_t i) -> float {
+    mg_row_store(out + (int64_t)e * opitch, (int64_t)n_img + n_tail, (int64_t)c, [&](int64_t i) -> float {
         return i < n_img ? (float)img[i] : tail[i - n_img];
     });
 }
@@ -209,11 +180,6 @@ __global__ __launch_bounds__(MG_OBS_THREADS) void mg_obs_goal_direction_kernel(
 }
 
 /* ------------------------------------------------------------------------------------------------ C ABI */
-static inline int mg_obs_launched(void)
-{
-    return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
-}
-
 static inline bool mg_obs_grid_ok(int64_t threads, unsigned *blocks)
 {
     const int64_t b = (threads + MG_OBS_THREADS - 1) / MG_OBS_THREADS;
@@ -229,13 +195,13 @@ extern "C" int mg_obs_onehot(const uint8_t *image, int64_t image_pitch, int n_en
     const int64_t in_row = (int64_t)n_cells * 3, row = (int64_t)n_cells * MG_OBS_ONEHOT_BITS;
     if (row >= ((int64_t)1 << 31) - 64) return TW_E_ARG;
     if ((image_pitch != 0 && image_pitch < in_row) || (out_pitch != 0 && out_pitch < row)) return TW_E_ARG;
-    const int64_t cpr = (row + 15 + 15) / 16;               /* one more chunk when the row's base is off alignment */
+    const int64_t cpr = mg_row_chunks(row, 16);
     unsigned blocks;
     if (!mg_obs_grid_ok(cpr * n_envs, &blocks)) return TW_E_ARG;
     if (error && hipMemsetAsync(error, 0, sizeof(int32_t) * (size_t)n_envs, (hipStream_t)stream) != hipSuccess) return TW_E_HIP;
     hipLaunchKernelGGL(mg_obs_onehot_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, image,
                        image_pitch ? image_pitch : in_row, n_envs, n_cells, out, out_pitch ? out_pitch : row, error, (int)cpr);
-    return mg_obs_launched();
+    return mg_launched();
 }
 
 extern "C" int mg_obs_full(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
@@ -247,12 +213,12 @@ extern "C" int mg_obs_full(const uint8_t *type, const uint8_t *colour, const uin
     const int64_t row = (int64_t)width * height * 3;
     if (row >= ((int64_t)1 << 31) - 64) return TW_E_ARG;
     if (out_pitch != 0 && out_pitch < row) return TW_E_ARG;
-    const int64_t bpe = ((row + 15 + 15) / 16 + MG_OBS_FULL_CHUNKS - 1) / MG_OBS_FULL_CHUNKS;
+    const int64_t bpe = (mg_row_chunks(row, 16) + MG_OBS_FULL_CHUNKS - 1) / MG_OBS_FULL_CHUNKS;
     if (bpe * n_envs >= ((int64_t)1 << 31)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_full_kernel, dim3((unsigned)(bpe * n_envs)), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream,
                        type, colour, state, n_envs, width, height, agent_x, agent_y, agent_dir, agent_stride, out,
                        out_pitch ? out_pitch : row, error, (int)bpe);
-    return mg_obs_launched();
+    return mg_launched();
 }
 
 extern "C" int mg_obs_symbolic(const uint8_t *type, int n_envs, int width, int height, int32_t *out, void *stream)
@@ -260,12 +226,12 @@ extern "C" int mg_obs_symbolic(const uint8_t *type, int n_envs, int width, int h
     if (!type || !out || n_envs <= 0 || width <= 0 || height <= 0 || ((uintptr_t)out & 3)) return TW_E_ARG;
     const int64_t total = (int64_t)n_envs * width * height * 3;
     if ((int64_t)width * height * 3 >= ((int64_t)1 << 31) || total >= ((int64_t)1 << 31)) return TW_E_ARG;
-    const int64_t chunks = (total + 3 + 3) / 4;
+    const int64_t chunks = mg_row_chunks(total, 4);
     unsigned blocks;
     if (!mg_obs_grid_ok(chunks, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_symbolic_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, type, width,
                        height, out, total, chunks);
-    return mg_obs_launched();
+    return mg_launched();
 }
 
 extern "C" int mg_obs_flat(const uint8_t *image, int64_t image_pitch, int n_envs, int n_img, const float *tail, int n_tail,
@@ -276,13 +242,13 @@ extern "C" int mg_obs_flat(const uint8_t *image, int64_t image_pitch, int n_envs
     const int64_t row = (int64_t)n_img + n_tail;
     if (row >= ((int64_t)1 << 29)) return TW_E_ARG;
     if ((image_pitch != 0 && image_pitch < n_img) || (out_pitch != 0 && out_pitch < row)) return TW_E_ARG;
-    const int64_t cpr = (row + 3 + 3) / 4;
+    const int64_t cpr = mg_row_chunks(row, 4);
     unsigned blocks;
     if (!mg_obs_grid_ok(cpr * n_envs, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_flat_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, image,
                        image_pitch ? image_pitch : (int64_t)n_img, n_envs, n_img, tail, n_tail, out,
                        out_pitch ? out_pitch : row, (int)cpr);
-    return mg_obs_launched();
+    return mg_launched();
 }
 
 extern "C" int mg_obs_goal_index(const uint8_t *type, int n_envs, int width, int height, int32_t *goal_index, void *stream)
@@ -293,7 +259,7 @@ extern "C" int mg_obs_goal_index(const uint8_t *type, int n_envs, int width, int
     if (!mg_obs_grid_ok((int64_t)n_envs * 64, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_goal_index_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, type, n_envs,
                        width * height, goal_index);
-    return mg_obs_launched();
+    return mg_launched();
 }
 
 extern "C" int mg_obs_angle_table_size(int width, int height)
@@ -316,5 +282,5 @@ extern "C" int mg_obs_goal_direction(const int32_t *goal_index, int n_envs, int 
     if (!mg_obs_grid_ok(n_envs, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_goal_direction_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream,
                        goal_index, n_envs, width, height, agent_x, agent_y, agent_stride, mode, angle_table, out, error);
-    return mg_obs_launched();
+    return mg_launched();
 }

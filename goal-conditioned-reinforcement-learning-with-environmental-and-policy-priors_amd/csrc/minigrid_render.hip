@@ -23,6 +23,7 @@
 
 #include "minigrid_render.h"
 #include "minigrid_view.h"
+#include "row_store.h"
 #include "twoarmy.h"
 #include "view_map.h"
 
@@ -265,8 +266,8 @@ struct mg_view_cells {
     }
 };
 
-/* Workgroup b of frame o owns the 16-byte-aligned chunks [b * MG_RENDER_CHUNKS, (b + 1) * MG_RENDER_CHUNKS) of the
- * frame, counted from the aligned address at or below the frame's first byte.  It first resolves the cells of the
+/* Workgroup b of frame o owns the chunks [b * MG_RENDER_CHUNKS, (b + 1) * MG_RENDER_CHUNKS) of the frame, a row of
+ * row_store.h (aligned 16-byte stores inside the frame, its two ends byte by byte).  It first resolves the cells of the
  * tile rows its span touches into atlas tile indices (LDS), then every lane builds whole chunks: a chunk walks the
  * frame's bytes as (tile row j, pixel row r, tile column i, byte k of the tile's run of tile_size * 3 bytes), fetching
  * four source bytes at a time while they stay inside one run.  W x H are the frame's cells; what they show is Cells'. */
@@ -290,12 +291,8 @@ __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_kernel(
     const int run = ts * 3, rowB = W * run, B = rowB * ts, tileB = ts * run, HW = W * H;
     const int F = B * H;
     uint8_t *fb = frame + (int64_t)o * pitch;
-    const int s = (int)((uintptr_t)fb & 15);
-    const int total = (s + F + 15) >> 4;
-    const int c0 = b * MG_RENDER_CHUNKS;
-    const int c1 = min(c0 + MG_RENDER_CHUNKS, total);
-    const int p_lo = max(0, 16 * c0 - s), p_hi = min(F, 16 * c1 - s);          /* frame bytes of this workgroup */
-    const int j0 = p_lo / B, j1 = (p_hi - 1) / B;
+    const mg_row_span_t<int> g = mg_row_span(mg_row_misalign(fb, 16), F, b, MG_RENDER_CHUNKS, 16);
+    const int j0 = g.p_lo / B, j1 = (g.p_hi - 1) / B;       /* tile rows of this workgroup's frame bytes */
     const Cells src(src_args, e, W, H);
 
     for (int t = tid; t < (j1 - j0 + 1) * W; t += MG_RENDER_THREADS) {
@@ -315,9 +312,8 @@ __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_kernel(
     __syncthreads();
     if (b == 0 && error && tid == 0) error[o] = (wave_bad[0] | wave_bad[1] | wave_bad[2] | wave_bad[3]) ? 1 : 0;
 
-    for (int c = c0 + tid; c < c1; c += MG_RENDER_THREADS) {
-        const int p = 16 * c - s;
-        if (p >= 0 && p + 16 <= F) {
+    for (int c = g.c0 + tid; c < g.c1; c += MG_RENDER_THREADS)
+        mg_row_store(fb, F, c, [&](int p) {
             int j = p / B, rem = p - j * B;
             int r = rem / rowB, xb = rem - r * rowB;
             int i = xb / run, k = xb - i * run;
@@ -340,22 +336,18 @@ __global__ __launch_bounds__(MG_RENDER_THREADS) void mg_render_kernel(
                     w[d] = v;
                 }
             }
-            *reinterpret_cast<uint4 *>(fb + p) = make_uint4(w[0], w[1], w[2], w[3]);
-        } else {                                            /* the frame's first / last chunk: only its own bytes */
-            for (int q = max(p, 0); q < min(p + 16, F); q++) {
-                const int j = q / B, rem = q - j * B;
-                const int r = rem / rowB, xb = rem - r * rowB;
-                const int i = xb / run, k = xb - i * run;
-                fb[q] = atlas[(int)tidx[(j - j0) * W + i] * tileB + r * run + k];
-            }
-        }
-    }
+            return make_uint4(w[0], w[1], w[2], w[3]);
+        }, [&](int q) {
+            const int j = q / B, rem = q - j * B;
+            const int r = rem / rowB, xb = rem - r * rowB;
+            const int i = xb / run, k = xb - i * run;
+            return atlas[(int)tidx[(j - j0) * W + i] * tileB + r * run + k];
+        });
 }
 
 /* ------------------------------------------------------------------------------------------------ highlight */
-/* get_full_render: top_left = pos + f * (V - 1) - r * (V / 2), view cell (vi, vj) lies at top_left - f * vj + r * vi
- * with f = DIR_TO_VEC[dir] and r = (-f.y, f.x).  f and r are orthonormal, so a world cell at offset d from top_left
- * is view cell (vi, vj) = (d . r, -d . f): each world cell looks its view cell up, no scatter. */
+/* get_full_render highlights the world cells of the agent's view window (view_map.h): each world cell looks its view
+ * cell (vi, vj) up, no scatter. */
 __global__ void mg_highlight_mask_kernel(const uint8_t *__restrict__ vis, int N, int W, int H,
                                          const int32_t *__restrict__ agent_x, const int32_t *__restrict__ agent_y,
                                          const int32_t *__restrict__ agent_dir, int astride, int V, uint8_t *__restrict__ out)
@@ -363,14 +355,11 @@ __global__ void mg_highlight_mask_kernel(const uint8_t *__restrict__ vis, int N,
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (int64_t)N * W * H) return;
     const int e = (int)(g / (W * H)), cell = (int)(g - (int64_t)e * W * H);
-    const int x = cell % W, y = cell / W;
     const int d = agent_dir[(int64_t)e * astride] & 3;
-    const int fx = d == 0 ? 1 : (d == 2 ? -1 : 0), fy = d == 1 ? 1 : (d == 3 ? -1 : 0);
-    const int rx = -fy, ry = fx;
-    const int tx = agent_x[(int64_t)e * astride] + fx * (V - 1) - rx * (V / 2);
-    const int ty = agent_y[(int64_t)e * astride] + fy * (V - 1) - ry * (V / 2);
-    const int dx = x - tx, dy = y - ty;
-    const int vi = dx * rx + dy * ry, vj = -(dx * fx + dy * fy);
+    int topx, topy, vi, vj;
+    mg_view_top(agent_x[(int64_t)e * astride], agent_y[(int64_t)e * astride], d, V, topx, topy);
+    const int x = cell % W, y = cell / W;
+    mg_view_from_slice((d + 1) & 3, V, x - topx, y - topy, vi, vj);
     uint8_t v = 0;
     if (vi >= 0 && vi < V && vj >= 0 && vj < V) v = vis ? (vis[((int64_t)e * V + vi) * V + vj] != 0) : 1;
     out[g] = v;
@@ -420,7 +409,7 @@ extern "C" int mg_render_build_atlas(int tile_size, uint8_t *atlas, void *stream
     mg_fill_consts(&k);
     hipLaunchKernelGGL(mg_render_atlas_kernel, dim3(MG_RENDER_TILES), dim3(MG_RENDER_THREADS), 0, (hipStream_t)stream,
                        tile_size, atlas, k);
-    return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
+    return mg_launched();
 }
 
 /* The frame-side argument rules and launch geometry of both entry points: n_out frames of width x height cells. */
@@ -436,8 +425,7 @@ static int mg_launch_frames(const typename Cells::args &src, int n_envs, int wid
     if (fbytes >= ((int64_t)1 << 31) - 64 || (int64_t)width * height >= ((int64_t)1 << 31)) return TW_E_ARG;
     if (frame_pitch != 0 && frame_pitch < fbytes) return TW_E_ARG;
     const int64_t pitch = frame_pitch ? frame_pitch : fbytes;
-    /* one more chunk than the frame's bytes need when its base is off alignment */
-    const int64_t bpf = ((fbytes + 15 + 15) / 16 + MG_RENDER_CHUNKS - 1) / MG_RENDER_CHUNKS;
+    const int64_t bpf = (mg_row_chunks(fbytes, 16) + MG_RENDER_CHUNKS - 1) / MG_RENDER_CHUNKS;
     if (bpf * n_out >= ((int64_t)1 << 31)) return TW_E_ARG;
     int64_t bands = ((int64_t)MG_RENDER_CHUNKS * 16 + band - 1) / band + 1;      /* tile rows one workgroup can touch */
     if (bands > height) bands = height;
@@ -446,7 +434,7 @@ static int mg_launch_frames(const typename Cells::args &src, int n_envs, int wid
     hipLaunchKernelGGL(mg_render_kernel<Cells>, dim3((unsigned)(bpf * n_out)), dim3(MG_RENDER_THREADS), (size_t)lds,
                        (hipStream_t)stream, src, n_envs, width, height, env_index, atlas, tile_size, frame, pitch, error,
                        (int)bpf);
-    return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
+    return mg_launched();
 }
 
 extern "C" int mg_render(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
@@ -487,5 +475,5 @@ extern "C" int mg_highlight_mask(const uint8_t *vis_mask, int n_envs, int width,
     if ((cells + 255) / 256 >= ((int64_t)1 << 31)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_highlight_mask_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        vis_mask, n_envs, width, height, agent_x, agent_y, agent_dir, agent_stride, view_size, out);
-    return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
+    return mg_launched();
 }

@@ -20,4 +20,12 @@ __device__ __forceinline__ void mg_view_to_slice(int k, int V, int i, int j, int
     sj = k == 0 ? j : (k == 1 ? i : (k == 2 ? V - 1 - j : V - 1 - i));
 }
 
+// The inverse: window cell (si, sj) -> view cell (i, j); inside the view exactly when the window cell is inside the window.
+__device__ __forceinline__ void mg_view_from_slice(int k, int V, int si, int sj, int &i, int &j) {
+    i = (k & 1) ? sj : si;                                  // k odd swaps the axes; then i flips for k = 2, 3,
+    j = (k & 1) ? si : sj;                                  // j for k = 1, 2
+    if (k & 2) i = V - 1 - i;
+    if ((k + 1) & 2) j = V - 1 - j;
+}
+
 #endif  // TWOARMY_VIEW_MAP_H

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._marshal import inner, ptr, stream
 from ._lib import (FIELDS, TW_CELLS, TW_DRAW_WORDS, TW_F_AUTORESET, TW_F_MATRIX_CODE, TW_F_POLICY_IDX, TW_F_SLAB_HIPMALLOC,
                    TW_REC_WORDS)
 
@@ -22,20 +23,6 @@ def obs_pitch_for(view):
     return (view * view * 3 + 15) // 16 * 16
 
 
-def _ptr(t, dtype=None):
-    if t is None:
-        return None
-    assert t.is_cuda, "engine buffers must be device tensors"
-    if dtype is not None:
-        assert t.dtype == dtype, "expected %s, got %s" % (dtype, t.dtype)
-    return C.c_void_p(t.data_ptr())
-
-
-def _dense(t, dtype):
-    assert t is None or (t.is_contiguous() and t.dtype == dtype), "expected contiguous %s" % dtype
-    return _ptr(t)
-
-
 def _pitched(t, lead, inner_shape, dtype):
     """(pointer, pitch in elements) of a [*lead, *inner_shape] tensor whose rows may be padded."""
     if t is None:
@@ -43,10 +30,7 @@ def _pitched(t, lead, inner_shape, dtype):
     assert t.is_cuda and t.dtype == dtype, "expected %s device tensor" % dtype
     nlead = len(lead)
     assert tuple(t.shape) == tuple(lead) + tuple(inner_shape), (tuple(t.shape), lead, inner_shape)
-    inner = 1
-    for d in range(t.dim() - 1, nlead - 1, -1):            # inner dims must be dense
-        assert t.stride(d) == inner or t.shape[d] == 1, "inner dims of an engine buffer must be dense"
-        inner *= t.shape[d]
+    row = inner(t, nlead)
     # row pitch from the innermost leading dim of size > 1 (strides of size-1 dims are arbitrary)
     pitch, mult = None, 1
     for d in range(nlead - 1, -1, -1):
@@ -58,8 +42,8 @@ def _pitched(t, lead, inner_shape, dtype):
                 assert t.stride(d) == pitch * mult, "leading dims must be dense"
         mult *= t.shape[d]
     if pitch is None:
-        pitch = inner
-    assert pitch >= inner
+        pitch = row
+    assert pitch >= row
     return C.c_void_p(t.data_ptr()), int(pitch)
 
 
@@ -92,11 +76,11 @@ class _OutputSlab:
             _lib.check(_lib.lib().tw_alloc_outputs(engine._h, int(T), int(flags), C.byref(self.out)), "tw_alloc_outputs")
         self.backing = int(self.out.backing)
 
-    def tensor(self, ptr, nbytes, dtype):
-        t = torch.as_tensor(_DevSpan(self, ptr, nbytes), device=self.device)
-        if t.data_ptr() != int(ptr) or t.device != self.device:
+    def tensor(self, addr, nbytes, dtype):
+        t = torch.as_tensor(_DevSpan(self, addr, nbytes), device=self.device)
+        if t.data_ptr() != int(addr) or t.device != self.device:
             raise _lib.TwoarmyLibraryError("torch did not alias the engine slab (got %s at %#x for %#x on %s)"
-                                           % (t.device, t.data_ptr(), int(ptr), self.device))
+                                           % (t.device, t.data_ptr(), int(addr), self.device))
         return t.view(dtype)
 
     def __del__(self):
@@ -124,7 +108,7 @@ class TwoarmyEngine:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.variant, self.num_envs, self.view_size = variant, int(num_envs), int(view_size)
         self.seed, self.env_id0 = int(seed), int(env_id0)
-        self._h = C.c_void_p()
+        self._h, self._own_views = C.c_void_p(), None
         lib = _lib.lib()
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
@@ -142,16 +126,13 @@ class TwoarmyEngine:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             _lib.lib().tw_destroy(self._h)
-            self._h = None
+            self._h = self._own_views = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_pipeline(self, enable):
         _lib.check(_lib.lib().tw_set_pipeline(self._h, int(bool(enable))), "tw_set_pipeline")
@@ -253,7 +234,7 @@ class TwoarmyEngine:
     def reset(self, mask=None, obs=None):
         V = self.view_size
         op, opitch = _pitched(obs, (self.num_envs,), (V, V, 3), torch.uint8)
-        _lib.check(_lib.lib().tw_reset(self._h, _dense(mask, torch.uint8), op, opitch, self._stream()), "tw_reset")
+        _lib.check(_lib.lib().tw_reset(self._h, ptr(mask, torch.uint8), op, opitch, stream(self.device)), "tw_reset")
         return obs
 
     @staticmethod
@@ -280,13 +261,13 @@ class TwoarmyEngine:
                       ("truncated", torch.uint8)):
             t = out.get(k)
             assert t is None or (t.is_contiguous() and t.dtype == dt and tuple(t.shape[:len(lead)]) == lead), k
-        return [op, opitch, mp, mpitch, _ptr(out.get("pos")), _ptr(out.get("reward")), _ptr(out.get("terminated")),
-                _ptr(out.get("truncated"))], flags
+        return [op, opitch, mp, mpitch, ptr(out.get("pos")), ptr(out.get("reward")), ptr(out.get("terminated")),
+                ptr(out.get("truncated"))], flags
 
     def _launch(self, fn, name, lead, T, actions, draws, out, flags):
         outs, flags = self._out_args(lead, out, flags)
-        args = [self._h] + ([T] if T is not None else []) + [_dense(actions, torch.int32), _ptr(draws)] + outs + [
-            flags, self._stream()]
+        args = [self._h] + ([T] if T is not None else []) + [ptr(actions, torch.int32), ptr(draws)] + outs + [
+            flags, stream(self.device)]
         _lib.check(fn(*args), name)
         return out
 
@@ -307,13 +288,13 @@ class TwoarmyEngine:
 
     def fill_actions(self, T):
         a = torch.empty((T, self.num_envs), dtype=torch.int32, device=self.device)
-        _lib.check(_lib.lib().tw_fill_actions(self._h, T, _ptr(a), self._stream()), "tw_fill_actions")
+        _lib.check(_lib.lib().tw_fill_actions(self._h, T, ptr(a), stream(self.device)), "tw_fill_actions")
         return a
 
     def gen_obs(self, view_size=None):
         V = view_size or self.view_size
         obs = torch.empty((self.num_envs, V, V, 3), dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.lib().tw_gen_obs(self._h, V, _ptr(obs), 0, self._stream()), "tw_gen_obs")
+        _lib.check(_lib.lib().tw_gen_obs(self._h, V, ptr(obs), 0, stream(self.device)), "tw_gen_obs")
         return obs
 
     def render(self, env_index=None, tile_size=17, highlight=False, out=None):
@@ -321,91 +302,71 @@ class TwoarmyEngine:
         engine's planes and records (tw_state_ptrs) on the current stream: no host copy of the state.  env_index:
         int32 device tensor of the envs to draw (None = all); highlight: brighten the agent's view_size x view_size
         view as the reference's `highlight=True` does (Twoarmy sees through walls: the whole view)."""
-        from .minigrid_render import TileAtlas
-        lib = _lib.lib()
-        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(lib.tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
-        ts, N, S = int(tile_size), self.num_envs, 17
-        n = N if env_index is None else int(env_index.shape[0])
-        frame = out if out is not None else torch.empty((n, S * ts, S * ts, 3), dtype=torch.uint8, device=self.device)
-        assert frame.shape == (n, S * ts, S * ts, 3) and frame.dtype == torch.uint8 and frame.is_contiguous()
-        atlas = TileAtlas.get(ts, self.device)
-        ax, ay, ad = (C.c_void_p(rec.value + 4 * FIELDS[k]) for k in ("AX", "AY", "DIR"))
-        with torch.cuda.device(self.device):
-            hm = None
-            if highlight:
-                hm = torch.empty((N, TW_CELLS), dtype=torch.uint8, device=self.device)
-                _lib.check(lib.mg_highlight_mask(None, N, S, S, ax, ay, ad, TW_REC_WORDS, self.view_size, _ptr(hm),
-                                                 self._stream()), "mg_highlight_mask")
-            _lib.check(lib.mg_render(ty, co, None, N, S, S, ax, ay, ad, TW_REC_WORDS, _dense(env_index, torch.int32), n,
-                                     _ptr(hm) if hm is not None else None, _ptr(atlas.tiles), ts, _ptr(frame), 0, None,
-                                     self._stream()), "mg_render")
-        return frame
+        from . import minigrid_render as mr
+        ty, co, agent = self._views()
+        hm = mr.highlight_mask(None, 17, 17, *agent, self.view_size, n_envs=self.num_envs) if highlight else None
+        return mr.render(ty, co, None, 17, 17, *agent, tile_size, highlight=hm, env_index=env_index, out=out)
 
     def render_pov(self, env_index=None, tile_size=17, view_size=None, out=None):
         """RGB frames of MiniGridEnv.get_pov_render, uint8[n, V*ts, V*ts, 3] (V = view_size, default the engine's):
         the agent's view with the agent at the bottom centre pointing up, every cell highlighted (Twoarmy sees through
         walls and carries nothing).  Drawn like render(): from the engine's planes and records, on the current stream."""
-        from .minigrid_render import TileAtlas
-        lib = _lib.lib()
+        from . import minigrid_render as mr
+        ty, co, agent = self._views()
+        return mr.render_pov(ty, co, None, 17, 17, *agent, view_size or self.view_size, tile_size, env_index=env_index,
+                             out=out)
+
+    def _state_ptrs(self):
+        """(type planes, colour planes, records): device addresses of the engine's state, fixed for its life."""
         ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(lib.tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
-        ts, N, S, V = int(tile_size), self.num_envs, 17, int(view_size or self.view_size)
-        n = N if env_index is None else int(env_index.shape[0])
-        frame = out if out is not None else torch.empty((n, V * ts, V * ts, 3), dtype=torch.uint8, device=self.device)
-        assert frame.shape == (n, V * ts, V * ts, 3) and frame.dtype == torch.uint8 and frame.is_contiguous()
-        atlas = TileAtlas.get(ts, self.device)
-        ax, ay, ad = (C.c_void_p(rec.value + 4 * FIELDS[k]) for k in ("AX", "AY", "DIR"))
-        with torch.cuda.device(self.device):
-            _lib.check(lib.mg_render_pov(ty, co, None, N, S, S, ax, ay, ad, TW_REC_WORDS, None,
-                                         _dense(env_index, torch.int32), n, None, V, _ptr(atlas.tiles), ts, _ptr(frame), 0,
-                                         None, self._stream()), "mg_render_pov")
-        return frame
+        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
+        return ty.value, co.value, rec.value
+
+    def _views(self, owner=None):
+        """(type, colour) uint8[N, 289] and the (TW_AX, TW_AY, TW_DIR) columns of the records as int32 [N,
+        TW_REC_WORDS]: device views of the engine's own state (no copy).  Views that are handed out keep `owner` (the
+        engine) alive; render() and render_pov() use one set of their own, built once."""
+        if owner is None and self._own_views is not None:
+            return self._own_views
+        N, flat = self.num_envs, []
+        for addr, nbytes in zip(self._state_ptrs(), (N * TW_CELLS, N * TW_CELLS, N * TW_REC_WORDS * 4)):
+            t = torch.as_tensor(_DevSpan(owner, addr, nbytes), device=self.device)
+            if t.data_ptr() != addr:
+                raise _lib.TwoarmyLibraryError("torch did not alias the engine's state")
+            flat.append(t)
+        rec = flat[2].view(torch.int32).view(N, TW_REC_WORDS)
+        views = (flat[0].view(N, TW_CELLS), flat[1].view(N, TW_CELLS), tuple(rec[:, FIELDS[k]] for k in ("AX", "AY", "DIR")))
+        if owner is None:
+            self._own_views = views
+        return views
 
     def dir_ptr(self):
         """(address, stride_t, stride_n) of the agents' directions in the engine's records (tw_state_ptrs), in int32
         elements: one value per env, as ppo_ops.bonus_scan(dir_ptr=...) takes it.  After an auto-reset the record holds
         the new episode's direction."""
-        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
-        return rec.value + 4 * FIELDS["DIR"], 0, TW_REC_WORDS
-
-    def agent_ptrs(self):
-        """(address of TW_AX, of TW_AY, of TW_DIR, stride in int32 elements) in the engine's records: the `agent_ptrs`
-        argument of minigrid_obs.full_obs / goal_direction, which then read the agent where it lives."""
-        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
-        return tuple(rec.value + 4 * FIELDS[k] for k in ("AX", "AY", "DIR")) + (TW_REC_WORDS,)
+        return self._state_ptrs()[2] + 4 * FIELDS["DIR"], 0, TW_REC_WORDS
 
     def plane_views(self):
         """(type, colour) uint8[N, 289] device views of the engine's own planes (tw_state_ptrs; no copy): cell (x, y)
         at y*17 + x.  They show the state of the moment a kernel reads them."""
-        ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
-        out = []
-        for p in (ty, co):
-            t = torch.as_tensor(_DevSpan(self, p.value, self.num_envs * TW_CELLS), device=self.device)
-            if t.data_ptr() != p.value:
-                raise _lib.TwoarmyLibraryError("torch did not alias the engine's planes")
-            out.append(t.view(self.num_envs, TW_CELLS))
-        return tuple(out)
+        return self._views(self)[:2]
+
+    def agent_views(self):
+        """(x, y, dir) int32[N] strided device views of TW_AX, TW_AY and TW_DIR in the engine's records (no copy): the
+        agent_* arguments of minigrid_obs and minigrid_render, which then read the agent where it lives."""
+        return self._views(self)[2]
 
     def dir_view(self):
         """int32[N] strided device view of the same directions (no copy)."""
-        addr = self.dir_ptr()[0] - 4 * FIELDS["DIR"]
-        span = _DevSpan(self, addr, self.num_envs * TW_REC_WORDS * 4)
-        t = torch.as_tensor(span, device=self.device)
-        if t.data_ptr() != addr:
-            raise _lib.TwoarmyLibraryError("torch did not alias the engine's records")
-        return t.view(torch.int32).view(self.num_envs, TW_REC_WORDS)[:, FIELDS["DIR"]]
+        return self.agent_views()[2]
 
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""
         ms = C.c_float()
         flags = (TW_F_AUTORESET if autoreset else 0) | TW_F_POLICY_IDX
         outs, flags = self._out_args((T, self.num_envs), out, flags)
-        _lib.check(_lib.lib().tw_time_rollout(self._h, T, _dense(actions, torch.int32), *outs, flags, iters,
-                                              self._stream(), C.byref(ms)), "tw_time_rollout")
+        _lib.check(_lib.lib().tw_time_rollout(self._h, T, ptr(actions, torch.int32), *outs, flags, iters,
+                                              stream(self.device), C.byref(ms)), "tw_time_rollout")
         return ms.value
 
     # ------------------------------------------------------------------ state

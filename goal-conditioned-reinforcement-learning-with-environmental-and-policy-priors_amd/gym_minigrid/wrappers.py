@@ -210,7 +210,7 @@ class FullyObsWrapper(_ObservationWrapper):
         from .. import minigrid_obs
         u = self.unwrapped
         ty, co = self._eng.plane_views()
-        out = minigrid_obs.full_obs(ty, co, None, u.width, u.height, agent_ptrs=self._eng.agent_ptrs())
+        out = minigrid_obs.full_obs(ty, co, None, u.width, u.height, *self._eng.agent_views())
         return {**obs, "image": out[0].cpu().numpy()}
 
 
@@ -280,7 +280,7 @@ class DirectionObsWrapper(_ObservationWrapper):
         mode = "angle" if self.type == "angle" else "slope"
         if mode == "angle" and self._table is None:
             self._table = minigrid_obs.angle_table(u.width, u.height, self._device)
-        out = minigrid_obs.goal_direction(self._goal_index, u.width, u.height, agent_ptrs=self._eng.agent_ptrs(), mode=mode,
+        out = minigrid_obs.goal_direction(self._goal_index, u.width, u.height, *self._eng.agent_views()[:2], mode=mode,
                                           table=self._table)
         obs["goal_direction"] = out.cpu().numpy()[0]
         return obs

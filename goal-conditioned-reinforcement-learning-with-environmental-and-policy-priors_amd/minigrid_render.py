@@ -1,33 +1,15 @@
 """Torch front end of the device renderer (include/minigrid_render.h): MiniGridEnv.get_full_render and get_pov_render
 of the reference (gym_minigrid/minigrid.py:662-747, 1498-1563 and rendering.py) for N worlds kept as
 structure-of-arrays planes on the GPU, byte for byte.  A tile atlas is rasterised once per (device, tile size); a frame
-is then a gather from it.  No CPU fallback."""
-import ctypes as C
-
+is then a gather from it.  agent_* are 1-D int32 device tensors, dense or the column views of the engine's records
+(TwoarmyEngine.agent_views()); their shared stride is what the C ABI is told.  No CPU fallback."""
 import torch
 
 from . import _lib
+from ._marshal import agent_arrays, call, ptr
 
 MG_RENDER_TILES = 600
 MG_RENDER_MAX_TILE = 256
-
-
-def _p(t, dtype):
-    if t is None:
-        return None
-    assert t.is_cuda and t.is_contiguous() and t.dtype == dtype, "expected contiguous %s device tensor" % dtype
-    return C.c_void_p(t.data_ptr())
-
-
-def _ap(t, stride):
-    """Agent arrays: int32 device tensors; with a stride other than 1 only the base address is taken (e.g. a column
-    view of the engine's records)."""
-    assert t.is_cuda and t.dtype == torch.int32 and (stride != 1 or t.is_contiguous())
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def atlas_bytes(tile_size):
@@ -54,11 +36,9 @@ class TileAtlas:
         n = atlas_bytes(self.tile_size)
         self.tiles = torch.empty(n, dtype=torch.uint8, device=self.device).view(MG_RENDER_TILES, self.tile_size,
                                                                                  self.tile_size, 3)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mg_render_build_atlas(self.tile_size, _p(self.tiles, torch.uint8), _stream(self.device)),
-                       "mg_render_build_atlas")
-            # frames may be rendered on any stream later: the atlas is complete before the constructor returns
-            torch.cuda.current_stream(self.device).synchronize()
+        call("mg_render_build_atlas", self.device, self.tile_size, ptr(self.tiles, torch.uint8))
+        # frames may be rendered on any stream later: the atlas is complete before the constructor returns
+        torch.cuda.current_stream(self.device).synchronize()
 
     @classmethod
     def get(cls, tile_size, device):
@@ -72,31 +52,27 @@ class TileAtlas:
 
 
 def render(type_plane, colour_plane, state_plane, width, height, agent_x, agent_y, agent_dir, tile_size, highlight=None,
-           env_index=None, out=None, error=None, agent_stride=1):
+           env_index=None, out=None, error=None):
     """-> uint8[n, H*ts, W*ts, 3], the frames of Grid.render.  Planes uint8[N, H*W] (state_plane, highlight may be
-    None); agent_* int32 device tensors read at [e * agent_stride]; env_index int32[n] picks the envs to draw (None =
-    all); error int32[n] receives 1 where a world holds a cell that is not drawn (lava, unknown codes)."""
+    None); agent_* int32 device tensors, dense or the column views of the engine's records (_marshal.agent_arrays);
+    env_index int32[n] picks the envs to draw (None = all); error int32[n] receives 1 where a world holds a cell that is
+    not drawn (lava, unknown codes)."""
     N = type_plane.shape[0]
     W, H, ts = int(width), int(height), int(tile_size)
     assert type_plane.shape == (N, W * H) and colour_plane.shape == (N, W * H)
     dev = type_plane.device
     n = N if env_index is None else env_index.shape[0]
     frame = out if out is not None else torch.empty((n, H * ts, W * ts, 3), dtype=torch.uint8, device=dev)
-    assert frame.shape == (n, H * ts, W * ts, 3)
-    if agent_stride == 1:
-        assert agent_x.numel() >= N and agent_y.numel() >= N and agent_dir.numel() >= N
+    assert frame.shape == (n, H * ts, W * ts, 3) and agent_x.shape[0] >= N
     atlas = TileAtlas.get(ts, dev)
-    with torch.cuda.device(dev):                    # the launch goes to the planes' device, whichever is current
-        _lib.check(_lib.lib().mg_render(
-            _p(type_plane, torch.uint8), _p(colour_plane, torch.uint8), _p(state_plane, torch.uint8), N, W, H,
-            _ap(agent_x, agent_stride), _ap(agent_y, agent_stride), _ap(agent_dir, agent_stride), int(agent_stride),
-            _p(env_index, torch.int32), n, _p(highlight, torch.uint8), _p(atlas.tiles, torch.uint8), ts,
-            _p(frame, torch.uint8), 0, _p(error, torch.int32), _stream(dev)), "mg_render")
+    call("mg_render", dev, ptr(type_plane, torch.uint8), ptr(colour_plane, torch.uint8), ptr(state_plane, torch.uint8), N,
+         W, H, *agent_arrays(agent_x, agent_y, agent_dir), ptr(env_index, torch.int32), n, ptr(highlight, torch.uint8),
+         ptr(atlas.tiles, torch.uint8), ts, ptr(frame, torch.uint8), 0, ptr(error, torch.int32))
     return frame
 
 
 def render_pov(type_plane, colour_plane, state_plane, width, height, agent_x, agent_y, agent_dir, view_size, tile_size,
-               carrying=None, vis_mask=None, env_index=None, out=None, error=None, agent_stride=1, see_through_walls=True):
+               carrying=None, vis_mask=None, env_index=None, out=None, error=None, see_through_walls=True):
     """-> uint8[n, V*ts, V*ts, 3], the frames of get_pov_render: the agent's V x V view drawn unmasked, the carried
     object (carrying uint8[N, 3], None = nothing) under the agent, the cells of vis_mask (uint8[N, V, V] from gen_obs)
     highlighted.  vis_mask None: every cell, or with see_through_walls=False the mask of one mg_gen_obs launch (dense
@@ -107,37 +83,28 @@ def render_pov(type_plane, colour_plane, state_plane, width, height, agent_x, ag
     dev = type_plane.device
     n = N if env_index is None else env_index.shape[0]
     frame = out if out is not None else torch.empty((n, V * ts, V * ts, 3), dtype=torch.uint8, device=dev)
-    assert frame.shape == (n, V * ts, V * ts, 3)
+    assert frame.shape == (n, V * ts, V * ts, 3) and agent_x.shape[0] >= N
     assert carrying is None or carrying.shape == (N, 3)
-    if agent_stride == 1:
-        assert agent_x.numel() >= N and agent_y.numel() >= N and agent_dir.numel() >= N
     atlas = TileAtlas.get(ts, dev)
-    with torch.cuda.device(dev):
-        if vis_mask is None and not see_through_walls:
-            from . import minigrid_view
-            assert agent_stride == 1, "mg_gen_obs reads dense agent arrays"
-            vis_mask = minigrid_view.gen_obs(type_plane, colour_plane, state_plane, W, H, agent_x, agent_y, agent_dir, V,
-                                             see_through_walls=False, carrying=carrying)[1]
-        assert vis_mask is None or vis_mask.shape == (N, V, V)
-        _lib.check(_lib.lib().mg_render_pov(
-            _p(type_plane, torch.uint8), _p(colour_plane, torch.uint8), _p(state_plane, torch.uint8), N, W, H,
-            _ap(agent_x, agent_stride), _ap(agent_y, agent_stride), _ap(agent_dir, agent_stride), int(agent_stride),
-            _p(carrying, torch.uint8), _p(env_index, torch.int32), n, _p(vis_mask, torch.uint8), V,
-            _p(atlas.tiles, torch.uint8), ts, _p(frame, torch.uint8), 0, _p(error, torch.int32), _stream(dev)),
-            "mg_render_pov")
+    if vis_mask is None and not see_through_walls:
+        from . import minigrid_view
+        vis_mask = minigrid_view.gen_obs(type_plane, colour_plane, state_plane, W, H, agent_x, agent_y, agent_dir, V,
+                                         see_through_walls=False, carrying=carrying)[1]
+    assert vis_mask is None or vis_mask.shape == (N, V, V)
+    call("mg_render_pov", dev, ptr(type_plane, torch.uint8), ptr(colour_plane, torch.uint8), ptr(state_plane, torch.uint8),
+         N, W, H, *agent_arrays(agent_x, agent_y, agent_dir), ptr(carrying, torch.uint8), ptr(env_index, torch.int32), n,
+         ptr(vis_mask, torch.uint8), V, ptr(atlas.tiles, torch.uint8), ts, ptr(frame, torch.uint8), 0,
+         ptr(error, torch.int32))
     return frame
 
 
-def highlight_mask(vis_mask, width, height, agent_x, agent_y, agent_dir, view_size, n_envs=None, agent_stride=1, out=None):
+def highlight_mask(vis_mask, width, height, agent_x, agent_y, agent_dir, view_size, n_envs=None, out=None):
     """get_full_render's highlight loop: vis_mask uint8[N, V, V] from gen_obs (None = every view cell visible) ->
     uint8[N, H*W] in world coordinates."""
     N = vis_mask.shape[0] if vis_mask is not None else int(n_envs)
     dev = agent_x.device
     mask = out if out is not None else torch.empty((N, int(width) * int(height)), dtype=torch.uint8, device=dev)
-    assert mask.shape == (N, int(width) * int(height))
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mg_highlight_mask(
-            _p(vis_mask, torch.uint8), N, int(width), int(height), _ap(agent_x, agent_stride), _ap(agent_y, agent_stride),
-            _ap(agent_dir, agent_stride), int(agent_stride), int(view_size), _p(mask, torch.uint8), _stream(dev)),
-            "mg_highlight_mask")
+    assert mask.shape == (N, int(width) * int(height)) and agent_x.shape[0] >= N
+    call("mg_highlight_mask", dev, ptr(vis_mask, torch.uint8), N, int(width), int(height),
+         *agent_arrays(agent_x, agent_y, agent_dir), int(view_size), ptr(mask, torch.uint8))
     return mask

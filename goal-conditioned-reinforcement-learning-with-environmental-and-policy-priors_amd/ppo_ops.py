@@ -5,19 +5,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _p(t, dtype=None):
-    if t is None:
-        return None
-    assert t.is_cuda and t.is_contiguous(), "PPO kernels take contiguous device tensors"
-    if dtype is not None:
-        assert t.dtype == dtype, "expected %s got %s" % (dtype, t.dtype)
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+from ._marshal import ptr as _p, stream as _stream
 
 
 def sample(probs, uniforms=None, seed=0, offset=0, offset_dev=None):

@@ -137,20 +137,20 @@ class TwoarmyVecEnv:
             return self.render_pov(out=out)
         ty, co, agent = self._state()
         if kind == "full":
-            return mo.full_obs(ty, co, None, 17, 17, agent_ptrs=agent, out=out)
+            return mo.full_obs(ty, co, None, 17, 17, *agent, out=out)
         return mo.symbolic_obs(ty, 17, 17, out=out)
 
     def _state(self):
-        """(type plane, colour plane, agent_ptrs) of the engine: views and addresses that hold for the engine's life."""
+        """(type plane, colour plane, agent views) of the engine: views that hold for the engine's life."""
         if self._state_src is None:
-            self._state_src = self.engine.plane_views() + (self.engine.agent_ptrs(),)
+            self._state_src = self.engine.plane_views() + (self.engine.agent_views(),)
         return self._state_src
 
     def _emit_direction(self, slot):
         if self._goal_index is None:                     # once, as DirectionObsWrapper caches goal_position
             self._goal_index = self._mo.goal_index(self._state()[0], 17, 17)
-        return self._mo.goal_direction(self._goal_index, 17, 17, agent_ptrs=self._state()[2],
-                                       mode=self.goal_direction, table=self._angle_table, out=self._dir_buf[slot])
+        return self._mo.goal_direction(self._goal_index, 17, 17, *self._state()[2][:2], mode=self.goal_direction,
+                                       table=self._angle_table, out=self._dir_buf[slot])
 
     def step(self, actions):
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()

@@ -25,6 +25,11 @@ def _lib():
     return _lib
 
 
+def _marshal():
+    from twoarmy_amd import _marshal
+    return _marshal
+
+
 def _dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
@@ -437,7 +442,7 @@ def test_bias_relu_grid_stride_vs_float64(C):
     y = _dyadic(rs, (npix, C), 64, 4)
     b = _dyadic(rs, (C,), 64, 2)
     t, tb = _dev(y), _dev(b)
-    _lib().check(_lib().lib().ppo_bias_relu_nhwc(_ops()._p(t), _ops()._p(tb), npix, C, _ops()._stream(t)),
+    _lib().check(_lib().lib().ppo_bias_relu_nhwc(_marshal().ptr(t), _marshal().ptr(tb), npix, C, _marshal().stream(t)),
                  "ppo_bias_relu_nhwc")
     ref = np.maximum(y.astype(np.float64) + b.astype(np.float64), 0.0)      # exact in fp32 (multiples of 1/64, < 8)
     assert np.array_equal(t.cpu().numpy().astype(np.float64), ref)
@@ -450,8 +455,9 @@ def _relu_bwd(gy, y, C):
     tg, ty = _dev(gy), _dev(y)
     gx = torch.empty_like(tg)
     part = torch.empty((max(blocks, 1), C), dtype=torch.float32, device=DEV)
-    _lib().check(lib.ppo_relu_bwd_bias_grad_nhwc(_ops()._p(tg), _ops()._p(ty), _ops()._p(gx), _ops()._p(part), npix, C,
-                                                 _ops()._stream(tg)), "ppo_relu_bwd_bias_grad_nhwc")
+    m = _marshal()
+    _lib().check(lib.ppo_relu_bwd_bias_grad_nhwc(m.ptr(tg), m.ptr(ty), m.ptr(gx), m.ptr(part), npix, C, m.stream(tg)),
+                 "ppo_relu_bwd_bias_grad_nhwc")
     return blocks, gx, part
 
 

@@ -192,14 +192,14 @@ def test_lstm_cell_rejections_launch_nothing():
     """H % 4, no pre-activations at all, pointers off 16-byte alignment by one float, a row pitch shorter than a row or
     no multiple of 4 floats, an empty batch: TW_E_ARG on the host, c and h untouched."""
     import ctypes as C
-    from twoarmy_amd import _lib, ppo_ops
+    from twoarmy_amd import _lib, _marshal
     lib = _lib.lib()
     B, H = 5, 8
     store = {k: torch.full((B * 4 * H + 8,), 0.5, device=DEV) for k in ("ga", "gb", "bias", "c", "h")}
 
     def call(B_=B, H_=H, ldb=4 * H, off=(), null=()):
         p = {k: (None if k in null else C.c_void_p(v.data_ptr() + (4 if k in off else 0))) for k, v in store.items()}
-        rc = lib.ppo_lstm_cell(p["ga"], p["gb"], ldb, p["bias"], p["c"], p["h"], B_, H_, ppo_ops._stream(store["c"]))
+        rc = lib.ppo_lstm_cell(p["ga"], p["gb"], ldb, p["bias"], p["c"], p["h"], B_, H_, _marshal.stream(store["c"]))
         torch.cuda.synchronize()
         return rc
 

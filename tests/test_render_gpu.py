@@ -281,8 +281,7 @@ def test_record_strided_agents_env_index_errors_and_single_frame():
     empty = rr.render_tile(1, 0, 0, int(ad[2]) if (ax[2], ay[2]) == (5, 0) else -1, 0, ts)
     assert np.array_equal(got[1].reshape(H * ts, W * ts, 3)[0:ts, 5 * ts:6 * ts], empty)
     # n_out = 1, error NULL, through the front end with a strided view of the records
-    one = _mr().render(d[0], d[1], d[2], W, H, rec_d[:, 0], rec_d[:, 1], rec_d[:, 2], ts, env_index=_dev(idx[3:4]),
-                       agent_stride=TW_REC_WORDS)
+    one = _mr().render(d[0], d[1], d[2], W, H, rec_d[:, 0], rec_d[:, 1], rec_d[:, 2], ts, env_index=_dev(idx[3:4]))
     assert np.array_equal(one.cpu().numpy()[0], ref[2])
 
 
