@@ -106,6 +106,10 @@ _SIGS.update({
     "mg_obs_goal_index": (C.c_int, [_vp, _i, _i, _i, _vp, _vp]),
     "mg_obs_angle_table_size": (C.c_int, [_i, _i]),
     "mg_obs_goal_direction": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    # include/minigrid_nav.h
+    "mg_nav_field": (C.c_int, [_vp, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp,
+                               _vp]),
+    "mg_nav_lookup": (C.c_int, [_vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ppo_her_relabel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
     "ppo_her_relabel_window": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _i, _vp,

@@ -1,0 +1,215 @@
+/*
+ * minigrid_nav.hip -- shortest-path distance fields and expert actions on the device (C ABI: include/minigrid_nav.h).
+ *
+ *   mg_nav_field_kernel    the flood runs on row bit masks: one lane per world row holds `open` (enterable cells) and
+ *                          `reached` as 32-bit masks, two envs per 64-lane wavefront (lanes 0..31 / 32..63).  A step is
+ *                          (reached | reached << 1 | reached >> 1 | row above | row below) & open, the neighbour rows
+ *                          taken by cross-lane shuffles; one ballot per step decides "nothing new".  The loop holds no
+ *                          LDS read and no barrier, and ends after at most width*height steps whatever the input.
+ *                          Cells reached in step k get k written into an LDS uint16 image (a walk over the new bits of
+ *                          the row); the image then leaves whole through the aligned row store (row_store.h), and one
+ *                          lane per env reads the agent's cell and its four neighbours from it.
+ *   mg_nav_lookup_kernel   one lane per (step, env): the cell of the position (visit_cell.h) indexes the env's field.
+ *
+ * Integer work only, no atomics: the results do not depend on scheduling.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "minigrid_nav.h"
+#include "row_store.h"
+#include "twoarmy.h"
+#include "visit_cell.h"
+
+namespace {
+
+constexpr int NAV_SIDE = MG_NAV_MAX_SIDE;
+constexpr int NAV_CELLS = NAV_SIDE * NAV_SIDE;
+constexpr int NAV_THREADS = 256;                       // 4 wavefronts
+constexpr int NAV_ENVS = NAV_THREADS / NAV_SIDE;       // 8 envs per workgroup: 4096 envs are 512 workgroups
+constexpr uint32_t NAV_T_DOOR = 4, NAV_T_GOAL = 8;
+static_assert(NAV_SIDE == 32 && VISIT_MAX_SIDE == NAV_SIDE, "one lane per row, one mask bit per column");
+
+// f(x, byte) for the W bytes at rowp, read as aligned words (the over-read rule of minigrid_nav.h).
+template <typename F> __device__ __forceinline__ void nav_row_bytes(const uint8_t *rowp, int W, F f)
+{
+    const int mis = (int)((uintptr_t)rowp & 3);
+    const uint32_t *wp = reinterpret_cast<const uint32_t *>(rowp - mis);
+    const int nw = (mis + W + 3) >> 2;
+    for (int k = 0; k < nw; ++k) {
+        const uint32_t w = wp[k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = 4 * k + j - mis;
+            if (x >= 0 && x < W) f(x, (w >> (8 * j)) & 255u);
+        }
+    }
+}
+
+// the 32 ballot bits of this lane's half of the wavefront
+__device__ __forceinline__ uint32_t nav_half_ballot(bool p, int half)
+{
+    return (uint32_t)(__ballot(p) >> (32 * half));
+}
+
+// image and the wave's own LDS traffic: orders what other lanes of the wavefront wrote before what this lane reads
+__device__ __forceinline__ void nav_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const int32_t *__restrict__ goal_x, const int32_t *__restrict__ goal_y, int gstride,
+    const int32_t *__restrict__ agent_x, const int32_t *__restrict__ agent_y, int astride, uint16_t *__restrict__ dist,
+    int64_t pitch, int32_t *__restrict__ agent_dist, int32_t *__restrict__ agent_action, int32_t *__restrict__ error)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_ENVS][NAV_CELLS];
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, r = lane & 31;
+    const int slot = tid >> 5;                                              // env of the workgroup: one half wavefront
+    const int e = blockIdx.x * NAV_ENVS + slot;
+    const int HW = W * H;
+    const bool row = e < N && r < H;                                        // this lane holds a row of the world
+    uint16_t *img = image[slot];
+
+    // every cell starts unreachable
+    for (int c = r; c < NAV_CELLS / 8; c += 32)
+        reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    nav_wave_sync();                                                        // before other lanes write steps into it
+
+    uint32_t open = 0, goals = 0;
+    if (row) {
+        const size_t off = (size_t)e * HW + (size_t)r * W;
+        uint32_t doors = 0;
+        nav_row_bytes(type + off, W, [&](int x, uint32_t t) {
+            if (t < 16u && ((pass_types >> t) & 1u)) {
+                if (t == NAV_T_DOOR) doors |= 1u << x; else open |= 1u << x;
+            }
+            if (t == NAV_T_GOAL) goals |= 1u << x;
+        });
+        if (doors != 0u && state != nullptr && !doors_open) {
+            uint32_t shut = 0;
+            nav_row_bytes(state + off, W, [&](int x, uint32_t s) { if (s != 0u) shut |= 1u << x; });
+            doors &= ~shut;
+        }
+        open |= doors;
+    }
+
+    // sources
+    int err = 0;
+    uint32_t reached = 0;
+    if (goal_x != nullptr) {
+        const bool in_n = e < N;
+        const int gx = in_n ? goal_x[(int64_t)e * gstride] : 0, gy = in_n ? goal_y[(int64_t)e * gstride] : 0;
+        if (gx < 0 || gx >= W || gy < 0 || gy >= H) err = 2;
+        else if (r == gy) reached = (1u << gx) & open;
+    } else {
+        reached = goals & open;
+    }
+    const uint32_t sourced = nav_half_ballot(reached != 0u, half);         // every lane votes: err may differ per env
+    if (err == 0 && sourced == 0u) err = 1;
+
+    // the flood
+    uint32_t fresh = reached;
+    const int cap = HW;
+    for (int k = 0;; ++k) {
+        for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[r * W + (__ffs(m) - 1)] = (uint16_t)k;
+        if (k >= cap) break;
+        const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
+        uint32_t next = reached | reached << 1 | reached >> 1;
+        if (r > 0) next |= up;
+        if (r < 31) next |= dn;
+        fresh = next & open & ~reached;
+        reached |= fresh;
+        if (__ballot(fresh != 0u) == 0ull) break;                           // wavefront-uniform: both envs are done
+    }
+    nav_wave_sync();
+
+    if (e >= N) return;                                                     // a whole half wavefront at once
+    if (agent_dist != nullptr || agent_action != nullptr || (error != nullptr && agent_x != nullptr)) {
+        if (r == 0) {
+            const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride];
+            int d = MG_NAV_UNREACHABLE, a = MG_NAV_ACTION_NONE;
+            if (ax < 0 || ax >= W || ay < 0 || ay >= H) {
+                if (err == 0) err = 3;
+            } else {
+                const int c = ay * W + ax;
+                d = img[c];
+                if (d == 0) a = MG_NAV_ACTION_STAY;
+                else if (d != MG_NAV_UNREACHABLE) {
+                    const int want = d - 1;
+                    if (ax > 0 && img[c - 1] == want) a = 0;
+                    else if (ax < W - 1 && img[c + 1] == want) a = 1;
+                    else if (ay > 0 && img[c - W] == want) a = 2;
+                    else if (ay < H - 1 && img[c + W] == want) a = 3;
+                }
+            }
+            if (agent_dist) agent_dist[e] = d;
+            if (agent_action) agent_action[e] = a;
+        }
+    }
+    if (error != nullptr && r == 0) error[e] = err;
+    if (dist != nullptr) {
+        uint16_t *ob = dist + (int64_t)e * pitch;
+        const int chunks = mg_row_chunks_at<int>(mg_row_misalign(ob, 8), HW, 8);
+        for (int c = r; c < chunks; c += 32)
+            mg_row_store(ob, HW, c, [&](int q) -> uint16_t { return img[q]; });
+    }
+}
+
+constexpr int NAV_LOOKUP_THREADS = 256;
+
+__global__ __launch_bounds__(NAV_LOOKUP_THREADS) void mg_nav_lookup_kernel(const uint16_t *__restrict__ dist, int64_t pitch,
+                                                                           int N, int W, int H,
+                                                                           const float2 *__restrict__ pos, int64_t M,
+                                                                           uint16_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * NAV_LOOKUP_THREADS + threadIdx.x;
+    if (i >= M) return;
+    const int n = (int)(i % N);
+    const float2 p = pos[i];
+    const int c = visit_cell(p.x, p.y, W, H);
+    out[i] = c < W * H ? dist[(int64_t)n * pitch + c] : (uint16_t)MG_NAV_UNREACHABLE;
+}
+
+bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
+
+}  // namespace
+
+extern "C" int mg_nav_field(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                            uint32_t pass_types, int flags, const int32_t *goal_x, const int32_t *goal_y, int goal_stride,
+                            const int32_t *agent_x, const int32_t *agent_y, int agent_stride, uint16_t *dist,
+                            int64_t dist_pitch, int32_t *agent_dist, int32_t *agent_action, int32_t *error, void *stream)
+{
+    if (!type || n_envs <= 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
+    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
+    if ((uintptr_t)dist & 1u) return TW_E_ARG;
+    if ((goal_x == nullptr) != (goal_y == nullptr) || (agent_x == nullptr) != (agent_y == nullptr)) return TW_E_ARG;
+    if ((agent_dist || agent_action) && !agent_x) return TW_E_ARG;
+    if ((goal_x && goal_stride <= 0) || (agent_x && agent_stride <= 0)) return TW_E_ARG;
+    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
+    hipLaunchKernelGGL(mg_nav_field_kernel, dim3((n_envs + NAV_ENVS - 1) / NAV_ENVS), dim3(NAV_THREADS), 0,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, dist, pitch, agent_dist, agent_action,
+                       error);
+    return mg_launched();
+}
+
+extern "C" int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height, const float *pos,
+                             int T, uint16_t *out, void *stream)
+{
+    if (!dist || !pos || !out || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
+    if (((uintptr_t)dist & 1u) || ((uintptr_t)out & 1u) || ((uintptr_t)pos & 7u)) return TW_E_ARG;
+    const int64_t M = (int64_t)T * n_envs;
+    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (M == 0) return TW_OK;
+    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
+    hipLaunchKernelGGL(mg_nav_lookup_kernel, dim3((unsigned)((M + NAV_LOOKUP_THREADS - 1) / NAV_LOOKUP_THREADS)),
+                       dim3(NAV_LOOKUP_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
+                       reinterpret_cast<const float2 *>(pos), M, out);
+    return mg_launched();
+}

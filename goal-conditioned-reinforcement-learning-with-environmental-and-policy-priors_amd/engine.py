@@ -317,7 +317,8 @@ class TwoarmyEngine:
                              out=out)
 
     def _state_ptrs(self):
-        """(type planes, colour planes, records): device addresses of the engine's state, fixed for its life."""
+        """(type planes, colour planes, records): device addresses of the engine's state as it stands.  A pipelined
+        rollout (T >= 8 with auto-reset) writes the ping-pong partner and swaps the two, so ask again after one."""
         ty, co, rec = C.c_void_p(), C.c_void_p(), C.c_void_p()
         _lib.check(_lib.lib().tw_state_ptrs(self._h, C.byref(ty), C.byref(co), C.byref(rec)), "tw_state_ptrs")
         return ty.value, co.value, rec.value
@@ -325,11 +326,13 @@ class TwoarmyEngine:
     def _views(self, owner=None):
         """(type, colour) uint8[N, 289] and the (TW_AX, TW_AY, TW_DIR) columns of the records as int32 [N,
         TW_REC_WORDS]: device views of the engine's own state (no copy).  Views that are handed out keep `owner` (the
-        engine) alive; render() and render_pov() use one set of their own, built once."""
-        if owner is None and self._own_views is not None:
-            return self._own_views
+        engine) alive; render(), render_pov() and distance_field() use one set of their own, rebuilt when a pipelined
+        rollout has swapped the state's buffers."""
+        addrs = self._state_ptrs()                     # a pipelined rollout swaps the state with its ping-pong partner
+        if owner is None and self._own_views is not None and self._own_views[0] == addrs:
+            return self._own_views[1]
         N, flat = self.num_envs, []
-        for addr, nbytes in zip(self._state_ptrs(), (N * TW_CELLS, N * TW_CELLS, N * TW_REC_WORDS * 4)):
+        for addr, nbytes in zip(addrs, (N * TW_CELLS, N * TW_CELLS, N * TW_REC_WORDS * 4)):
             t = torch.as_tensor(_DevSpan(owner, addr, nbytes), device=self.device)
             if t.data_ptr() != addr:
                 raise _lib.TwoarmyLibraryError("torch did not alias the engine's state")
@@ -337,7 +340,7 @@ class TwoarmyEngine:
         rec = flat[2].view(torch.int32).view(N, TW_REC_WORDS)
         views = (flat[0].view(N, TW_CELLS), flat[1].view(N, TW_CELLS), tuple(rec[:, FIELDS[k]] for k in ("AX", "AY", "DIR")))
         if owner is None:
-            self._own_views = views
+            self._own_views = (addrs, views)
         return views
 
     def dir_ptr(self):
@@ -348,7 +351,8 @@ class TwoarmyEngine:
 
     def plane_views(self):
         """(type, colour) uint8[N, 289] device views of the engine's own planes (tw_state_ptrs; no copy): cell (x, y)
-        at y*17 + x.  They show the state of the moment a kernel reads them."""
+        at y*17 + x.  They show the state of the moment a kernel reads them, until a pipelined rollout (T >= 8 with
+        auto-reset) swaps the buffers: take new views after one.  step() and shorter rollouts write in place."""
         return self._views(self)[:2]
 
     def agent_views(self):
@@ -359,6 +363,21 @@ class TwoarmyEngine:
     def dir_view(self):
         """int32[N] strided device view of the same directions (no copy)."""
         return self.agent_views()[2]
+
+    def distance_field(self, goal=None, pass_types=None, agent=True, out=None, want_field=True, agent_out=None,
+                       error_out=None):
+        """Shortest-path distances of the engine's worlds as they stand (minigrid_nav.distance_field, one launch, read
+        from the engine's own planes and records: no gather pass, no host copy) -> (dist uint16[N, 289] or None,
+        agent_dist int32[N], agent_action int32[N], error int32[N]).  goal: (x, y) int32[N] device tensors, None = the
+        goal cell of the plane; pass_types: minigrid_nav.PASS_DEFAULT (what the agent may step on now: balls and
+        patrols block) or | PASS_BALL for the static map; want_field=False: the agent's two values only; agent_out =
+        (agent_dist, agent_action), error_out: int32[N] tensors to write into.  Twoarmy has no doors, hence no state
+        plane."""
+        from . import minigrid_nav as nav
+        ty, _, ag = self._views()
+        return nav.distance_field(ty, None, 17, 17, nav.PASS_DEFAULT if pass_types is None else pass_types, goal=goal,
+                                  agent=ag[:2] if agent else None, out=out, want_field=want_field,
+                                  agent_out=agent_out, error_out=error_out)
 
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""

@@ -1,0 +1,87 @@
+"""Torch front end of the shortest-path kernels (include/minigrid_nav.h, csrc/minigrid_nav.hip): how many moves every cell
+of N grid worlds lies from the goal, and which of mg_step's four moves an agent on a shortest path makes next.  World planes
+are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are int32[N] tensors, dense or the column views
+of the engine's records (TwoarmyEngine.agent_views()), read where they live.  One launch per call, on the tensors' device.
+No CPU fallback."""
+import torch
+
+from ._marshal import agent_arrays, call, ptr, rows
+
+MAX_SIDE = 32
+UNREACHABLE = 0xFFFF
+PASS_DEFAULT = 0x0B1B                 # mg_step's rule: types 0, 1, 3, 8, 9, 11 and open doors (bit 4)
+PASS_LAVA, PASS_BALL = 1 << 9, 1 << 6  # clear PASS_LAVA to keep out of the lava, set PASS_BALL to walk through balls
+DOORS_OPEN = 1
+ACTION_STAY, ACTION_NONE = 6, -1
+
+
+DIST_DTYPE = torch.uint16
+
+
+def distance_field(type_plane, state_plane, width, height, pass_types=PASS_DEFAULT, goal=None, agent=None, out=None,
+                   doors_open=False, want_field=True, want_error=True, agent_out=None, error_out=None):
+    """-> (dist, agent_dist, agent_action, error).
+    dist uint16[N, H*W]: moves to the nearest source through enterable cells, UNREACHABLE elsewhere (`out`: a [N, H*W]
+    tensor whose rows may be padded; want_field=False: no field, None is returned).  goal = (x, y) int32[N] tensors, or
+    None: every cell of type 8.  agent = (x, y) int32[N] tensors -> agent_dist int32[N] and agent_action int32[N]
+    (0 left, 1 right, 2 up, 3 down, 6 stay on a source, -1 unreachable), else None.  error int32[N]: 0 ok, 1 no source,
+    2 source outside the world, 3 agent outside the world.  agent_out = (agent_dist, agent_action) and error_out:
+    contiguous int32[N] tensors to write into, so that a call per step allocates nothing."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state_plane is None or state_plane.shape == (N, W * H)
+    dev = type_plane.device
+    dp, dpitch = None, 0
+    if out is not None or want_field:
+        if out is None:
+            out = torch.empty((N, W * H), dtype=DIST_DTYPE, device=dev)
+        dp, dpitch, No, row = rows(out, DIST_DTYPE)
+        assert No == N and row == W * H and out.device == dev
+    gx = gy = ax = ay = None
+    gstride = astride = 1
+    if goal is not None:
+        gx, gy, _, gstride = agent_arrays(goal[0], goal[1])
+        assert goal[0].shape[0] >= N and goal[0].device == dev
+    adist = aact = None
+    if agent is not None:
+        ax, ay, _, astride = agent_arrays(agent[0], agent[1])
+        assert agent[0].shape[0] >= N and agent[0].device == dev
+        adist, aact = agent_out if agent_out is not None else (_int32(None, N, dev), _int32(None, N, dev))
+        _int32(adist, N, dev), _int32(aact, N, dev)
+    else:
+        assert agent_out is None, "agent_out without agent"
+    err = _int32(error_out, N, dev) if want_error or error_out is not None else None
+    call("mg_nav_field", dev, ptr(type_plane, torch.uint8), ptr(state_plane, torch.uint8), N, W, H, int(pass_types),
+         DOORS_OPEN if doors_open else 0, gx, gy, gstride, ax, ay, astride, dp, dpitch, ptr(adist), ptr(aact), ptr(err))
+    return out, adist, aact, err
+
+
+def _int32(t, N, dev):
+    """t, checked to be a contiguous int32[N] tensor on dev; a new one for None."""
+    if t is None:
+        return torch.empty(N, dtype=torch.int32, device=dev)
+    assert t.shape == (N,) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous(), "expected int32[N] on the planes' device"
+    return t
+
+
+def lookup(dist, pos, width, height, out=None):
+    """dist uint16[N, H*W] (one field per env, rows may be padded), pos float32[T, N, 2] = (y, x) after each step (or
+    [N, 2]: one step) -> uint16[T, N] ([N]): the distance of the cell each position lies in by the rule of the visit
+    counters, UNREACHABLE for a position outside the world."""
+    W, H = int(width), int(height)
+    dp, dpitch, N, row = rows(dist, DIST_DTYPE)
+    assert row == W * H
+    one = pos.dim() == 2
+    p = pos.view(1, -1, 2) if one else pos
+    assert p.dtype == torch.float32 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dist.device
+    T = p.shape[0]
+    if out is None:
+        out = torch.empty((T, N), dtype=DIST_DTYPE, device=dist.device)
+    assert out.shape == (T, N) and out.dtype == DIST_DTYPE
+    call("mg_nav_lookup", dist.device, dp, dpitch, N, W, H, ptr(p), T, ptr(out))
+    return out.view(N) if one else out
+
+
+def as_int(t):
+    """uint16 distances as int32 (whatever 16-bit dtype stores them)."""
+    return t.view(torch.int16).to(torch.int32) & 0xFFFF

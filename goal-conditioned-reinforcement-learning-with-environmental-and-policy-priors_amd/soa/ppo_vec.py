@@ -96,6 +96,7 @@ class VecPPOTrainer:
         self.her_seed = int(getattr(engine, "seed", 9981))
         self.episodes = None                  # EpisodeTracker, made by the first account_episodes()
         self.visits = None                    # VisitTracker, made by the first account_visits()
+        self.nav_field = self.goal_dist = None  # made by the first account_distance()
         self.bonus = None                     # BonusTracker, made by enable_bonus()
         self.reward_train = self.reward       # what targets and hindsight records use: the shaped reward when a bonus is on
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
@@ -484,6 +485,36 @@ class VecPPOTrainer:
         if self.visits is None:
             raise RuntimeError("visit_stats() before account_visits()")
         return self.visits.read()
+
+    # ------------------------------------------------------------------ distance to the goal
+    def account_distance(self):
+        """Distance to the goal at every step of the rollout just collected (call after collect(), before
+        carry_over()): ONE field of the static map per env -- balls and patrols passable, the wall drops as they stand
+        at the rollout's end -- and one lookup over the after-step positions; `goal_dist` uint16[T, N] afterwards
+        (65535 where a wall has dropped onto the cell since).  Under in-kernel auto-reset the terminal state is gone
+        but the terminal position is in the stream.  Two launches, no host synchronisation."""
+        from .. import minigrid_nav as nav
+        if self.nav_field is None:
+            self.nav_field = torch.empty((self.N, 289), dtype=nav.DIST_DTYPE, device=self.device)
+            self.goal_dist = torch.empty((self.T, self.N), dtype=nav.DIST_DTYPE, device=self.device)
+        self.engine.distance_field(pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, agent=False, out=self.nav_field)
+        nav.lookup(self.nav_field, self.pos[4:4 + self.T], 17, 17, out=self.goal_dist)
+        return self.goal_dist
+
+    def distance_stats(self):
+        """{"end_mean", "end_min": over the done steps of the last accounted rollout, "mean": over all its steps,
+        "cut_off": steps whose cell is unreachable in the field (left out of the three)}; None where nothing counts.
+        One device-to-host copy."""
+        if self.goal_dist is None:
+            raise RuntimeError("distance_stats() before account_distance()")
+        from .. import minigrid_nav as nav
+        d = nav.as_int(self.goal_dist).long()
+        ok = d != nav.UNREACHABLE
+        end = ok & ((self.term | self.trunc) != 0)
+        v = torch.stack([end.sum(), (d * end).sum(), torch.where(end, d, nav.UNREACHABLE).min(), ok.sum(), (d * ok).sum(),
+                         (~ok).sum()]).cpu().tolist()
+        return {"end_mean": v[1] / v[0] if v[0] else None, "end_min": v[2] if v[0] else None,
+                "mean": v[4] / v[3] if v[3] else None, "cut_off": v[5]}
 
     def stats(self):
         done = (self.term | self.trunc) != 0

@@ -10,6 +10,8 @@ Reference-only flags that concerned the matplotlib window / absolute log paths a
 the device, and --track_buffer_file DIR its track dump (heatmap.py:79) for the first --dump_envs envs.
 --bonus {state,action,both} shapes the training reward with the reference's count-based exploration bonuses
 (gym_minigrid/wrappers.py:34-102), counted on the device; off by default.
+--goal_distance adds the shortest-path distance to the goal (static map) at the done steps and over all steps of every
+rollout to the log line: one field and one lookup launch per rollout (minigrid_nav); off by default.
 """
 import argparse
 import os
@@ -90,7 +92,19 @@ def build_parser():
     p.add_argument("--bonus_dir", default=None, metavar="DIR",
                    help="with --bonus: write DIR/bonus_<update>_rank<r>.npz with the count maps (state [17, 17], action "
                         "[4, 7, 17, 17], summed over the rank's envs) once per update; off by default")
+    p.add_argument("--goal_distance", action="store_true",
+                   help="once per rollout: the shortest-path distance to the goal on the static map (balls and patrols "
+                        "passable) at every step, one field and one lookup launch on the device; adds `goal_dist end "
+                        "mean/min` over the finished episodes and `goal_dist mean` over all steps to the log line; off by default")
     return p
+
+
+def distance_fields(ds):
+    """Tail of the log line with --goal_distance (VecPPOTrainer.distance_stats())."""
+    def f(x, fmt):
+        return "-" if x is None else fmt % x
+    return " goal_dist end mean/min %s/%s goal_dist mean %s" % (f(ds["end_mean"], "%.2f"), f(ds["end_min"], "%d"),
+                                                               f(ds["mean"], "%.2f"))
 
 
 def dump_bonus(bs, path, update, rank):
@@ -215,6 +229,8 @@ def main(argv=None, predictor=False, soa=False):
         trainer.account_episodes()
         if args.visit_dir:
             trainer.account_visits(trainer.her)
+        if args.goal_distance:
+            trainer.account_distance()
         es = None
         if args.score == "episode":
             es = trainer.episode_stats()
@@ -241,6 +257,8 @@ def main(argv=None, predictor=False, soa=False):
             if args.bonus_dir:
                 dump_bonus(bs, args.bonus_dir, u, rank)
             tail += " bonus mean %.4f" % bs["mean"]
+        if args.goal_distance:                                  # behind every other field
+            tail += distance_fields(trainer.distance_stats())
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

@@ -32,6 +32,12 @@ shows, and info["final_goal_direction"] under auto-reset.  "onehot" and "flat" a
 "full", "symbolic", "rgb", "rgb_partial" and the goal direction read the engine's state after the step, so with autoreset=True the env steps
 without the in-kernel reset, emits the final observation, resets the finished envs (engine.reset(mask=done)) and emits
 again; everything else the env returns is what the default env returns.
+`goal_distance=True` adds info["goal_distance"] int32[N], the moves on a shortest path from the agent to the goal through
+the cells it may enter now (balls and patrols block; 65535 = cut off), and info["expert_action"] int32[N], the first move
+of such a path as an ENV action (0 left, 1 right, 2 up, 3 down, 6 stay, -1 none): one more launch per step
+(minigrid_nav, agent values only, no field).  Both describe the state the env returns: under auto-reset those of a done
+env belong to the new episode, as the direction of a done step does for the action bonus.  The two tensors are the env's
+own and are overwritten by the next step, like final_observation.
 """
 import torch
 
@@ -44,7 +50,7 @@ class TwoarmyVecEnv:
     def __init__(self, env_id="MiniGrid-twoarmy-17x17-v6", num_envs=4096, agent_view_size=17, device=None,
                  seed=9981, env_id0=0, policy_actions=True, autoreset=True, record_episode_statistics=False,
                  tile_size=17, highlight=False, record_visitation=False, state_bonus=False, action_bonus=False,
-                 bonus_scope="env", bonus_scale=1.0, observation="image", goal_direction=None):
+                 bonus_scope="env", bonus_scale=1.0, observation="image", goal_direction=None, goal_distance=False):
         self.variant = _IDS[env_id]
         self.num_envs = int(num_envs)
         self.view_size = agent_view_size
@@ -94,6 +100,9 @@ class TwoarmyVecEnv:
                 self._dir_buf = [torch.empty(N, dtype=torch.float64, device=d) for _ in range(2)]
                 if goal_direction == "angle":
                     self._angle_table = minigrid_obs.angle_table(17, 17, d)
+        self.goal_distance = bool(goal_distance)
+        if self.goal_distance:                            # distance, action, error: overwritten by the next step
+            self._nav_buf = tuple(torch.empty(self.num_envs, dtype=torch.int32, device=self.device) for _ in range(3))
         self.episode_tracker = None
         if record_episode_statistics:
             from .episode_stats import EpisodeTracker
@@ -141,7 +150,8 @@ class TwoarmyVecEnv:
         return mo.symbolic_obs(ty, 17, 17, out=out)
 
     def _state(self):
-        """(type plane, colour plane, agent views) of the engine: views that hold for the engine's life."""
+        """(type plane, colour plane, agent views) of the engine: views that hold while the engine writes its state in place, as step() and
+        reset() do (a pipelined rollout would swap the buffers; this env launches none)."""
         if self._state_src is None:
             self._state_src = self.engine.plane_views() + (self.engine.agent_views(),)
         return self._state_src
@@ -193,6 +203,10 @@ class TwoarmyVecEnv:
             vt.account(o["pos"], o["terminated"], o["truncated"])
             info["visitation"] = {"cells": vt.ep_cells[0], "first_visit": vt.first_visit[0].bool()}
             info["_visitation"] = done
+        if self.goal_distance:
+            d, act, err = self._nav_buf
+            self.engine.distance_field(want_field=False, agent_out=(d, act), error_out=err)
+            info["goal_distance"], info["expert_action"] = d, act
         reward = o["reward"]
         if self.bonus_tracker is not None:
             # the wrappers see the env's action (policy index 4 is actions.done = 6) and the direction in the records

@@ -1,0 +1,86 @@
+/*
+ * minigrid_nav.h -- C ABI of the shortest-path kernels (libtwoarmy_hip.so, <package>/csrc/minigrid_nav.hip): how many
+ * moves every cell of N grid worlds lies from the goal, and which move an agent on a shortest path makes next.
+ *
+ * The reference has nothing of the kind (its progress signals are the sparse return and the visited cells); on the host
+ * this is one breadth-first search per env and query.  Here it is one launch for all envs.
+ *
+ * Conventions as in minigrid_view.h / minigrid_obs.h: device pointers, caller-owned, `stream` = hipStream_t as void*,
+ * asynchronous, 0 = ok / negative = TW_E_*; TW_E_ARG is returned before anything is launched.
+ *
+ * World and moves.  The world is the `type` / `state` planes of minigrid_view.h: uint8[n_envs][height*width], cell
+ * (x, y) at y*width + x, `state` nullable (NULL = every door open).  1 <= width, height <= MG_NAV_MAX_SIDE.  Moves are
+ * the four absolute moves of mg_step: 0 left (x - 1), 1 right (x + 1), 2 up (y - 1), 3 down (y + 1).
+ *
+ * Enterable cells.  A cell is enterable iff bit `type` of the 16-bit mask pass_types is set; a door (type 4) must in
+ * addition be open (state == 0) unless MG_NAV_DOORS_OPEN is given; a type code >= 16 is never enterable.
+ * MG_NAV_PASS_DEFAULT is the rule of mg_step (mg_step_kernel, csrc/minigrid_view.hip): types 0, 1 (empty), 3 (floor),
+ * 8 (goal), 9 (lava), 11 (subgoal) and open doors.  Clear bit 9 to keep out of the lava; set bit 6 to walk through the
+ * balls (the prior of the static map).
+ *
+ * Sources.  goal_x / goal_y: int32, env e at [e * goal_stride], one source cell per env.  Both NULL: the sources are
+ * all cells of type 8 (goal) of that env -- a multi-source search.
+ *
+ * Distance.  dist[c] = the least number of moves from cell c to a source through enterable cells only.  A source is 0,
+ * but only if it is enterable itself.  Every cell that is not enterable or not connected to a source is
+ * MG_NAV_UNREACHABLE.  Distances are uint16 (a serpentine in a 32 x 32 world is longer than 255 moves).
+ *
+ * Expert action of an agent at (agent_x, agent_y) (int32, env e at [e * agent_stride]): 6 (done / stay) at distance
+ * 0; otherwise the first of 0 left, 1 right, 2 up, 3 down whose neighbour cell has distance dist - 1; -1 if the agent's
+ * cell is unreachable.  agent_dist is the distance of the agent's cell as int32 (MG_NAV_UNREACHABLE = 65535 included).
+ *
+ * error int32[n_envs] (nullable), one code per env, the first that applies of
+ *   2  a given source lies outside the world             (the whole field is MG_NAV_UNREACHABLE)
+ *   1  no source: no goal cell in the plane, or no source that is enterable   (the same)
+ *   3  the agent lies outside the world: agent_dist = MG_NAV_UNREACHABLE, agent_action = -1, the field is computed
+ *   0  ok
+ *
+ * Reads.  The planes are read as 4-byte-aligned words, as mg_gen_obs reads them: the words that hold the first and the
+ * last byte of a plane array are read whole, i.e. up to 3 bytes before its start / after its end inside the same
+ * aligned word (always inside the caller's allocation when that starts and ends on 4-byte boundaries, as hipMalloc /
+ * torch allocations do).  Those neighbour bytes never reach a result.
+ * Writes.  Each field row leaves as aligned 16-byte stores (8 distances), its first and last chunk element by element
+ * (csrc/row_store.h); dist needs 2-byte alignment only, and nothing outside the first width*height elements of a row
+ * is written.
+ */
+#ifndef MINIGRID_NAV_H
+#define MINIGRID_NAV_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MG_NAV_MAX_SIDE 32
+#define MG_NAV_UNREACHABLE 0xFFFF
+#define MG_NAV_PASS_DEFAULT 0x0B1B   /* bits 0, 1, 3, 4 (doors: open ones), 8, 9, 11 */
+#define MG_NAV_DOORS_OPEN 1          /* flags: treat every door as open, whatever `state` says */
+#define MG_NAV_ACTION_STAY 6
+#define MG_NAV_ACTION_NONE (-1)
+
+/* One launch: the field of every env and / or the distance and expert action of its agent.
+ *   dist          uint16[n_envs][dist_pitch] (nullable; dist_pitch in elements, 0 = dense width*height)
+ *   agent_dist    int32[n_envs] (nullable), agent_action int32[n_envs] (nullable): need agent_x and agent_y
+ * With dist NULL and the agent outputs given nothing but those 8 bytes per env (and error) is written.
+ * TW_E_ARG: n_envs <= 0, a side <= 0 or > MG_NAV_MAX_SIDE, NULL type, pass_types > 0xFFFF, flags other than
+ * MG_NAV_DOORS_OPEN, 0 < dist_pitch < width*height or dist_pitch < 0, dist not 2-byte aligned, only one of goal_x /
+ * goal_y or of agent_x / agent_y, agent outputs without agent arrays, a stride <= 0 of arrays that are given. */
+int mg_nav_field(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height, uint32_t pass_types,
+                 int flags, const int32_t *goal_x, const int32_t *goal_y, int goal_stride, const int32_t *agent_x,
+                 const int32_t *agent_y, int agent_stride, uint16_t *dist, int64_t dist_pitch, int32_t *agent_dist,
+                 int32_t *agent_action, int32_t *error, void *stream);
+
+/* The distance at every step of a rollout from ONE field per env: pos float[T][n_envs][2] = (y, x) after each step
+ * (8-byte aligned), the stream ppo_visit_hist reads, with its cell rule (csrc/visit_cell.h: truncation inside the
+ * world; NaN, +-inf and everything outside are no cell); out uint16[T][n_envs] = dist[n][cell], or
+ * MG_NAV_UNREACHABLE for a position outside the world.  One launch; T == 0 launches nothing.
+ * TW_E_ARG: NULL dist / pos / out, n_envs <= 0, T < 0, a side <= 0 or > MG_NAV_MAX_SIDE, 0 < dist_pitch < width*height
+ * or dist_pitch < 0, dist or out not 2-byte aligned, pos not 8-byte aligned, T * n_envs >= 2^40. */
+int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height, const float *pos, int T,
+                  uint16_t *out, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MINIGRID_NAV_H */

@@ -8,6 +8,10 @@ Prints one JSON line per configuration: views/s and the HBM roofline fraction fo
                                                           view sizes 17 and 7, each beside a torch composition of the
                                                           same result and the fill_ rate of a buffer of its size; median
                                                           and range of --repeats windows of --obs_iters launches
+  python tools/view_bench.py --nav [--obs_envs 4096]      the distance fields (minigrid_nav) on Twoarmy's 17x17 worlds: the
+                                                          field, the agent's values alone and the lookup over T = 128
+                                                          steps, beside a torch dilation loop that builds the same field
+                                                          and the fill_ rate of each output size; windows as for --obs
 """
 import argparse
 import json
@@ -23,6 +27,7 @@ ap.add_argument("--envs", type=int, default=262144)
 ap.add_argument("--size", type=int, default=17)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--obs", action="store_true")
+ap.add_argument("--nav", action="store_true")
 ap.add_argument("--obs_envs", type=int, default=4096)
 ap.add_argument("--obs_iters", type=int, default=200)
 ap.add_argument("--repeats", type=int, default=9)
@@ -110,8 +115,89 @@ def obs_rows():
     row("goal_direction angle", S, "torch div+atan", lambda: torch.atan((14 - ay).double() / (2 - ax).double()), 8 * N)
 
 
+def nav_rows():
+    """One JSON line per (kind, implementation)."""
+    import statistics
+    from twoarmy_amd import minigrid_nav as nav
+    from twoarmy_amd.engine import TwoarmyEngine
+    N, S, T = a.obs_envs, 17, 128
+    eng = TwoarmyEngine(4, N, 17, device=dev)
+    eng.reset()
+    ty = eng.plane_views()[0]
+    agent = eng.agent_views()[:2]
+
+    def window(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.obs_iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.obs_iters * 1e3                         # us per call
+
+    def row(kind, impl, fn, out_bytes, check=None):
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        us = sorted(window(fn) for _ in range(a.repeats))
+        med = statistics.median(us)
+        print(json.dumps({"kind": kind, "impl": impl, "envs": N, "out_MB": out_bytes / 1e6, "us_median": med, "us_min": us[0],
+                          "us_max": us[-1], "store_GBs": out_bytes / med / 1e3, "equal": check}), flush=True)
+
+    passable = torch.zeros(256, dtype=torch.bool, device=dev)
+    passable[[t for t in range(16) if (nav.PASS_DEFAULT >> t) & 1]] = True
+
+    def dilation():
+        """The same field from whole-tensor ops: 4-neighbour dilation of the reached set until it stops changing (one
+        host synchronisation per step, to see that it has)."""
+        ok = passable[ty.long()].view(N, S, S)
+        reached = (ty.view(N, S, S) == 8) & ok
+        d = torch.where(reached, 0, nav.UNREACHABLE).to(torch.int32)
+        k = 0
+        while True:
+            k += 1
+            grown = reached.clone()
+            grown[:, 1:] |= reached[:, :-1]
+            grown[:, :-1] |= reached[:, 1:]
+            grown[:, :, 1:] |= reached[:, :, :-1]
+            grown[:, :, :-1] |= reached[:, :, 1:]
+            fresh = grown & ok & ~reached
+            if not bool(fresh.any()):
+                return d.view(N, S * S)
+            d = torch.where(fresh, k, d)
+            reached |= fresh
+
+    field = torch.empty((N, S * S), dtype=nav.DIST_DTYPE, device=dev)
+    nav.distance_field(ty, None, S, S, out=field, want_error=False)
+    same = bool(torch.equal(nav.as_int(field), dilation()))
+    row("field 17x17", "mg_nav_field", lambda: nav.distance_field(ty, None, S, S, out=field, want_error=False),
+        field.numel() * 2, same)
+    row("field 17x17", "torch dilation loop", dilation, field.numel() * 2)
+    row("field 17x17", "torch fill_", lambda: field.view(torch.int16).fill_(1), field.numel() * 2)
+    ad, aa = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(2))
+    row("agent only", "mg_nav_field", lambda: nav.distance_field(ty, None, S, S, agent=agent, want_field=False,
+                                                                 want_error=False, agent_out=(ad, aa)), 8 * N)
+    row("agent only", "mg_nav_field, results allocated per call",
+        lambda: nav.distance_field(ty, None, S, S, agent=agent, want_field=False, want_error=False), 8 * N)
+    g = torch.Generator(device="cpu").manual_seed(3)
+    pos = (torch.rand((T, N, 2), generator=g) * S).to(dev)
+    out = torch.empty((T, N), dtype=nav.DIST_DTYPE, device=dev)
+    nav.lookup(field, pos, S, S, out=out)
+    want = nav.as_int(field)[torch.arange(N, device=dev), (pos[..., 0].long() * S + pos[..., 1].long())]
+    row("lookup T=128", "mg_nav_lookup", lambda: nav.lookup(field, pos, S, S, out=out), out.numel() * 2,
+        bool(torch.equal(nav.as_int(out), want)))
+    row("lookup T=128", "torch gather", lambda: field.view(torch.int16)[torch.arange(N, device=dev),
+                                                                        (pos[..., 0].long() * S + pos[..., 1].long())],
+        out.numel() * 2)
+    row("lookup T=128", "torch fill_", lambda: out.view(torch.int16).fill_(1), out.numel() * 2)
+    eng.close()
+
+
 if a.obs:
     obs_rows()
+    sys.exit(0)
+if a.nav:
+    nav_rows()
     sys.exit(0)
 N, W = a.envs, a.size
 g = torch.Generator(device="cpu").manual_seed(1)
