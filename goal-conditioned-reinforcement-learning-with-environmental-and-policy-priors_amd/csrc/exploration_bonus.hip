@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "twoarmy.h"
 #include "twoarmy_ppo.h"
 #include "visit_cell.h"
@@ -215,8 +216,6 @@ bool bonus_geom_ok(int width, int height, int n_actions) {
     return visit_grid_ok(width, height) && n_actions >= 1 && n_actions <= BONUS_MAX_ACTIONS;
 }
 
-int bonus_launched() { return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP; }
-
 }  // namespace
 
 extern "C" {
@@ -260,7 +259,7 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
     if (scope == 0) {
         hipLaunchKernelGGL(ppo_bonus_env_kernel, dim3(N), dim3(64), 0, s, in, reward, keep, kind_mask, scale,
                            (uint32_t *)state_table, (uint32_t *)action_table, bonus_state, bonus_action, reward_out);
-        return bonus_launched();
+        return tw_launched(__func__);
     }
     const int Ks = (int)bonus_keys_host(1, width, height, n_actions), Ka = (int)bonus_keys_host(2, width, height, n_actions);
     uint32_t *hist_state = (uint32_t *)workspace;
@@ -283,7 +282,7 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
                            kind_mask, scale, (const int64_t *)state_table, (const int64_t *)action_table, hist_state,
                            hist_action, bonus_state, bonus_action, reward_out);
     }
-    return bonus_launched();
+    return tw_launched(__func__);
 }
 
 }  // extern "C"

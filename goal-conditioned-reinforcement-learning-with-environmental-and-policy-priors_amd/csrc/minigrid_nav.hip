@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "minigrid_nav.h"
 #include "row_store.h"
 #include "twoarmy.h"
@@ -195,7 +196,7 @@ extern "C" int mg_nav_field(const uint8_t *type, const uint8_t *state, int n_env
                        (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
                        goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, dist, pitch, agent_dist, agent_action,
                        error);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height, const float *pos,
@@ -211,5 +212,5 @@ extern "C" int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_env
     hipLaunchKernelGGL(mg_nav_lookup_kernel, dim3((unsigned)((M + NAV_LOOKUP_THREADS - 1) / NAV_LOOKUP_THREADS)),
                        dim3(NAV_LOOKUP_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
                        reinterpret_cast<const float2 *>(pos), M, out);
-    return mg_launched();
+    return tw_launched(__func__);
 }

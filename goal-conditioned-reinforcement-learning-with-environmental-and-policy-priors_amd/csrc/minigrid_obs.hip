@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "minigrid_obs.h"
 #include "row_store.h"
 #include "twoarmy.h"
@@ -201,7 +202,7 @@ extern "C" int mg_obs_onehot(const uint8_t *image, int64_t image_pitch, int n_en
     if (error && hipMemsetAsync(error, 0, sizeof(int32_t) * (size_t)n_envs, (hipStream_t)stream) != hipSuccess) return TW_E_HIP;
     hipLaunchKernelGGL(mg_obs_onehot_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, image,
                        image_pitch ? image_pitch : in_row, n_envs, n_cells, out, out_pitch ? out_pitch : row, error, (int)cpr);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_obs_full(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
@@ -218,7 +219,7 @@ extern "C" int mg_obs_full(const uint8_t *type, const uint8_t *colour, const uin
     hipLaunchKernelGGL(mg_obs_full_kernel, dim3((unsigned)(bpe * n_envs)), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream,
                        type, colour, state, n_envs, width, height, agent_x, agent_y, agent_dir, agent_stride, out,
                        out_pitch ? out_pitch : row, error, (int)bpe);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_obs_symbolic(const uint8_t *type, int n_envs, int width, int height, int32_t *out, void *stream)
@@ -231,7 +232,7 @@ extern "C" int mg_obs_symbolic(const uint8_t *type, int n_envs, int width, int h
     if (!mg_obs_grid_ok(chunks, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_symbolic_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, type, width,
                        height, out, total, chunks);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_obs_flat(const uint8_t *image, int64_t image_pitch, int n_envs, int n_img, const float *tail, int n_tail,
@@ -248,7 +249,7 @@ extern "C" int mg_obs_flat(const uint8_t *image, int64_t image_pitch, int n_envs
     hipLaunchKernelGGL(mg_obs_flat_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, image,
                        image_pitch ? image_pitch : (int64_t)n_img, n_envs, n_img, tail, n_tail, out,
                        out_pitch ? out_pitch : row, (int)cpr);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_obs_goal_index(const uint8_t *type, int n_envs, int width, int height, int32_t *goal_index, void *stream)
@@ -259,7 +260,7 @@ extern "C" int mg_obs_goal_index(const uint8_t *type, int n_envs, int width, int
     if (!mg_obs_grid_ok((int64_t)n_envs * 64, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_goal_index_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream, type, n_envs,
                        width * height, goal_index);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_obs_angle_table_size(int width, int height)
@@ -282,5 +283,5 @@ extern "C" int mg_obs_goal_direction(const int32_t *goal_index, int n_envs, int 
     if (!mg_obs_grid_ok(n_envs, &blocks)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_obs_goal_direction_kernel, dim3(blocks), dim3(MG_OBS_THREADS), 0, (hipStream_t)stream,
                        goal_index, n_envs, width, height, agent_x, agent_y, agent_stride, mode, angle_table, out, error);
-    return mg_launched();
+    return tw_launched(__func__);
 }

@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "launch.h"
 #include "minigrid_render.h"
 #include "minigrid_view.h"
 #include "row_store.h"
@@ -409,7 +410,7 @@ extern "C" int mg_render_build_atlas(int tile_size, uint8_t *atlas, void *stream
     mg_fill_consts(&k);
     hipLaunchKernelGGL(mg_render_atlas_kernel, dim3(MG_RENDER_TILES), dim3(MG_RENDER_THREADS), 0, (hipStream_t)stream,
                        tile_size, atlas, k);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 /* The frame-side argument rules and launch geometry of both entry points: n_out frames of width x height cells. */
@@ -434,7 +435,7 @@ static int mg_launch_frames(const typename Cells::args &src, int n_envs, int wid
     hipLaunchKernelGGL(mg_render_kernel<Cells>, dim3((unsigned)(bpf * n_out)), dim3(MG_RENDER_THREADS), (size_t)lds,
                        (hipStream_t)stream, src, n_envs, width, height, env_index, atlas, tile_size, frame, pitch, error,
                        (int)bpf);
-    return mg_launched();
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_render(const uint8_t *type, const uint8_t *colour, const uint8_t *state, int n_envs, int width,
@@ -475,5 +476,5 @@ extern "C" int mg_highlight_mask(const uint8_t *vis_mask, int n_envs, int width,
     if ((cells + 255) / 256 >= ((int64_t)1 << 31)) return TW_E_ARG;
     hipLaunchKernelGGL(mg_highlight_mask_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        vis_mask, n_envs, width, height, agent_x, agent_y, agent_dir, agent_stride, view_size, out);
-    return mg_launched();
+    return tw_launched(__func__);
 }

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "minigrid_view.h"
 #include "twoarmy.h"
 #include "view_map.h"
@@ -455,7 +456,7 @@ extern "C" int mg_gen_obs(const uint8_t *type, const uint8_t *colour, const uint
     }
 #undef MG_LAUNCH_COLS
 #undef MG_LAUNCH
-    return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
+    return tw_launched(__func__);
 }
 
 extern "C" int mg_step(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
@@ -468,5 +469,5 @@ extern "C" int mg_step(const uint8_t *type, const uint8_t *state, int n_envs, in
     hipLaunchKernelGGL(mg_step_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, type, state, n_envs,
                        width, height, action, agent_x, agent_y, agent_dir, step_count, max_steps, reward, terminated,
                        truncated, error);
-    return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP;
+    return tw_launched(__func__);
 }

@@ -8,24 +8,14 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "launch.h"
+#include "philox.h"
 #include "twoarmy.h"
 #include "twoarmy_ppo.h"
 
 namespace {
 
 constexpr float CAT_EPS = FLT_EPSILON;          // torch.finfo(float32).eps used by probs_to_logits
-
-__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t &c0, uint32_t &c1, uint32_t &c2,
-                                              uint32_t &c3) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 
 // ------------------------------------------------------------------ categorical sample
 template <int A>
@@ -949,11 +939,6 @@ __global__ __launch_bounds__(256) void ppo_lstm_cell_kernel(const float4 *__rest
     h[i] = hv;
 }
 
-int check_launch() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? TW_OK : TW_E_HIP;
-}
-
 }  // namespace
 
 extern "C" {
@@ -980,7 +965,7 @@ int ppo_sample_dev(const float *probs, int B, int A, const float *uniforms, uint
     default: return TW_E_ARG;
     }
 #undef PPO_SAMPLE_LAUNCH
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_gae(const float *reward, const float *value, const float *next_value, const uint8_t *done, float gamma,
@@ -992,7 +977,7 @@ int ppo_gae(const float *reward, const float *value, const float *next_value, co
     else
         hipLaunchKernelGGL(ppo_gae_kernel<16>, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream, reward, value,
                            next_value, done, gamma, lambda, use_done_mask, T, N, adv, target, ret);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_adv_norm(float *adv, int64_t n, float eps, double *workspace, void *stream) {
@@ -1004,7 +989,7 @@ int ppo_adv_norm(float *adv, int64_t n, float eps, double *workspace, void *stre
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_moments_kernel, dim3(nblocks), dim3(256), 0, st, adv, n, workspace);
     hipLaunchKernelGGL(ppo_normalise_kernel, dim3(nblocks2), dim3(256), 0, st, adv, n, eps, workspace, nblocks);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_loss_fwd_bwd(const float *probs, const int32_t *action, const float *old_logp, const float *adv,
@@ -1026,7 +1011,7 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
     hipLaunchKernelGGL(ppo_loss_kernel<5>, dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
                        target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace);
     hipLaunchKernelGGL(ppo_loss_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, nblocks, n_valid, losses);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_gather_stack(const float *frames, int frame_pitch, const float *pos_frames, int N, const int32_t *k_idx,
@@ -1036,7 +1021,7 @@ int ppo_gather_stack(const float *frames, int frame_pitch, const float *pos_fram
     if (pos_out && (!pos_frames || !init_pos)) return TW_E_ARG;
     hipLaunchKernelGGL(ppo_gather_stack_kernel<float>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, frames, frame_pitch,
                        pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_gather_stack_u8(const uint8_t *frames, int frame_pitch, const float *pos_frames, int N, const int32_t *k_idx,
@@ -1046,7 +1031,7 @@ int ppo_gather_stack_u8(const uint8_t *frames, int frame_pitch, const float *pos
     if (pos_out && (!pos_frames || !init_pos)) return TW_E_ARG;
     hipLaunchKernelGGL(ppo_gather_stack_kernel<uint8_t>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, frames,
                        frame_pitch, pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_her_relabel_window(const float *pos, const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0,
@@ -1061,7 +1046,7 @@ int ppo_her_relabel_window(const float *pos, const uint8_t *terminated, const ui
     hipLaunchKernelGGL(ppo_her_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, pos, terminated, truncated, age0,
                        reward, choices, (uint32_t)seed, (uint32_t)(seed >> 32), env_id0, step0, T, N, max_goals, skip,
                        offsets, counts, out_t, out_n, out_goal, out_reward, out_done);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_her_relabel(const float *pos, const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0,
@@ -1077,7 +1062,7 @@ int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int3
     if (!terminated || !truncated || !age0 || !age || T <= 0 || N <= 0) return TW_E_ARG;
     hipLaunchKernelGGL(ppo_age_scan_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, terminated,
                        truncated, age0, T, N, age);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
@@ -1085,7 +1070,7 @@ int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8
     if (!reward || !terminated || !truncated || !carry_return || !carry_length || T <= 0 || N <= 0) return TW_E_ARG;
     hipLaunchKernelGGL(ppo_episode_scan_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, reward, terminated,
                        truncated, T, N, carry_return, carry_length, ep_return, ep_length);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_episode_summary_workspace(int T, int N) {
@@ -1111,7 +1096,7 @@ int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const
                        truncated, reward, action, M, per_block, per_thread, keep, gain, workspace);
     hipLaunchKernelGGL(ppo_episode_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, nblocks, A, score, summary,
                        action_hist, reward_hist);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_bias_relu_nhwc(float *y, const float *bias, int64_t n_pixels, int C, void *stream) {
@@ -1120,7 +1105,7 @@ int ppo_bias_relu_nhwc(float *y, const float *bias, int64_t n_pixels, int C, voi
     const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
     hipLaunchKernelGGL(ppo_bias_relu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4 *>(y),
                        reinterpret_cast<const float4 *>(bias), n4, C / 4);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_relu_bwd_bias_grad_nhwc_blocks(int64_t n_pixels, int C) {
@@ -1138,7 +1123,7 @@ int ppo_relu_bwd_bias_grad_nhwc(const float *gy, const float *y, float *gx, floa
     hipLaunchKernelGGL(ppo_relu_bwd_bias_grad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4 *>(gy), reinterpret_cast<const float4 *>(y),
                        reinterpret_cast<float4 *>(gx), reinterpret_cast<float4 *>(partial), (size_t)n_pixels, C / 4, ppb);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_conv1_up4_bias_relu(const float *frames, int B, int F, const float *folded_w, const float *bias, float *out,
@@ -1161,7 +1146,7 @@ int ppo_conv1_up4_bias_relu_c(const float *frames, int B, int F, int C_out, cons
     else if (F == 1 && C_out == 16) PPO_CONV1_LAUNCH(1, 4);
     else return TW_E_ARG;
 #undef PPO_CONV1_LAUNCH
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_conv1_up4_bwd_groups(int B) { return B <= 0 ? TW_E_ARG : (B < 256 ? B : 256); }
@@ -1184,7 +1169,7 @@ int ppo_conv1_up4_bwd(const float *frames, int B, int F, const float *gy, const 
                            reinterpret_cast<float4 *>(gb_partial), B);
     else
         return TW_E_ARG;
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_decoder_frames(const float *z, int n_frames, const float *w1, const float *b1, const float *w2, const float *b2,
@@ -1193,7 +1178,7 @@ int ppo_decoder_frames(const float *z, int n_frames, const float *w1, const floa
     const int grid = n_frames < 512 ? n_frames : 512;          // 120 KB of LDS: one workgroup per CU, two rounds of them
     hipLaunchKernelGGL(ppo_decoder_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, n_frames, w1, b1, w2,
                        b2, kfold, b3, frames);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 int ppo_lstm_cell(const float *gates_a, const float *gates_b, long long ldb, const float *bias, float *c, float *h, int B,
@@ -1209,7 +1194,7 @@ int ppo_lstm_cell(const float *gates_a, const float *gates_b, long long ldb, con
                        reinterpret_cast<const float4 *>(gates_a), reinterpret_cast<const float4 *>(gates_b), ldb / 4,
                        reinterpret_cast<const float4 *>(bias), reinterpret_cast<float4 *>(c), reinterpret_cast<float4 *>(h),
                        B, H / 4);
-    return check_launch();
+    return tw_launched(__func__);
 }
 
 }  // extern "C"

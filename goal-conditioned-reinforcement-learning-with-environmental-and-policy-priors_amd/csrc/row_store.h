@@ -42,8 +42,6 @@ template <typename I> MG_ROW_FN mg_row_span_t<I> mg_row_span(int s, I F, I b, I 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 
-#include "twoarmy.h"
-
 // Store chunk c of the row: whole(p) -> the uint4 of elements p .. p + E - 1, one(q) -> element q.
 template <typename T, typename I, typename Whole, typename One>
 __device__ __forceinline__ void mg_row_store(T *base, I F, I c, Whole whole, One one)
@@ -66,9 +64,6 @@ __device__ __forceinline__ void mg_row_store(T *base, I F, I c, One one)
         return w.u;
     }, one);
 }
-
-// Result of an ABI function whose last act was a kernel launch.
-static inline int mg_launched(void) { return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP; }
 #endif
 
 #endif  // TWOARMY_ROW_STORE_H

@@ -39,6 +39,8 @@
 #include <utility>
 #include <vector>
 
+#include "launch.h"
+#include "philox.h"
 #include "twoarmy.h"
 
 namespace {
@@ -111,19 +113,7 @@ struct Params {
     const uint32_t *pipe_tab; // per-engine constant tables of the pipelined kernel (tw_pipe_tables_kernel)
 };
 
-// ---------------------------------------------------------------- Philox4x32-10
-__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t &c0, uint32_t &c1,
-                                              uint32_t &c2, uint32_t &c3) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
+// ---------------------------------------------------------------- Philox4x32-10 (philox.h)
 // all four words of one draw block: counter = (env_id, t, block, 'TWOA')
 __device__ __forceinline__ void draw_block(uint32_t k0, uint32_t k1, uint32_t env_id, uint32_t t, uint32_t block,
                                            uint32_t (&w)[4]) {
@@ -1621,11 +1611,6 @@ __global__ void tw_fill_actions_kernel(Params p, int32_t *out) {
     out[i] = (int32_t)(w[0] % 5u);
 }
 
-int g_last_hip_error = 0;
-char g_last_error_msg[256] = "";
-
-
-
 }  // namespace
 
 // ======================================================================= host side / C ABI
@@ -1656,14 +1641,6 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
-
-int hip_fail_at(hipError_t e, const char *what, int line) {
-    g_last_hip_error = (int)e;
-    snprintf(g_last_error_msg, sizeof(g_last_error_msg), "%s (line %d): %s", what, line, hipGetErrorString(e));
-    return TW_E_HIP;
-}
-#define hip_fail(e) hip_fail_at((e), "hip", __LINE__)
-#define HIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return hip_fail_at(_e, #expr, __LINE__); } while (0)
 
 Params base_params(const tw_engine *e) {
     Params p;
@@ -1729,7 +1706,7 @@ int launch_sequential(const tw_engine *e, const Params &p, hipStream_t st) {
     if (p.only_if_flagged && grid > 256) grid = 256;        // grid-stride fallback launch (see tw_rollout_kernel)
     const KernelFn k = ROLLOUT_KERNELS[4 * log2i(E) + 2 * (e->variant == 6) + params_fast(e, p, false)];
     hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, st, p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_LAUNCHED();
     return TW_OK;
 }
 
@@ -1764,7 +1741,7 @@ int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *
     const int layout = (flags & TW_F_MATRIX_CODE) ? 2 : (p.record ? 1 : 0);
     const KernelFn k = PIPE_KERNELS[12 * (e->variant == 6) + 4 * layout + log2i(pg) - 1];
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * PWAVES), PIPE_LDS_BYTES, st, p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_LAUNCHED();
     p.only_if_flagged = 1;
     const int rc = launch_sequential(e, p, st);
     if (rc != TW_OK) return rc;
@@ -1813,7 +1790,7 @@ int tw_create(tw_engine **out, int variant, int n_envs, int view_size, int devic
     Params p = base_params(e);
     hipLaunchKernelGGL(tw_pipe_tables_kernel, dim3(1), dim3(64), 0, 0, e->pipe_tab, e->view);
     hipLaunchKernelGGL(tw_reset_kernel, dim3(n_envs), dim3(64), 0, 0, p, (const uint8_t *)nullptr, 0);
-    hipError_t le = hipGetLastError();
+    hipError_t le = tw_launch_status();
     if (le == hipSuccess) le = hipStreamSynchronize(0);
     if (le != hipSuccess) { tw_destroy(e); return hip_fail(le); }
     *out = e;
@@ -1863,7 +1840,7 @@ int tw_reset(tw_engine *e, const uint8_t *mask, uint8_t *obs, int obs_pitch, voi
     if (obs_pitch > 0) p.obs_pitch = obs_pitch;
     if (p.obs_pitch < e->view * e->view * 3) return TW_E_ARG;
     hipLaunchKernelGGL(tw_reset_kernel, dim3(e->n_envs), dim3(64), 0, (hipStream_t)stream, p, mask, 1);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_LAUNCHED();
     return TW_OK;
 }
 
@@ -1893,7 +1870,7 @@ int tw_fill_actions(tw_engine *e, int T, int32_t *actions, void *stream) {
     const int total = T * e->n_envs;
     hipLaunchKernelGGL(tw_fill_actions_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, p,
                        actions);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_LAUNCHED();
     return TW_OK;
 }
 
@@ -1934,7 +1911,7 @@ int tw_gen_obs(tw_engine *e, int view_size, uint8_t *obs, int obs_pitch, void *s
     p.obs_pitch = obs_pitch > 0 ? obs_pitch : view_size * view_size * 3;
     if (p.obs_pitch < view_size * view_size * 3) return TW_E_ARG;
     hipLaunchKernelGGL(tw_gen_obs_kernel, dim3(e->n_envs), dim3(64), 0, (hipStream_t)stream, p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_LAUNCHED();
     return TW_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.h"
 #include "twoarmy.h"
 #include "twoarmy_ppo.h"
 #include "visit_cell.h"
@@ -131,8 +132,6 @@ __global__ __launch_bounds__(VISIT_HIST_THREADS) void ppo_visit_hist_kernel(
     }
 }
 
-int visit_launched() { return hipGetLastError() == hipSuccess ? TW_OK : TW_E_HIP; }
-
 }  // namespace
 
 extern "C" {
@@ -151,7 +150,7 @@ int ppo_visit_scan(const float *pos, const uint8_t *terminated, const uint8_t *t
     hipLaunchKernelGGL(ppo_visit_scan_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        reinterpret_cast<const float2 *>(pos), terminated, truncated, T, N, width, height, carry,
                        first_visit, ep_cells);
-    return visit_launched();
+    return tw_launched(__func__);
 }
 
 int ppo_visit_hist(const float *pos, int T, int N, const uint8_t *mask, const int32_t *t_idx, const int32_t *n_idx, int B,
@@ -168,7 +167,7 @@ int ppo_visit_hist(const float *pos, int T, int N, const uint8_t *mask, const in
     hipLaunchKernelGGL(ppo_visit_hist_kernel, dim3(blocks), dim3(VISIT_HIST_THREADS), 0, (hipStream_t)stream,
                        reinterpret_cast<const float2 *>(pos), T, N, mask, t_idx, n_idx, M, width, height,
                        reinterpret_cast<unsigned long long *>(counts));
-    return visit_launched();
+    return tw_launched(__func__);
 }
 
 }  // extern "C"

@@ -4,8 +4,9 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-from ._marshal import ptr as _p, stream as _stream
+from ._marshal import call as _call, ptr as _p, query as _query
+
+_CL = torch.channels_last
 
 
 def sample(probs, uniforms=None, seed=0, offset=0, offset_dev=None):
@@ -14,8 +15,8 @@ def sample(probs, uniforms=None, seed=0, offset=0, offset_dev=None):
     B, A = probs.shape
     action = torch.empty(B, dtype=torch.int32, device=probs.device)
     logp = torch.empty(B, dtype=torch.float32, device=probs.device)
-    _lib.check(_lib.lib().ppo_sample_dev(_p(probs, torch.float32), B, A, _p(uniforms, torch.float32), seed, offset,
-                                         _p(offset_dev, torch.int64), _p(action), _p(logp), _stream(probs)), "ppo_sample")
+    _call("ppo_sample_dev", probs, _p(probs, torch.float32), B, A, _p(uniforms, torch.float32), seed, offset,
+          _p(offset_dev, torch.int64), _p(action), _p(logp))
     return action, logp
 
 
@@ -25,15 +26,14 @@ def gae(reward, value, next_value, done=None, gamma=0.99, lam=0.0, use_done_mask
     adv = torch.empty_like(reward)
     target = torch.empty_like(reward)
     ret = torch.empty_like(reward) if want_ret else None
-    _lib.check(_lib.lib().ppo_gae(_p(reward, torch.float32), _p(value, torch.float32), _p(next_value, torch.float32),
-                                  _p(done, torch.uint8), gamma, lam, int(bool(use_done_mask)), T, N, _p(adv), _p(target),
-                                  _p(ret), _stream(reward)), "ppo_gae")
+    _call("ppo_gae", reward, _p(reward, torch.float32), _p(value, torch.float32), _p(next_value, torch.float32),
+          _p(done, torch.uint8), gamma, lam, int(bool(use_done_mask)), T, N, _p(adv), _p(target), _p(ret))
     return adv, target, ret
 
 
 def adv_norm_(adv, eps=1e-8):
     ws = torch.empty(4096, dtype=torch.float64, device=adv.device)
-    _lib.check(_lib.lib().ppo_adv_norm(_p(adv, torch.float32), adv.numel(), eps, _p(ws), _stream(adv)), "ppo_adv_norm")
+    _call("ppo_adv_norm", adv, _p(adv, torch.float32), adv.numel(), eps, _p(ws))
     return adv
 
 
@@ -65,10 +65,9 @@ def ppo_losses(probs, value, action, old_logp, adv, target_v, clip=0.1, ent_coef
         gp = torch.empty_like(probs_c)
         gv = torch.empty_like(value_c)
         ws = torch.empty(2 * ((B + 255) // 256), dtype=torch.float32, device=probs.device)
-        _lib.check(_lib.lib().ppo_loss_fwd_bwd_masked(
-            _p(probs_c, torch.float32), _p(action.contiguous(), torch.int32), _p(old_logp.contiguous().view(-1)),
-            _p(adv.contiguous().view(-1)), _p(value_c), _p(target_v.contiguous().view(-1)), B, n_valid, A, float(clip),
-            float(ent_coef), _p(losses), _p(gp), _p(gv), _p(ws), _stream(probs)), "ppo_loss_fwd_bwd_masked")
+        _call("ppo_loss_fwd_bwd_masked", probs, _p(probs_c, torch.float32), _p(action.contiguous(), torch.int32),
+              _p(old_logp.contiguous().view(-1)), _p(adv.contiguous().view(-1)), _p(value_c),
+              _p(target_v.contiguous().view(-1)), B, n_valid, A, float(clip), float(ent_coef), _p(losses), _p(gp), _p(gv), _p(ws))
     return _AttachGrad.apply(probs, losses[0], gp), _AttachGrad.apply(value, losses[1], gv)
 
 
@@ -82,19 +81,18 @@ def gather_stack(frames, pos_frames, k_idx, n_idx, age, init_frame, init_pos):
     out = torch.empty((B, 4, 289), dtype=torch.float32, device=frames.device)
     pos_out = torch.empty((B, 4, 2), dtype=torch.float32, device=frames.device) if pos_frames is not None else None
     assert frames.dtype in (torch.float32, torch.uint8)
-    fn = _lib.lib().ppo_gather_stack if frames.dtype == torch.float32 else _lib.lib().ppo_gather_stack_u8
-    _lib.check(fn(
-        C.c_void_p(frames.data_ptr()), pitch, _p(pos_frames, torch.float32), N, _p(k_idx, torch.int32),
-        _p(n_idx, torch.int32), _p(age, torch.int32), _p(init_frame, torch.float32), _p(init_pos, torch.float32), B,
-        _p(out), _p(pos_out), _stream(frames)), "ppo_gather_stack")
+    _call("ppo_gather_stack" if frames.dtype == torch.float32 else "ppo_gather_stack_u8", frames,
+          C.c_void_p(frames.data_ptr()), pitch, _p(pos_frames, torch.float32), N, _p(k_idx, torch.int32),
+          _p(n_idx, torch.int32), _p(age, torch.int32), _p(init_frame, torch.float32), _p(init_pos, torch.float32), B,
+          _p(out), _p(pos_out))
     return out, pos_out
 
 
 def age_scan(terminated, truncated, age0):
     T, N = terminated.shape
     age = torch.empty((T + 1, N), dtype=torch.int32, device=terminated.device)
-    _lib.check(_lib.lib().ppo_age_scan(_p(terminated, torch.uint8), _p(truncated, torch.uint8), _p(age0, torch.int32),
-                                       T, N, _p(age), _stream(terminated)), "ppo_age_scan")
+    _call("ppo_age_scan", terminated, _p(terminated, torch.uint8), _p(truncated, torch.uint8), _p(age0, torch.int32),
+          T, N, _p(age))
     return age
 
 
@@ -112,17 +110,14 @@ def episode_scan(reward, terminated, truncated, carry_return, carry_length, want
     elif want_steps:
         ep_return = torch.empty((T, N), dtype=torch.float64, device=reward.device)
         ep_length = torch.empty((T, N), dtype=torch.int32, device=reward.device)
-    _lib.check(_lib.lib().ppo_episode_scan(_p(reward, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
-                                           T, N, _p(carry_return, torch.float64), _p(carry_length, torch.int32),
-                                           _p(ep_return, torch.float64), _p(ep_length, torch.int32), _stream(reward)),
-               "ppo_episode_scan")
+    _call("ppo_episode_scan", reward, _p(reward, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
+          T, N, _p(carry_return, torch.float64), _p(carry_length, torch.int32), _p(ep_return, torch.float64),
+          _p(ep_length, torch.int32))
     return ep_return, ep_length
 
 
 def episode_summary_workspace(T, N):
-    n = _lib.lib().ppo_episode_summary_workspace(int(T), int(N))
-    _lib.check(min(n, 0), "ppo_episode_summary_workspace")
-    return n
+    return _query("ppo_episode_summary_workspace", int(T), int(N))
 
 
 def episode_summary(ep_return, ep_length, terminated, truncated, reward, action=None, n_actions=5, keep=0.99, gain=0.01,
@@ -140,18 +135,15 @@ def episode_summary(ep_return, ep_length, terminated, truncated, reward, action=
         workspace = torch.empty(need, dtype=torch.float64, device=dev)
     assert workspace.numel() >= need and summary.numel() == 8 and action_hist.numel() == n_actions and reward_hist.numel() == 6
     assert ep_return.shape == (T, N) and ep_length.shape == (T, N) and (action is None or action.shape == (T, N))
-    _lib.check(_lib.lib().ppo_episode_summary(
-        _p(ep_return, torch.float64), _p(ep_length, torch.int32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
-        _p(reward, torch.float32), _p(action, torch.int32), int(n_actions), T, N, float(keep), float(gain),
-        _p(score, torch.float64), _p(summary, torch.float64), _p(action_hist, torch.int64), _p(reward_hist, torch.int64),
-        _p(workspace, torch.float64), _stream(reward)), "ppo_episode_summary")
+    _call("ppo_episode_summary", reward, _p(ep_return, torch.float64), _p(ep_length, torch.int32), _p(terminated, torch.uint8),
+          _p(truncated, torch.uint8), _p(reward, torch.float32), _p(action, torch.int32), int(n_actions), T, N, float(keep),
+          float(gain), _p(score, torch.float64), _p(summary, torch.float64), _p(action_hist, torch.int64),
+          _p(reward_hist, torch.int64), _p(workspace, torch.float64))
     return summary, action_hist, reward_hist
 
 
 def visit_carry_words(width, height, N):
-    n = _lib.lib().ppo_visit_carry_words(int(width), int(height), int(N))
-    _lib.check(min(n, 0), "ppo_visit_carry_words")
-    return n
+    return _query("ppo_visit_carry_words", int(width), int(height), int(N))
 
 
 def visit_scan(pos, terminated, truncated, carry, width=17, height=17, want_steps=True, out=None):
@@ -168,9 +160,8 @@ def visit_scan(pos, terminated, truncated, carry, width=17, height=17, want_step
     elif want_steps:
         first_visit = torch.empty((T, N), dtype=torch.uint8, device=pos.device)
         ep_cells = torch.empty((T, N), dtype=torch.int32, device=pos.device)
-    _lib.check(_lib.lib().ppo_visit_scan(_p(pos, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
-                                         T, N, int(width), int(height), _p(carry, torch.int32), _p(first_visit, torch.uint8),
-                                         _p(ep_cells, torch.int32), _stream(pos)), "ppo_visit_scan")
+    _call("ppo_visit_scan", pos, _p(pos, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8), T, N,
+          int(width), int(height), _p(carry, torch.int32), _p(first_visit, torch.uint8), _p(ep_cells, torch.int32))
     return first_visit, ep_cells
 
 
@@ -186,9 +177,8 @@ def visit_hist(pos, counts, width=17, height=17, mask=None, t_idx=None, n_idx=No
     assert t_idx is None or n_idx.numel() == B
     if t_idx is not None and B == 0:
         return counts
-    _lib.check(_lib.lib().ppo_visit_hist(_p(pos, torch.float32), T, N, _p(mask, torch.uint8), _p(t_idx, torch.int32),
-                                         _p(n_idx, torch.int32), B, int(width), int(height), _p(counts, torch.int64),
-                                         _stream(pos)), "ppo_visit_hist")
+    _call("ppo_visit_hist", pos, _p(pos, torch.float32), T, N, _p(mask, torch.uint8), _p(t_idx, torch.int32),
+          _p(n_idx, torch.int32), B, int(width), int(height), _p(counts, torch.int64))
     return counts
 
 
@@ -198,17 +188,13 @@ BONUS_SCOPES = {"env": 0, "shared": 1}
 
 def bonus_table_words(kind, scope, width=17, height=17, n_actions=7, N=1):
     """32-bit words of one count table (kind "state" / "action", scope "env" / "shared"; ppo_bonus_table_words)."""
-    n = _lib.lib().ppo_bonus_table_words(BONUS_KINDS[kind], BONUS_SCOPES[scope], int(width), int(height), int(n_actions),
-                                         int(N))
-    _lib.check(min(n, 0), "ppo_bonus_table_words")
-    return n
+    return _query("ppo_bonus_table_words", BONUS_KINDS[kind], BONUS_SCOPES[scope], int(width), int(height),
+                  int(n_actions), int(N))
 
 
 def bonus_workspace_bytes(kind_mask, scope, T, width=17, height=17, n_actions=7):
-    n = _lib.lib().ppo_bonus_workspace_bytes(int(kind_mask), BONUS_SCOPES[scope], int(T), int(width), int(height),
-                                             int(n_actions))
-    _lib.check(min(n, 0), "ppo_bonus_workspace_bytes")
-    return n
+    return _query("ppo_bonus_workspace_bytes", int(kind_mask), BONUS_SCOPES[scope], int(T), int(width), int(height),
+                  int(n_actions))
 
 
 def bonus_scan(pos, action, reward, state_table=None, action_table=None, scope="env", scale=1.0, width=17, height=17,
@@ -238,11 +224,10 @@ def bonus_scan(pos, action, reward, state_table=None, action_table=None, scope="
         assert workspace.numel() * 4 >= need
     for kind, tab in (("state", state_table), ("action", action_table)):
         assert tab is None or tab.numel() == bonus_table_words(kind, scope, width, height, n_actions, N)
-    _lib.check(_lib.lib().ppo_bonus_scan(
-        _p(pos, torch.float32), _p(action, torch.int32), dp, st, sn, _p(reward, torch.float32), _p(keep, torch.uint8), T, N,
-        int(width), int(height), int(n_actions), mask, BONUS_SCOPES[scope], float(scale), _p(state_table, torch.int32),
-        _p(action_table, torch.int32), _p(bonus_state, torch.float32), _p(bonus_action, torch.float32),
-        _p(reward_out, torch.float32), _p(workspace, torch.int32), _stream(pos)), "ppo_bonus_scan")
+    _call("ppo_bonus_scan", pos, _p(pos, torch.float32), _p(action, torch.int32), dp, st, sn, _p(reward, torch.float32),
+          _p(keep, torch.uint8), T, N, int(width), int(height), int(n_actions), mask, BONUS_SCOPES[scope], float(scale),
+          _p(state_table, torch.int32), _p(action_table, torch.int32), _p(bonus_state, torch.float32),
+          _p(bonus_action, torch.float32), _p(reward_out, torch.float32), _p(workspace, torch.int32))
     return reward_out
 
 
@@ -260,8 +245,7 @@ def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, 
     args = [_p(pos, torch.float32), _p(terminated.contiguous(), torch.uint8), _p(truncated.contiguous(), torch.uint8),
             _p(age0.contiguous(), torch.int32), _p(reward.contiguous(), torch.float32), _p(choices), int(seed),
             int(env_id0), int(step0), T, N, int(max_goals), int(skip)]
-    fn = _lib.lib().ppo_her_relabel_window
-    _lib.check(fn(*args, None, _p(counts), None, None, None, None, None, _stream(pos)), "ppo_her_relabel_window")
+    _call("ppo_her_relabel_window", pos, *args, None, _p(counts), None, None, None, None, None)
     incl = torch.cumsum(counts.long(), 0)
     H = int(incl[-1])                                   # the one host sync: the record count sizes the outputs
     offsets = (incl - counts.long()).contiguous()
@@ -270,8 +254,8 @@ def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, 
                reward=torch.empty(H, dtype=torch.float32, device=dev), done=torch.empty(H, dtype=torch.uint8, device=dev),
                counts=counts)
     if H:
-        _lib.check(fn(*args, _p(offsets), _p(counts), _p(out["t"]), _p(out["n"]), _p(out["goal"]), _p(out["reward"]),
-                      _p(out["done"]), _stream(pos)), "ppo_her_relabel_window")
+        _call("ppo_her_relabel_window", pos, *args, _p(offsets), _p(counts), _p(out["t"]), _p(out["n"]), _p(out["goal"]),
+              _p(out["reward"]), _p(out["done"]))
     return out
 
 
@@ -285,8 +269,7 @@ class _ConvBiasReLU(torch.autograd.Function):
         y = torch.ops.aten.convolution(x, w, None, list(stride), [0, 0], [1, 1], False, [0, 0], 1)
         assert y.is_contiguous(memory_format=torch.channels_last), "conv epilogue kernels need channels-last activations"
         B, Cc, H, W = y.shape
-        _lib.check(_lib.lib().ppo_bias_relu_nhwc(C.c_void_p(y.data_ptr()), _p(b.detach(), torch.float32), B * H * W, Cc,
-                                                 _stream(y)), "ppo_bias_relu_nhwc")
+        _call("ppo_bias_relu_nhwc", y, _p(y, None, _CL), _p(b.detach(), torch.float32), B * H * W, Cc)
         ctx.save_for_backward(x, w, y)
         ctx.stride = list(stride)
         return y
@@ -297,12 +280,10 @@ class _ConvBiasReLU(torch.autograd.Function):
         gy = gy.contiguous(memory_format=torch.channels_last)
         B, Cc, H, W = y.shape
         npix = B * H * W
-        blocks = _lib.lib().ppo_relu_bwd_bias_grad_nhwc_blocks(npix, Cc)
+        blocks = _query("ppo_relu_bwd_bias_grad_nhwc_blocks", npix, Cc)
         g = torch.empty_like(y)                                   # channels-last like y
         partial = torch.empty((blocks, Cc), dtype=torch.float32, device=y.device)
-        _lib.check(_lib.lib().ppo_relu_bwd_bias_grad_nhwc(C.c_void_p(gy.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                          C.c_void_p(g.data_ptr()), _p(partial), npix, Cc, _stream(y)),
-                   "ppo_relu_bwd_bias_grad_nhwc")
+        _call("ppo_relu_bwd_bias_grad_nhwc", y, _p(gy, None, _CL), _p(y, None, _CL), _p(g, None, _CL), _p(partial), npix, Cc)
         gx, gw, _ = torch.ops.aten.convolution_backward(g, x, w, None, ctx.stride, [0, 0], [1, 1], False, [0, 0], 1,
                                                         [bool(ctx.needs_input_grad[0]), True, False])
         return gx, gw, partial.sum(0), None
@@ -337,9 +318,8 @@ def conv1_up4_bias_relu_infer(frames, weight, bias):
     Cout = weight.shape[0]
     y = torch.empty((B, Cout, 33, 33), dtype=torch.float32, device=frames.device, memory_format=torch.channels_last)
     wf = fold_conv1_weights(weight)
-    _lib.check(_lib.lib().ppo_conv1_up4_bias_relu_c(_p(frames.contiguous(), torch.float32), B, F, Cout, _p(wf),
-                                                    _p(bias.contiguous(), torch.float32), C.c_void_p(y.data_ptr()),
-                                                    _stream(y)), "ppo_conv1_up4_bias_relu_c")
+    _call("ppo_conv1_up4_bias_relu_c", y, _p(frames.contiguous(), torch.float32), B, F, Cout, _p(wf),
+          _p(bias.contiguous(), torch.float32), _p(y, None, _CL))
     return y
 
 
@@ -356,8 +336,8 @@ class _Conv1Up4(torch.autograd.Function):
         if wf is None:
             wf = fold_conv1_weights(w)
         fr = frames.contiguous()
-        _lib.check(_lib.lib().ppo_conv1_up4_bias_relu(_p(fr, torch.float32), B, F, _p(wf), _p(b.detach().contiguous()),
-                                                      C.c_void_p(y.data_ptr()), _stream(y)), "ppo_conv1_up4_bias_relu")
+        _call("ppo_conv1_up4_bias_relu", y, _p(fr, torch.float32), B, F, _p(wf), _p(b.detach().contiguous()),
+              _p(y, None, _CL))
         ctx.save_for_backward(fr, w, y)
         return y
 
@@ -366,11 +346,11 @@ class _Conv1Up4(torch.autograd.Function):
         fr, w, y = ctx.saved_tensors
         gy = gy.contiguous(memory_format=torch.channels_last)
         B, F = fr.shape[0], fr.shape[1]
-        groups = _lib.lib().ppo_conv1_up4_bwd_groups(B)
+        groups = _query("ppo_conv1_up4_bwd_groups", B)
         gw_part = torch.empty((groups, 2, 2, 2, 2, F, 64), dtype=torch.float32, device=y.device)
         gb_part = torch.empty((groups, 4, 64), dtype=torch.float32, device=y.device)
-        _lib.check(_lib.lib().ppo_conv1_up4_bwd(_p(fr, torch.float32), B, F, C.c_void_p(gy.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                _p(gw_part), _p(gb_part), _stream(y)), "ppo_conv1_up4_bwd")
+        _call("ppo_conv1_up4_bwd", y, _p(fr, torch.float32), B, F, _p(gy, None, _CL), _p(y, None, _CL), _p(gw_part),
+              _p(gb_part))
         return None, unfold_conv1_grad(gw_part.sum(0)).to(w.dtype), gb_part.sum((0, 1)), None
 
 
@@ -409,12 +389,9 @@ def decoder_frames(z, w1, b1, w2, b2, w3, b3):
     n = z.shape[0]
     out = torch.empty((n, 289), dtype=torch.float32, device=z.device)
     if n:
-        _lib.check(_lib.lib().ppo_decoder_frames(_p(z), n, _p(w1.detach().contiguous(), torch.float32),
-                                                 _p(b1.detach().contiguous(), torch.float32),
-                                                 _p(w2.detach().contiguous(), torch.float32),
-                                                 _p(b2.detach().contiguous(), torch.float32),
-                                                 _p(fold_decoder_tail(w3.detach())), 0.0, _p(out), _stream(z)),
-                   "ppo_decoder_frames")
+        _call("ppo_decoder_frames", z, _p(z), n, _p(w1.detach().contiguous(), torch.float32),
+              _p(b1.detach().contiguous(), torch.float32), _p(w2.detach().contiguous(), torch.float32),
+              _p(b2.detach().contiguous(), torch.float32), _p(fold_decoder_tail(w3.detach())), 0.0, _p(out))
         out += b3.detach().view(1, 1)            # the bias as a device-side add: no host synchronisation in the rollout
     return out
 
@@ -432,5 +409,5 @@ def lstm_cell_(gates, c, gates_b=None, bias=None):
         assert gates_b.shape == (B, H4) and gates_b.stride(1) == 1 and gates_b.dtype == torch.float32 and gates_b.is_cuda
         pb, ldb = C.c_void_p(gates_b.data_ptr()), gates_b.stride(0) if B > 1 else H4
     h = torch.empty_like(c)
-    _lib.check(_lib.lib().ppo_lstm_cell(_p(gates), pb, ldb, _p(bias), _p(c), _p(h), B, H, _stream(c)), "ppo_lstm_cell")
+    _call("ppo_lstm_cell", c, _p(gates), pb, ldb, _p(bias), _p(c), _p(h), B, H)
     return h

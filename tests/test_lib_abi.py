@@ -16,6 +16,59 @@ def _declared():
     return syms
 
 
+def _prototypes():
+    """{name: (return type, [parameter types])} of every prototype in include/*.h, each type as the header spells it
+    with `const` and the parameter's name dropped and every pointer reduced to "*".  The headers are plain C with one
+    declarator per parameter."""
+    protos = {}
+    for fn in sorted(os.listdir(os.path.join(ROOT, "include"))):
+        txt = open(os.path.join(ROOT, "include", fn)).read()
+        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+        txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+        for ret, name, params in re.findall(r"([A-Za-z_][\w \*\n]*?)\b((?:tw|ppo|mg)_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+            assert name not in protos, "%s is declared twice" % name
+            params = [] if params.strip() == "void" else params.split(",")
+
+            def kind(decl, named):
+                if "*" in decl:
+                    return "char *" if re.sub(r"\bconst\b", "", decl).split() == ["char", "*"] else "*"
+                words = [w for w in decl.split() if w != "const"]
+                return " ".join(words[:-1] if named else words)
+            protos[name] = (kind(ret, False), [kind(p, True) for p in params])
+    return protos
+
+
+def test_ctypes_signatures_mirror_the_headers():
+    """Every entry of _lib._SIGS against the prototype it mirrors: the parameter count, each parameter's class and the
+    return type.  A pointer of any type is a ctypes pointer; an integer or floating type is the ctypes type of exactly
+    that C type, so an `int` where the header says `int64_t` fails."""
+    import ctypes as C
+    import twoarmy_amd
+    scalar = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+              "uint32_t": C.c_uint32, "float": C.c_float, "double": C.c_double}
+
+    def matches(ctype, kind, is_return):
+        if kind == "char *" and is_return:
+            return ctype is C.c_char_p
+        if kind in ("*", "char *"):
+            return ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer)
+        return ctype is scalar[kind]                 # an unknown C type is a KeyError: extend the classes on purpose
+
+    protos, sigs = _prototypes(), twoarmy_amd._lib._SIGS
+    assert set(protos) == set(sigs) == _declared()
+    bad = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = sigs[name]
+        if not matches(res, ret, True):
+            bad.append("%s returns %s, the table says %s" % (name, ret, res.__name__))
+        if len(args) != len(params):
+            bad.append("%s takes %d arguments, the table says %d" % (name, len(params), len(args)))
+            continue
+        bad += ["%s argument %d is %s, the table says %s" % (name, i, k, a.__name__)
+                for i, (a, k) in enumerate(zip(args, params)) if not matches(a, k, False)]
+    assert not bad, "\n".join(bad)
+
+
 def test_library_loads_and_exports_all_declared_symbols():
     import __graft_entry__ as ge
     ge.build()
