@@ -86,6 +86,7 @@ _SIGS.update({
     "ppo_adv_norm": (C.c_int, [_vp, _i64, _f, _vp, _vp]),
     "ppo_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "ppo_loss_fwd_bwd_masked": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "ppo_prior_loss_fwd_bwd": (C.c_int, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "ppo_gather_stack": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mg_gen_obs": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "mg_step": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -110,6 +111,7 @@ _SIGS.update({
     "mg_nav_field": (C.c_int, [_vp, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp,
                                _vp]),
     "mg_nav_lookup": (C.c_int, [_vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "mg_nav_optimal_moves": (C.c_int, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "ppo_her_relabel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
     "ppo_her_relabel_window": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _i, _vp,

@@ -10,6 +10,11 @@
  *                          the row); the image then leaves whole through the aligned row store (row_store.h), and one
  *                          lane per env reads the agent's cell and its four neighbours from it.
  *   mg_nav_lookup_kernel   one lane per (step, env): the cell of the position (visit_cell.h) indexes the env's field.
+ *   mg_nav_moves_kernel    the set of optimal moves of every acting state of a rollout.  A workgroup owns NAV_MOVES_ELEMS
+ *                          consecutive (step, env) elements: it reads their positions (and ages) coalesced, one element
+ *                          per lane and round, looks the cell and its four neighbours up in the env's field (a 578-byte
+ *                          row that stays in cache) and parks mask and distance in LDS; the two outputs then leave
+ *                          through the aligned row store, each as the 16-byte chunks of its own alignment.
  *
  * Integer work only, no atomics: the results do not depend on scheduling.
  */
@@ -175,6 +180,73 @@ __global__ __launch_bounds__(NAV_LOOKUP_THREADS) void mg_nav_lookup_kernel(const
     out[i] = c < W * H ? dist[(int64_t)n * pitch + c] : (uint16_t)MG_NAV_UNREACHABLE;
 }
 
+// ------------------------------------------------------------------ optimal-move sets of a rollout's acting states
+constexpr int NAV_MOVES_THREADS = 256;
+constexpr int NAV_MOVES_ELEMS = 2048;                  // elements per workgroup: 4096 x 128 are 256 workgroups
+constexpr int NAV_MOVES_ROUNDS = (NAV_MOVES_ELEMS + 16 + NAV_MOVES_THREADS - 1) / NAV_MOVES_THREADS;
+static_assert(NAV_MOVES_ELEMS % 16 == 0, "whole chunks of both outputs");
+
+// The optimal moves on cell c of a field row (minigrid_nav.h): bit k = neighbour k lies one move nearer; 0x10 on a source.
+__device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ row, int c, int W, int H, uint32_t &d)
+{
+    d = row[c];
+    if (d == 0u) return 0x10u;
+    if (d == (uint32_t)MG_NAV_UNREACHABLE) return 0u;
+    const int y = c / W, x = c - y * W;
+    const uint32_t want = d - 1u;
+    uint32_t m = 0;
+    if (x > 0 && row[c - 1] == want) m |= 1u;
+    if (x < W - 1 && row[c + 1] == want) m |= 2u;
+    if (y > 0 && row[c - W] == want) m |= 4u;
+    if (y < H - 1 && row[c + W] == want) m |= 8u;
+    return m;
+}
+
+__global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_moves_kernel(
+    const uint16_t *__restrict__ dist, int64_t pitch, int N, int W, int H, const float2 *__restrict__ pos,
+    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int64_t M, uint8_t *__restrict__ moves,
+    uint16_t *__restrict__ acting_dist)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_moves[NAV_MOVES_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint16_t s_dist[NAV_MOVES_ELEMS];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    // this workgroup's chunks of either output and the positions they hold: both within [ELEMS * b - 15, ELEMS * (b + 1))
+    const int sm = mg_row_misalign(moves, 16), sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
+    const mg_row_span_t<int64_t> km = mg_row_span<int64_t>(sm, M, b, NAV_MOVES_ELEMS / 16, 16);
+    const mg_row_span_t<int64_t> kd = mg_row_span<int64_t>(sd, M, b, NAV_MOVES_ELEMS / 8, 8);
+    const int64_t bm = 16 * km.c0 - sm, bd = 8 * kd.c0 - sd;               // position of LDS slot 0 of either image
+    const int HW = W * H;
+    float2 init = make_float2(0.f, 0.f);
+    if (age != nullptr) init = make_float2(init_pos[0], init_pos[1]);
+
+    const int64_t p0 = (int64_t)NAV_MOVES_ELEMS * b - 16;
+#pragma unroll 1
+    for (int k = 0; k < NAV_MOVES_ROUNDS; ++k) {
+        const int64_t p = p0 + k * NAV_MOVES_THREADS + tid;
+        const bool in_m = p >= km.p_lo && p < km.p_hi;
+        const bool in_d = acting_dist != nullptr && p >= kd.p_lo && p < kd.p_hi;
+        if (!(in_m || in_d)) continue;                                      // both spans lie inside [0, M)
+        float2 q = pos[p];
+        if (age != nullptr && age[p] <= 0) q = init;
+        const int c = visit_cell(q.x, q.y, W, H);
+        uint32_t d = MG_NAV_UNREACHABLE, m = 0;
+        if (c < HW) m = nav_move_set(dist + (int64_t)(p % N) * pitch, c, W, H, d);
+        if (in_m) s_moves[(int)(p - bm)] = (uint8_t)m;
+        if (in_d) s_dist[(int)(p - bd)] = (uint16_t)d;
+    }
+    __syncthreads();
+
+    for (int64_t c = km.c0 + tid; c < km.c1; c += NAV_MOVES_THREADS)
+        mg_row_store(moves, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_moves + (int)(p - bm)); },
+                     [&](int64_t q) { return s_moves[(int)(q - bm)]; });
+    if (acting_dist != nullptr)
+        for (int64_t c = kd.c0 + tid; c < kd.c1; c += NAV_MOVES_THREADS)
+            mg_row_store(acting_dist, M, c,
+                         [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_dist + (int)(p - bd)); },
+                         [&](int64_t q) { return s_dist[(int)(q - bd)]; });
+}
+
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
 
 }  // namespace
@@ -212,5 +284,24 @@ extern "C" int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_env
     hipLaunchKernelGGL(mg_nav_lookup_kernel, dim3((unsigned)((M + NAV_LOOKUP_THREADS - 1) / NAV_LOOKUP_THREADS)),
                        dim3(NAV_LOOKUP_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
                        reinterpret_cast<const float2 *>(pos), M, out);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_optimal_moves(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height,
+                                    const float *pos, const int32_t *age, const float *init_pos, int T, uint8_t *moves,
+                                    uint16_t *acting_dist, void *stream)
+{
+    if (!dist || !pos || !moves || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
+    if (((uintptr_t)dist & 1u) || ((uintptr_t)acting_dist & 1u) || ((uintptr_t)pos & 7u)) return TW_E_ARG;
+    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    const int64_t M = (int64_t)T * n_envs;
+    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (M == 0) return TW_OK;
+    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
+    // chunks are counted from the aligned address below either output: up to 15 positions more than M
+    hipLaunchKernelGGL(mg_nav_moves_kernel, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
+                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
+                       reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
     return tw_launched(__func__);
 }

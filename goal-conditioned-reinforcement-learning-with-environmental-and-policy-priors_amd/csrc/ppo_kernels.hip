@@ -420,6 +420,102 @@ __global__ void ppo_loss_finalize_kernel(const float *__restrict__ ws, int nbloc
     }
 }
 
+// ------------------------------------------------------------------ shortest-path prior: set-valued imitation term
+// One row of the prior (twoarmy_ppo.h): S = sum p, q = p / S, m = the mass on the masked actions summed in ascending a,
+// rest = the mass on the others (the upper clamp is decided on `rest`, which is accurate where m is within rounding of
+// 1), top = arg-max of q, lowest index on ties.
+template <int A> struct prior_row_t { float S, m, rest; int top; };
+template <int A> __device__ __forceinline__ prior_row_t<A> prior_row(const float *__restrict__ p, uint32_t mask)
+{
+    float v[A], S = 0.f;
+#pragma unroll
+    for (int k = 0; k < A; ++k) { v[k] = p[k]; S += v[k]; }
+    prior_row_t<A> r = {S, 0.f, 0.f, 0};
+    float best = 0.f;
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        const float q = v[k] / S;
+        if ((mask >> k) & 1u) r.m += q; else r.rest += q;
+        if (k == 0 || q > best) { best = q; r.top = k; }
+    }
+    return r;
+}
+
+// pass 1: per-workgroup partial sums {loss, mass} and counts {labelled, arg-max in the mask} -> ws[4 * block]
+template <int A>
+__global__ __launch_bounds__(256) void ppo_prior_partial_kernel(const float *__restrict__ probs,
+                                                                const uint8_t *__restrict__ moves, int n_valid,
+                                                                float *__restrict__ ws) {
+    __shared__ float sl[256], sm[256];
+    __shared__ int sc[256], sg[256];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    float l = 0.f, m = 0.f;
+    int lab = 0, agree = 0;
+    const uint32_t mask = b < n_valid ? (uint32_t)moves[b] & ((1u << A) - 1u) : 0u;
+    if (mask != 0u) {
+        const prior_row_t<A> r = prior_row<A>(probs + (size_t)b * A, mask);
+        const float mc = r.rest < CAT_EPS ? 1.0f - CAT_EPS : fminf(fmaxf(r.m, CAT_EPS), 1.0f - CAT_EPS);
+        l = -logf(mc);
+        m = r.m;
+        lab = 1;
+        agree = (int)((mask >> r.top) & 1u);
+    }
+    sl[threadIdx.x] = l; sm[threadIdx.x] = m; sc[threadIdx.x] = lab; sg[threadIdx.x] = agree;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sl[threadIdx.x] += sl[threadIdx.x + s]; sm[threadIdx.x] += sm[threadIdx.x + s];
+            sc[threadIdx.x] += sc[threadIdx.x + s]; sg[threadIdx.x] += sg[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ws[4 * blockIdx.x] = sl[0]; ws[4 * blockIdx.x + 1] = sm[0];
+        ws[4 * blockIdx.x + 2] = __int_as_float(sc[0]); ws[4 * blockIdx.x + 3] = __int_as_float(sg[0]);
+    }
+}
+
+// pass 2: every workgroup adds the partial counts in block order (the same value everywhere), writes its rows of the
+// gradient, and workgroup 0 writes the means and the counts.
+template <int A>
+__global__ __launch_bounds__(256) void ppo_prior_grad_kernel(const float *__restrict__ probs, const uint8_t *__restrict__ moves,
+                                                             int B, int n_valid, float coef, const float *__restrict__ ws,
+                                                             int nblocks, float *__restrict__ out, int32_t *__restrict__ counts,
+                                                             float *__restrict__ grad_probs) {
+    __shared__ int s_lab;
+    if (threadIdx.x == 0) {
+        int lab = 0, agree = 0;
+        float l = 0.f, m = 0.f;
+        for (int k = 0; k < nblocks; ++k) {                                 // fixed order
+            l += ws[4 * k]; m += ws[4 * k + 1];
+            lab += __float_as_int(ws[4 * k + 2]); agree += __float_as_int(ws[4 * k + 3]);
+        }
+        s_lab = lab;
+        if (blockIdx.x == 0) {
+            out[0] = lab > 0 ? coef * (l / (float)lab) : 0.f;
+            out[1] = lab > 0 ? m / (float)lab : 0.f;
+            counts[0] = lab; counts[1] = agree;
+        }
+    }
+    __syncthreads();
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    float g[A];
+#pragma unroll
+    for (int k = 0; k < A; ++k) g[k] = 0.f;
+    const uint32_t mask = b < n_valid ? (uint32_t)moves[b] & ((1u << A) - 1u) : 0u;
+    if (mask != 0u) {
+        const prior_row_t<A> r = prior_row<A>(probs + (size_t)b * A, mask);
+        if (r.m >= CAT_EPS && r.rest >= CAT_EPS) {                          // inside the clamp: the gradient passes
+            const float scale = coef / (float)s_lab, in = 1.0f - 1.0f / r.m;
+#pragma unroll
+            for (int k = 0; k < A; ++k) g[k] = (((mask >> k) & 1u) ? in : 1.0f) / r.S * scale;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < A; ++k) grad_probs[(size_t)b * A + k] = g[k];
+}
+
 // ------------------------------------------------------------------ stack gather / age scan
 // frame element -> fp32 policy input: identity for float frames, 4-entry LUT for uint8 code frames (TW_F_MATRIX_CODE)
 __device__ __forceinline__ float frame_value(float v) { return v; }
@@ -1011,6 +1107,28 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
     hipLaunchKernelGGL(ppo_loss_kernel<5>, dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
                        target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace);
     hipLaunchKernelGGL(ppo_loss_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, nblocks, n_valid, losses);
+    return tw_launched(__func__);
+}
+
+int ppo_prior_loss_fwd_bwd(const float *probs, const uint8_t *moves, int B, int n_valid, int A, float coef, float *out,
+                           int32_t *counts, float *grad_probs, float *workspace, void *stream) {
+    if (!probs || !moves || !out || !counts || !grad_probs || !workspace || B <= 0 || n_valid < 0 || n_valid > B)
+        return TW_E_ARG;
+    const int nblocks = (B + 255) / 256;
+    hipStream_t st = (hipStream_t)stream;
+#define PPO_PRIOR_LAUNCH(AA) do { \
+        hipLaunchKernelGGL(ppo_prior_partial_kernel<AA>, dim3(nblocks), dim3(256), 0, st, probs, moves, n_valid, workspace); \
+        hipLaunchKernelGGL(ppo_prior_grad_kernel<AA>, dim3(nblocks), dim3(256), 0, st, probs, moves, B, n_valid, coef, \
+                           workspace, nblocks, out, counts, grad_probs); } while (0)
+    switch (A) {
+    case 5: PPO_PRIOR_LAUNCH(5); break;
+    case 2: PPO_PRIOR_LAUNCH(2); break;
+    case 3: PPO_PRIOR_LAUNCH(3); break;
+    case 4: PPO_PRIOR_LAUNCH(4); break;
+    case 7: PPO_PRIOR_LAUNCH(7); break;
+    default: return TW_E_ARG;
+    }
+#undef PPO_PRIOR_LAUNCH
     return tw_launched(__func__);
 }
 

@@ -13,6 +13,7 @@ PASS_DEFAULT = 0x0B1B                 # mg_step's rule: types 0, 1, 3, 8, 9, 11 
 PASS_LAVA, PASS_BALL = 1 << 9, 1 << 6  # clear PASS_LAVA to keep out of the lava, set PASS_BALL to walk through balls
 DOORS_OPEN = 1
 ACTION_STAY, ACTION_NONE = 6, -1
+MOVE_STAY = 1 << 4                    # optimal_moves: the bit of a source cell (bits 0..3: left, right, up, down)
 
 
 DIST_DTYPE = torch.uint16
@@ -80,6 +81,45 @@ def lookup(dist, pos, width, height, out=None):
     assert out.shape == (T, N) and out.dtype == DIST_DTYPE
     call("mg_nav_lookup", dist.device, dp, dpitch, N, W, H, ptr(p), T, ptr(out))
     return out.view(N) if one else out
+
+
+def optimal_moves(dist, pos, width, height, age=None, init_pos=None, out=None, dist_out=None):
+    """The set of optimal moves at every acting state of a rollout (mg_nav_optimal_moves, include/minigrid_nav.h).
+    dist uint16[N, H*W] (one field per env, rows may be padded), pos float32[T, N, 2] = (y, x) BEFORE each step, age
+    int32[T, N] with init_pos float32[2]: where age <= 0 the acting position is init_pos (ppo_gather_stack's rule); both
+    None: pos as it stands.  -> (moves uint8[T, N], acting_dist uint16[T, N]): bit k of moves = move k (left, right, up,
+    down) leads one step nearer, MOVE_STAY on a source, 0 on an unreachable cell or outside the world.  out / dist_out:
+    tensors to write into; dist_out=False: no distances (None is returned for them).  One launch."""
+    W, H = int(width), int(height)
+    dp, dpitch, N, row = rows(dist, DIST_DTYPE)
+    assert row == W * H
+    dev = dist.device
+    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
+    T = pos.shape[0]
+    assert (age is None) == (init_pos is None), "age and init_pos come together"
+    if age is not None:
+        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    if out is None:
+        out = torch.empty((T, N), dtype=torch.uint8, device=dev)
+    assert out.shape == (T, N) and out.device == dev
+    if dist_out is None:
+        dist_out = torch.empty((T, N), dtype=DIST_DTYPE, device=dev)
+    elif dist_out is False:
+        dist_out = None
+    assert dist_out is None or (dist_out.shape == (T, N) and dist_out.device == dev)
+    call("mg_nav_optimal_moves", dev, dp, dpitch, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
+         ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+def to_policy_mask(moves, n_actions):
+    """Move sets (optimal_moves) as masks over POLICY indices, the inverse of the policy-index -> env-action map (policy
+    index k < 4 is move k, the last index n_actions - 1 is the env's `done`): bits 0 .. min(4, n_actions - 1) - 1 stay, the
+    stay bit moves to bit n_actions - 1.  A torch op on uint8 tensors of any shape."""
+    A = int(n_actions)
+    assert moves.dtype == torch.uint8 and 2 <= A <= 8
+    low = moves & ((1 << min(4, A - 1)) - 1)
+    return low | (((moves >> 4) & 1) << (A - 1))
 
 
 def as_int(t):

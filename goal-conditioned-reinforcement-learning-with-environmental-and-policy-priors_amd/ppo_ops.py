@@ -71,6 +71,26 @@ def ppo_losses(probs, value, action, old_logp, adv, target_v, clip=0.1, ent_coef
     return _AttachGrad.apply(probs, losses[0], gp), _AttachGrad.apply(value, losses[1], gv)
 
 
+def prior_loss(probs, moves, coef, n_valid=None):
+    """Set-valued imitation term of the shortest-path prior (ppo_prior_loss_fwd_bwd, include/twoarmy_ppo.h):
+    coef * mean over the labelled rows of -log(mass of Categorical(probs) on the optimal actions).  moves uint8[B]: a mask
+    over policy indices (minigrid_nav.to_policy_mask); rows from n_valid on are padding.  -> (loss, (out, counts)): loss is
+    an autograd node on probs like ppo_losses' (so `(action_loss + loss).backward()` works); out f32[2] = (loss, mean
+    mass on the optimal actions) and counts i32[2] = (labelled rows, rows whose arg-max is optimal) stay on the device."""
+    B, A = probs.shape
+    n_valid = B if n_valid is None else int(n_valid)
+    assert moves.shape == (B,) and moves.device == probs.device
+    with torch.no_grad():
+        probs_c = probs.detach().contiguous()
+        out = torch.empty(2, dtype=torch.float32, device=probs.device)
+        counts = torch.empty(2, dtype=torch.int32, device=probs.device)
+        gp = torch.empty_like(probs_c)
+        ws = torch.empty(4 * ((B + 255) // 256), dtype=torch.float32, device=probs.device)
+        _call("ppo_prior_loss_fwd_bwd", probs, _p(probs_c, torch.float32), _p(moves, torch.uint8), B, n_valid, A, float(coef),
+              _p(out), _p(counts), _p(gp), _p(ws))
+    return _AttachGrad.apply(probs, out[0], gp), (out, counts)
+
+
 def gather_stack(frames, pos_frames, k_idx, n_idx, age, init_frame, init_pos):
     """frames [K,N,pitch>=289] (may be a [..., :289] view of a 292-pitched buffer) -> ([B,4,289], [B,4,2]).
     uint8 frames are matrix codes (TW_F_MATRIX_CODE) and are expanded to fp32 on the fly."""

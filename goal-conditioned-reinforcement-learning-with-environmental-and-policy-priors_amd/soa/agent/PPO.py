@@ -108,13 +108,16 @@ class PPO:
         return self._run(self.critic, x, p, g)
 
     @torch.no_grad()
-    def act_batch(self, frames4, pos4, goal, uniforms=None, offset_dev=None, offset_add=0, x=None):
+    def act_batch(self, frames4, pos4, goal, uniforms=None, offset_dev=None, offset_add=0, x=None, probs_out=None):
         """frames4 [B,4,289], pos4 [B,4,2], goal [B,2] (device) -> (action int32[B], logp float[B]).
         offset_dev (int64[1] device tensor): the sampler's stream position is *offset_dev + offset_add instead of
         self.sample_count -- for launches recorded in a HIP graph, whose position must live in device memory.
-        x: policy_input(frames4) when the caller has already computed it."""
+        x: policy_input(frames4) when the caller has already computed it.  probs_out: a [B, A] tensor that receives the
+        acting distribution (the shortest-path prior's statistics)."""
         self.actor.eval()
         probs = self.actor_probs(self.policy_input(frames4) if x is None else x, pos4, goal)
+        if probs_out is not None:
+            probs_out.copy_(probs)
         if offset_dev is not None:
             return ppo_ops.sample(probs, uniforms, seed=self.sample_seed, offset=int(offset_add), offset_dev=offset_dev)
         a, logp = ppo_ops.sample(probs, uniforms, seed=self.sample_seed, offset=self.sample_count)
@@ -166,19 +169,26 @@ class PPO:
         n_valid: the first n_valid rows are real samples, the rest pads the minibatch to a fixed shape."""
         return self.minibatch_step_x(self.policy_input(s0), p0, g, a, old_logp, adv, target_v, n_valid)
 
-    def minibatch_step_x(self, x0, p0, g, a, old_logp, adv, target_v, n_valid=None):
-        """minibatch_step on already assembled network inputs (frames incl. any predicted ones)."""
+    def minibatch_step_x(self, x0, p0, g, a, old_logp, adv, target_v, n_valid=None, prior=None):
+        """minibatch_step on already assembled network inputs (frames incl. any predicted ones).
+        prior = (moves uint8[B], coef): the shortest-path prior -- the actor's backward runs on action_loss +
+        ppo_ops.prior_loss(probs, moves, coef) (moves: masks over policy indices); the critic and the two returned
+        losses are untouched.  None: no such term, nothing launched."""
         probs = self.actor_probs(x0, p0, g)
         value = self.critic_value(x0, p0, g)
         action_loss, value_loss = ppo_ops.ppo_losses(probs, value, a, old_logp, adv, target_v,
                                                      clip=self.clip_param, ent_coef=self.entropy_coef, n_valid=n_valid)
+        actor_loss, prior_loss = action_loss, None
+        if prior is not None:
+            prior_loss, _ = ppo_ops.prior_loss(probs, prior[0], prior[1], n_valid=n_valid)
+            actor_loss = action_loss + prior_loss
         bucket = self.grad_sync if hasattr(self.grad_sync, "reduce_async") else None
         if bucket is not None:
             # multi-GPU, dist.GradBucket([actor params, critic params]): gradients are views into one flat buffer; the
             # actor's all-reduce is in flight while the critic's backward computes
             split = len(bucket.parts) == 2               # [actor, critic]; a one-group bucket is reduced after both
             bucket.zero()
-            action_loss.backward()
+            actor_loss.backward()
             if split:
                 bucket.reduce_async(0)
             value_loss.backward()
@@ -187,7 +197,7 @@ class PPO:
         else:
             self.optimizer_actor.zero_grad()
             self.optimizer_critic.zero_grad()
-            action_loss.backward()
+            actor_loss.backward()
             value_loss.backward()
             if self.grad_sync is not None:
                 self.grad_sync(list(self.actor.parameters()) + list(self.critic.parameters()))
@@ -198,6 +208,8 @@ class PPO:
         self.optimizer_critic.step()
         self.writer.add_scalar("loss/action_loss_update", action_loss.detach(), self.update_count)
         self.writer.add_scalar("loss/value_loss_update", value_loss.detach(), self.update_count)
+        if prior_loss is not None:
+            self.writer.add_scalar("loss/prior_loss_update", prior_loss.detach(), self.update_count)
         self.update_count += 1
         return action_loss.detach(), value_loss.detach()
 

@@ -97,6 +97,9 @@ class VecPPOTrainer:
         self.episodes = None                  # EpisodeTracker, made by the first account_episodes()
         self.visits = None                    # VisitTracker, made by the first account_visits()
         self.nav_field = self.goal_dist = None  # made by the first account_distance()
+        self._nav_field_at = -1               # env_steps when nav_field was last computed: one field per rollout
+        self.prior = None                     # shortest-path prior: {"coef", "decay", "updates"}, made by enable_prior()
+        self.expert_moves = self.expert_dist = self.act_probs = None   # made by enable_prior() / label_expert()
         self.bonus = None                     # BonusTracker, made by enable_bonus()
         self.reward_train = self.reward       # what targets and hindsight records use: the shaped reward when a bonus is on
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
@@ -137,6 +140,9 @@ class VecPPOTrainer:
                 x = self.agent.policy_input(s4)
                 self.pred_frames[t] = x[:, 4:]
                 a, logp = self.agent.act_batch(s4, p4, self.goal, None if uniforms is None else uniforms[t], x=x)
+            elif self.act_probs is not None:          # enable_prior(): the acting distribution is kept for prior_stats()
+                a, logp = self.agent.act_batch(s4, p4, self.goal, None if uniforms is None else uniforms[t],
+                                               offset_dev=offset_dev, offset_add=t * N, probs_out=self.act_probs[t])
             elif offset_dev is None:
                 a, logp = self.agent.act_batch(s4, p4, self.goal, None if uniforms is None else uniforms[t])
             else:
@@ -349,6 +355,9 @@ class VecPPOTrainer:
     def update(self, permutations=None):
         ag = self.agent
         T, N = self.T, self.N
+        prior_coef = 0.0 if self.prior is None else self.prior_coef()
+        if prior_coef != 0.0 and self._moves_at != self.env_steps:
+            raise RuntimeError("enable_prior(): call label_expert() after collect() and before update()")
         t_begin = time.perf_counter() if self.time_phases else 0.0
         adv, target = self.compute_targets()
         if self.time_phases:
@@ -365,6 +374,12 @@ class VecPPOTrainer:
             smp_n = torch.cat([smp_n, h["n"]])
         flat = smp_t.long() * N + smp_n.long()                        # action / old log-prob are those of (t, n)
         act, logp = self.action.view(-1)[flat], self.logp.view(-1)[flat]
+        smp_moves = None
+        if prior_coef != 0.0:
+            from .. import minigrid_nav as nav
+            # hindsight records get mask 0: their goal is not the field's source
+            smp_moves = torch.zeros(total, dtype=torch.uint8, device=self.device)
+            smp_moves[:T * N] = nav.to_policy_mask(self.expert_moves, self.act_probs.shape[-1]).view(-1)
         ag.actor.train(); ag.critic.train()
         la = lv = None
         local_steps = n_steps = -(-total // self.minibatch)
@@ -386,8 +401,13 @@ class VecPPOTrainer:
                     idx = torch.cat([idx, idx[torch.arange(self.minibatch - n_valid, device=self.device) % n_valid]])
                 with torch.no_grad():
                     x0, p0 = self._policy_x(smp_t[idx], smp_n[idx], False)
-                la, lv = ag.minibatch_step_x(x0, p0, self.goal_input(smp_goal[idx], False), act[idx],
-                                             logp[idx].view(-1, 1), adv[idx].view(-1, 1), target[idx].view(-1, 1), n_valid)
+                if smp_moves is None:
+                    la, lv = ag.minibatch_step_x(x0, p0, self.goal_input(smp_goal[idx], False), act[idx],
+                                                 logp[idx].view(-1, 1), adv[idx].view(-1, 1), target[idx].view(-1, 1), n_valid)
+                else:
+                    la, lv = ag.minibatch_step_x(x0, p0, self.goal_input(smp_goal[idx], False), act[idx],
+                                                 logp[idx].view(-1, 1), adv[idx].view(-1, 1), target[idx].view(-1, 1), n_valid,
+                                                 prior=(smp_moves[idx], prior_coef))
                 done_steps += 1
             assert done_steps == n_steps or not synced, (done_steps, n_steps)
         if ag.use_lr_decay:
@@ -398,6 +418,8 @@ class VecPPOTrainer:
             self.last_update_timing = {"targets_s": t_targets - t_begin, "epochs_s": t_end - t_targets,
                                        "epoch_s": (t_end - t_targets) / max(1, ag.K_epochs), "samples": int(total)}
         self.her = None
+        if self.prior is not None:
+            self.prior["updates"] += 1
         return la, lv
 
     def her_switch(self, her, score):
@@ -494,12 +516,22 @@ class VecPPOTrainer:
         (65535 where a wall has dropped onto the cell since).  Under in-kernel auto-reset the terminal state is gone
         but the terminal position is in the stream.  Two launches, no host synchronisation."""
         from .. import minigrid_nav as nav
-        if self.nav_field is None:
-            self.nav_field = torch.empty((self.N, 289), dtype=nav.DIST_DTYPE, device=self.device)
+        if self.goal_dist is None:
             self.goal_dist = torch.empty((self.T, self.N), dtype=nav.DIST_DTYPE, device=self.device)
-        self.engine.distance_field(pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, agent=False, out=self.nav_field)
+        self._static_field(reuse=False)
         nav.lookup(self.nav_field, self.pos[4:4 + self.T], 17, 17, out=self.goal_dist)
         return self.goal_dist
+
+    def _static_field(self, reuse):
+        """`nav_field` <- the field of the static map (balls and patrols passable, the wall drops as they stand now);
+        reuse: keep the one already computed for this rollout."""
+        from .. import minigrid_nav as nav
+        if self.nav_field is None:
+            self.nav_field = torch.empty((self.N, 289), dtype=nav.DIST_DTYPE, device=self.device)
+        if not (reuse and self._nav_field_at == self.env_steps):
+            self.engine.distance_field(pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, agent=False, out=self.nav_field)
+            self._nav_field_at = self.env_steps
+        return self.nav_field
 
     def distance_stats(self):
         """{"end_mean", "end_min": over the done steps of the last accounted rollout, "mean": over all its steps,
@@ -515,6 +547,63 @@ class VecPPOTrainer:
                          (~ok).sum()]).cpu().tolist()
         return {"end_mean": v[1] / v[0] if v[0] else None, "end_min": v[2] if v[0] else None,
                 "mean": v[4] / v[3] if v[3] else None, "cut_off": v[5]}
+
+    # ------------------------------------------------------------------ shortest-path prior
+    def enable_prior(self, coef, decay=1.0):
+        """Train the actor with the shortest-path prior: update() adds coef * decay^(updates done) times the set-valued
+        imitation term (ppo_ops.prior_loss) over the optimal-move sets label_expert() makes to the actor's loss of every
+        minibatch.  Rewards, returns, targets, advantages, the critic, the running score and the HER switch are
+        untouched (this is no reward shaping).  coef = 0: label and report only, no loss launch.  From here on the
+        rollout also keeps its acting distributions (T x N x 5 floats) for prior_stats()."""
+        import inspect
+        if "probs_out" not in inspect.signature(self.agent.act_batch).parameters or self.cache_predictions:
+            raise ValueError("the shortest-path prior needs the plain PPO agent's act_batch")
+        self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0}
+        self.act_probs = torch.zeros((self.T, self.N, 5), dtype=torch.float32, device=self.device)
+        self._moves_at = -1
+        self._graph = None                    # a captured rollout does not write act_probs
+        return self.prior
+
+    def prior_coef(self):
+        """The coefficient of the next update(): coef * decay^(updates done)."""
+        return self.prior["coef"] * self.prior["decay"] ** self.prior["updates"]
+
+    def label_expert(self):
+        """Optimal-move sets of every acting state of the rollout just collected (call after collect(), before
+        carry_over()): the static-map field exactly as account_distance() takes it (reused if that already ran for this
+        rollout) and ONE mg_nav_optimal_moves launch over the positions before each step, episode starts at the reset
+        position; `expert_moves` uint8[T, N] (bits: left, right, up, down, stay) and `expert_dist` uint16[T, N]
+        afterwards.  No host synchronisation."""
+        from .. import minigrid_nav as nav
+        T, N = self.T, self.N
+        self._static_field(reuse=True)
+        if self.expert_moves is None:
+            self.expert_moves = torch.empty((T, N), dtype=torch.uint8, device=self.device)
+            self.expert_dist = torch.empty((T, N), dtype=nav.DIST_DTYPE, device=self.device)
+        nav.optimal_moves(self.nav_field, self.pos[3:3 + T], 17, 17, age=self.age[:-1], init_pos=self.init_pos,
+                          out=self.expert_moves, dist_out=self.expert_dist)
+        self._moves_at = self.env_steps
+        return self.expert_moves
+
+    def prior_stats(self):
+        """How the policy that ACTED in the last labelled rollout stands to the expert: {"agree": share of the labelled
+        steps whose taken action is an optimal move, "opt_mass": mean probability it put on the optimal moves,
+        "labelled": steps with a non-empty move set, "coef": the coefficient of the next update()}; None where nothing
+        is labelled.  One device-to-host copy."""
+        if self.prior is None or self.expert_moves is None:
+            raise RuntimeError("prior_stats() before enable_prior() and label_expert()")
+        from .. import minigrid_nav as nav
+        A = self.act_probs.shape[-1]
+        mask = nav.to_policy_mask(self.expert_moves, A).to(torch.int32)
+        lab = mask != 0
+        hit = ((mask >> self.action) & 1) != 0
+        bits = ((mask.unsqueeze(-1) >> torch.arange(A, device=self.device, dtype=torch.int32)) & 1).double()
+        p = self.act_probs.double()
+        mass = (p * bits).sum(-1) / p.sum(-1)
+        v = torch.stack([lab.sum().double(), (hit & lab).sum().double(), torch.where(lab, mass, 0.0).sum()]).cpu().tolist()
+        n = int(v[0])
+        return {"agree": v[1] / n if n else None, "opt_mass": v[2] / n if n else None, "labelled": n,
+                "coef": self.prior_coef()}
 
     def stats(self):
         done = (self.term | self.trunc) != 0

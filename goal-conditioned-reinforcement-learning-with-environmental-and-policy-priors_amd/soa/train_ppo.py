@@ -12,6 +12,9 @@ the device, and --track_buffer_file DIR its track dump (heatmap.py:79) for the f
 (gym_minigrid/wrappers.py:34-102), counted on the device; off by default.
 --goal_distance adds the shortest-path distance to the goal (static map) at the done steps and over all steps of every
 rollout to the log line: one field and one lookup launch per rollout (minigrid_nav); off by default.
+--prior_coef C [--prior_decay D] trains the actor with the shortest-path prior: C * D^update times the set-valued
+imitation loss over the optimal moves of every acting state (one label launch per rollout, one loss launch pair per
+minibatch); --expert_agreement only labels and reports.  Both append `expert agree` / `opt_mass` to the log line; off by default.
 """
 import argparse
 import os
@@ -96,7 +99,23 @@ def build_parser():
                    help="once per rollout: the shortest-path distance to the goal on the static map (balls and patrols "
                         "passable) at every step, one field and one lookup launch on the device; adds `goal_dist end "
                         "mean/min` over the finished episodes and `goal_dist mean` over all steps to the log line; off by default")
+    p.add_argument("--prior_coef", type=float, default=0.0,
+                   help="shortest-path prior: add C * (the mean of -log of the policy's mass on the optimal moves of the "
+                        "static map) to the actor's loss of every minibatch; rewards, returns and the critic are untouched; "
+                        "plain PPO agent only; 0 = off")
+    p.add_argument("--prior_decay", type=float, default=1.0, help="with --prior_coef: the coefficient of update u is C * D^u")
+    p.add_argument("--expert_agreement", action="store_true",
+                   help="label every rollout with the optimal moves and append `expert agree` (share of the taken actions "
+                        "that are optimal) and `opt_mass` (the acting policy's mean mass on the optimal moves) to the log "
+                        "line, without training on them; implied by --prior_coef")
     return p
+
+
+def prior_fields(ps):
+    """Tail of the log line with --prior_coef / --expert_agreement (VecPPOTrainer.prior_stats())."""
+    if not ps["labelled"]:
+        return " expert agree - opt_mass -"
+    return " expert agree %.3f opt_mass %.3f" % (ps["agree"], ps["opt_mass"])
 
 
 def distance_fields(ds):
@@ -216,6 +235,11 @@ def main(argv=None, predictor=False, soa=False):
     if args.bonus != "none":
         trainer.enable_bonus(("state", "action") if args.bonus == "both" else (args.bonus,), args.bonus_scope,
                              args.bonus_scale)
+    use_prior = args.prior_coef != 0.0 or args.expert_agreement
+    if use_prior:
+        if predictor or soa:
+            raise SystemExit("--prior_coef / --expert_agreement: plain PPO agent only")
+        trainer.enable_prior(args.prior_coef, args.prior_decay)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
@@ -231,6 +255,8 @@ def main(argv=None, predictor=False, soa=False):
             trainer.account_visits(trainer.her)
         if args.goal_distance:
             trainer.account_distance()
+        if use_prior:
+            trainer.label_expert()
         es = None
         if args.score == "episode":
             es = trainer.episode_stats()
@@ -240,6 +266,10 @@ def main(argv=None, predictor=False, soa=False):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         n_her = 0 if trainer.her is None else int(trainer.her["t"].numel())
+        ps = trainer.prior_stats() if use_prior else None       # the policy that acted, before the update changes it
+        if use_prior:
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()                            # the statistics are not part of the update's time
         la, lv = trainer.update()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
@@ -259,6 +289,8 @@ def main(argv=None, predictor=False, soa=False):
             tail += " bonus mean %.4f" % bs["mean"]
         if args.goal_distance:                                  # behind every other field
             tail += distance_fields(trainer.distance_stats())
+        if use_prior:                                           # behind every other field
+            tail += prior_fields(ps)
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

@@ -80,6 +80,30 @@ int mg_nav_field(const uint8_t *type, const uint8_t *state, int n_envs, int widt
 int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height, const float *pos, int T,
                   uint16_t *out, void *stream);
 
+/* The SET of optimal moves at every acting state of a rollout, from ONE field per env (as mg_nav_lookup takes it).
+ *   pos       float[T][n_envs][2] = (y, x) BEFORE step t (8-byte aligned)
+ *   age       int32[T][n_envs] (nullable): steps taken in the running episode before step t
+ *   init_pos  float[2] on the device, the position after a reset; required when age is given
+ * The acting position of (t, n) is age[t][n] <= 0 ? init_pos : pos[t][n] -- the rule by which ppo_gather_stack fills the
+ * newest slot of a stack -- and its cell comes from the rule of the visit counters (csrc/visit_cell.h), as in
+ * mg_nav_lookup.  With d = the distance of that cell:
+ *   moves uint8[T][n_envs]:  bit k (k = 0..3: left, right, up, down, the moves of mg_step) is set iff the neighbour in
+ *       direction k lies inside the world and has distance d - 1; bit MG_NAV_MOVE_STAY_BIT (and no other) is set iff
+ *       d == 0; the value is 0 where the position is no cell or the cell is MG_NAV_UNREACHABLE.
+ *   acting_dist uint16[T][n_envs] (nullable): d, or MG_NAV_UNREACHABLE where the position is no cell.
+ * Invariant: the lowest set bit of moves, with bit 4 read as MG_NAV_ACTION_STAY, is the agent_action mg_nav_field
+ * reports for an agent on that cell of the same field; 0 corresponds to MG_NAV_ACTION_NONE.
+ * One launch; T == 0 launches nothing.  Both outputs leave as aligned 16-byte stores, element by element only in the
+ * first and last chunk of a workgroup's share (csrc/row_store.h); moves needs no alignment, and nothing outside the
+ * first T * n_envs elements of either output is written.
+ * TW_E_ARG: NULL dist / pos / moves, n_envs <= 0, T < 0, a side <= 0 or > MG_NAV_MAX_SIDE, 0 < dist_pitch < width*height
+ * or dist_pitch < 0, dist or acting_dist not 2-byte aligned, pos not 8-byte aligned, age or init_pos not 4-byte aligned,
+ * age without init_pos, T * n_envs >= 2^40. */
+#define MG_NAV_MOVE_STAY_BIT 4
+int mg_nav_optimal_moves(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height, const float *pos,
+                         const int32_t *age, const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

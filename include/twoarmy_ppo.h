@@ -71,6 +71,26 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
                             float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
                             void *stream);
 
+/* Shortest-path prior: a set-valued imitation term on the actor, forward + backward for one minibatch.  No reference
+ * counterpart; the labels are the optimal-move sets of mg_nav_optimal_moves (minigrid_nav.h).
+ *   probs float[B][A] (A as for ppo_sample); moves uint8[B]: a mask over POLICY indices, bit a set iff action a is optimal
+ *   (bits >= A are ignored).  A row is labelled iff it lies below n_valid (0 <= n_valid <= B; the rest is padding) and its
+ *   masked bits are non-zero.
+ * With Categorical(probs) semantics as in ppo_sample: q = p / sum(p); m = sum of q[a] over the mask in ascending a;
+ *   l = -log(clamp(m, eps, 1 - eps)), eps = FLT_EPSILON -- a single-bit mask gives -Categorical(probs=p).log_prob(a).
+ *   out[0] = coef * mean of l over the labelled rows; out[1] = mean of m over them
+ *   counts[0] = labelled rows; counts[1] = labelled rows whose arg-max of q (lowest index on ties) lies in the mask
+ *   grad_probs[b][j] = coef / counts[0] * (1 - [j in mask] / m) / sum(p) = d out[0] / d probs[b][j] inside the clamp,
+ *   eps <= m <= 1 - eps (torch.clamp passes the gradient on the closed interval); 0 where the clamp is active and for
+ *   unlabelled and padding rows.  Whether the upper clamp is active is decided on the mass OUTSIDE the mask (< eps),
+ *   which is accurate where m itself is within rounding of 1: a mask that holds all the mass, a full mask included,
+ *   always has l = -log(1 - eps) and gradient 0.
+ * With no labelled row out = {0, 0}, counts = {0, 0} and every gradient is 0.
+ * Deterministic: per-workgroup partial sums (a 256-wide tree) in `workspace`, added in block order; two calls give equal
+ * bits.  workspace: >= 4 * ceil(B/256) floats.  Two launches. */
+int ppo_prior_loss_fwd_bwd(const float *probs, const uint8_t *moves, int B, int n_valid, int A, float coef, float *out,
+                           int32_t *counts, float *grad_probs, float *workspace, void *stream);
+
 /* Policy-input assembly from time-major frames (replaces the 5-deep np.delete/np.append stacks of
  * train_ppo.py:116-121 and the [0:4] / [1:5] slices of PPO.py:113-114,124).  For sample b with newest
  * frame index k_b (row of `frames`), env n_b and age_b = number of env steps taken in the current

@@ -74,6 +74,21 @@ carry_r, carry_l = torch.zeros(N, dtype=torch.float64, device=dev), torch.zeros(
 ep_r, ep_l = ppo_ops.episode_scan(rw5, term, trunc, carry_r, carry_l)
 report("ppo_episode_scan (per-step outputs)", T * N * (4 + 1 + 1 + 8 + 4),
        timed(lambda: ppo_ops.episode_scan(rw5, term, trunc, carry_r, carry_l, out=(ep_r, ep_l))), "latency-bound: one lane per env")
+# Shortest-path prior: the label launch over a whole rollout (one field per env, every acting state) and the set-valued
+# imitation loss with its gradient over the same 524 288 rows; ppo_episode_scan above is the yardstick.
+from twoarmy_amd import minigrid_nav as nav  # noqa: E402
+nav_dist = torch.randint(0, 40, (N, 289), generator=g, dtype=torch.int16).to(dev).view(torch.uint16)
+pos_b = torch.randint(1, 16, (T, N, 2), generator=g).float().to(dev)
+age_tn = torch.randint(0, 50, (T, N), generator=g, dtype=torch.int32).to(dev)
+init_yx = torch.tensor([15.0, 3.0], device=dev)
+mv_out = torch.empty((T, N), dtype=torch.uint8, device=dev)
+ad_out = torch.empty((T, N), dtype=torch.uint16, device=dev)
+report("mg_nav_optimal_moves (4096 x 128, moves + acting_dist)", T * N * (8 + 4 + 1 + 2) + N * 578,
+       timed(lambda: nav.optimal_moves(nav_dist, pos_b, 17, 17, age=age_tn, init_pos=init_yx, out=mv_out, dist_out=ad_out)),
+       "one launch")
+mv_flat = torch.randint(0, 32, (T * N,), generator=g, dtype=torch.uint8).to(dev)
+report("ppo_prior_loss_fwd_bwd (524288 x 5)", T * N * (A * 4 + 1) * 2 + T * N * A * 4,
+       timed(lambda: ppo_ops.prior_loss(probs, mv_flat, 0.1)), "two launches, probs and moves read twice; includes 5 allocations")
 ep_score = torch.zeros(1, dtype=torch.float64, device=dev)
 ep_out = (torch.empty(8, dtype=torch.float64, device=dev), torch.empty(A, dtype=torch.int64, device=dev),
           torch.empty(6, dtype=torch.int64, device=dev),
