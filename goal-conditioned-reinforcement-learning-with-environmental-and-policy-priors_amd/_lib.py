@@ -25,6 +25,9 @@ FIELDS = dict(AX=0, AY=1, DIR=2, STEP_COUNT=3, STEP_MOVE=4, PONE=5, PATROL=6, UP
               O2Y=30, O2_VALID=34, GOAL_X=35, GOAL_Y=36, T=37, ERROR=38, MAX_STEPS=39, EPISODES=40,
               LAST_REWARD=41, LAST_TERM=42, LAST_TRUNC=43, WALL_I1=44, WALL_I2=45)
 
+# info[0..7] of tw_last_launch (include/twoarmy.h)
+LAUNCH_FIELDS = ("pipelined", "PG", "LAYOUT", "pipe_grid", "E", "FAST", "seq_grid", "T")
+
 ENV_ERRORS = {1: AttributeError, 2: AssertionError, 3: TypeError}
 
 
@@ -59,6 +62,7 @@ _SIGS = {
     "tw_set_envs_per_wave": (C.c_int, [_vp, C.c_int]),
     "tw_set_pipeline": (C.c_int, [_vp, C.c_int]),
     "tw_fallback_count": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "tw_last_launch": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "tw_fill_actions": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "tw_state_ptrs": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "tw_get_state_host": (C.c_int, [_vp, _vp, _vp, _vp]),

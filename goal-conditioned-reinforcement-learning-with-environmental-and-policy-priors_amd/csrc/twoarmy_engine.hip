@@ -1628,6 +1628,7 @@ struct tw_engine {
     int pipeline;                   // 1 = use the pipelined kernel when eligible (TW_PIPELINE=0 disables)
     int *fb_count;                  // device counter: pipelined launches re-run by the sequential fallback
     uint32_t *pipe_tab;             // constant tables of the pipelined kernel (static image, per-lane emission constants)
+    int last[8];                    // what the most recent tw_step / tw_rollout launched (tw_last_launch; enum below)
 };
 
 namespace {
@@ -1699,14 +1700,20 @@ constexpr auto PIPE_KERNELS = pipe_table(std::make_index_sequence<24>{});
 constexpr int PIPE_MIN_T = 8;
 constexpr size_t PIPE_LDS_BYTES = (size_t)(PWAVES * ENV_WORDS + PCH * PG_MAX + PG_MAX * REC + 4 + (PCH + 1) * PG_MAX) * 4;   // ~117 KB; drw has a spare row
 
-int launch_sequential(const tw_engine *e, const Params &p, hipStream_t st) {
+// tw_last_launch: written by the two launch functions from the very values that index the kernel tables and size the grids
+enum { LL_PIPELINED = 0, LL_PG, LL_LAYOUT, LL_PIPE_GRID, LL_E, LL_FAST, LL_SEQ_GRID, LL_T };
+
+int launch_sequential(tw_engine *e, const Params &p, hipStream_t st) {
     const int E = pick_envs_per_wave(e);
     if (E != 1 && E != 2 && E != 4) return TW_E_ARG;
     int grid = (e->n_envs + E - 1) / E;
     if (p.only_if_flagged && grid > 256) grid = 256;        // grid-stride fallback launch (see tw_rollout_kernel)
-    const KernelFn k = ROLLOUT_KERNELS[4 * log2i(E) + 2 * (e->variant == 6) + params_fast(e, p, false)];
+    const int fast = params_fast(e, p, false);
+    const KernelFn k = ROLLOUT_KERNELS[4 * log2i(E) + 2 * (e->variant == 6) + fast];
     hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, st, p);
     HIP_TRY_LAUNCHED();
+    if (!p.only_if_flagged) e->last[LL_PIPELINED] = e->last[LL_PG] = e->last[LL_LAYOUT] = e->last[LL_PIPE_GRID] = 0;
+    e->last[LL_E] = E; e->last[LL_FAST] = fast; e->last[LL_SEQ_GRID] = grid; e->last[LL_T] = p.T;
     return TW_OK;
 }
 
@@ -1745,6 +1752,7 @@ int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *
     p.only_if_flagged = 1;
     const int rc = launch_sequential(e, p, st);
     if (rc != TW_OK) return rc;
+    e->last[LL_PIPELINED] = 1; e->last[LL_PG] = pg; e->last[LL_LAYOUT] = layout; e->last[LL_PIPE_GRID] = grid;
     uint8_t *t8; int32_t *t32;
     t8 = e->type; e->type = e->type2; e->type2 = t8;
     t8 = e->colour; e->colour = e->colour2; e->colour2 = t8;
@@ -1817,6 +1825,12 @@ int tw_fallback_count(tw_engine *e, int *count) {
     DeviceGuard g(e->device);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(count, e->fb_count, sizeof(int), hipMemcpyDeviceToHost));
+    return TW_OK;
+}
+
+int tw_last_launch(const tw_engine *e, int *info) {
+    if (!e || !info) return TW_E_ARG;
+    memcpy(info, e->last, sizeof(e->last));
     return TW_OK;
 }
 

@@ -143,6 +143,13 @@ class TwoarmyEngine:
         _lib.check(_lib.lib().tw_fallback_count(self._h, C.byref(n)), "tw_fallback_count")
         return n.value
 
+    def last_launch(self):
+        """What the most recent step / rollout launched (tw_last_launch): {pipelined, PG, LAYOUT, pipe_grid, E, FAST,
+        seq_grid, T}; with pipelined = 1 the sequential fields describe the fallback launch behind the pipelined kernel."""
+        info = (C.c_int * len(_lib.LAUNCH_FIELDS))()
+        _lib.check(_lib.lib().tw_last_launch(self._h, info), "tw_last_launch")
+        return dict(zip(_lib.LAUNCH_FIELDS, info))
+
     def set_envs_per_wave(self, e):
         _lib.check(_lib.lib().tw_set_envs_per_wave(self._h, int(e)), "tw_set_envs_per_wave")
 
@@ -156,7 +163,8 @@ class TwoarmyEngine:
         a uint8 matrix tensor selects that mode in step/rollout.
         slab (default: on for the native layout with every output): the buffers are carved out of ONE slab the
         library allocates (tw_alloc_outputs) -- the same placement for every user of the C ABI; the tensors keep the
-        slab alive.  slab=False takes them from torch's caching allocator."""
+        slab alive.  slab=False takes them from torch's caching allocator; slab="hipmalloc" asks for a slab backed by
+        plain hipMalloc memory (TW_F_SLAB_HIPMALLOC) instead of mapped 2 MiB chunks."""
         N, V = self.num_envs, self.view_size
         lead = (N,) if T is None else (T, N)
         d = self.device
@@ -165,7 +173,8 @@ class TwoarmyEngine:
             slab = (not dense) and obs and matrix
         if slab:
             assert not dense and obs and matrix, "the engine slab holds the native layout with every output"
-            return self._slab_outputs(T, lead, matrix_codes)
+            assert slab is True or slab == "hipmalloc", slab
+            return self._slab_outputs(T, lead, matrix_codes, hipmalloc=slab == "hipmalloc")
         if dense:
             o = torch.empty(lead + (V, V, 3), dtype=torch.uint8, device=d) if obs else None
             m = torch.empty(lead + (TW_CELLS,), dtype=torch.uint8 if matrix_codes else torch.float32, device=d) \
@@ -187,9 +196,9 @@ class TwoarmyEngine:
             truncated=torch.empty(lead, dtype=torch.uint8, device=d),
         )
 
-    def _slab_outputs(self, T, lead, matrix_codes):
+    def _slab_outputs(self, T, lead, matrix_codes, hipmalloc=False):
         N, V = self.num_envs, self.view_size
-        flags = TW_F_MATRIX_CODE if matrix_codes else 0
+        flags = (TW_F_MATRIX_CODE if matrix_codes else 0) | (TW_F_SLAB_HIPMALLOC if hipmalloc else 0)
         owner = _OutputSlab(self, 1 if T is None else T, flags)
         fell_back = False
         try:

@@ -128,6 +128,20 @@ int tw_set_pipeline(tw_engine *e, int enable);
  * Synchronises the device. */
 int tw_fallback_count(tw_engine *e, int *count);
 
+/* What the most recent successful tw_step / tw_rollout (or tw_time_rollout) of this engine launched, recorded on the
+ * host from the values that selected the kernels and sized their grids (all 0 before the first launch; a rejected call
+ * leaves it unchanged; no device work):
+ *   info[0] pipelined   1 = the pipelined kernel ran, with the sequential kernel behind it as flag-gated fallback
+ *   info[1] PG          envs per workgroup of the pipelined kernel: 2, 4, 8, 16          (0 when pipelined = 0)
+ *   info[2] LAYOUT      0 two float streams, 1 one stream of float records, 2 code frames (0 when pipelined = 0)
+ *   info[3] pipe_grid   workgroups of the pipelined kernel = ceil(n_envs / PG)            (0 when pipelined = 0)
+ *   info[4] E           envs per wavefront of the sequential kernel: 1, 2, 4
+ *   info[5] FAST        1 = its instantiation with every layout decision folded at compile time
+ *   info[6] seq_grid    its workgroups: ceil(n_envs / E), at most 256 for the fallback launch (grid stride)
+ *   info[7] T           steps of the launch
+ * With pipelined = 1, info[4..6] describe the fallback launch.  `info` points to eight ints. */
+int tw_last_launch(const tw_engine *e, int *info);       /* info: int[8] */
+
 /* Fill int32[T][N] with the Philox action-slot policy indices the engine would use for its next
  * T steps (t counted from each env's current TW_T). */
 int tw_fill_actions(tw_engine *e, int T, int32_t *actions, void *stream);

@@ -113,11 +113,11 @@ def test_views_vs_reference_golden(golden_dir):
 _REF_CACHE = {}
 
 
-def _oracle(variant, N, T, view, env0):
-    key = (variant, N, T, view, env0)
+def _oracle(variant, N, T, view, env0, autoreset=True):
+    key = (variant, N, T, view, env0, autoreset)
     if key not in _REF_CACHE:
         _REF_CACHE.clear()
-        _REF_CACHE[key] = orc.rollout(variant, N, T, SEED, env0=env0, view=view)
+        _REF_CACHE[key] = orc.rollout(variant, N, T, SEED, env0=env0, view=view, autoreset=autoreset)
     return _REF_CACHE[key]
 
 
@@ -125,22 +125,46 @@ CODE_VALUES = np.array([0.9, -0.9, -0.5, 0.3], np.float32)
 
 
 def _compare_rollout(variant, N, T, view, env0=0, chunk=None, dense=False, epw=0, supply_actions=False,
-                     pipeline=True, codes=False):
+                     pipeline=True, codes=False, slab=None, autoreset=True, draws=None, step_api=False, expect=None,
+                     before=None, after=None):
     """supply_actions=True feeds the (identical) Philox action stream through HBM, which makes the launch
-    eligible for the pipelined kernel (logic wave + emission waves); otherwise the sequential kernel runs."""
+    eligible for the pipelined kernel (logic wave + emission waves); otherwise the sequential kernel runs.
+    chunk: launch length, or the list of launch lengths; step_api: one tw_step per step instead; slab / autoreset /
+    draws ([T, N, 8] int32): as alloc_outputs / rollout take them.  expect: dict, or function of the launch's length
+    that returns one, compared with last_launch() after EVERY launch, so a case that means to cover one instantiation
+    cannot quietly run another.  before / after(eng, out): hooks around the launches (prefill / inspect the raw rows)."""
     eng = _engine(variant, N, view, seed=SEED, env_id0=env0)
     eng.set_envs_per_wave(epw)
     eng.set_pipeline(pipeline)
-    ref = _oracle(variant, N, T, view, env0)
-    out = eng.alloc_outputs(T, dense=dense, matrix_codes=codes)
+    ref = _oracle(variant, N, T, view, env0, autoreset)
+    out = eng.alloc_outputs(T, dense=dense, matrix_codes=codes, slab=slab)
     acts = eng.fill_actions(T) if supply_actions else None
-    if chunk is None:
-        eng.rollout(T, out, actions=acts)
-    else:                                  # same thing in several launches: state must carry over exactly
-        for t0 in range(0, T, chunk):
-            t1 = min(T, t0 + chunk)
-            sub = {k: (v[t0:t1] if v is not None else None) for k, v in out.items()}
-            eng.rollout(t1 - t0, sub, actions=None if acts is None else acts[t0:t1])
+    if before is not None:
+        before(eng, out)
+
+    def selected(tlen):
+        if expect is not None:
+            want = expect(tlen) if callable(expect) else expect
+            got = eng.last_launch()
+            assert {k: got[k] for k in want} == want, (tlen, got)
+
+    if step_api:
+        for t in range(T):
+            eng.step(acts[t], {k: v[t] for k, v in out.items()}, draws=None if draws is None else draws[t],
+                     autoreset=autoreset, policy_idx=True)
+            selected(1)
+    else:                                  # several launches compute the same thing: state must carry over exactly
+        lens = [T] if chunk is None else list(chunk) if isinstance(chunk, (list, tuple)) else \
+            [min(chunk, T - t0) for t0 in range(0, T, chunk)]
+        assert sum(lens) == T
+        t0 = 0
+        for n in lens:
+            t1 = t0 + n
+            sub = out if n == T else {k: (v[t0:t1] if v is not None else None) for k, v in out.items()}
+            eng.rollout(n, sub, actions=None if acts is None else acts[t0:t1],
+                        draws=None if draws is None else draws[t0:t1], autoreset=autoreset)
+            selected(n)
+            t0 = t1
     torch.cuda.synchronize()
     for k in ("obs", "matrix", "pos", "reward", "terminated", "truncated"):
         got = out[k].cpu().numpy()
@@ -151,6 +175,8 @@ def _compare_rollout(variant, N, T, view, env0=0, chunk=None, dense=False, epw=0
         if not np.array_equal(got, ref[k]):
             bad = np.argwhere(got != ref[k])[0]
             raise AssertionError("%s mismatch first at %s: got %s want %s" % (k, bad, got[tuple(bad)], ref[k][tuple(bad)]))
+    if after is not None:
+        after(eng, out)
     # final state must equal the oracle-independent sequential kernel's (checked via a second engine)
     eng.close()
     return ref
@@ -297,6 +323,21 @@ def _canon(state):
     return ty, co, rec
 
 
+def _inject(eng, case, envs):
+    """Leave normal play in `envs` through set_state: "drift" moves the ball triple off its closed-form cycle, "grid"
+    puts a foreign object into the map.  Either makes the pipelined kernel flag the launch for the sequential one."""
+    Fd = _fields()
+    ty, co, rec = eng.get_state()
+    for n in envs:
+        if case == "drift":
+            ty[n, 8 * 17 + 7] = 1; co[n, 8 * 17 + 7] = 0; ty[n, 8 * 17 + 10] = 6; co[n, 8 * 17 + 10] = 4
+            rec[n, Fd["OBX"]:Fd["OBX"] + 3] = [8, 9, 10]
+        else:
+            assert case == "grid"
+            ty[n, 3 * 17 + 3] = 2; co[n, 3 * 17 + 3] = 5
+    eng.set_state(ty, co, rec)
+
+
 def test_pipelined_falls_back_on_abnormal_state_and_illegal_actions():
     """Anything outside normal play must come out exactly as the sequential kernel computes it:
     (a) injected drifted balls, (b) env actions 4/5 (AttributeError in the reference), (c) a foreign grid cell."""
@@ -310,14 +351,8 @@ def test_pipelined_falls_back_on_abnormal_state_and_illegal_actions():
         if case == "illegal":
             acts = acts.clone(); acts[3, 5] = 4; acts[7, 50] = 5; policy_idx = False
         for eng in (a, b):
-            ty, co, rec = eng.get_state()
-            if case == "drift":
-                for n in (0, 17, 95):
-                    ty[n, 8 * 17 + 7] = 1; co[n, 8 * 17 + 7] = 0; ty[n, 8 * 17 + 10] = 6; co[n, 8 * 17 + 10] = 4
-                    rec[n, Fd["OBX"]:Fd["OBX"] + 3] = [8, 9, 10]
-            if case == "grid":
-                ty[40, 3 * 17 + 3] = 2; co[40, 3 * 17 + 3] = 5
-            eng.set_state(ty, co, rec)
+            if case != "illegal":
+                _inject(eng, case, (0, 17, 95) if case == "drift" else (40,))
         oa, ob = a.alloc_outputs(T), b.alloc_outputs(T)
         a.rollout(T, oa, actions=acts, policy_idx=policy_idx)
         b.rollout(T, ob, actions=acts, policy_idx=policy_idx)
@@ -337,7 +372,10 @@ def test_pipelined_falls_back_on_abnormal_state_and_illegal_actions():
 @pytest.mark.parametrize("dense,epw", [(False, 0), (False, 1), (False, 4), (True, 0), (True, 1)])
 def test_rollout_4096_vs_oracle(variant, dense, epw):
     """BASELINE config 2: 4096 envs, fused T-step launch, bit-exact obs/matrix/reward/done vs the CPU oracle.
-    Native (16-byte pitched, register-packed path) and dense (generic path) layouts; 1/2/4 envs per wave."""
+    Native (16-byte pitched) and dense layouts; 1/2/4 envs per wave.  The actions come from the in-kernel Philox slot
+    (actions=None), so every case runs the FAST = false instantiation of its E, which picks the register-packed path
+    for native rows and the generic one for dense rows at run time.  The FAST = true instantiations (supplied actions)
+    are in test_engine_instantiations_gpu.py."""
     ref = _compare_rollout(variant, 4096, 200, 17, dense=dense, epw=epw)
     assert ref["truncated"].sum() > 0
 
@@ -360,7 +398,8 @@ def test_native_layout_pad_is_zero():
                                                    (4, 15, 333, 70, 5), (6, 9, 4099, 66, 0)])
 @pytest.mark.parametrize("dense,epw", [(False, 0), (True, 2), (False, 4)])
 def test_rollout_shapes_vs_oracle(variant, view, N, T, env0, dense, epw):
-    """ragged N (not a multiple of 2/4/64), small views, sharded env-id offsets, both layouts"""
+    """ragged N (not a multiple of 2/4/64), small views, sharded env-id offsets, both layouts -- all with actions=None,
+    i.e. in the FAST = false instantiation of each E (its native / dense paths are chosen at run time)."""
     _compare_rollout(variant, N, T, view, env0=env0, dense=dense, epw=epw)
 
 
