@@ -15,6 +15,12 @@
  *                          per lane and round, looks the cell and its four neighbours up in the env's field (a 578-byte
  *                          row that stays in cache) and parks mask and distance in LDS; the two outputs then leave
  *                          through the aligned row store, each as the 16-byte chunks of its own alignment.
+ *   mg_nav_goal_kernel     the same move sets for records that each name their own goal (hindsight records).  A workgroup
+ *                          owns NAV_GOAL_ELEMS consecutive records: it parks (env, goal cell, acting cell) of each in LDS,
+ *                          marks the heads (records whose (env, goal cell) differs from their predecessor's, and the
+ *                          first one), compacts them into a list, and its eight half wavefronts flood one head's goal each
+ *                          -- the field kernel's row masks and step, into a 2 KiB LDS image of their own -- and label the
+ *                          head's run from that image.  No field reaches HBM; the outputs leave as the moves kernel's do.
  *
  * Integer work only, no atomics: the results do not depend on scheduling.
  */
@@ -66,6 +72,53 @@ __device__ __forceinline__ void nav_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Every cell of a 32 x 32 image starts unreachable: the 32 lanes of a half wavefront, then nav_wave_sync().
+__device__ __forceinline__ void nav_image_clear(uint16_t *img, int r)
+{
+    for (int c = r; c < NAV_CELLS / 8; c += 32)
+        reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+}
+
+// The enterable cells of the world row at type + off (state + off) as a bit mask, bit x = cell x (minigrid_nav.h:
+// "Enterable cells", read by its over-read rule); goals = the cells of type 8.
+__device__ __forceinline__ uint32_t nav_open_row(const uint8_t *__restrict__ type, const uint8_t *__restrict__ state,
+                                                 size_t off, int W, uint32_t pass_types, int doors_open, uint32_t &goals)
+{
+    uint32_t open = 0, doors = 0;
+    goals = 0;
+    nav_row_bytes(type + off, W, [&](int x, uint32_t t) {
+        if (t < 16u && ((pass_types >> t) & 1u)) {
+            if (t == NAV_T_DOOR) doors |= 1u << x; else open |= 1u << x;
+        }
+        if (t == NAV_T_GOAL) goals |= 1u << x;
+    });
+    if (doors != 0u && state != nullptr && !doors_open) {
+        uint32_t shut = 0;
+        nav_row_bytes(state + off, W, [&](int x, uint32_t s) { if (s != 0u) shut |= 1u << x; });
+        doors &= ~shut;
+    }
+    return open | doors;
+}
+
+// The flood of one half wavefront's world from the cells in `reached` (lane r holds row r; rows outside the world have
+// open = 0): cells reached in step k get k written into img.  The exit ballot is wavefront-wide, so EVERY lane of the
+// wavefront calls this together; a half with reached = 0 floods nothing.  At most cap steps whatever the input.
+__device__ __forceinline__ void nav_flood(uint16_t *img, int r, int W, int cap, uint32_t open, uint32_t reached)
+{
+    uint32_t fresh = reached;
+    for (int k = 0;; ++k) {
+        for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[r * W + (__ffs(m) - 1)] = (uint16_t)k;
+        if (k >= cap) break;
+        const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
+        uint32_t next = reached | reached << 1 | reached >> 1;
+        if (r > 0) next |= up;
+        if (r < 31) next |= dn;
+        fresh = next & open & ~reached;
+        reached |= fresh;
+        if (__ballot(fresh != 0u) == 0ull) break;                           // wavefront-uniform: both worlds are done
+    }
+}
+
 __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
     int doors_open, const int32_t *__restrict__ goal_x, const int32_t *__restrict__ goal_y, int gstride,
@@ -80,28 +133,11 @@ __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     const bool row = e < N && r < H;                                        // this lane holds a row of the world
     uint16_t *img = image[slot];
 
-    // every cell starts unreachable
-    for (int c = r; c < NAV_CELLS / 8; c += 32)
-        reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    nav_image_clear(img, r);                                                // every cell starts unreachable
     nav_wave_sync();                                                        // before other lanes write steps into it
 
     uint32_t open = 0, goals = 0;
-    if (row) {
-        const size_t off = (size_t)e * HW + (size_t)r * W;
-        uint32_t doors = 0;
-        nav_row_bytes(type + off, W, [&](int x, uint32_t t) {
-            if (t < 16u && ((pass_types >> t) & 1u)) {
-                if (t == NAV_T_DOOR) doors |= 1u << x; else open |= 1u << x;
-            }
-            if (t == NAV_T_GOAL) goals |= 1u << x;
-        });
-        if (doors != 0u && state != nullptr && !doors_open) {
-            uint32_t shut = 0;
-            nav_row_bytes(state + off, W, [&](int x, uint32_t s) { if (s != 0u) shut |= 1u << x; });
-            doors &= ~shut;
-        }
-        open |= doors;
-    }
+    if (row) open = nav_open_row(type, state, (size_t)e * HW + (size_t)r * W, W, pass_types, doors_open, goals);
 
     // sources
     int err = 0;
@@ -117,20 +153,7 @@ __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     const uint32_t sourced = nav_half_ballot(reached != 0u, half);         // every lane votes: err may differ per env
     if (err == 0 && sourced == 0u) err = 1;
 
-    // the flood
-    uint32_t fresh = reached;
-    const int cap = HW;
-    for (int k = 0;; ++k) {
-        for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[r * W + (__ffs(m) - 1)] = (uint16_t)k;
-        if (k >= cap) break;
-        const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
-        uint32_t next = reached | reached << 1 | reached >> 1;
-        if (r > 0) next |= up;
-        if (r < 31) next |= dn;
-        fresh = next & open & ~reached;
-        reached |= fresh;
-        if (__ballot(fresh != 0u) == 0ull) break;                           // wavefront-uniform: both envs are done
-    }
+    nav_flood(img, r, W, HW, open, reached);
     nav_wave_sync();
 
     if (e >= N) return;                                                     // a whole half wavefront at once
@@ -247,6 +270,148 @@ __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_moves_kernel(
                          [&](int64_t q) { return s_dist[(int)(q - bd)]; });
 }
 
+// ------------------------------------------------------------------ optimal-move sets of records with goals of their own
+constexpr int NAV_GOAL_THREADS = 256;
+constexpr int NAV_GOAL_HALVES = NAV_GOAL_THREADS / 32;  // 8 half wavefronts, one flood each at a time
+constexpr int NAV_GOAL_ELEMS = 1024;                    // records per workgroup: 500 k records are 490 workgroups
+constexpr int NAV_GOAL_SLOTS = NAV_GOAL_ELEMS + 16;     // both outputs' chunks lie within [ELEMS * b - 15, ELEMS * (b + 1))
+constexpr int NAV_GOAL_ROUNDS = (NAV_GOAL_SLOTS + NAV_GOAL_THREADS - 1) / NAV_GOAL_THREADS;
+constexpr uint16_t NAV_NO_CELL = 0xFFFF;
+static_assert(NAV_GOAL_ELEMS % 16 == 0, "whole chunks of both outputs");
+static_assert(NAV_GOAL_SLOTS <= 0xFFFF, "slots are listed as uint16");
+
+__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
+    const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos, const int32_t *__restrict__ age,
+    const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
+    __shared__ __attribute__((aligned(16))) uint8_t s_moves[NAV_GOAL_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint16_t s_dist[NAV_GOAL_ELEMS];
+    __shared__ int32_t s_env[NAV_GOAL_SLOTS];           // the key of a record: its env, -1 for a record without a result,
+    __shared__ uint16_t s_goal[NAV_GOAL_SLOTS];         //   and its goal cell
+    __shared__ uint16_t s_cell[NAV_GOAL_SLOTS];         // its acting cell, NAV_NO_CELL where the position is none
+    __shared__ uint16_t s_head[NAV_GOAL_SLOTS + 1];     // the slots of the heads in ascending order, then the end slot
+    __shared__ int s_count[NAV_GOAL_ROUNDS][NAV_GOAL_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, half = tid >> 5;
+    const int64_t b = blockIdx.x;
+    // this workgroup's chunks of either output and the records they hold, as in mg_nav_moves_kernel
+    const int sm = mg_row_misalign(moves, 16), sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
+    const mg_row_span_t<int64_t> km = mg_row_span<int64_t>(sm, M, b, NAV_GOAL_ELEMS / 16, 16);
+    const mg_row_span_t<int64_t> kd = mg_row_span<int64_t>(sd, M, b, NAV_GOAL_ELEMS / 8, 8);
+    const int64_t bm = 16 * km.c0 - sm, bd = 8 * kd.c0 - sd;               // record of LDS slot 0 of either image
+    const bool has_m = km.c0 < km.c1, has_d = acting_dist != nullptr && kd.c0 < kd.c1;
+    const int64_t p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;                    // record of slot 0 of the key arrays
+    int64_t lo = 0, hi = 0;                                                 // the records of this workgroup: both spans
+    if (has_m) { lo = km.p_lo; hi = km.p_hi; }
+    if (has_d) { lo = has_m && lo < kd.p_lo ? lo : kd.p_lo; hi = has_m && hi > kd.p_hi ? hi : kd.p_hi; }
+    // 0 < slot_lo <= slot_hi <= SLOTS; a workgroup that holds neither span (the last one may) has no slots: both 0
+    const int slot_lo = has_m || has_d ? (int)(lo - p0) : 0, slot_hi = has_m || has_d ? (int)(hi - p0) : 0;
+    const int HW = W * H;
+    float2 init = make_float2(0.f, 0.f);
+    if (age != nullptr) init = make_float2(init_pos[0], init_pos[1]);
+
+    // keys and acting cells: every global read of a record happens here, one record per lane and round
+#pragma unroll 1
+    for (int k = 0; k < NAV_GOAL_ROUNDS; ++k) {
+        const int i = k * NAV_GOAL_THREADS + tid;
+        if (i < slot_lo || i >= slot_hi) continue;
+        const int64_t p = p0 + i;
+        const int t = rec_t[p], n = rec_n[p];
+        const int gc = visit_cell(rec_goal[2 * p], rec_goal[2 * p + 1], W, H);   // (y, x); 4-byte aligned: two loads
+        int env = -1, ac = NAV_NO_CELL;
+        if (t >= 0 && t < T && n >= 0 && n < N && gc < HW) {
+            const int64_t at = (int64_t)t * N + n;
+            float2 q = pos[at];
+            if (age != nullptr && age[at] <= 0) q = init;
+            const int c = visit_cell(q.x, q.y, W, H);
+            env = n;
+            if (c < HW) ac = c;
+        }
+        s_env[i] = env;
+        s_goal[i] = (uint16_t)gc;
+        s_cell[i] = (uint16_t)ac;
+    }
+    __syncthreads();
+
+    // heads, counted per wavefront and round (the round's ballot stays in registers), then listed in ascending order
+    unsigned long long heads[NAV_GOAL_ROUNDS];
+#pragma unroll
+    for (int k = 0; k < NAV_GOAL_ROUNDS; ++k) {
+        const int i = k * NAV_GOAL_THREADS + tid;
+        const bool hd = i >= slot_lo && i < slot_hi &&
+                        (i == slot_lo || s_env[i] != s_env[i - 1] || s_goal[i] != s_goal[i - 1]);
+        heads[k] = __ballot(hd);
+        if (lane == 0) s_count[k][wave] = __popcll(heads[k]);
+    }
+    __syncthreads();
+    int n_heads = 0;
+#pragma unroll
+    for (int k = 0; k < NAV_GOAL_ROUNDS; ++k) {
+        const int i = k * NAV_GOAL_THREADS + tid;
+        const unsigned long long hb = heads[k];
+        const bool hd = (hb >> lane) & 1ull;
+        int before = n_heads;
+        for (int w = 0; w < NAV_GOAL_THREADS / 64; ++w) {
+            const int cnt = s_count[k][w];
+            if (w < wave) before += cnt;
+            n_heads += cnt;
+        }
+        if (hd) s_head[before + __popcll(hb & ((1ull << lane) - 1ull))] = (uint16_t)i;
+    }
+    if (tid == 0) s_head[n_heads] = (uint16_t)slot_hi;
+    __syncthreads();
+
+    // one head per half wavefront and round: flood its goal, label its run.  Both halves of a wavefront go round together.
+    uint16_t *img = image[half];
+    const int per = (n_heads + NAV_GOAL_HALVES - 1) / NAV_GOAL_HALVES;
+    const int j_end = (half + 1) * per < n_heads ? (half + 1) * per : n_heads;
+    int cur_env = -1;
+    uint32_t open = 0;
+#pragma unroll 1
+    for (int it = 0; it < per; ++it) {
+        const int j = half * per + it;
+        const bool mine = j < j_end;
+        const int s0 = mine ? s_head[j] : 0, s1 = mine ? s_head[j + 1] : 0;
+        const int env = mine ? s_env[s0] : -1;
+        uint32_t reached = 0;
+        if (env >= 0) {
+            if (env != cur_env) {                                           // the previous head's world stays in `open`
+                uint32_t goals;
+                open = r < H ? nav_open_row(type, state, (size_t)env * HW + (size_t)r * W, W, pass_types, doors_open, goals)
+                             : 0u;
+                cur_env = env;
+            }
+            const int gc = s_goal[s0], gy = gc / W;
+            if (r == gy) reached = (1u << (gc - gy * W)) & open;
+            nav_image_clear(img, r);
+        }
+        nav_wave_sync();                                                    // before other lanes write steps into it
+        nav_flood(img, r, W, HW, env >= 0 ? open : 0u, reached);
+        nav_wave_sync();
+        for (int i = s0 + r; i < s1; i += 32) {
+            const int c = s_cell[i];
+            uint32_t d = MG_NAV_UNREACHABLE, m = 0;
+            if (env >= 0 && c != NAV_NO_CELL) m = nav_move_set(img, c, W, H, d);
+            const int64_t p = p0 + i;
+            if (has_m && p >= km.p_lo && p < km.p_hi) s_moves[(int)(p - bm)] = (uint8_t)m;
+            if (has_d && p >= kd.p_lo && p < kd.p_hi) s_dist[(int)(p - bd)] = (uint16_t)d;
+        }
+        nav_wave_sync();                                                    // the labels are read before the image is reset
+    }
+    __syncthreads();
+
+    for (int64_t c = km.c0 + tid; c < km.c1; c += NAV_GOAL_THREADS)
+        mg_row_store(moves, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_moves + (int)(p - bm)); },
+                     [&](int64_t q) { return s_moves[(int)(q - bm)]; });
+    if (acting_dist != nullptr)
+        for (int64_t c = kd.c0 + tid; c < kd.c1; c += NAV_GOAL_THREADS)
+            mg_row_store(acting_dist, M, c,
+                         [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_dist + (int)(p - bd)); },
+                         [&](int64_t q) { return s_dist[(int)(q - bd)]; });
+}
+
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
 
 }  // namespace
@@ -303,5 +468,26 @@ extern "C" int mg_nav_optimal_moves(const uint16_t *dist, int64_t dist_pitch, in
     hipLaunchKernelGGL(mg_nav_moves_kernel, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
                        dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
                        reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_goal_moves(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                 uint32_t pass_types, int flags, const int32_t *rec_t, const int32_t *rec_n,
+                                 const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
+                                 const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream)
+{
+    if (!type || !rec_t || !rec_n || !rec_goal || !pos || !moves) return TW_E_ARG;
+    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
+    if (((uintptr_t)pos & 7u) || ((uintptr_t)acting_dist & 1u)) return TW_E_ARG;
+    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
+    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (n_records == 0) return TW_OK;
+    // chunks are counted from the aligned address below either output: up to 15 records more than n_records
+    hipLaunchKernelGGL(mg_nav_goal_kernel, dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)),
+                       dim3(NAV_GOAL_THREADS), 0, (hipStream_t)stream, type, state, n_envs, width, height, pass_types,
+                       flags & MG_NAV_DOORS_OPEN, rec_t, rec_n, rec_goal, n_records,
+                       reinterpret_cast<const float2 *>(pos), age, init_pos, T, moves, acting_dist);
     return tw_launched(__func__);
 }

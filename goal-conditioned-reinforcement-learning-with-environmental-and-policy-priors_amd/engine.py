@@ -388,6 +388,18 @@ class TwoarmyEngine:
                                   agent=ag[:2] if agent else None, out=out, want_field=want_field,
                                   agent_out=agent_out, error_out=error_out)
 
+    def goal_moves(self, her, pos, age=None, init_pos=None, pass_types=None, out=None, dist_out=None):
+        """Optimal-move sets of hindsight records under their own goals in the engine's worlds as they stand
+        (minigrid_nav.goal_moves, one launch, read from the engine's own planes) -> (moves uint8[R], acting_dist
+        uint16[R]).  her: the records of ppo_ops.her_relabel (its "t", "n" and "goal"); pos float32[T, N, 2] BEFORE each
+        step, age int32[T, N] and init_pos float32[2] as minigrid_nav.optimal_moves takes them; pass_types as in
+        distance_field."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        return nav.goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17,
+                              nav.PASS_DEFAULT if pass_types is None else pass_types, age=age, init_pos=init_pos, out=out,
+                              dist_out=dist_out)
+
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""
         ms = C.c_float()

@@ -1,7 +1,8 @@
 """Torch front end of the shortest-path kernels (include/minigrid_nav.h, csrc/minigrid_nav.hip): how many moves every cell
 of N grid worlds lies from the goal, and which of mg_step's four moves an agent on a shortest path makes next.  World planes
 are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are int32[N] tensors, dense or the column views
-of the engine's records (TwoarmyEngine.agent_views()), read where they live.  One launch per call, on the tensors' device.
+of the engine's records (TwoarmyEngine.agent_views()), read where they live.  goal_moves labels records that each name a
+goal of their own (hindsight records) without a field in memory.  One launch per call, on the tensors' device.
 No CPU fallback."""
 import torch
 
@@ -109,6 +110,44 @@ def optimal_moves(dist, pos, width, height, age=None, init_pos=None, out=None, d
     assert dist_out is None or (dist_out.shape == (T, N) and dist_out.device == dev)
     call("mg_nav_optimal_moves", dev, dp, dpitch, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
          ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+def goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, pass_types=PASS_DEFAULT, age=None, init_pos=None,
+               state=None, doors_open=False, out=None, dist_out=None):
+    """The set of optimal moves of records that each name their own goal (mg_nav_goal_moves, include/minigrid_nav.h):
+    type_plane (state) uint8[N, H*W] as distance_field takes them; rec_t, rec_n int32[R] and rec_goal float32[R, 2] =
+    (y, x), the t, n and goal of ppo_ops.her_relabel's records; pos float32[T, N, 2], age int32[T, N] and init_pos
+    float32[2] as optimal_moves takes them.  -> (moves uint8[R], acting_dist uint16[R]): per record what optimal_moves
+    gives in the field of the record's env flooded from the record's goal cell; 0 / UNREACHABLE for a record whose t,
+    n, goal or acting position names nothing.  out / dist_out: tensors to write into; dist_out=False: no distances
+    (None is returned for them).  One launch (none for R = 0), no host synchronisation."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state is None or state.shape == (N, W * H)
+    dev = type_plane.device
+    R = rec_t.shape[0]
+    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
+    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
+    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
+    T = pos.shape[0]
+    assert (age is None) == (init_pos is None), "age and init_pos come together"
+    if age is not None:
+        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    if out is None:
+        out = torch.empty((R,), dtype=torch.uint8, device=dev)
+    assert out.shape == (R,) and out.device == dev
+    if dist_out is None:
+        dist_out = torch.empty((R,), dtype=DIST_DTYPE, device=dev)
+    elif dist_out is False:
+        dist_out = None
+    assert dist_out is None or (dist_out.shape == (R,) and dist_out.device == dev)
+    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, dist_out
+    call("mg_nav_goal_moves", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
+         DOORS_OPEN if doors_open else 0, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32),
+         R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, ptr(out, torch.uint8),
+         ptr(dist_out, DIST_DTYPE))
     return out, dist_out
 
 

@@ -100,6 +100,8 @@ class VecPPOTrainer:
         self._nav_field_at = -1               # env_steps when nav_field was last computed: one field per rollout
         self.prior = None                     # shortest-path prior: {"coef", "decay", "updates"}, made by enable_prior()
         self.expert_moves = self.expert_dist = self.act_probs = None   # made by enable_prior() / label_expert()
+        self.her_moves = self.her_dist = None # labels of the hindsight records (enable_prior(hindsight=True)) ...
+        self._her_moves_of = None             # ... and the records (the dict relabel() made) they belong to
         self.bonus = None                     # BonusTracker, made by enable_bonus()
         self.reward_train = self.reward       # what targets and hindsight records use: the shaped reward when a bonus is on
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
@@ -358,6 +360,9 @@ class VecPPOTrainer:
         prior_coef = 0.0 if self.prior is None else self.prior_coef()
         if prior_coef != 0.0 and self._moves_at != self.env_steps:
             raise RuntimeError("enable_prior(): call label_expert() after collect() and before update()")
+        her_prior = prior_coef != 0.0 and self.prior["hindsight"] and self.her is not None and self.her["t"].numel() > 0
+        if her_prior and self._her_moves_of is not self.her:
+            raise RuntimeError("enable_prior(hindsight=True): call label_expert() after relabel() and before update()")
         t_begin = time.perf_counter() if self.time_phases else 0.0
         adv, target = self.compute_targets()
         if self.time_phases:
@@ -377,9 +382,12 @@ class VecPPOTrainer:
         smp_moves = None
         if prior_coef != 0.0:
             from .. import minigrid_nav as nav
-            # hindsight records get mask 0: their goal is not the field's source
+            # hindsight records get mask 0 (their goal is not the field's source) unless they were labelled under
+            # their own goals: enable_prior(hindsight=True)
             smp_moves = torch.zeros(total, dtype=torch.uint8, device=self.device)
             smp_moves[:T * N] = nav.to_policy_mask(self.expert_moves, self.act_probs.shape[-1]).view(-1)
+            if her_prior:
+                smp_moves[T * N:] = nav.to_policy_mask(self.her_moves, self.act_probs.shape[-1])
         ag.actor.train(); ag.critic.train()
         la = lv = None
         local_steps = n_steps = -(-total // self.minibatch)
@@ -549,16 +557,19 @@ class VecPPOTrainer:
                 "mean": v[4] / v[3] if v[3] else None, "cut_off": v[5]}
 
     # ------------------------------------------------------------------ shortest-path prior
-    def enable_prior(self, coef, decay=1.0):
+    def enable_prior(self, coef, decay=1.0, hindsight=False):
         """Train the actor with the shortest-path prior: update() adds coef * decay^(updates done) times the set-valued
         imitation term (ppo_ops.prior_loss) over the optimal-move sets label_expert() makes to the actor's loss of every
         minibatch.  Rewards, returns, targets, advantages, the critic, the running score and the HER switch are
         untouched (this is no reward shaping).  coef = 0: label and report only, no loss launch.  From here on the
-        rollout also keeps its acting distributions (T x N x 5 floats) for prior_stats()."""
+        rollout also keeps its acting distributions (T x N x 5 floats) for prior_stats().  hindsight=True: the
+        hindsight records of relabel() are labelled too, each under its own goal (one mg_nav_goal_moves launch in
+        label_expert()), and enter the term with those labels instead of an empty mask."""
         import inspect
         if "probs_out" not in inspect.signature(self.agent.act_batch).parameters or self.cache_predictions:
             raise ValueError("the shortest-path prior needs the plain PPO agent's act_batch")
-        self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0}
+        self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0, "hindsight": bool(hindsight)}
+        self.her_moves = self.her_dist = self._her_moves_of = None
         self.act_probs = torch.zeros((self.T, self.N, 5), dtype=torch.float32, device=self.device)
         self._moves_at = -1
         self._graph = None                    # a captured rollout does not write act_probs
@@ -573,7 +584,10 @@ class VecPPOTrainer:
         carry_over()): the static-map field exactly as account_distance() takes it (reused if that already ran for this
         rollout) and ONE mg_nav_optimal_moves launch over the positions before each step, episode starts at the reset
         position; `expert_moves` uint8[T, N] (bits: left, right, up, down, stay) and `expert_dist` uint16[T, N]
-        afterwards.  No host synchronisation."""
+        afterwards.  With enable_prior(hindsight=True) and records from relabel() (call it first): ONE
+        mg_nav_goal_moves launch more labels every hindsight record under its own goal, on the engine's planes as they
+        stand and the same static map; `her_moves` uint8[R] and `her_dist` uint16[R] afterwards.  No host
+        synchronisation."""
         from .. import minigrid_nav as nav
         T, N = self.T, self.N
         self._static_field(reuse=True)
@@ -583,13 +597,21 @@ class VecPPOTrainer:
         nav.optimal_moves(self.nav_field, self.pos[3:3 + T], 17, 17, age=self.age[:-1], init_pos=self.init_pos,
                           out=self.expert_moves, dist_out=self.expert_dist)
         self._moves_at = self.env_steps
+        self.her_moves = self.her_dist = self._her_moves_of = None
+        if self.prior is not None and self.prior["hindsight"] and self.her is not None and self.her["t"].numel():
+            self.her_moves, self.her_dist = self.engine.goal_moves(
+                self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL)
+            self._her_moves_of = self.her                     # these labels belong to these records
         return self.expert_moves
 
     def prior_stats(self):
         """How the policy that ACTED in the last labelled rollout stands to the expert: {"agree": share of the labelled
         steps whose taken action is an optimal move, "opt_mass": mean probability it put on the optimal moves,
-        "labelled": steps with a non-empty move set, "coef": the coefficient of the next update()}; None where nothing
-        is labelled.  One device-to-host copy."""
+        "labelled": steps with a non-empty move set, "coef": the coefficient of the next update(), "her_labelled":
+        hindsight records with a non-empty move set under their own goal, "her_agree": the share of those whose TAKEN
+        action is an optimal move towards that goal -- how direct the relabelled trajectories are; no opt_mass for them:
+        the acting distribution was conditioned on the other goal}; None where nothing is labelled (the two her_ fields:
+        without labelled records).  One device-to-host copy."""
         if self.prior is None or self.expert_moves is None:
             raise RuntimeError("prior_stats() before enable_prior() and label_expert()")
         from .. import minigrid_nav as nav
@@ -600,10 +622,17 @@ class VecPPOTrainer:
         bits = ((mask.unsqueeze(-1) >> torch.arange(A, device=self.device, dtype=torch.int32)) & 1).double()
         p = self.act_probs.double()
         mass = (p * bits).sum(-1) / p.sum(-1)
-        v = torch.stack([lab.sum().double(), (hit & lab).sum().double(), torch.where(lab, mass, 0.0).sum()]).cpu().tolist()
-        n = int(v[0])
+        sums = [lab.sum().double(), (hit & lab).sum().double(), torch.where(lab, mass, 0.0).sum()]
+        her = self.her_moves is not None and self._her_moves_of is self.her
+        if her:
+            h = self.her
+            hmask = nav.to_policy_mask(self.her_moves, A).to(torch.int32)
+            hact = self.action.view(-1)[h["t"].long() * self.N + h["n"].long()]
+            sums += [(hmask != 0).sum().double(), (((hmask >> hact) & 1) != 0).sum().double()]
+        v = torch.stack(sums).cpu().tolist()
+        n, hn = int(v[0]), int(v[3]) if her else 0
         return {"agree": v[1] / n if n else None, "opt_mass": v[2] / n if n else None, "labelled": n,
-                "coef": self.prior_coef()}
+                "coef": self.prior_coef(), "her_labelled": hn if her else None, "her_agree": v[4] / hn if hn else None}
 
     def stats(self):
         done = (self.term | self.trunc) != 0

@@ -15,6 +15,8 @@ rollout to the log line: one field and one lookup launch per rollout (minigrid_n
 --prior_coef C [--prior_decay D] trains the actor with the shortest-path prior: C * D^update times the set-valued
 imitation loss over the optimal moves of every acting state (one label launch per rollout, one loss launch pair per
 minibatch); --expert_agreement only labels and reports.  Both append `expert agree` / `opt_mass` to the log line; off by default.
+--prior_hindsight (with either) also labels the hindsight records, each under its own goal (one more launch per rollout),
+trains on those labels too and appends `her agree`; off by default.
 """
 import argparse
 import os
@@ -108,14 +110,22 @@ def build_parser():
                    help="label every rollout with the optimal moves and append `expert agree` (share of the taken actions "
                         "that are optimal) and `opt_mass` (the acting policy's mean mass on the optimal moves) to the log "
                         "line, without training on them; implied by --prior_coef")
+    p.add_argument("--prior_hindsight", action="store_true",
+                   help="with --prior_coef / --expert_agreement: label the hindsight records too, each under its own goal "
+                        "(one more launch per rollout), let them enter the prior term with those labels instead of none, "
+                        "and append `her agree` (share of the labelled records whose taken action is an optimal move "
+                        "towards the hindsight goal) to the log line")
     return p
 
 
-def prior_fields(ps):
-    """Tail of the log line with --prior_coef / --expert_agreement (VecPPOTrainer.prior_stats())."""
-    if not ps["labelled"]:
-        return " expert agree - opt_mass -"
-    return " expert agree %.3f opt_mass %.3f" % (ps["agree"], ps["opt_mass"])
+def prior_fields(ps, hindsight=False):
+    """Tail of the log line with --prior_coef / --expert_agreement (VecPPOTrainer.prior_stats()); hindsight: with
+    --prior_hindsight."""
+    tail = " expert agree %.3f opt_mass %.3f" % (ps["agree"], ps["opt_mass"]) if ps["labelled"] else \
+        " expert agree - opt_mass -"
+    if hindsight:
+        tail += " her agree %.3f" % ps["her_agree"] if ps["her_labelled"] else " her agree -"
+    return tail
 
 
 def distance_fields(ds):
@@ -180,6 +190,8 @@ def dump_track(trainer, path, update, k):
 
 def main(argv=None, predictor=False, soa=False):
     args = build_parser().parse_args(argv)
+    if args.prior_hindsight and not (args.prior_coef != 0.0 or args.expert_agreement):
+        raise SystemExit("--prior_hindsight needs --prior_coef or --expert_agreement")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -239,7 +251,7 @@ def main(argv=None, predictor=False, soa=False):
     if use_prior:
         if predictor or soa:
             raise SystemExit("--prior_coef / --expert_agreement: plain PPO agent only")
-        trainer.enable_prior(args.prior_coef, args.prior_decay)
+        trainer.enable_prior(args.prior_coef, args.prior_decay, hindsight=args.prior_hindsight)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
@@ -290,7 +302,7 @@ def main(argv=None, predictor=False, soa=False):
         if args.goal_distance:                                  # behind every other field
             tail += distance_fields(trainer.distance_stats())
         if use_prior:                                           # behind every other field
-            tail += prior_fields(ps)
+            tail += prior_fields(ps, args.prior_hindsight)
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

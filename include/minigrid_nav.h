@@ -104,6 +104,42 @@ int mg_nav_optimal_moves(const uint16_t *dist, int64_t dist_pitch, int n_envs, i
                          const int32_t *age, const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist,
                          void *stream);
 
+/* The same move sets for records that each name their OWN goal (hindsight records): one launch floods the goal of every
+ * run of records on the device and labels the run, and no field reaches memory.
+ *   rec_t, rec_n  int32[n_records]: the step and the env of a record;  rec_goal float[n_records][2] = (y, x): its goal
+ *                 -- the t, n and goal arrays ppo_her_relabel writes (twoarmy_ppo.h)
+ *   pos, age, init_pos, T: exactly as in mg_nav_optimal_moves (pos BEFORE step t; the acting position of record b is
+ *                 age[t][n] <= 0 ? init_pos : pos[t][n] with t = rec_t[b], n = rec_n[b])
+ *   type, state, n_envs, width, height, pass_types, flags: the world, its moves and its enterable cells exactly as in
+ *                 mg_nav_field (state nullable)
+ * The goal cell and the acting cell come from the rule of the visit counters (visit_cell, csrc/visit_cell.h).  Per
+ * record: the result of record b depends on record b alone, never on its neighbours, the order of the records or how
+ * they are grouped.  Let F be the field mg_nav_field computes for env rec_n[b] with the goal cell as its single source;
+ * moves[b] and acting_dist[b] are what mg_nav_optimal_moves gives for the acting cell in F: bits 0..3 set iff that
+ * neighbour lies inside the world and one move nearer, bit MG_NAV_MOVE_STAY_BIT alone at distance 0, the value 0 where
+ * the acting cell is unreachable.
+ * moves[b] = 0 and acting_dist[b] = MG_NAV_UNREACHABLE when rec_t[b] is outside [0, T), rec_n[b] is outside
+ * [0, n_envs), the goal is no cell (NaN, +-inf, outside the world), the goal cell is not enterable, or the acting
+ * position is no cell.  No such record addresses any memory outside its arrays.
+ *   moves uint8[n_records];  acting_dist uint16[n_records] (nullable)
+ * Invariant: for records that share one goal per env the outputs equal mg_nav_field(goal_x, goal_y) followed by
+ * mg_nav_optimal_moves on the same positions.
+ * One launch, no atomics; n_records == 0 returns 0 and launches nothing.  A workgroup owns 1024 consecutive records and
+ * floods once per run of equal (env, goal cell) among them, so records sorted into such runs (ppo_her_relabel's
+ * emission order) cost the fewest floods; the results do not depend on it.
+ * Reads: the planes by the over-read rule above (the aligned words that hold the first and the last byte of a world
+ * row are read whole).  Writes: both outputs leave as aligned 16-byte stores, element by element only in the first and
+ * last chunk of a workgroup's share (csrc/row_store.h); moves needs no alignment, and nothing outside the first
+ * n_records elements of either output is written.
+ * TW_E_ARG: NULL type / rec_t / rec_n / rec_goal / pos / moves, n_envs <= 0, a side <= 0 or > MG_NAV_MAX_SIDE,
+ * pass_types > 0xFFFF, flags other than MG_NAV_DOORS_OPEN, pos not 8-byte aligned, rec_t, rec_n, rec_goal, age or
+ * init_pos not 4-byte aligned, acting_dist not 2-byte aligned, age without init_pos, T < 0, n_records < 0,
+ * n_records >= 2^40. */
+int mg_nav_goal_moves(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                      uint32_t pass_types, int flags, const int32_t *rec_t, const int32_t *rec_n,
+                      const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
+                      const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

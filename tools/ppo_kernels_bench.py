@@ -86,6 +86,35 @@ ad_out = torch.empty((T, N), dtype=torch.uint16, device=dev)
 report("mg_nav_optimal_moves (4096 x 128, moves + acting_dist)", T * N * (8 + 4 + 1 + 2) + N * 578,
        timed(lambda: nav.optimal_moves(nav_dist, pos_b, 17, 17, age=age_tn, init_pos=init_yx, out=mv_out, dist_out=ad_out)),
        "one launch")
+# The same labels for hindsight records under their own goals: the records of a REAL relabelled 4096 x 128 rollout (an
+# untrained policy on v6), labelled on the engine's planes.  The flood work scales with the heads -- records whose (env,
+# goal cell) differs from their predecessor's, plus the first of every 1024 -- not with the bytes; the row above is the
+# yardstick.  A record, no threshold.  The head count below is the one at 16-byte aligned outputs (torch allocations: a
+# workgroup's share then starts at a multiple of 1024) and for goals inside the world (relabelled goals are visited
+# positions, so truncation is the kernel's cell rule).
+from twoarmy_amd.engine import TwoarmyEngine  # noqa: E402
+from twoarmy_amd.soa.agent.PPO import PPO  # noqa: E402
+from twoarmy_amd.soa.ppo_vec import VecPPOTrainer  # noqa: E402
+torch.manual_seed(0)
+h_eng = TwoarmyEngine(6, N, 17, device=dev, seed=9981)
+h_tr = VecPPOTrainer(PPO().to(dev).use_nhwc(), h_eng, rollout_steps=T, minibatch=B)
+h_tr.collect()
+her = h_tr.relabel()
+R = int(her["t"].numel())
+h_cell = her["goal"][:, 0].long() * 17 + her["goal"][:, 1].long()
+h_head = torch.ones(R, dtype=torch.bool, device=dev)
+h_head[1:] = (her["n"][1:] != her["n"][:-1]) | (h_cell[1:] != h_cell[:-1])
+h_head[::1024] = True
+n_heads = int(h_head.sum())
+hm_out, hd_out = torch.empty(R, dtype=torch.uint8, device=dev), torch.empty(R, dtype=torch.uint16, device=dev)
+h_pos, h_age = h_tr.pos[3:3 + T], h_tr.age[:-1]
+h_s = timed(lambda: h_eng.goal_moves(her, h_pos, h_age, h_tr.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
+                                     out=hm_out, dist_out=hd_out))
+report("mg_nav_goal_moves (%d hindsight records of a 4096 x 128 rollout, %d heads)" % (R, n_heads),
+       R * (4 + 4 + 8 + 8 + 4 + 1 + 2) + N * 289, h_s,
+       "one launch; %d records, %d heads, %.1f floods per us" % (R, n_heads, n_heads / (h_s * 1e6)))
+h_eng.close()
+del h_tr, h_eng, her
 mv_flat = torch.randint(0, 32, (T * N,), generator=g, dtype=torch.uint8).to(dev)
 report("ppo_prior_loss_fwd_bwd (524288 x 5)", T * N * (A * 4 + 1) * 2 + T * N * A * 4,
        timed(lambda: ppo_ops.prior_loss(probs, mv_flat, 0.1)), "two launches, probs and moves read twice; includes 5 allocations")
