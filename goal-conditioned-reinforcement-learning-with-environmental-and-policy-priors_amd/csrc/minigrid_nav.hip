@@ -21,6 +21,13 @@
  *                          first one), compacts them into a list, and its eight half wavefronts flood one head's goal each
  *                          -- the field kernel's row masks and step, into a 2 KiB LDS image of their own -- and label the
  *                          head's run from that image.  No field reaches HBM; the outputs leave as the moves kernel's do.
+ *   mg_nav_timed_field_kernel<P>  the flood over (cell, phase) of a world whose blockers move with period P: the lane of a
+ *                          row holds `free` and `reached` of all P phases in registers (P is a template parameter, every
+ *                          phase loop is unrolled), a round is reached[p] |= dilate(reached[p + 1 mod P]) & free[p] with
+ *                          dilate = the field kernel's step plus the row itself (waiting), all phases from the masks of
+ *                          the round before; one ballot per round decides "nothing new in any phase".  The image is
+ *                          P * W*H distances per env in dynamic LDS, and the envs per workgroup (8, 4 or 2) follow from it.
+ *                          The moves kernel serves the timed fields too (TIMED: the phase comes from the element's age).
  *
  * Integer work only, no atomics: the results do not depend on scheduling.
  */
@@ -210,7 +217,11 @@ constexpr int NAV_MOVES_ROUNDS = (NAV_MOVES_ELEMS + 16 + NAV_MOVES_THREADS - 1) 
 static_assert(NAV_MOVES_ELEMS % 16 == 0, "whole chunks of both outputs");
 
 // The optimal moves on cell c of a field row (minigrid_nav.h): bit k = neighbour k lies one move nearer; 0x10 on a source.
-__device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ row, int c, int W, int H, uint32_t &d)
+// `next` is the row the move arrives in: `row` itself for a static field, the next phase's for a timed one, where staying
+// on c may be a move nearer too (WAIT: the stay bit then joins the others).
+template <bool WAIT = false>
+__device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ row, const uint16_t *__restrict__ next, int c,
+                                                 int W, int H, uint32_t &d)
 {
     d = row[c];
     if (d == 0u) return 0x10u;
@@ -218,15 +229,20 @@ __device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ ro
     const int y = c / W, x = c - y * W;
     const uint32_t want = d - 1u;
     uint32_t m = 0;
-    if (x > 0 && row[c - 1] == want) m |= 1u;
-    if (x < W - 1 && row[c + 1] == want) m |= 2u;
-    if (y > 0 && row[c - W] == want) m |= 4u;
-    if (y < H - 1 && row[c + W] == want) m |= 8u;
+    if (x > 0 && next[c - 1] == want) m |= 1u;
+    if (x < W - 1 && next[c + 1] == want) m |= 2u;
+    if (y > 0 && next[c - W] == want) m |= 4u;
+    if (y < H - 1 && next[c + W] == want) m |= 8u;
+    if (WAIT && next[c] == want) m |= 0x10u;
     return m;
 }
 
-__global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_moves_kernel(
-    const uint16_t *__restrict__ dist, int64_t pitch, int N, int W, int H, const float2 *__restrict__ pos,
+// The phase of a clock value (minigrid_nav.h): 0 up to the episode's first step, the clock mod P after it.
+__device__ __forceinline__ int nav_phase(int clock, int P) { return clock <= 0 ? 0 : clock % P; }
+
+// TIMED: dist holds P fields per env, age is given and is the clock of the element (mg_nav_timed_moves).
+template <bool TIMED> __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_moves_kernel(
+    const uint16_t *__restrict__ dist, int64_t pitch, int P, int N, int W, int H, const float2 *__restrict__ pos,
     const int32_t *__restrict__ age, const float *__restrict__ init_pos, int64_t M, uint8_t *__restrict__ moves,
     uint16_t *__restrict__ acting_dist)
 {
@@ -251,10 +267,18 @@ __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_moves_kernel(
         const bool in_d = acting_dist != nullptr && p >= kd.p_lo && p < kd.p_hi;
         if (!(in_m || in_d)) continue;                                      // both spans lie inside [0, M)
         float2 q = pos[p];
-        if (age != nullptr && age[p] <= 0) q = init;
+        const int clock = age != nullptr ? age[p] : 1;
+        if (clock <= 0) q = init;
         const int c = visit_cell(q.x, q.y, W, H);
         uint32_t d = MG_NAV_UNREACHABLE, m = 0;
-        if (c < HW) m = nav_move_set(dist + (int64_t)(p % N) * pitch, c, W, H, d);
+        if (TIMED) {
+            const int ph = nav_phase(clock, P);
+            const uint16_t *f = dist + (int64_t)(p % N) * P * pitch;
+            if (c < HW) m = nav_move_set<true>(f + ph * pitch, f + (ph + 1 == P ? 0 : ph + 1) * pitch, c, W, H, d);
+        } else if (c < HW) {
+            const uint16_t *f = dist + (int64_t)(p % N) * pitch;
+            m = nav_move_set(f, f, c, W, H, d);
+        }
         if (in_m) s_moves[(int)(p - bm)] = (uint8_t)m;
         if (in_d) s_dist[(int)(p - bd)] = (uint16_t)d;
     }
@@ -393,7 +417,7 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
         for (int i = s0 + r; i < s1; i += 32) {
             const int c = s_cell[i];
             uint32_t d = MG_NAV_UNREACHABLE, m = 0;
-            if (env >= 0 && c != NAV_NO_CELL) m = nav_move_set(img, c, W, H, d);
+            if (env >= 0 && c != NAV_NO_CELL) m = nav_move_set(img, img, c, W, H, d);
             const int64_t p = p0 + i;
             if (has_m && p >= km.p_lo && p < km.p_hi) s_moves[(int)(p - bm)] = (uint8_t)m;
             if (has_d && p >= kd.p_lo && p < kd.p_hi) s_dist[(int)(p - bd)] = (uint16_t)d;
@@ -411,6 +435,139 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
                          [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_dist + (int)(p - bd)); },
                          [&](int64_t q) { return s_dist[(int)(q - bd)]; });
 }
+
+// ------------------------------------------------------------------ time-expanded fields: blockers that move with period P
+constexpr int NAV_MAX_PERIOD = MG_NAV_MAX_PERIOD;
+constexpr int NAV_TIMED_LDS = 48 * 1024;               // the image of a workgroup where 4 or 8 envs share one: 3 fit on a CU
+// uint16 elements of one phase's image: whole 16-byte chunks, so that every env's images start on one
+__host__ __device__ inline int nav_timed_cells(int HW) { return (HW + 7) & ~7; }
+// Envs of a workgroup: 8 as in the field kernel while their images fit NAV_TIMED_LDS, else 4, else 2 (one wavefront; at
+// P = 16 and 32 x 32 cells that is 64 KiB, the most a launch asks for).
+inline int nav_timed_envs(int HW, int P)
+{
+    int envs = NAV_ENVS;
+    while (envs > 2 && (size_t)envs * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)NAV_TIMED_LDS) envs >>= 1;
+    return envs;
+}
+
+// reached | its four neighbours, before the mask of free cells: the field kernel's step plus the row itself (waiting)
+__device__ __forceinline__ uint32_t nav_dilate(uint32_t reached, int r)
+{
+    const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
+    uint32_t next = reached | reached << 1 | reached >> 1;
+    if (r > 0) next |= up;
+    if (r < 31) next |= dn;
+    return next;
+}
+
+template <int P> __global__ __launch_bounds__(NAV_THREADS) void mg_nav_timed_field_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const uint32_t *__restrict__ blocked, int64_t bstride, const int32_t *__restrict__ goal_x,
+    const int32_t *__restrict__ goal_y, int gstride, const int32_t *__restrict__ agent_x,
+    const int32_t *__restrict__ agent_y, const int32_t *__restrict__ agent_clock, int astride,
+    uint16_t *__restrict__ dist, int64_t pitch, int32_t *__restrict__ agent_dist, int32_t *__restrict__ agent_action,
+    int32_t *__restrict__ error)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t timed_image[];  // [envs of the workgroup][P][cells]
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, r = lane & 31;
+    const int slot = tid >> 5;                                              // env of the workgroup: one half wavefront
+    const int e = blockIdx.x * (int)(blockDim.x >> 5) + slot;
+    const int HW = W * H, cells = nav_timed_cells(HW);
+    const bool row = e < N && r < H;                                        // this lane holds a row of the world
+    uint16_t *img = timed_image + (size_t)slot * P * cells;
+
+    for (int c = r; c < P * cells / 8; c += 32)                             // every state starts unreachable
+        reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    nav_wave_sync();                                                        // before other lanes write rounds into it
+
+    uint32_t open = 0, goals = 0;
+    if (row) open = nav_open_row(type, state, (size_t)e * HW + (size_t)r * W, W, pass_types, doors_open, goals);
+    uint32_t fr[P], reached[P];                                             // free and reached cells of the row per phase
+#pragma unroll
+    for (int p = 0; p < P; ++p) fr[p] = row ? open & ~blocked[(int64_t)e * bstride + p * H + r] : 0u;
+
+    // sources: the same cells in every phase, each where it is free
+    int err = 0;
+    uint32_t src = 0;
+    if (goal_x != nullptr) {
+        const bool in_n = e < N;
+        const int gx = in_n ? goal_x[(int64_t)e * gstride] : 0, gy = in_n ? goal_y[(int64_t)e * gstride] : 0;
+        if (gx < 0 || gx >= W || gy < 0 || gy >= H) err = 2;
+        else if (r == gy) src = 1u << gx;
+    } else {
+        src = goals;
+    }
+    uint32_t any = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        reached[p] = src & fr[p];
+        any |= reached[p];
+        for (uint32_t m = reached[p]; m != 0u; m &= m - 1u) img[p * cells + r * W + (__ffs(m) - 1)] = 0;
+    }
+    const uint32_t sourced = nav_half_ballot(any != 0u, half);             // every lane votes: err may differ per env
+    if (err == 0 && sourced == 0u) err = 1;
+
+    // Round k: the states k transitions from a source.  Every phase reads its successor's mask of the round before:
+    // phase p is updated before phase p + 1, and the last phase reads the dilation of phase 0 taken first.
+    const int cap = HW * P;
+    for (int k = 1; k <= cap; ++k) {
+        const uint32_t d0 = nav_dilate(reached[0], r);
+        any = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const uint32_t d = p + 1 < P ? nav_dilate(reached[p + 1 < P ? p + 1 : 0], r) : d0;
+            const uint32_t fresh = d & fr[p] & ~reached[p];
+            reached[p] |= fresh;
+            any |= fresh;
+            for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[p * cells + r * W + (__ffs(m) - 1)] = (uint16_t)k;
+        }
+        if (__ballot(any != 0u) == 0ull) break;                             // wavefront-uniform: both worlds are done
+    }
+    nav_wave_sync();
+
+    if (e >= N) return;                                                     // a whole half wavefront at once
+    if (agent_dist != nullptr || agent_action != nullptr || (error != nullptr && agent_x != nullptr)) {
+        if (r == 0) {
+            const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride];
+            int d = MG_NAV_UNREACHABLE, a = MG_NAV_ACTION_NONE;
+            if (ax < 0 || ax >= W || ay < 0 || ay >= H) {
+                if (err == 0) err = 3;
+            } else {
+                const int ph = nav_phase(agent_clock != nullptr ? agent_clock[(int64_t)e * astride] : 0, P);
+                const uint16_t *next = img + (ph + 1 == P ? 0 : ph + 1) * cells;
+                const int c = ay * W + ax;
+                d = img[ph * cells + c];
+                if (d == 0) a = MG_NAV_ACTION_STAY;
+                else if (d != MG_NAV_UNREACHABLE) {
+                    const int want = d - 1;
+                    if (ax > 0 && next[c - 1] == want) a = 0;
+                    else if (ax < W - 1 && next[c + 1] == want) a = 1;
+                    else if (ay > 0 && next[c - W] == want) a = 2;
+                    else if (ay < H - 1 && next[c + W] == want) a = 3;
+                    else a = MG_NAV_ACTION_STAY;                            // waiting is the only optimal move
+                }
+            }
+            if (agent_dist) agent_dist[e] = d;
+            if (agent_action) agent_action[e] = a;
+        }
+    }
+    if (error != nullptr && r == 0) error[e] = err;
+    if (dist != nullptr) {
+        for (int p = 0; p < P; ++p) {
+            uint16_t *ob = dist + ((int64_t)e * P + p) * pitch;
+            const uint16_t *ip = img + p * cells;
+            const int chunks = mg_row_chunks_at<int>(mg_row_misalign(ob, 8), HW, 8);
+            for (int c = r; c < chunks; c += 32)
+                mg_row_store(ob, HW, c, [&](int q) -> uint16_t { return ip[q]; });
+        }
+    }
+}
+
+using nav_timed_kernel_t = decltype(&mg_nav_timed_field_kernel<1>);
+template <int... Ps> constexpr nav_timed_kernel_t nav_timed_kernel_of[] = {mg_nav_timed_field_kernel<Ps + 1>...};
+constexpr const nav_timed_kernel_t *nav_timed_kernels =                    // [P - 1]
+    nav_timed_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
+static_assert(NAV_MAX_PERIOD == 16, "one instantiation per period");
 
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
 
@@ -465,8 +622,8 @@ extern "C" int mg_nav_optimal_moves(const uint16_t *dist, int64_t dist_pitch, in
     if (M == 0) return TW_OK;
     const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
     // chunks are counted from the aligned address below either output: up to 15 positions more than M
-    hipLaunchKernelGGL(mg_nav_moves_kernel, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
-                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
+    hipLaunchKernelGGL(mg_nav_moves_kernel<false>, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
+                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, 1, n_envs, width, height,
                        reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
     return tw_launched(__func__);
 }
@@ -489,5 +646,50 @@ extern "C" int mg_nav_goal_moves(const uint8_t *type, const uint8_t *state, int 
                        dim3(NAV_GOAL_THREADS), 0, (hipStream_t)stream, type, state, n_envs, width, height, pass_types,
                        flags & MG_NAV_DOORS_OPEN, rec_t, rec_n, rec_goal, n_records,
                        reinterpret_cast<const float2 *>(pos), age, init_pos, T, moves, acting_dist);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_timed_field(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                  uint32_t pass_types, int flags, const uint32_t *blocked, int64_t blocked_env_stride,
+                                  int period, const int32_t *goal_x, const int32_t *goal_y, int goal_stride,
+                                  const int32_t *agent_x, const int32_t *agent_y, const int32_t *agent_clock,
+                                  int agent_stride, uint16_t *dist, int64_t dist_pitch, int32_t *agent_dist,
+                                  int32_t *agent_action, int32_t *error, void *stream)
+{
+    if (!type || n_envs <= 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
+    if (period < 1 || period > NAV_MAX_PERIOD || !blocked || ((uintptr_t)blocked & 3u)) return TW_E_ARG;
+    if (blocked_env_stride < 0 || (blocked_env_stride != 0 && blocked_env_stride < (int64_t)period * height)) return TW_E_ARG;
+    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
+    if ((uintptr_t)dist & 1u) return TW_E_ARG;
+    if ((goal_x == nullptr) != (goal_y == nullptr) || (agent_x == nullptr) != (agent_y == nullptr)) return TW_E_ARG;
+    if ((agent_dist || agent_action || agent_clock) && !agent_x) return TW_E_ARG;
+    if ((goal_x && goal_stride <= 0) || (agent_x && agent_stride <= 0)) return TW_E_ARG;
+    const int HW = width * height, envs = nav_timed_envs(HW, period);
+    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)HW;
+    const size_t lds = (size_t)envs * period * nav_timed_cells(HW) * sizeof(uint16_t);
+    hipLaunchKernelGGL(nav_timed_kernels[period - 1], dim3((n_envs + envs - 1) / envs), dim3(32 * envs), lds,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       blocked, blocked_env_stride, goal_x, goal_y, goal_stride, agent_x, agent_y, agent_clock,
+                       agent_stride, dist, pitch, agent_dist, agent_action, error);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                                  const float *pos, const int32_t *age, const float *init_pos, int T, uint8_t *moves,
+                                  uint16_t *acting_dist, void *stream)
+{
+    if (!dist || !pos || !moves || !age || !init_pos || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (period < 1 || period > NAV_MAX_PERIOD) return TW_E_ARG;
+    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
+    if (((uintptr_t)dist & 1u) || ((uintptr_t)acting_dist & 1u) || ((uintptr_t)pos & 7u)) return TW_E_ARG;
+    if (((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    const int64_t M = (int64_t)T * n_envs;
+    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (M == 0) return TW_OK;
+    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
+    hipLaunchKernelGGL(mg_nav_moves_kernel<true>, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
+                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, period, n_envs, width, height,
+                       reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
     return tw_launched(__func__);
 }

@@ -388,6 +388,31 @@ class TwoarmyEngine:
                                   agent=ag[:2] if agent else None, out=out, want_field=want_field,
                                   agent_out=agent_out, error_out=error_out)
 
+    def timed_field(self, avoid_risk=False, goal=None, agent=True, out=None, want_field=True, agent_out=None,
+                    error_out=None):
+        """Time-expanded shortest paths of the engine's worlds (minigrid_nav.timed_field, one launch, read from the
+        engine's own planes and the AX / AY / STEP_MOVE words of its records) -> (dist uint16[N, 6, 289] or None,
+        agent_dist int32[N], agent_action int32[N], error int32[N]).  The row-8 balls are planned by their period-6
+        schedule (minigrid_nav.twoarmy_schedule; phase = step_move % 6), so the expert waits for the gap to open
+        instead of walking into a ball: agent_action 6 off the goal means "wait one step".  avoid_risk: also keep out
+        of the -0.1 cell under each ball.  The plane's own balls are passable (PASS_BALL): only the schedule blocks.
+        v6: the two constant 2x2 wall blocks are planned as present from the reset on (they appear with the agent's
+        first step out of the start corner, and no block cell touches a corner cell), so one field at a reset serves the
+        whole episode, exactly.  v4: the blocks are drawn at random and the patrol groups move behind RNG gates: the
+        field plans on the planes as they stand (blocks once they have dropped) and does NOT schedule the patrols --
+        their balls are passable, as in the static prior.  The other arguments as in distance_field."""
+        from . import minigrid_nav as nav
+        ty, _, ag = self._views()
+        key = (bool(avoid_risk), ty.device)
+        if getattr(self, "_schedules", None) is None:
+            self._schedules = {}
+        if key not in self._schedules:
+            self._schedules[key] = nav.twoarmy_schedule(avoid_risk, blocks=self.variant == 6, device=ty.device)
+        clock = ag[0].as_strided(ag[0].shape, ag[0].stride(), ag[0].storage_offset() + FIELDS["STEP_MOVE"] - FIELDS["AX"])
+        return nav.timed_field(ty, None, 17, 17, self._schedules[key], nav.PASS_DEFAULT | nav.PASS_BALL, goal=goal,
+                               agent=ag[:2] if agent else None, clock=clock if agent else None, out=out,
+                               want_field=want_field, agent_out=agent_out, error_out=error_out)
+
     def goal_moves(self, her, pos, age=None, init_pos=None, pass_types=None, out=None, dist_out=None):
         """Optimal-move sets of hindsight records under their own goals in the engine's worlds as they stand
         (minigrid_nav.goal_moves, one launch, read from the engine's own planes) -> (moves uint8[R], acting_dist

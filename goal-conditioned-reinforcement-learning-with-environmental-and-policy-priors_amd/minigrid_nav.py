@@ -2,13 +2,17 @@
 of N grid worlds lies from the goal, and which of mg_step's four moves an agent on a shortest path makes next.  World planes
 are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are int32[N] tensors, dense or the column views
 of the engine's records (TwoarmyEngine.agent_views()), read where they live.  goal_moves labels records that each name a
-goal of their own (hindsight records) without a field in memory.  One launch per call, on the tensors' device.
-No CPU fallback."""
+goal of their own (hindsight records) without a field in memory.  timed_field / timed_moves do the same for worlds whose
+blockers move with a period (a search over (cell, phase): the expert may wait).  One launch per call, on the tensors'
+device.  No CPU fallback."""
+import ctypes
+
 import torch
 
 from ._marshal import agent_arrays, call, ptr, rows
 
 MAX_SIDE = 32
+MAX_PERIOD = 16                       # timed_field: phases of a schedule
 UNREACHABLE = 0xFFFF
 PASS_DEFAULT = 0x0B1B                 # mg_step's rule: types 0, 1, 3, 8, 9, 11 and open doors (bit 4)
 PASS_LAVA, PASS_BALL = 1 << 9, 1 << 6  # clear PASS_LAVA to keep out of the lava, set PASS_BALL to walk through balls
@@ -149,6 +153,121 @@ def goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, pass_type
          R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, ptr(out, torch.uint8),
          ptr(dist_out, DIST_DTYPE))
     return out, dist_out
+
+
+def _schedule(blocked, N, H, dev):
+    """(pointer, env stride in words, P) of a schedule tensor: int32 / uint32 [P, H] (shared) or [N, P, H] (per env)."""
+    assert blocked.dtype in (torch.int32, torch.uint32) and blocked.is_cuda and blocked.device == dev, \
+        "expected a 32-bit schedule on the planes' device"
+    assert blocked.dim() in (2, 3) and blocked.shape[-1] == H and blocked.is_contiguous(), "expected [P, H] or [N, P, H]"
+    P = blocked.shape[-2]
+    assert 1 <= P <= MAX_PERIOD and (blocked.dim() == 2 or blocked.shape[0] == N)
+    return ptr(blocked), (0 if blocked.dim() == 2 else P * H), P
+
+
+def timed_field(type_plane, state_plane, width, height, blocked, pass_types=PASS_DEFAULT, goal=None, agent=None,
+                clock=None, out=None, doors_open=False, want_field=True, want_error=True, agent_out=None, error_out=None):
+    """distance_field for a world whose blockers move with a period (mg_nav_timed_field, include/minigrid_nav.h)
+    -> (dist, agent_dist, agent_action, error).
+    blocked: int32 / uint32 [P, H] (one schedule for all envs) or [N, P, H]: bit x of word y of phase p = cell (x, y) is
+    occupied at phase p.  dist uint16[N, P, H*W]: transitions (a move or a wait, the phase advancing by one) from (cell,
+    phase) to the nearest source, UNREACHABLE where the cell is not free at that phase or no path exists (`out`: a
+    [N, P, H*W] tensor whose rows may be padded; want_field=False: None).  agent = (x, y) int32[N] with clock int32[N]
+    sharing their stride (None: phase 0): the agent's phase is clock <= 0 ? 0 : clock % P.  agent_action: 0..3 a move, 6
+    stay on a source OR wait for the blockers, -1 unreachable.  Everything else as distance_field takes and returns it."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state_plane is None or state_plane.shape == (N, W * H)
+    dev = type_plane.device
+    bp, bstride, P = _schedule(blocked, N, H, dev)
+    dp, dpitch = None, 0
+    if out is not None or want_field:
+        if out is None:
+            out = torch.empty((N, P, W * H), dtype=DIST_DTYPE, device=dev)
+        assert out.dim() == 3 and out.shape == (N, P, W * H) and out.device == dev and out.dtype == DIST_DTYPE
+        assert out.stride(2) == 1 or W * H == 1, "the rows must be dense"
+        dpitch = out.stride(1) if P > 1 else (out.stride(0) if N > 1 else W * H)
+        assert dpitch >= W * H and (N == 1 or out.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
+        dp = _marshal_ptr(out)
+    gx = gy = ax = ay = cp = None
+    gstride = astride = 1
+    if goal is not None:
+        gx, gy, _, gstride = agent_arrays(goal[0], goal[1])
+        assert goal[0].shape[0] >= N and goal[0].device == dev
+    adist = aact = None
+    if agent is not None:
+        ax, ay, cp, astride = agent_arrays(agent[0], agent[1], clock)
+        assert agent[0].shape[0] >= N and agent[0].device == dev
+        adist, aact = agent_out if agent_out is not None else (_int32(None, N, dev), _int32(None, N, dev))
+        _int32(adist, N, dev), _int32(aact, N, dev)
+    else:
+        assert agent_out is None and clock is None, "agent_out or clock without agent"
+    err = _int32(error_out, N, dev) if want_error or error_out is not None else None
+    call("mg_nav_timed_field", dev, ptr(type_plane, torch.uint8), ptr(state_plane, torch.uint8), N, W, H, int(pass_types),
+         DOORS_OPEN if doors_open else 0, bp, bstride, P, gx, gy, gstride, ax, ay, cp, astride, dp, dpitch, ptr(adist),
+         ptr(aact), ptr(err))
+    return out, adist, aact, err
+
+
+def _marshal_ptr(t):
+    """Address of a device tensor whose (padded) layout the caller has checked."""
+    assert t.is_cuda
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def timed_moves(dist, pos, width, height, age, init_pos, out=None, dist_out=None):
+    """optimal_moves for a timed field (mg_nav_timed_moves, include/minigrid_nav.h): dist uint16[N, P, H*W] as
+    timed_field returns it (rows may be padded), pos float32[T, N, 2] = (y, x) BEFORE each step, age int32[T, N] (the
+    clock as well: the phase of (t, n) is age <= 0 ? 0 : age % P) and init_pos float32[2], both required.
+    -> (moves uint8[T, N], acting_dist uint16[T, N]): bits 0..3 = the move leads one transition nearer, MOVE_STAY = on a
+    source, or waiting is optimal; 0 on an unreachable state or outside the world.  out / dist_out as in optimal_moves."""
+    W, H = int(width), int(height)
+    assert dist.is_cuda and dist.dtype == DIST_DTYPE and dist.dim() == 3 and dist.shape[2] == W * H
+    N, P = dist.shape[0], dist.shape[1]
+    assert dist.stride(2) == 1 or W * H == 1, "the rows must be dense"
+    dpitch = dist.stride(1) if P > 1 else (dist.stride(0) if N > 1 else W * H)
+    assert dpitch >= W * H and (N == 1 or dist.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
+    dev = dist.device
+    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
+    T = pos.shape[0]
+    assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
+    assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    if out is None:
+        out = torch.empty((T, N), dtype=torch.uint8, device=dev)
+    assert out.shape == (T, N) and out.device == dev
+    if dist_out is None:
+        dist_out = torch.empty((T, N), dtype=DIST_DTYPE, device=dev)
+    elif dist_out is False:
+        dist_out = None
+    assert dist_out is None or (dist_out.shape == (T, N) and dist_out.device == dev)
+    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, dist_out
+    call("mg_nav_timed_moves", dev, _marshal_ptr(dist), int(dpitch), P, N, W, H, ptr(pos), ptr(age, torch.int32),
+         ptr(init_pos, torch.float32), T, ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+TWOARMY_PERIOD = 6
+_TWOARMY_BALL_X0 = (7, 8, 7, 6, 6, 6)      # x of the first of the three row-8 balls by step_move % 6 (twoarmy_v6.py:96-109)
+_TWOARMY_V6_BLOCKS = ((4, 11), (5, 11), (4, 12), (5, 12), (8, 11), (8, 12), (9, 11), (9, 12))   # twoarmy_v6.py:186-197
+
+
+def twoarmy_schedule(avoid_risk=False, blocks=False, device=None):
+    """The period-6 schedule of Twoarmy's row-8 balls, int32[6, 17], built on the host: phase = step_move % 6, the balls
+    at x0, x0 + 1, x0 + 2 of row 8 with x0 = 7, 8, 7, 6, 6, 6 (they move before the agent does, so phase p holds where
+    they stand once step_move is p).  Use it with pass_types | PASS_BALL: the plane's own ball cells are then enterable
+    and only the schedule blocks.  avoid_risk: also block, at the same phase, the row-9 cell under each ball (the -0.1
+    cell of twoarmy_v6.py:241-243).  blocks: also block v6's two constant 2x2 wall blocks at every phase (they appear
+    with the agent's first step out of the start corner).  device None: a host tensor."""
+    rows = [[0] * 17 for _ in range(TWOARMY_PERIOD)]
+    for p, x0 in enumerate(_TWOARMY_BALL_X0):
+        rows[p][8] = 7 << x0
+        if avoid_risk:
+            rows[p][9] = 7 << x0
+        if blocks:
+            for x, y in _TWOARMY_V6_BLOCKS:
+                rows[p][y] |= 1 << x
+    return torch.tensor(rows, dtype=torch.int32, device=device)
 
 
 def to_policy_mask(moves, n_actions):

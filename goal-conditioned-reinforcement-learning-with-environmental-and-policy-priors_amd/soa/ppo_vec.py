@@ -557,18 +557,23 @@ class VecPPOTrainer:
                 "mean": v[4] / v[3] if v[3] else None, "cut_off": v[5]}
 
     # ------------------------------------------------------------------ shortest-path prior
-    def enable_prior(self, coef, decay=1.0, hindsight=False):
+    def enable_prior(self, coef, decay=1.0, hindsight=False, timed=False):
         """Train the actor with the shortest-path prior: update() adds coef * decay^(updates done) times the set-valued
         imitation term (ppo_ops.prior_loss) over the optimal-move sets label_expert() makes to the actor's loss of every
         minibatch.  Rewards, returns, targets, advantages, the critic, the running score and the HER switch are
         untouched (this is no reward shaping).  coef = 0: label and report only, no loss launch.  From here on the
         rollout also keeps its acting distributions (T x N x 5 floats) for prior_stats().  hindsight=True: the
         hindsight records of relabel() are labelled too, each under its own goal (one mg_nav_goal_moves launch in
-        label_expert()), and enter the term with those labels instead of an empty mask."""
+        label_expert()), and enter the term with those labels instead of an empty mask.  timed=True: the rollout's own
+        labels come from the time-expanded search (TwoarmyEngine.timed_field, mg_nav_timed_moves): the row-8 balls follow
+        their schedule and "wait one step" (the stay bit, policy index 4) is a label where the gap is closed; the
+        hindsight labels stay those of the static map."""
         import inspect
         if "probs_out" not in inspect.signature(self.agent.act_batch).parameters or self.cache_predictions:
             raise ValueError("the shortest-path prior needs the plain PPO agent's act_batch")
-        self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0, "hindsight": bool(hindsight)}
+        self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0, "hindsight": bool(hindsight),
+                      "timed": bool(timed)}
+        self.timed_field = None               # uint16[N, 6, 289], made by the first label_expert() with timed=True
         self.her_moves = self.her_dist = self._her_moves_of = None
         self.act_probs = torch.zeros((self.T, self.N, 5), dtype=torch.float32, device=self.device)
         self._moves_at = -1
@@ -587,15 +592,24 @@ class VecPPOTrainer:
         afterwards.  With enable_prior(hindsight=True) and records from relabel() (call it first): ONE
         mg_nav_goal_moves launch more labels every hindsight record under its own goal, on the engine's planes as they
         stand and the same static map; `her_moves` uint8[R] and `her_dist` uint16[R] afterwards.  No host
-        synchronisation."""
+        synchronisation.  With enable_prior(timed=True) the field is TwoarmyEngine.timed_field's (six phases per env, the
+        engine's planes as they stand) and the labels are mg_nav_timed_moves', the age of a step being its clock."""
         from .. import minigrid_nav as nav
         T, N = self.T, self.N
-        self._static_field(reuse=True)
+        timed = self.prior is not None and self.prior["timed"]
         if self.expert_moves is None:
             self.expert_moves = torch.empty((T, N), dtype=torch.uint8, device=self.device)
             self.expert_dist = torch.empty((T, N), dtype=nav.DIST_DTYPE, device=self.device)
-        nav.optimal_moves(self.nav_field, self.pos[3:3 + T], 17, 17, age=self.age[:-1], init_pos=self.init_pos,
-                          out=self.expert_moves, dist_out=self.expert_dist)
+        if timed:                             # the same two launches: a field of six phases, labels by the age as clock
+            if self.timed_field is None:
+                self.timed_field = torch.empty((N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
+            self.engine.timed_field(agent=False, out=self.timed_field)
+            nav.timed_moves(self.timed_field, self.pos[3:3 + T], 17, 17, self.age[:-1], self.init_pos,
+                            out=self.expert_moves, dist_out=self.expert_dist)
+        else:
+            self._static_field(reuse=True)
+            nav.optimal_moves(self.nav_field, self.pos[3:3 + T], 17, 17, age=self.age[:-1], init_pos=self.init_pos,
+                              out=self.expert_moves, dist_out=self.expert_dist)
         self._moves_at = self.env_steps
         self.her_moves = self.her_dist = self._her_moves_of = None
         if self.prior is not None and self.prior["hindsight"] and self.her is not None and self.her["t"].numel():

@@ -17,6 +17,9 @@ imitation loss over the optimal moves of every acting state (one label launch pe
 minibatch); --expert_agreement only labels and reports.  Both append `expert agree` / `opt_mass` to the log line; off by default.
 --prior_hindsight (with either) also labels the hindsight records, each under its own goal (one more launch per rollout),
 trains on those labels too and appends `her agree`; off by default.
+--prior_timed (with either) takes the rollout's labels from the time-expanded search instead: the row-8 balls follow their
+period-6 schedule and "wait one step" is a label where the gap is closed (minigrid_nav.timed_field / timed_moves: the
+same two launches per rollout); off by default.
 """
 import argparse
 import os
@@ -115,6 +118,10 @@ def build_parser():
                         "(one more launch per rollout), let them enter the prior term with those labels instead of none, "
                         "and append `her agree` (share of the labelled records whose taken action is an optimal move "
                         "towards the hindsight goal) to the log line")
+    p.add_argument("--prior_timed", action="store_true",
+                   help="with --prior_coef / --expert_agreement: label the rollout with the time-expanded expert, which "
+                        "plans the row-8 balls by their period-6 schedule and waits for the gap instead of walking into "
+                        "a ball; the hindsight labels stay those of the static map")
     return p
 
 
@@ -192,6 +199,8 @@ def main(argv=None, predictor=False, soa=False):
     args = build_parser().parse_args(argv)
     if args.prior_hindsight and not (args.prior_coef != 0.0 or args.expert_agreement):
         raise SystemExit("--prior_hindsight needs --prior_coef or --expert_agreement")
+    if args.prior_timed and not (args.prior_coef != 0.0 or args.expert_agreement):
+        raise SystemExit("--prior_timed needs --prior_coef or --expert_agreement")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -251,7 +260,7 @@ def main(argv=None, predictor=False, soa=False):
     if use_prior:
         if predictor or soa:
             raise SystemExit("--prior_coef / --expert_agreement: plain PPO agent only")
-        trainer.enable_prior(args.prior_coef, args.prior_decay, hindsight=args.prior_hindsight)
+        trainer.enable_prior(args.prior_coef, args.prior_decay, hindsight=args.prior_hindsight, timed=args.prior_timed)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):

@@ -37,7 +37,9 @@ the cells it may enter now (balls and patrols block; 65535 = cut off), and info[
 of such a path as an ENV action (0 left, 1 right, 2 up, 3 down, 6 stay, -1 none): one more launch per step
 (minigrid_nav, agent values only, no field).  Both describe the state the env returns: under auto-reset those of a done
 env belong to the new episode, as the direction of a done step does for the action bonus.  The two tensors are the env's
-own and are overwritten by the next step, like final_observation.
+own and are overwritten by the next step, like final_observation.  `goal_distance="timed"` fills the same two fields
+from the time-expanded search instead (TwoarmyEngine.timed_field: the row-8 balls follow their schedule, the distance
+counts moves AND waits, and expert_action 6 away from the goal means "wait one step"): one launch per step as well.
 """
 import torch
 
@@ -100,7 +102,8 @@ class TwoarmyVecEnv:
                 self._dir_buf = [torch.empty(N, dtype=torch.float64, device=d) for _ in range(2)]
                 if goal_direction == "angle":
                     self._angle_table = minigrid_obs.angle_table(17, 17, d)
-        self.goal_distance = bool(goal_distance)
+        assert goal_distance in (True, False, "timed"), "goal_distance: True, False or \"timed\""
+        self.goal_distance = goal_distance
         if self.goal_distance:                            # distance, action, error: overwritten by the next step
             self._nav_buf = tuple(torch.empty(self.num_envs, dtype=torch.int32, device=self.device) for _ in range(3))
         self.episode_tracker = None
@@ -205,7 +208,8 @@ class TwoarmyVecEnv:
             info["_visitation"] = done
         if self.goal_distance:
             d, act, err = self._nav_buf
-            self.engine.distance_field(want_field=False, agent_out=(d, act), error_out=err)
+            field = self.engine.timed_field if self.goal_distance == "timed" else self.engine.distance_field
+            field(want_field=False, agent_out=(d, act), error_out=err)
             info["goal_distance"], info["expert_action"] = d, act
         reward = o["reward"]
         if self.bonus_tracker is not None:

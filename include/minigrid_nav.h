@@ -140,6 +140,64 @@ int mg_nav_goal_moves(const uint8_t *type, const uint8_t *state, int n_envs, int
                       const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                       const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream);
 
+/* ---- Time-expanded fields: blockers that move with a period (the balls of Twoarmy's door gap).
+ *
+ * The world, the moves, the enterable cells, pass_types, flags, the sources (a given cell per env, or all goal cells)
+ * and the over-read rule are exactly those of mg_nav_field.  New are a period P, 1 <= P <= MG_NAV_MAX_PERIOD, and a
+ * schedule of the cells that are occupied at each of the P phases.
+ *
+ * Schedule.  blocked: uint32[.][P][height] (4-byte aligned); word y of phase p has bit x set iff cell (x, y) is occupied
+ * at phase p.  Bits at or above `width` are ignored.  blocked_env_stride, in words: 0 = one schedule shared by all envs;
+ * otherwise it is at least P*height and env e reads from e*blocked_env_stride.
+ *
+ * Free cells.  free[p] = the enterable cells that are not blocked at phase p.
+ *
+ * Transition.  From (c, p) the agent goes to (c', (p + 1) mod P), where c' is c itself (it waits) or one of c's four
+ * neighbours inside the world; the transition exists iff c' is in free[(p + 1) mod P].  This one condition says all of:
+ * the blockers move before the agent does, a blocker keeps the agent out of its cell, and a blocker that moves onto a
+ * waiting agent hits it.
+ *
+ * Distance.  dist[p][c] = the least number of transitions from (c, p) to any state whose cell is a source.  It is
+ * defined for c in free[p] only: a source in free[p] is 0, every other state -- not free, or with no path to a source
+ * -- is MG_NAV_UNREACHABLE.  Distances are below width*height*P <= 16384.
+ *
+ * Phase from the clock.  The phase of a clock value k (int32) is k <= 0 ? 0 : k mod P -- the rule by which `age` selects
+ * init_pos in mg_nav_optimal_moves.  The engine's TW_STEP_MOVE word and the trainer's age array are such clocks.
+ *
+ * Expert action at (c, p) with d = dist[p][c]: 6 if d == 0; otherwise the first of 0 left, 1 right, 2 up, 3 down whose
+ * c' lies inside the world and has dist[(p + 1) mod P][c'] == d - 1; otherwise 6 (wait: then dist[(p + 1) mod P][c] ==
+ * d - 1 holds); -1 if d is MG_NAV_UNREACHABLE.  Move set: bits 0..3 on the same condition as the four moves, bit
+ * MG_NAV_MOVE_STAY_BIT iff d == 0 (then alone) or waiting is optimal.  Invariant: the lowest set bit of the move set,
+ * with bit 4 read as 6, is the expert action; a move set of 0 corresponds to -1.
+ *
+ * error: the codes of mg_nav_field; 1 = no source that is free at any phase (the whole field is MG_NAV_UNREACHABLE). */
+#define MG_NAV_MAX_PERIOD 16
+
+/* One launch for all envs: the P fields of every env and / or the distance and expert action of its agent.
+ *   dist         uint16[n_envs][P][dist_pitch] (nullable; dist_pitch in elements, 0 = dense width*height); each of the
+ *                n_envs * P rows is written as mg_nav_field writes a row
+ *   agent_clock  int32, env e at [e * agent_stride] like agent_x / agent_y (nullable: phase 0)
+ *   agent_dist, agent_action int32[n_envs] (nullable): need agent_x and agent_y
+ * The flood ends after at most width*height*P rounds whatever the input.
+ * TW_E_ARG: the cases of mg_nav_field; period outside 1..MG_NAV_MAX_PERIOD; NULL or misaligned blocked;
+ * blocked_env_stride < 0 or 0 < blocked_env_stride < P*height; agent_clock without agent_x / agent_y. */
+int mg_nav_timed_field(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                       uint32_t pass_types, int flags, const uint32_t *blocked, int64_t blocked_env_stride, int period,
+                       const int32_t *goal_x, const int32_t *goal_y, int goal_stride, const int32_t *agent_x,
+                       const int32_t *agent_y, const int32_t *agent_clock, int agent_stride, uint16_t *dist,
+                       int64_t dist_pitch, int32_t *agent_dist, int32_t *agent_action, int32_t *error, void *stream);
+
+/* mg_nav_optimal_moves for a timed field: dist uint16[n_envs][P][dist_pitch] as mg_nav_timed_field writes it, and age
+ * (required, with init_pos) is also the clock: the state of (t, n) is the acting cell -- age[t][n] <= 0 ? init_pos :
+ * pos[t][n], by the rule of the visit counters -- at the phase of age[t][n].
+ *   moves uint8[T][n_envs]: the move set above; 0 where the position is no cell or the state is unreachable.
+ *   acting_dist uint16[T][n_envs] (nullable): the state's distance; MG_NAV_UNREACHABLE in the same places.
+ * One launch; T == 0 launches nothing.  Stores, alignment and sizes as in mg_nav_optimal_moves.
+ * TW_E_ARG: the cases of mg_nav_optimal_moves; NULL age or init_pos; period outside 1..MG_NAV_MAX_PERIOD. */
+int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                       const float *pos, const int32_t *age, const float *init_pos, int T, uint8_t *moves,
+                       uint16_t *acting_dist, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
