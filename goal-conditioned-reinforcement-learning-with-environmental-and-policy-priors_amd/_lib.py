@@ -121,6 +121,9 @@ _SIGS.update({
     "mg_nav_timed_field": (C.c_int, [_vp, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp,
                                      _i64, _vp, _vp, _vp, _vp]),
     "mg_nav_timed_moves": (C.c_int, [_vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mg_nav_timed_goal_moves": (C.c_int, [_vp, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _i64, _i, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp, _i, _vp, _vp, _vp]),
+    "mg_nav_timed_goal_floods": (C.c_int, [_i, _i, _i]),
     "ppo_her_relabel": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
     "ppo_her_relabel_window": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _i, _i, _i, _i, _vp,

@@ -28,6 +28,11 @@
  *                          the round before; one ballot per round decides "nothing new in any phase".  The image is
  *                          P * W*H distances per env in dynamic LDS, and the envs per workgroup (8, 4 or 2) follow from it.
  *                          The moves kernel serves the timed fields too (TIMED: the phase comes from the element's age).
+ *   mg_nav_timed_goal_kernel<P>   the goal kernel over (cell, phase): its staging, heads and stores (nav_goal_* below) and
+ *                          the timed field kernel's seed and round (nav_timed_*).  A record also keeps one phase byte; the
+ *                          phase is no part of a run's key, one flood serves every phase.  A flooding half wavefront owns
+ *                          an image of P * W*H distances in dynamic LDS, and as many halves flood at a time (8, 4, 2 or 1)
+ *                          as fit 64 KiB next to the staging; the other wavefronts skip the flood loop whole.
  *
  * Integer work only, no atomics: the results do not depend on scheduling.
  */
@@ -304,70 +309,98 @@ constexpr uint16_t NAV_NO_CELL = 0xFFFF;
 static_assert(NAV_GOAL_ELEMS % 16 == 0, "whole chunks of both outputs");
 static_assert(NAV_GOAL_SLOTS <= 0xFFFF, "slots are listed as uint16");
 
-__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
-    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
-    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
-    const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos, const int32_t *__restrict__ age,
-    const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+// What a workgroup keeps of its records besides the flood images: keys, heads and the labels on their way out.
+struct nav_goal_stage_t {
+    alignas(16) uint8_t moves[NAV_GOAL_ELEMS];
+    alignas(16) uint16_t dist[NAV_GOAL_ELEMS];
+    int32_t env[NAV_GOAL_SLOTS];                        // the key of a record: its env, -1 for a record without a result,
+    uint16_t goal[NAV_GOAL_SLOTS];                      //   and its goal cell
+    uint16_t cell[NAV_GOAL_SLOTS];                      // its acting cell, NAV_NO_CELL where the position is none
+    uint16_t head[NAV_GOAL_SLOTS + 1];                  // the slots of the heads in ascending order, then the end slot
+    int count[NAV_GOAL_ROUNDS][NAV_GOAL_THREADS / 64];
+};
+
+// A workgroup's chunks of either output and the records they hold, as in mg_nav_moves_kernel.
+struct nav_goal_share_t {
+    int sm, sd;
+    mg_row_span_t<int64_t> km, kd;
+    int64_t bm, bd;                                     // record of LDS slot 0 of either image
+    int64_t p0;                                         // record of slot 0 of the key arrays
+    bool has_m, has_d;
+    int slot_lo, slot_hi;                               // 0 < slot_lo <= slot_hi <= SLOTS, or both 0: no record
+};
+
+__device__ __forceinline__ nav_goal_share_t nav_goal_share(const uint8_t *moves, const uint16_t *acting_dist, int64_t M,
+                                                           int64_t b)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
-    __shared__ __attribute__((aligned(16))) uint8_t s_moves[NAV_GOAL_ELEMS];
-    __shared__ __attribute__((aligned(16))) uint16_t s_dist[NAV_GOAL_ELEMS];
-    __shared__ int32_t s_env[NAV_GOAL_SLOTS];           // the key of a record: its env, -1 for a record without a result,
-    __shared__ uint16_t s_goal[NAV_GOAL_SLOTS];         //   and its goal cell
-    __shared__ uint16_t s_cell[NAV_GOAL_SLOTS];         // its acting cell, NAV_NO_CELL where the position is none
-    __shared__ uint16_t s_head[NAV_GOAL_SLOTS + 1];     // the slots of the heads in ascending order, then the end slot
-    __shared__ int s_count[NAV_GOAL_ROUNDS][NAV_GOAL_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, half = tid >> 5;
-    const int64_t b = blockIdx.x;
-    // this workgroup's chunks of either output and the records they hold, as in mg_nav_moves_kernel
-    const int sm = mg_row_misalign(moves, 16), sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
-    const mg_row_span_t<int64_t> km = mg_row_span<int64_t>(sm, M, b, NAV_GOAL_ELEMS / 16, 16);
-    const mg_row_span_t<int64_t> kd = mg_row_span<int64_t>(sd, M, b, NAV_GOAL_ELEMS / 8, 8);
-    const int64_t bm = 16 * km.c0 - sm, bd = 8 * kd.c0 - sd;               // record of LDS slot 0 of either image
-    const bool has_m = km.c0 < km.c1, has_d = acting_dist != nullptr && kd.c0 < kd.c1;
-    const int64_t p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;                    // record of slot 0 of the key arrays
+    nav_goal_share_t g;
+    g.sm = mg_row_misalign(moves, 16);
+    g.sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
+    g.km = mg_row_span<int64_t>(g.sm, M, b, NAV_GOAL_ELEMS / 16, 16);
+    g.kd = mg_row_span<int64_t>(g.sd, M, b, NAV_GOAL_ELEMS / 8, 8);
+    g.bm = 16 * g.km.c0 - g.sm;
+    g.bd = 8 * g.kd.c0 - g.sd;
+    g.has_m = g.km.c0 < g.km.c1;
+    g.has_d = acting_dist != nullptr && g.kd.c0 < g.kd.c1;
+    g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
     int64_t lo = 0, hi = 0;                                                 // the records of this workgroup: both spans
-    if (has_m) { lo = km.p_lo; hi = km.p_hi; }
-    if (has_d) { lo = has_m && lo < kd.p_lo ? lo : kd.p_lo; hi = has_m && hi > kd.p_hi ? hi : kd.p_hi; }
-    // 0 < slot_lo <= slot_hi <= SLOTS; a workgroup that holds neither span (the last one may) has no slots: both 0
-    const int slot_lo = has_m || has_d ? (int)(lo - p0) : 0, slot_hi = has_m || has_d ? (int)(hi - p0) : 0;
-    const int HW = W * H;
+    if (g.has_m) { lo = g.km.p_lo; hi = g.km.p_hi; }
+    if (g.has_d) { lo = g.has_m && lo < g.kd.p_lo ? lo : g.kd.p_lo; hi = g.has_m && hi > g.kd.p_hi ? hi : g.kd.p_hi; }
+    // a workgroup that holds neither span (the last one may) has no slots
+    g.slot_lo = g.has_m || g.has_d ? (int)(lo - g.p0) : 0;
+    g.slot_hi = g.has_m || g.has_d ? (int)(hi - g.p0) : 0;
+    return g;
+}
+
+// Keys and acting cells: every global read of a record happens here, one record per lane and round; __syncthreads() after.
+// TIMED: age is given and is the record's clock too; its phase goes into s_phase (0 for a record without a result).
+template <bool TIMED> __device__ __forceinline__ void nav_goal_keys(
+    nav_goal_stage_t &st, uint8_t *s_phase, const nav_goal_share_t &g, int N, int W, int H, int P,
+    const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal,
+    const float2 *__restrict__ pos, const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T)
+{
+    const int tid = threadIdx.x, HW = W * H;
     float2 init = make_float2(0.f, 0.f);
     if (age != nullptr) init = make_float2(init_pos[0], init_pos[1]);
-
-    // keys and acting cells: every global read of a record happens here, one record per lane and round
 #pragma unroll 1
     for (int k = 0; k < NAV_GOAL_ROUNDS; ++k) {
         const int i = k * NAV_GOAL_THREADS + tid;
-        if (i < slot_lo || i >= slot_hi) continue;
-        const int64_t p = p0 + i;
+        if (i < g.slot_lo || i >= g.slot_hi) continue;
+        const int64_t p = g.p0 + i;
         const int t = rec_t[p], n = rec_n[p];
         const int gc = visit_cell(rec_goal[2 * p], rec_goal[2 * p + 1], W, H);   // (y, x); 4-byte aligned: two loads
-        int env = -1, ac = NAV_NO_CELL;
+        int env = -1, ac = NAV_NO_CELL, ph = 0;
         if (t >= 0 && t < T && n >= 0 && n < N && gc < HW) {
             const int64_t at = (int64_t)t * N + n;
             float2 q = pos[at];
-            if (age != nullptr && age[at] <= 0) q = init;
+            const int clock = age != nullptr ? age[at] : 1;
+            if (clock <= 0) q = init;
             const int c = visit_cell(q.x, q.y, W, H);
             env = n;
             if (c < HW) ac = c;
+            if (TIMED) ph = nav_phase(clock, P);
         }
-        s_env[i] = env;
-        s_goal[i] = (uint16_t)gc;
-        s_cell[i] = (uint16_t)ac;
+        st.env[i] = env;
+        st.goal[i] = (uint16_t)gc;
+        st.cell[i] = (uint16_t)ac;
+        if (TIMED) s_phase[i] = (uint8_t)ph;
     }
     __syncthreads();
+}
 
-    // heads, counted per wavefront and round (the round's ballot stays in registers), then listed in ascending order
+// Heads (records whose (env, goal cell) differs from their predecessor's, and the first one), counted per wavefront and
+// round (the round's ballot stays in registers), then listed in st.head in ascending order; -> their number.
+__device__ __forceinline__ int nav_goal_heads(nav_goal_stage_t &st, const nav_goal_share_t &g)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned long long heads[NAV_GOAL_ROUNDS];
 #pragma unroll
     for (int k = 0; k < NAV_GOAL_ROUNDS; ++k) {
         const int i = k * NAV_GOAL_THREADS + tid;
-        const bool hd = i >= slot_lo && i < slot_hi &&
-                        (i == slot_lo || s_env[i] != s_env[i - 1] || s_goal[i] != s_goal[i - 1]);
+        const bool hd = i >= g.slot_lo && i < g.slot_hi &&
+                        (i == g.slot_lo || st.env[i] != st.env[i - 1] || st.goal[i] != st.goal[i - 1]);
         heads[k] = __ballot(hd);
-        if (lane == 0) s_count[k][wave] = __popcll(heads[k]);
+        if (lane == 0) st.count[k][wave] = __popcll(heads[k]);
     }
     __syncthreads();
     int n_heads = 0;
@@ -378,14 +411,54 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
         const bool hd = (hb >> lane) & 1ull;
         int before = n_heads;
         for (int w = 0; w < NAV_GOAL_THREADS / 64; ++w) {
-            const int cnt = s_count[k][w];
+            const int cnt = st.count[k][w];
             if (w < wave) before += cnt;
             n_heads += cnt;
         }
-        if (hd) s_head[before + __popcll(hb & ((1ull << lane) - 1ull))] = (uint16_t)i;
+        if (hd) st.head[before + __popcll(hb & ((1ull << lane) - 1ull))] = (uint16_t)i;
     }
-    if (tid == 0) s_head[n_heads] = (uint16_t)slot_hi;
+    if (tid == 0) st.head[n_heads] = (uint16_t)g.slot_hi;
     __syncthreads();
+    return n_heads;
+}
+
+// the label of the record in slot i, parked for the stores
+__device__ __forceinline__ void nav_goal_label(nav_goal_stage_t &st, const nav_goal_share_t &g, int i, uint32_t m, uint32_t d)
+{
+    const int64_t p = g.p0 + i;
+    if (g.has_m && p >= g.km.p_lo && p < g.km.p_hi) st.moves[(int)(p - g.bm)] = (uint8_t)m;
+    if (g.has_d && p >= g.kd.p_lo && p < g.kd.p_hi) st.dist[(int)(p - g.bd)] = (uint16_t)d;
+}
+
+// both outputs leave as the moves kernel's do; after a __syncthreads()
+__device__ __forceinline__ void nav_goal_store(const nav_goal_stage_t &st, const nav_goal_share_t &g, int64_t M,
+                                               uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+{
+    const int tid = threadIdx.x;
+    for (int64_t c = g.km.c0 + tid; c < g.km.c1; c += NAV_GOAL_THREADS)
+        mg_row_store(moves, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(st.moves + (int)(p - g.bm)); },
+                     [&](int64_t q) { return st.moves[(int)(q - g.bm)]; });
+    if (acting_dist != nullptr)
+        for (int64_t c = g.kd.c0 + tid; c < g.kd.c1; c += NAV_GOAL_THREADS)
+            mg_row_store(acting_dist, M, c,
+                         [&](int64_t p) { return *reinterpret_cast<const uint4 *>(st.dist + (int)(p - g.bd)); },
+                         [&](int64_t q) { return st.dist[(int)(q - g.bd)]; });
+}
+
+__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
+    const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos, const int32_t *__restrict__ age,
+    const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
+    __shared__ nav_goal_stage_t st;
+    const int tid = threadIdx.x, r = tid & 31, half = tid >> 5;
+    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
+    const int HW = W * H;
+
+    nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos, age, init_pos, T);
+    const int n_heads = nav_goal_heads(st, g);
 
     // one head per half wavefront and round: flood its goal, label its run.  Both halves of a wavefront go round together.
     uint16_t *img = image[half];
@@ -397,8 +470,8 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
     for (int it = 0; it < per; ++it) {
         const int j = half * per + it;
         const bool mine = j < j_end;
-        const int s0 = mine ? s_head[j] : 0, s1 = mine ? s_head[j + 1] : 0;
-        const int env = mine ? s_env[s0] : -1;
+        const int s0 = mine ? st.head[j] : 0, s1 = mine ? st.head[j + 1] : 0;
+        const int env = mine ? st.env[s0] : -1;
         uint32_t reached = 0;
         if (env >= 0) {
             if (env != cur_env) {                                           // the previous head's world stays in `open`
@@ -407,7 +480,7 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
                              : 0u;
                 cur_env = env;
             }
-            const int gc = s_goal[s0], gy = gc / W;
+            const int gc = st.goal[s0], gy = gc / W;
             if (r == gy) reached = (1u << (gc - gy * W)) & open;
             nav_image_clear(img, r);
         }
@@ -415,25 +488,15 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
         nav_flood(img, r, W, HW, env >= 0 ? open : 0u, reached);
         nav_wave_sync();
         for (int i = s0 + r; i < s1; i += 32) {
-            const int c = s_cell[i];
+            const int c = st.cell[i];
             uint32_t d = MG_NAV_UNREACHABLE, m = 0;
             if (env >= 0 && c != NAV_NO_CELL) m = nav_move_set(img, img, c, W, H, d);
-            const int64_t p = p0 + i;
-            if (has_m && p >= km.p_lo && p < km.p_hi) s_moves[(int)(p - bm)] = (uint8_t)m;
-            if (has_d && p >= kd.p_lo && p < kd.p_hi) s_dist[(int)(p - bd)] = (uint16_t)d;
+            nav_goal_label(st, g, i, m, d);
         }
         nav_wave_sync();                                                    // the labels are read before the image is reset
     }
     __syncthreads();
-
-    for (int64_t c = km.c0 + tid; c < km.c1; c += NAV_GOAL_THREADS)
-        mg_row_store(moves, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_moves + (int)(p - bm)); },
-                     [&](int64_t q) { return s_moves[(int)(q - bm)]; });
-    if (acting_dist != nullptr)
-        for (int64_t c = kd.c0 + tid; c < kd.c1; c += NAV_GOAL_THREADS)
-            mg_row_store(acting_dist, M, c,
-                         [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_dist + (int)(p - bd)); },
-                         [&](int64_t q) { return s_dist[(int)(q - bd)]; });
+    nav_goal_store(st, g, M, moves, acting_dist);
 }
 
 // ------------------------------------------------------------------ time-expanded fields: blockers that move with period P
@@ -458,6 +521,49 @@ __device__ __forceinline__ uint32_t nav_dilate(uint32_t reached, int r)
     if (r > 0) next |= up;
     if (r < 31) next |= dn;
     return next;
+}
+
+// The sources of a timed flood: the cells of `src` in every phase in which they are free, at distance 0.  -> the row's
+// sources of any phase.
+template <int P> __device__ __forceinline__ uint32_t nav_timed_seed(uint16_t *img, int cells, int r, int W, uint32_t src,
+                                                                    const uint32_t (&fr)[P], uint32_t (&reached)[P])
+{
+    uint32_t any = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        reached[p] = src & fr[p];
+        any |= reached[p];
+        for (uint32_t m = reached[p]; m != 0u; m &= m - 1u) img[p * cells + r * W + (__ffs(m) - 1)] = 0;
+    }
+    return any;
+}
+
+// Round k of a timed flood: the states k transitions from a source.  Every phase reads its successor's mask of the round
+// before: phase p is updated before phase p + 1, and the last phase reads the dilation of phase 0 taken first.
+// -> something was new in some world of the wavefront (one ballot: EVERY lane of the wavefront calls this together).
+template <int P> __device__ __forceinline__ bool nav_timed_round(uint16_t *img, int cells, int r, int W, int k,
+                                                                 const uint32_t (&fr)[P], uint32_t (&reached)[P])
+{
+    const uint32_t d0 = nav_dilate(reached[0], r);
+    uint32_t any = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const uint32_t d = p + 1 < P ? nav_dilate(reached[p + 1 < P ? p + 1 : 0], r) : d0;
+        const uint32_t fresh = d & fr[p] & ~reached[p];
+        reached[p] |= fresh;
+        any |= fresh;
+        for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[p * cells + r * W + (__ffs(m) - 1)] = (uint16_t)k;
+    }
+    return __ballot(any != 0u) != 0ull;
+}
+
+// The rounds of one half wavefront's world from the seeded masks, at most cap of them whatever the input.  A half with
+// reached = 0 in every phase floods nothing, whatever its fr.
+template <int P> __device__ __forceinline__ void nav_timed_flood(uint16_t *img, int cells, int r, int W, int cap,
+                                                                 const uint32_t (&fr)[P], uint32_t (&reached)[P])
+{
+    for (int k = 1; k <= cap; ++k)
+        if (!nav_timed_round<P>(img, cells, r, W, k, fr, reached)) break;    // wavefront-uniform: both worlds are done
 }
 
 template <int P> __global__ __launch_bounds__(NAV_THREADS) void mg_nav_timed_field_kernel(
@@ -497,32 +603,11 @@ template <int P> __global__ __launch_bounds__(NAV_THREADS) void mg_nav_timed_fie
     } else {
         src = goals;
     }
-    uint32_t any = 0;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        reached[p] = src & fr[p];
-        any |= reached[p];
-        for (uint32_t m = reached[p]; m != 0u; m &= m - 1u) img[p * cells + r * W + (__ffs(m) - 1)] = 0;
-    }
+    const uint32_t any = nav_timed_seed<P>(img, cells, r, W, src, fr, reached);
     const uint32_t sourced = nav_half_ballot(any != 0u, half);             // every lane votes: err may differ per env
     if (err == 0 && sourced == 0u) err = 1;
 
-    // Round k: the states k transitions from a source.  Every phase reads its successor's mask of the round before:
-    // phase p is updated before phase p + 1, and the last phase reads the dilation of phase 0 taken first.
-    const int cap = HW * P;
-    for (int k = 1; k <= cap; ++k) {
-        const uint32_t d0 = nav_dilate(reached[0], r);
-        any = 0;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const uint32_t d = p + 1 < P ? nav_dilate(reached[p + 1 < P ? p + 1 : 0], r) : d0;
-            const uint32_t fresh = d & fr[p] & ~reached[p];
-            reached[p] |= fresh;
-            any |= fresh;
-            for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[p * cells + r * W + (__ffs(m) - 1)] = (uint16_t)k;
-        }
-        if (__ballot(any != 0u) == 0ull) break;                             // wavefront-uniform: both worlds are done
-    }
+    nav_timed_flood<P>(img, cells, r, W, HW * P, fr, reached);
     nav_wave_sync();
 
     if (e >= N) return;                                                     // a whole half wavefront at once
@@ -568,6 +653,92 @@ template <int... Ps> constexpr nav_timed_kernel_t nav_timed_kernel_of[] = {mg_na
 constexpr const nav_timed_kernel_t *nav_timed_kernels =                    // [P - 1]
     nav_timed_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 static_assert(NAV_MAX_PERIOD == 16, "one instantiation per period");
+
+// ------------------------------------------------------------------ timed move sets of records with goals of their own
+// mg_nav_goal_kernel over (cell, phase): the same staging, heads and stores; a flooding half wavefront owns an image of
+// P * cells distances in dynamic LDS, and `flooders` (8, 4, 2 or 1: nav_timed_goal_flooders) of the 8 halves flood at a time.
+// The phase is no part of a run's key: one flood serves the records of every phase.
+inline int nav_timed_goal_flooders(int HW, int P)
+{
+    const size_t fixed = sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + 64;    // static LDS and what aligning it may cost
+    int f = NAV_GOAL_HALVES;
+    while (f > 1 && fixed + (size_t)f * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)64 * 1024) f >>= 1;
+    return f;
+}
+static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + 64 + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
+              "one image of the longest period and the largest world fits next to the staging");
+
+template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_timed_goal_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const uint32_t *__restrict__ blocked, int64_t bstride, const int32_t *__restrict__ rec_t,
+    const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos,
+    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves,
+    uint16_t *__restrict__ acting_dist, int flooders)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t goal_image[];   // [flooders][P][cells]
+    __shared__ nav_goal_stage_t st;
+    __shared__ uint8_t s_phase[NAV_GOAL_SLOTS];                             // the phase of a record's clock
+    const int tid = threadIdx.x, r = tid & 31, half = tid >> 5;
+    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
+    const int HW = W * H, cells = nav_timed_cells(HW);
+
+    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos, age, init_pos, T);
+    const int n_heads = nav_goal_heads(st, g);
+
+    // One head per flooding half wavefront and round.  Whole wavefronts enter or skip the loop: one goes round when its
+    // first half floods, an idle second half beside it with empty masks (the ballot of a round is wavefront-wide); the
+    // trip count is the workgroup's, and no workgroup barrier stands inside the loop.
+    const bool floods = half < flooders;
+    if ((half & ~1) < flooders) {
+        uint16_t *img = goal_image + (size_t)(floods ? half : 0) * P * cells;
+        const int per = (n_heads + flooders - 1) / flooders;
+        const int j_end = !floods ? 0 : (half + 1) * per < n_heads ? (half + 1) * per : n_heads;
+        int cur_env = -1;
+        uint32_t fr[P], reached[P];                                         // free and reached cells of the row per phase
+#pragma unroll
+        for (int p = 0; p < P; ++p) fr[p] = 0u;
+#pragma unroll 1
+        for (int it = 0; it < per; ++it) {
+            const int j = half * per + it;
+            const bool mine = floods && j < j_end;
+            const int s0 = mine ? st.head[j] : 0, s1 = mine ? st.head[j + 1] : 0;
+            const int env = mine ? st.env[s0] : -1;
+            uint32_t src = 0;
+            if (env >= 0) {
+                if (env != cur_env) {                                       // the previous head's world stays in `fr`
+                    uint32_t goals, open = 0;
+                    if (r < H) open = nav_open_row(type, state, (size_t)env * HW + (size_t)r * W, W, pass_types, doors_open, goals);
+#pragma unroll
+                    for (int p = 0; p < P; ++p) fr[p] = r < H ? open & ~blocked[(int64_t)env * bstride + p * H + r] : 0u;
+                    cur_env = env;
+                }
+                const int gc = st.goal[s0], gy = gc / W;
+                if (r == gy) src = 1u << (gc - gy * W);
+                for (int c = r; c < P * cells / 8; c += 32)                 // every state starts unreachable
+                    reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+            }
+            nav_wave_sync();                                                // before other lanes write rounds into it
+            nav_timed_seed<P>(img, cells, r, W, src, fr, reached);          // src = 0: nothing is reached, nothing written
+            nav_timed_flood<P>(img, cells, r, W, HW * P, fr, reached);
+            nav_wave_sync();
+            for (int i = s0 + r; i < s1; i += 32) {
+                const int c = st.cell[i], ph = s_phase[i];
+                uint32_t d = MG_NAV_UNREACHABLE, m = 0;
+                if (env >= 0 && c != NAV_NO_CELL)
+                    m = nav_move_set<true>(img + ph * cells, img + (ph + 1 == P ? 0 : ph + 1) * cells, c, W, H, d);
+                nav_goal_label(st, g, i, m, d);
+            }
+            nav_wave_sync();                                                // the labels are read before the image is reset
+        }
+    }
+    __syncthreads();
+    nav_goal_store(st, g, M, moves, acting_dist);
+}
+
+using nav_timed_goal_kernel_t = decltype(&mg_nav_timed_goal_kernel<1>);
+template <int... Ps> constexpr nav_timed_goal_kernel_t nav_timed_goal_kernel_of[] = {mg_nav_timed_goal_kernel<Ps + 1>...};
+constexpr const nav_timed_goal_kernel_t *nav_timed_goal_kernels =          // [P - 1]
+    nav_timed_goal_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
 
@@ -691,5 +862,38 @@ extern "C" int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int 
     hipLaunchKernelGGL(mg_nav_moves_kernel<true>, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
                        dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, period, n_envs, width, height,
                        reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_timed_goal_floods(int width, int height, int period)
+{
+    if (!nav_sides_ok(width, height) || period < 1 || period > NAV_MAX_PERIOD) return TW_E_ARG;
+    return nav_timed_goal_flooders(width * height, period);
+}
+
+extern "C" int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                       uint32_t pass_types, int flags, const uint32_t *blocked,
+                                       int64_t blocked_env_stride, int period, const int32_t *rec_t, const int32_t *rec_n,
+                                       const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
+                                       const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream)
+{
+    if (!type || !rec_t || !rec_n || !rec_goal || !pos || !moves || !age || !init_pos) return TW_E_ARG;
+    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
+    if (period < 1 || period > NAV_MAX_PERIOD || !blocked || ((uintptr_t)blocked & 3u)) return TW_E_ARG;
+    if (blocked_env_stride < 0 || (blocked_env_stride != 0 && blocked_env_stride < (int64_t)period * height)) return TW_E_ARG;
+    if (((uintptr_t)pos & 7u) || ((uintptr_t)acting_dist & 1u)) return TW_E_ARG;
+    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
+    if (((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (n_records == 0) return TW_OK;
+    const int HW = width * height, flooders = nav_timed_goal_flooders(HW, period);
+    const size_t lds = (size_t)flooders * period * nav_timed_cells(HW) * sizeof(uint16_t);
+    // chunks are counted from the aligned address below either output: up to 15 records more than n_records
+    hipLaunchKernelGGL(nav_timed_goal_kernels[period - 1],
+                       dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)), dim3(NAV_GOAL_THREADS), lds,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       blocked, blocked_env_stride, rec_t, rec_n, rec_goal, n_records,
+                       reinterpret_cast<const float2 *>(pos), age, init_pos, T, moves, acting_dist, flooders);
     return tw_launched(__func__);
 }

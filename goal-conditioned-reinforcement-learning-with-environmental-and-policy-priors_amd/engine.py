@@ -403,15 +403,21 @@ class TwoarmyEngine:
         their balls are passable, as in the static prior.  The other arguments as in distance_field."""
         from . import minigrid_nav as nav
         ty, _, ag = self._views()
-        key = (bool(avoid_risk), ty.device)
+        blocked = self._schedule(avoid_risk, ty.device)
+        clock = ag[0].as_strided(ag[0].shape, ag[0].stride(), ag[0].storage_offset() + FIELDS["STEP_MOVE"] - FIELDS["AX"])
+        return nav.timed_field(ty, None, 17, 17, blocked, nav.PASS_DEFAULT | nav.PASS_BALL, goal=goal,
+                               agent=ag[:2] if agent else None, clock=clock if agent else None, out=out,
+                               want_field=want_field, agent_out=agent_out, error_out=error_out)
+
+    def _schedule(self, avoid_risk, device):
+        """The cached minigrid_nav.twoarmy_schedule of this variant on `device`."""
+        from . import minigrid_nav as nav
+        key = (bool(avoid_risk), device)
         if getattr(self, "_schedules", None) is None:
             self._schedules = {}
         if key not in self._schedules:
-            self._schedules[key] = nav.twoarmy_schedule(avoid_risk, blocks=self.variant == 6, device=ty.device)
-        clock = ag[0].as_strided(ag[0].shape, ag[0].stride(), ag[0].storage_offset() + FIELDS["STEP_MOVE"] - FIELDS["AX"])
-        return nav.timed_field(ty, None, 17, 17, self._schedules[key], nav.PASS_DEFAULT | nav.PASS_BALL, goal=goal,
-                               agent=ag[:2] if agent else None, clock=clock if agent else None, out=out,
-                               want_field=want_field, agent_out=agent_out, error_out=error_out)
+            self._schedules[key] = nav.twoarmy_schedule(avoid_risk, blocks=self.variant == 6, device=device)
+        return self._schedules[key]
 
     def goal_moves(self, her, pos, age=None, init_pos=None, pass_types=None, out=None, dist_out=None):
         """Optimal-move sets of hindsight records under their own goals in the engine's worlds as they stand
@@ -424,6 +430,24 @@ class TwoarmyEngine:
         return nav.goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17,
                               nav.PASS_DEFAULT if pass_types is None else pass_types, age=age, init_pos=init_pos, out=out,
                               dist_out=dist_out)
+
+    def timed_goal_moves(self, her, pos, age, init_pos, avoid_risk=False, out=None, dist_out=None):
+        """goal_moves over (cell, phase): the optimal-move sets of hindsight records under their own goals with the
+        row-8 balls planned by their period-6 schedule (minigrid_nav.timed_goal_moves, one launch, read from the
+        engine's own planes, no field in memory) -> (moves uint8[R], acting_dist uint16[R]).  her, pos, age and
+        init_pos as goal_moves takes them, age and init_pos required: the age of a step is its clock, as in
+        minigrid_nav.timed_moves.  The stay bit off the goal means "wait one step".  The schedule is the one
+        timed_field() caches (avoid_risk as there), the plane's own balls are passable (PASS_BALL).
+        v6: the two constant 2x2 wall blocks are planned as present from the reset on, as in timed_field().  That
+        stays exact for hindsight goals inside the start corner as well: no block cell touches a corner cell, and a
+        shortest path between two cells of the corner stays inside the corner rectangle, so the labels of a record that
+        acts before the blocks have dropped, towards a goal it reached before they dropped, do not see them; every other
+        record's path leaves the corner and meets the blocks in place.  v4: the caveat of timed_field() holds unchanged
+        (blocks as they stand, patrols not scheduled)."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        return nav.timed_goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17, self._schedule(avoid_risk, ty.device),
+                                    age, init_pos, nav.PASS_DEFAULT | nav.PASS_BALL, out=out, dist_out=dist_out)
 
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""

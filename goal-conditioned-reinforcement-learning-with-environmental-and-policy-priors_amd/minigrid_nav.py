@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._marshal import agent_arrays, call, ptr, rows
+from ._marshal import agent_arrays, call, ptr, query, rows
 
 MAX_SIDE = 32
 MAX_PERIOD = 16                       # timed_field: phases of a schedule
@@ -245,6 +245,52 @@ def timed_moves(dist, pos, width, height, age, init_pos, out=None, dist_out=None
     call("mg_nav_timed_moves", dev, _marshal_ptr(dist), int(dpitch), P, N, W, H, ptr(pos), ptr(age, torch.int32),
          ptr(init_pos, torch.float32), T, ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
     return out, dist_out
+
+
+def timed_goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blocked, age, init_pos,
+                     pass_types=PASS_DEFAULT, state=None, doors_open=False, out=None, dist_out=None):
+    """goal_moves for a world whose blockers move with a period (mg_nav_timed_goal_moves, include/minigrid_nav.h): the
+    planes, the records (rec_t, rec_n int32[R], rec_goal float32[R, 2] = (y, x)) and pos float32[T, N, 2] as goal_moves
+    takes them, blocked int32 / uint32 [P, H] or [N, P, H] as timed_field takes it, age int32[T, N] (the clock as well: the
+    phase of a record is age[t, n] <= 0 ? 0 : age[t, n] % P) and init_pos float32[2], both required.
+    -> (moves uint8[R], acting_dist uint16[R]): per record what timed_moves gives in the time-expanded field of the
+    record's env flooded from the record's goal cell -- bits 0..3 = the move leads one transition nearer, MOVE_STAY = on
+    the goal, or waiting is optimal; 0 / UNREACHABLE for a record whose t, n, goal or acting position names nothing,
+    whose goal cell is free at no phase or whose state has no path.  out / dist_out as in goal_moves.  One launch (none
+    for R = 0), no field in memory, no host synchronisation."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state is None or state.shape == (N, W * H)
+    dev = type_plane.device
+    bp, bstride, P = _schedule(blocked, N, H, dev)
+    R = rec_t.shape[0]
+    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
+    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
+    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
+    T = pos.shape[0]
+    assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
+    assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    if out is None:
+        out = torch.empty((R,), dtype=torch.uint8, device=dev)
+    assert out.shape == (R,) and out.device == dev
+    if dist_out is None:
+        dist_out = torch.empty((R,), dtype=DIST_DTYPE, device=dev)
+    elif dist_out is False:
+        dist_out = None
+    assert dist_out is None or (dist_out.shape == (R,) and dist_out.device == dev)
+    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, dist_out
+    call("mg_nav_timed_goal_moves", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
+         DOORS_OPEN if doors_open else 0, bp, bstride, P, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32),
+         ptr(rec_goal, torch.float32), R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
+         ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+def timed_goal_floods(width, height, period):
+    """How many of a workgroup's 8 half wavefronts flood at a time in timed_goal_moves at this size and period (8, 4, 2
+    or 1: their images share 64 KiB of LDS with the staging) -- the launch's own host function."""
+    return query("mg_nav_timed_goal_floods", int(width), int(height), int(period))
 
 
 TWOARMY_PERIOD = 6

@@ -557,7 +557,7 @@ class VecPPOTrainer:
                 "mean": v[4] / v[3] if v[3] else None, "cut_off": v[5]}
 
     # ------------------------------------------------------------------ shortest-path prior
-    def enable_prior(self, coef, decay=1.0, hindsight=False, timed=False):
+    def enable_prior(self, coef, decay=1.0, hindsight=False, timed=False, hindsight_timed=False):
         """Train the actor with the shortest-path prior: update() adds coef * decay^(updates done) times the set-valued
         imitation term (ppo_ops.prior_loss) over the optimal-move sets label_expert() makes to the actor's loss of every
         minibatch.  Rewards, returns, targets, advantages, the critic, the running score and the HER switch are
@@ -566,13 +566,18 @@ class VecPPOTrainer:
         hindsight records of relabel() are labelled too, each under its own goal (one mg_nav_goal_moves launch in
         label_expert()), and enter the term with those labels instead of an empty mask.  timed=True: the rollout's own
         labels come from the time-expanded search (TwoarmyEngine.timed_field, mg_nav_timed_moves): the row-8 balls follow
-        their schedule and "wait one step" (the stay bit, policy index 4) is a label where the gap is closed; the
-        hindsight labels stay those of the static map."""
+        their schedule and "wait one step" (the stay bit, policy index 4) is a label where the gap is closed; this
+        switch leaves the hindsight labels those of the static map.  hindsight_timed=True (needs hindsight=True,
+        independent of timed): the hindsight records are labelled by the time-expanded search under their own goals
+        instead (one mg_nav_timed_goal_moves launch in place of the mg_nav_goal_moves one), the age of a step being its
+        clock."""
         import inspect
+        if hindsight_timed and not hindsight:
+            raise ValueError("enable_prior(hindsight_timed=True) needs hindsight=True")
         if "probs_out" not in inspect.signature(self.agent.act_batch).parameters or self.cache_predictions:
             raise ValueError("the shortest-path prior needs the plain PPO agent's act_batch")
         self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0, "hindsight": bool(hindsight),
-                      "timed": bool(timed)}
+                      "timed": bool(timed), "hindsight_timed": bool(hindsight_timed)}
         self.timed_field = None               # uint16[N, 6, 289], made by the first label_expert() with timed=True
         self.her_moves = self.her_dist = self._her_moves_of = None
         self.act_probs = torch.zeros((self.T, self.N, 5), dtype=torch.float32, device=self.device)
@@ -593,7 +598,10 @@ class VecPPOTrainer:
         mg_nav_goal_moves launch more labels every hindsight record under its own goal, on the engine's planes as they
         stand and the same static map; `her_moves` uint8[R] and `her_dist` uint16[R] afterwards.  No host
         synchronisation.  With enable_prior(timed=True) the field is TwoarmyEngine.timed_field's (six phases per env, the
-        engine's planes as they stand) and the labels are mg_nav_timed_moves', the age of a step being its clock."""
+        engine's planes as they stand) and the labels are mg_nav_timed_moves', the age of a step being its clock.  With
+        enable_prior(hindsight_timed=True) the launch over the hindsight records is mg_nav_timed_goal_moves instead
+        (TwoarmyEngine.timed_goal_moves): the same records, positions, ages and reset position, the balls on their
+        schedule."""
         from .. import minigrid_nav as nav
         T, N = self.T, self.N
         timed = self.prior is not None and self.prior["timed"]
@@ -613,8 +621,12 @@ class VecPPOTrainer:
         self._moves_at = self.env_steps
         self.her_moves = self.her_dist = self._her_moves_of = None
         if self.prior is not None and self.prior["hindsight"] and self.her is not None and self.her["t"].numel():
-            self.her_moves, self.her_dist = self.engine.goal_moves(
-                self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL)
+            if self.prior["hindsight_timed"]:
+                self.her_moves, self.her_dist = self.engine.timed_goal_moves(
+                    self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos)
+            else:
+                self.her_moves, self.her_dist = self.engine.goal_moves(
+                    self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL)
             self._her_moves_of = self.her                     # these labels belong to these records
         return self.expert_moves
 

@@ -20,6 +20,8 @@ trains on those labels too and appends `her agree`; off by default.
 --prior_timed (with either) takes the rollout's labels from the time-expanded search instead: the row-8 balls follow their
 period-6 schedule and "wait one step" is a label where the gap is closed (minigrid_nav.timed_field / timed_moves: the
 same two launches per rollout); off by default.
+--prior_hindsight_timed (with --prior_hindsight) labels the hindsight records by the time-expanded search too, each under
+its own goal (minigrid_nav.timed_goal_moves in place of goal_moves: still one launch per rollout); off by default.
 """
 import argparse
 import os
@@ -121,7 +123,11 @@ def build_parser():
     p.add_argument("--prior_timed", action="store_true",
                    help="with --prior_coef / --expert_agreement: label the rollout with the time-expanded expert, which "
                         "plans the row-8 balls by their period-6 schedule and waits for the gap instead of walking into "
-                        "a ball; the hindsight labels stay those of the static map")
+                        "a ball; the hindsight labels stay those of the static map unless --prior_hindsight_timed is given")
+    p.add_argument("--prior_hindsight_timed", action="store_true",
+                   help="with --prior_hindsight: label the hindsight records with the time-expanded expert as well, each "
+                        "under its own goal (a relabelled record is no longer taught to step into a row-8 ball); "
+                        "independent of --prior_timed")
     return p
 
 
@@ -199,6 +205,8 @@ def main(argv=None, predictor=False, soa=False):
     args = build_parser().parse_args(argv)
     if args.prior_hindsight and not (args.prior_coef != 0.0 or args.expert_agreement):
         raise SystemExit("--prior_hindsight needs --prior_coef or --expert_agreement")
+    if args.prior_hindsight_timed and not args.prior_hindsight:
+        raise SystemExit("--prior_hindsight_timed needs --prior_hindsight")
     if args.prior_timed and not (args.prior_coef != 0.0 or args.expert_agreement):
         raise SystemExit("--prior_timed needs --prior_coef or --expert_agreement")
     from .. import dist as twdist
@@ -260,7 +268,8 @@ def main(argv=None, predictor=False, soa=False):
     if use_prior:
         if predictor or soa:
             raise SystemExit("--prior_coef / --expert_agreement: plain PPO agent only")
-        trainer.enable_prior(args.prior_coef, args.prior_decay, hindsight=args.prior_hindsight, timed=args.prior_timed)
+        trainer.enable_prior(args.prior_coef, args.prior_decay, hindsight=args.prior_hindsight, timed=args.prior_timed,
+                             hindsight_timed=args.prior_hindsight_timed)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):

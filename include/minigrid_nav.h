@@ -198,6 +198,52 @@ int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int period, int
                        const float *pos, const int32_t *age, const float *init_pos, int T, uint8_t *moves,
                        uint16_t *acting_dist, void *stream);
 
+/* mg_nav_goal_moves over (cell, phase): the timed move sets of records that each name their OWN goal (hindsight records
+ * of a world whose blockers move).  One launch floods the goal of every run of records over (cell, phase) on the device
+ * and labels the run; no field reaches memory.
+ *   type, state, n_envs, width, height, pass_types, flags: the world, its moves, its enterable cells and the over-read
+ *                 rule exactly as in mg_nav_field (state nullable)
+ *   blocked, blocked_env_stride, period: the schedule; free cells, transition, distance, phase from the clock, move set
+ *                 and stay bit exactly as in the "time-expanded fields" block above
+ *   rec_t, rec_n, rec_goal, n_records, pos, age, init_pos, T: the records and the acting positions exactly as in
+ *                 mg_nav_goal_moves, except that age and init_pos are REQUIRED, as in mg_nav_timed_moves, and
+ *                 age[t][n] is also the record's clock (t = rec_t[b], n = rec_n[b])
+ * Per record: the result of record b depends on record b alone, never on its neighbours, the order of the records or how
+ * they are grouped.  Let F be what mg_nav_timed_field computes for env rec_n[b] with the record's goal cell (visit_cell
+ * of rec_goal[b]) as its single source -- a source is 0 in every phase in which it is free.  moves[b] and acting_dist[b]
+ * are what mg_nav_timed_moves gives in F for the acting cell (age[t][n] <= 0 ? init_pos : pos[t][n], by the rule of the
+ * visit counters) at the phase of age[t][n]: bits 0..3 set iff that neighbour lies inside the world and one transition
+ * nearer at the next phase, bit MG_NAV_MOVE_STAY_BIT iff the distance is 0 (then alone) or waiting is optimal.
+ * moves[b] = 0 and acting_dist[b] = MG_NAV_UNREACHABLE when rec_t[b] is outside [0, T), rec_n[b] is outside
+ * [0, n_envs), the goal is no cell (NaN, +-inf, outside the world), the goal cell is free at no phase, the acting
+ * position is no cell, or the state is unreachable (the acting cell is not free at its phase, or no path exists).  No
+ * such record addresses any memory outside its arrays.
+ *   moves uint8[n_records];  acting_dist uint16[n_records] (nullable)
+ * Invariants: (a) for records that share one goal per env the outputs equal mg_nav_timed_field(goal_x, goal_y) followed
+ * by mg_nav_timed_moves on the same positions; (b) with period = 1 and an all-zero schedule the outputs equal
+ * mg_nav_goal_moves'.
+ * One launch, no atomics; n_records == 0 returns 0 and launches nothing.  A workgroup owns 1024 consecutive records and
+ * floods once per run of equal (env, goal cell) among them -- the phase is no part of the key, one flood serves the
+ * records of every phase -- so records in ppo_her_relabel's emission order cost the fewest floods; the results do not
+ * depend on it.  A flood ends after at most width*height*P rounds whatever the input.  Every (width, height, period)
+ * the limits allow works: how many of a workgroup's 8 half wavefronts flood at a time (mg_nav_timed_goal_floods) follows
+ * from the size of one image, P * width*height distances.
+ * Reads and writes as in mg_nav_goal_moves: the planes by the over-read rule, both outputs as aligned 16-byte stores,
+ * element by element only in the first and last chunk of a workgroup's share; moves needs no alignment, and nothing
+ * outside the first n_records elements of either output is written.
+ * TW_E_ARG: the cases of mg_nav_goal_moves; NULL age or init_pos; period outside 1..MG_NAV_MAX_PERIOD; NULL or
+ * misaligned blocked; blocked_env_stride < 0 or 0 < blocked_env_stride < P*height. */
+int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                            uint32_t pass_types, int flags, const uint32_t *blocked, int64_t blocked_env_stride,
+                            int period, const int32_t *rec_t, const int32_t *rec_n, const float *rec_goal,
+                            int64_t n_records, const float *pos, const int32_t *age, const float *init_pos, int T,
+                            uint8_t *moves, uint16_t *acting_dist, void *stream);
+
+/* Host only, no launch: how many floods a workgroup of mg_nav_timed_goal_moves runs at a time at this size and period --
+ * 8, 4, 2 or 1, the most whose images fit 64 KiB of LDS next to the workgroup's staging (32 x 32 with P = 16: 1).
+ * TW_E_ARG: a side <= 0 or > MG_NAV_MAX_SIDE, period outside 1..MG_NAV_MAX_PERIOD. */
+int mg_nav_timed_goal_floods(int width, int height, int period);
+
 #ifdef __cplusplus
 }
 #endif

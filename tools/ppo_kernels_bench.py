@@ -113,6 +113,12 @@ h_s = timed(lambda: h_eng.goal_moves(her, h_pos, h_age, h_tr.init_pos, pass_type
 report("mg_nav_goal_moves (%d hindsight records of a 4096 x 128 rollout, %d heads)" % (R, n_heads),
        R * (4 + 4 + 8 + 8 + 4 + 1 + 2) + N * 289, h_s,
        "one launch; %d records, %d heads, %.1f floods per us" % (R, n_heads, n_heads / (h_s * 1e6)))
+# The same records labelled over (cell, phase): six phases per flood, the balls on their schedule.  The row above, taken
+# in the same process on the same records, is the yardstick.
+ht_s = timed(lambda: h_eng.timed_goal_moves(her, h_pos, h_age, h_tr.init_pos, out=hm_out, dist_out=hd_out))
+report("mg_nav_timed_goal_moves (the same %d records, %d heads, P = 6)" % (R, n_heads),
+       R * (4 + 4 + 8 + 8 + 4 + 1 + 2) + N * 289, ht_s,
+       "one launch; %.1f floods per us, %.2f x mg_nav_goal_moves" % (n_heads / (ht_s * 1e6), ht_s / h_s))
 h_eng.close()
 del h_tr, h_eng, her
 mv_flat = torch.randint(0, 32, (T * N,), generator=g, dtype=torch.uint8).to(dev)
