@@ -33,8 +33,17 @@
  *                          phase is no part of a run's key, one flood serves every phase.  A flooding half wavefront owns
  *                          an image of P * W*H distances in dynamic LDS, and as many halves flood at a time (8, 4, 2 or 1)
  *                          as fit 64 KiB next to the staging; the other wavefronts skip the flood loop whole.
+ *   mg_nav_shape_kernel    potential-based reward shaping of a rollout (minigrid_nav.h, "Reward shaping"): the moves
+ *                          kernel's shape -- a workgroup owns NAV_MOVES_ELEMS (step, env) elements, gathers the distances of
+ *                          the acting and the after-step state from the env's field, parks shaped reward, shaping term and
+ *                          mask in LDS and stores each as the chunks of its own alignment.  It reads `reward` for the
+ *                          elements it stores only, before the barrier: shaping in place is safe.
+ *   mg_nav_goal_shape_kernel   the same for records under goals of their own: the goal kernel's keys, heads and floods
+ *                          (nav_goal_keys, nav_goal_heads, nav_goal_floods: written once, the labelling is a parameter),
+ *                          a record also keeps its after-step cell; three float operations per record.
  *
- * Integer work only, no atomics: the results do not depend on scheduling.
+ * Integer work only but for the shaping term (three float32 operations, each rounded once: fp contract off), no atomics:
+ * the results do not depend on scheduling.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -354,10 +363,12 @@ __device__ __forceinline__ nav_goal_share_t nav_goal_share(const uint8_t *moves,
 
 // Keys and acting cells: every global read of a record happens here, one record per lane and round; __syncthreads() after.
 // TIMED: age is given and is the record's clock too; its phase goes into s_phase (0 for a record without a result).
-template <bool TIMED> __device__ __forceinline__ void nav_goal_keys(
-    nav_goal_stage_t &st, uint8_t *s_phase, const nav_goal_share_t &g, int N, int W, int H, int P,
+// G: the workgroup's records (p0, slot_lo, slot_hi).  more(i, p, at): what else a kernel keeps of the record p in slot i,
+// at = its element t * N + n, or -1 for a record without a result.
+template <bool TIMED, typename G, typename More> __device__ __forceinline__ void nav_goal_keys(
+    nav_goal_stage_t &st, uint8_t *s_phase, const G &g, int N, int W, int H, int P,
     const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal,
-    const float2 *__restrict__ pos, const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T)
+    const float2 *__restrict__ pos, const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T, More more)
 {
     const int tid = threadIdx.x, HW = W * H;
     float2 init = make_float2(0.f, 0.f);
@@ -370,8 +381,9 @@ template <bool TIMED> __device__ __forceinline__ void nav_goal_keys(
         const int t = rec_t[p], n = rec_n[p];
         const int gc = visit_cell(rec_goal[2 * p], rec_goal[2 * p + 1], W, H);   // (y, x); 4-byte aligned: two loads
         int env = -1, ac = NAV_NO_CELL, ph = 0;
+        int64_t at = -1;
         if (t >= 0 && t < T && n >= 0 && n < N && gc < HW) {
-            const int64_t at = (int64_t)t * N + n;
+            at = (int64_t)t * N + n;
             float2 q = pos[at];
             const int clock = age != nullptr ? age[at] : 1;
             if (clock <= 0) q = init;
@@ -384,13 +396,16 @@ template <bool TIMED> __device__ __forceinline__ void nav_goal_keys(
         st.goal[i] = (uint16_t)gc;
         st.cell[i] = (uint16_t)ac;
         if (TIMED) s_phase[i] = (uint8_t)ph;
+        more(i, p, at);
     }
     __syncthreads();
 }
 
+__device__ __forceinline__ void nav_goal_no_more(int, int64_t, int64_t) {}
+
 // Heads (records whose (env, goal cell) differs from their predecessor's, and the first one), counted per wavefront and
 // round (the round's ballot stays in registers), then listed in st.head in ascending order; -> their number.
-__device__ __forceinline__ int nav_goal_heads(nav_goal_stage_t &st, const nav_goal_share_t &g)
+template <typename G> __device__ __forceinline__ int nav_goal_heads(nav_goal_stage_t &st, const G &g)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned long long heads[NAV_GOAL_ROUNDS];
@@ -445,23 +460,15 @@ __device__ __forceinline__ void nav_goal_store(const nav_goal_stage_t &st, const
                          [&](int64_t q) { return st.dist[(int)(q - g.bd)]; });
 }
 
-__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
-    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
-    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
-    const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos, const int32_t *__restrict__ age,
-    const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+// One head per half wavefront and round: flood its goal into the half's image `img`, then label(i, img, ok) every record
+// (slot i) of its run; ok = the run has a result at all.  Both halves of a wavefront go round together, and EVERY lane of
+// the workgroup calls this.  What label() parks in LDS is ordered before the next flood; __syncthreads() before the stores.
+template <typename Label> __device__ __forceinline__ void nav_goal_floods(
+    const nav_goal_stage_t &st, uint16_t *img, int n_heads, const uint8_t *__restrict__ type,
+    const uint8_t *__restrict__ state, int W, int H, uint32_t pass_types, int doors_open, Label label)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
-    __shared__ nav_goal_stage_t st;
     const int tid = threadIdx.x, r = tid & 31, half = tid >> 5;
-    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
     const int HW = W * H;
-
-    nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos, age, init_pos, T);
-    const int n_heads = nav_goal_heads(st, g);
-
-    // one head per half wavefront and round: flood its goal, label its run.  Both halves of a wavefront go round together.
-    uint16_t *img = image[half];
     const int per = (n_heads + NAV_GOAL_HALVES - 1) / NAV_GOAL_HALVES;
     const int j_end = (half + 1) * per < n_heads ? (half + 1) * per : n_heads;
     int cur_env = -1;
@@ -487,14 +494,30 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
         nav_wave_sync();                                                    // before other lanes write steps into it
         nav_flood(img, r, W, HW, env >= 0 ? open : 0u, reached);
         nav_wave_sync();
-        for (int i = s0 + r; i < s1; i += 32) {
-            const int c = st.cell[i];
-            uint32_t d = MG_NAV_UNREACHABLE, m = 0;
-            if (env >= 0 && c != NAV_NO_CELL) m = nav_move_set(img, img, c, W, H, d);
-            nav_goal_label(st, g, i, m, d);
-        }
+        for (int i = s0 + r; i < s1; i += 32) label(i, img, env >= 0);
         nav_wave_sync();                                                    // the labels are read before the image is reset
     }
+}
+
+__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
+    const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos, const int32_t *__restrict__ age,
+    const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
+    __shared__ nav_goal_stage_t st;
+    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
+
+    nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
+    const int n_heads = nav_goal_heads(st, g);
+    nav_goal_floods(st, image[threadIdx.x >> 5], n_heads, type, state, W, H, pass_types, doors_open,
+                    [&](int i, const uint16_t *img, bool ok) {
+                        const int c = st.cell[i];
+                        uint32_t d = MG_NAV_UNREACHABLE, m = 0;
+                        if (ok && c != NAV_NO_CELL) m = nav_move_set(img, img, c, W, H, d);
+                        nav_goal_label(st, g, i, m, d);
+                    });
     __syncthreads();
     nav_goal_store(st, g, M, moves, acting_dist);
 }
@@ -682,7 +705,7 @@ template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_time
     const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
     const int HW = W * H, cells = nav_timed_cells(HW);
 
-    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos, age, init_pos, T);
+    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
     const int n_heads = nav_goal_heads(st, g);
 
     // One head per flooding half wavefront and round.  Whole wavefronts enter or skip the loop: one goes round when its
@@ -740,7 +763,209 @@ template <int... Ps> constexpr nav_timed_goal_kernel_t nav_timed_goal_kernel_of[
 constexpr const nav_timed_goal_kernel_t *nav_timed_goal_kernels =          // [P - 1]
     nav_timed_goal_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
+// ------------------------------------------------------------------ potential-based reward shaping from the fields
+// The three float operations of minigrid_nav.h ("Reward shaping"), each rounded once: nothing here may fuse.
+__device__ __forceinline__ float nav_phi(float scale, uint32_t d)
+{
+#pragma clang fp contract(off)
+    if (d == 0u) return 0.0f;
+    const float m = scale * (float)d;
+    return -m;
+}
+__device__ __forceinline__ float nav_shaping(float gamma, float phi_after, float phi_before)
+{
+#pragma clang fp contract(off)
+    const float g = gamma * phi_after;
+    return g - phi_before;
+}
+__device__ __forceinline__ float nav_shaped(float reward, float F)
+{
+#pragma clang fp contract(off)
+    return reward + F;
+}
+
+// F of a pair of distances and whether the element is shaped at all; terminal: phi_after = 0 whatever d_after is.
+__device__ __forceinline__ bool nav_shape_term(uint32_t d_before, uint32_t d_after, bool terminal, float scale, float gamma,
+                                               float &F)
+{
+    F = 0.0f;
+    if (d_before == (uint32_t)MG_NAV_UNREACHABLE || (!terminal && d_after == (uint32_t)MG_NAV_UNREACHABLE)) return false;
+    F = nav_shaping(gamma, terminal ? 0.0f : nav_phi(scale, d_after), nav_phi(scale, d_before));
+    return true;
+}
+
+// One output of a shaping kernel (E elements per 16-byte chunk): a workgroup's chunks of it, the elements they hold and
+// the element of slot 0 of its LDS staging, as mg_nav_moves_kernel keeps them for `moves` and `acting_dist`.
+struct nav_out_span_t {
+    mg_row_span_t<int64_t> k;
+    int64_t base;
+    bool has;                                           // the output is given and the workgroup holds some of it
+    __device__ __forceinline__ bool holds(int64_t p) const { return has && p >= k.p_lo && p < k.p_hi; }
+};
+template <typename T> __device__ __forceinline__ nav_out_span_t nav_out_span(const T *out, int64_t M, int64_t b, int elems)
+{
+    constexpr int E = 16 / sizeof(T);
+    const int s = out ? mg_row_misalign(out, E) : 0;
+    nav_out_span_t o;
+    o.k = mg_row_span<int64_t>(s, M, b, elems / E, E);
+    o.base = E * o.k.c0 - s;
+    o.has = out != nullptr && o.k.c0 < o.k.c1;
+    return o;
+}
+// the staged elements leave through the aligned row store; after a __syncthreads()
+template <typename T> __device__ __forceinline__ void nav_out_store(T *__restrict__ out, int64_t M, const nav_out_span_t &o,
+                                                                    const T *staged, int threads)
+{
+    if (!o.has) return;
+    for (int64_t c = o.k.c0 + threadIdx.x; c < o.k.c1; c += threads)
+        mg_row_store(out, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(staged + (int)(p - o.base)); },
+                     [&](int64_t q) { return staged[(int)(q - o.base)]; });
+}
+
+static_assert(NAV_MOVES_ELEMS % 16 == 0 && NAV_MOVES_ELEMS % 4 == 0, "whole chunks of the float outputs and of the mask");
+
+// TIMED: dist holds P fields per env and the phases come from the element's age; done is given iff the terminal rule is on.
+template <bool TIMED> __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_shape_kernel(
+    const uint16_t *__restrict__ dist, int64_t pitch, int P, int N, int W, int H, const float2 *__restrict__ pos_before,
+    const float2 *__restrict__ pos_after, const int32_t *__restrict__ age, const float *__restrict__ init_pos,
+    const uint8_t *__restrict__ done, const float *reward, int64_t M, float scale, float gamma, float *reward_out,
+    float *__restrict__ shaping, uint8_t *__restrict__ mask)
+{
+    __shared__ __attribute__((aligned(16))) float s_out[NAV_MOVES_ELEMS];
+    __shared__ __attribute__((aligned(16))) float s_f[NAV_MOVES_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint8_t s_mask[NAV_MOVES_ELEMS];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    // this workgroup's chunks of each output and the elements they hold: all within [ELEMS * b - 15, ELEMS * (b + 1))
+    const nav_out_span_t so = nav_out_span(reward_out, M, b, NAV_MOVES_ELEMS);
+    const nav_out_span_t sf = nav_out_span(shaping, M, b, NAV_MOVES_ELEMS);
+    const nav_out_span_t sm = nav_out_span(mask, M, b, NAV_MOVES_ELEMS);
+    const int HW = W * H;
+    float2 init = make_float2(0.f, 0.f);
+    if (age != nullptr) init = make_float2(init_pos[0], init_pos[1]);
+
+    const int64_t p0 = (int64_t)NAV_MOVES_ELEMS * b - 16;
+#pragma unroll 1
+    for (int k = 0; k < NAV_MOVES_ROUNDS; ++k) {
+        const int64_t p = p0 + k * NAV_MOVES_THREADS + tid;
+        const bool in_o = so.holds(p), in_f = sf.holds(p), in_m = sm.holds(p);
+        if (!(in_o || in_f || in_m)) continue;                              // every span lies inside [0, M)
+        float2 q = pos_before[p];
+        const float2 qa = pos_after[p];
+        const int clock = age != nullptr ? age[p] : 1;
+        if (clock <= 0) q = init;
+        const int cb = visit_cell(q.x, q.y, W, H), ca = visit_cell(qa.x, qa.y, W, H);
+        const bool terminal = done != nullptr && done[p] != 0;
+        const uint16_t *fb = dist + (int64_t)(p % N) * P * pitch, *fa = fb;
+        if (TIMED) {                                                        // the after state's clock is max(clock, 0) + 1
+            const int ph = nav_phase(clock, P);
+            fb += ph * pitch;
+            fa += (ph + 1 >= P ? 0 : ph + 1) * pitch;
+        }
+        const uint32_t db = cb < HW ? fb[cb] : (uint32_t)MG_NAV_UNREACHABLE;
+        const uint32_t da = ca < HW && !terminal ? fa[ca] : (uint32_t)MG_NAV_UNREACHABLE;
+        float F;
+        const bool shaped = nav_shape_term(db, da, terminal, scale, gamma, F);
+        if (in_o) {                                                         // read before the barrier, by the workgroup that
+            const float r = reward[p];                                      // stores it: reward_out may be reward itself
+            s_out[(int)(p - so.base)] = shaped ? nav_shaped(r, F) : r;
+        }
+        if (in_f) s_f[(int)(p - sf.base)] = F;
+        if (in_m) s_mask[(int)(p - sm.base)] = shaped ? 1 : 0;
+    }
+    __syncthreads();
+    nav_out_store(reward_out, M, so, s_out, NAV_MOVES_THREADS);
+    nav_out_store(shaping, M, sf, s_f, NAV_MOVES_THREADS);
+    nav_out_store(mask, M, sm, s_mask, NAV_MOVES_THREADS);
+}
+
+// What the goal kernel's staging lacks for shaping: the after-step cell of a record and the three outputs on their way out.
+constexpr uint16_t NAV_TERMINAL = 0xFFFE;               // an after-step "cell": the terminal rule applies, phi_after = 0
+struct nav_goal_shape_stage_t {
+    alignas(16) float out[NAV_GOAL_ELEMS];              // the record's reward from the keys on, shaped by its label
+    alignas(16) float f[NAV_GOAL_ELEMS];
+    alignas(16) uint8_t mask[NAV_GOAL_ELEMS];
+    uint16_t after[NAV_GOAL_SLOTS];                     // NAV_NO_CELL where the position is none, NAV_TERMINAL
+};
+static_assert(NAV_CELLS < NAV_TERMINAL, "the two marks are no cells");
+static_assert(sizeof(nav_goal_stage_t) + sizeof(nav_goal_shape_stage_t) + NAV_GOAL_HALVES * NAV_CELLS * sizeof(uint16_t) + 64
+                  <= 64 * 1024, "the staging of a shaping workgroup fits 64 KiB next to its 8 images");
+
+// a shaping workgroup's records: those of its three spans (nav_goal_keys, nav_goal_heads)
+struct nav_goal_shape_share_t {
+    nav_out_span_t so, sf, sm;
+    int64_t p0;                                         // record of slot 0 of the key arrays
+    int slot_lo, slot_hi;                               // 0 < slot_lo <= slot_hi <= SLOTS, or both 0: no record
+};
+
+__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_shape_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
+    const float *__restrict__ rec_goal, const uint8_t *__restrict__ rec_done, const float *rec_reward, int64_t M,
+    const float2 *__restrict__ pos_before, const float2 *__restrict__ pos_after, const int32_t *__restrict__ age,
+    const float *__restrict__ init_pos, int T, float scale, float gamma, float *reward_out, float *__restrict__ shaping,
+    uint8_t *__restrict__ mask)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
+    __shared__ nav_goal_stage_t st;
+    __shared__ nav_goal_shape_stage_t sh;
+    const int64_t b = blockIdx.x;
+    const int HW = W * H;
+    nav_goal_shape_share_t g;
+    g.so = nav_out_span(reward_out, M, b, NAV_GOAL_ELEMS);
+    g.sf = nav_out_span(shaping, M, b, NAV_GOAL_ELEMS);
+    g.sm = nav_out_span(mask, M, b, NAV_GOAL_ELEMS);
+    g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
+    {
+        int64_t lo = M, hi = 0;                                             // the records of this workgroup: all three spans
+        auto join = [&](const nav_out_span_t &o) {
+            if (o.has) { lo = lo < o.k.p_lo ? lo : o.k.p_lo; hi = hi > o.k.p_hi ? hi : o.k.p_hi; }
+        };
+        join(g.so); join(g.sf); join(g.sm);
+        g.slot_lo = lo < hi ? (int)(lo - g.p0) : 0;
+        g.slot_hi = lo < hi ? (int)(hi - g.p0) : 0;
+    }
+
+    nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos_before, age, init_pos, T,
+                         [&](int i, int64_t p, int64_t at) {
+                             int a = NAV_NO_CELL;
+                             if (at >= 0) {
+                                 if (rec_done != nullptr && rec_done[p] != 0) a = NAV_TERMINAL;
+                                 else {
+                                     const float2 q = pos_after[at];
+                                     const int c = visit_cell(q.x, q.y, W, H);
+                                     if (c < HW) a = c;
+                                 }
+                             }
+                             sh.after[i] = (uint16_t)a;
+                             // read before the barrier, by the workgroup that stores it: reward_out may be rec_reward
+                             if (g.so.holds(p)) sh.out[(int)(p - g.so.base)] = rec_reward[p];
+                         });
+    const int n_heads = nav_goal_heads(st, g);
+    nav_goal_floods(st, image[threadIdx.x >> 5], n_heads, type, state, W, H, pass_types, doors_open,
+                    [&](int i, const uint16_t *img, bool ok) {
+                        const int64_t p = g.p0 + i;
+                        const int c = st.cell[i], a = sh.after[i];
+                        float F = 0.0f;
+                        bool shaped = false;
+                        if (ok && c != NAV_NO_CELL && a != NAV_NO_CELL)
+                            shaped = nav_shape_term(img[c], a == NAV_TERMINAL ? (uint32_t)MG_NAV_UNREACHABLE : img[a],
+                                                    a == NAV_TERMINAL, scale, gamma, F);
+                        if (shaped && g.so.holds(p)) {
+                            float &o = sh.out[(int)(p - g.so.base)];
+                            o = nav_shaped(o, F);
+                        }
+                        if (g.sf.holds(p)) sh.f[(int)(p - g.sf.base)] = F;
+                        if (g.sm.holds(p)) sh.mask[(int)(p - g.sm.base)] = shaped ? 1 : 0;
+                    });
+    __syncthreads();
+    nav_out_store(reward_out, M, g.so, sh.out, NAV_GOAL_THREADS);
+    nav_out_store(shaping, M, g.sf, sh.f, NAV_GOAL_THREADS);
+    nav_out_store(mask, M, g.sm, sh.mask, NAV_GOAL_THREADS);
+}
+
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
+bool nav_finite(float v) { return __builtin_isfinite(v); }
 
 }  // namespace
 
@@ -895,5 +1120,64 @@ extern "C" int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state
                        (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
                        blocked, blocked_env_stride, rec_t, rec_n, rec_goal, n_records,
                        reinterpret_cast<const float2 *>(pos), age, init_pos, T, moves, acting_dist, flooders);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_shape(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                            const float *pos_before, const float *pos_after, const int32_t *age, const float *init_pos,
+                            const uint8_t *done, const float *reward, int T, float scale, float gamma, int flags,
+                            float *reward_out, float *shaping, uint8_t *mask, void *stream)
+{
+    if (!dist || !pos_before || !pos_after || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (period < 1 || period > NAV_MAX_PERIOD || (period > 1 && (!age || !init_pos))) return TW_E_ARG;
+    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
+    if (((uintptr_t)dist & 1u) || ((uintptr_t)pos_before & 7u) || ((uintptr_t)pos_after & 7u)) return TW_E_ARG;
+    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    if (((uintptr_t)reward & 3u) || ((uintptr_t)reward_out & 3u) || ((uintptr_t)shaping & 3u)) return TW_E_ARG;
+    if (!reward_out && !shaping && !mask) return TW_E_ARG;
+    if (reward_out && !reward) return TW_E_ARG;
+    if ((flags & ~MG_NAV_SHAPE_ZERO_TERMINAL) || ((flags & MG_NAV_SHAPE_ZERO_TERMINAL) && !done)) return TW_E_ARG;
+    if (!nav_finite(scale) || !nav_finite(gamma)) return TW_E_ARG;
+    const int64_t M = (int64_t)T * n_envs;
+    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (M == 0) return TW_OK;
+    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
+    const uint8_t *ends = (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? done : nullptr;
+    // chunks are counted from the aligned address below each output: up to 15 positions more than M
+    const dim3 grid((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS));
+    hipLaunchKernelGGL(period > 1 ? mg_nav_shape_kernel<true> : mg_nav_shape_kernel<false>, grid, dim3(NAV_MOVES_THREADS), 0,
+                       (hipStream_t)stream, dist, pitch, period, n_envs, width, height,
+                       reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
+                       init_pos, ends, reward, M, scale, gamma, reward_out, shaping, mask);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                 uint32_t pass_types, int flags, const int32_t *rec_t, const int32_t *rec_n,
+                                 const float *rec_goal, const uint8_t *rec_done, const float *rec_reward,
+                                 int64_t n_records, const float *pos_before, const float *pos_after, const int32_t *age,
+                                 const float *init_pos, int T, float scale, float gamma, float *reward_out, float *shaping,
+                                 uint8_t *mask, void *stream)
+{
+    if (!type || !rec_t || !rec_n || !rec_goal || !pos_before || !pos_after) return TW_E_ARG;
+    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (pass_types > 0xFFFFu || (flags & ~(MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL))) return TW_E_ARG;
+    if (((uintptr_t)pos_before & 7u) || ((uintptr_t)pos_after & 7u)) return TW_E_ARG;
+    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
+    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    if (((uintptr_t)rec_reward & 3u) || ((uintptr_t)reward_out & 3u) || ((uintptr_t)shaping & 3u)) return TW_E_ARG;
+    if (!reward_out && !shaping && !mask) return TW_E_ARG;
+    if (reward_out && !rec_reward) return TW_E_ARG;
+    if ((flags & MG_NAV_SHAPE_ZERO_TERMINAL) && !rec_done) return TW_E_ARG;
+    if (!nav_finite(scale) || !nav_finite(gamma)) return TW_E_ARG;
+    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (n_records == 0) return TW_OK;
+    const uint8_t *ends = (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? rec_done : nullptr;
+    // chunks are counted from the aligned address below each output: up to 15 records more than n_records
+    hipLaunchKernelGGL(mg_nav_goal_shape_kernel, dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)),
+                       dim3(NAV_GOAL_THREADS), 0, (hipStream_t)stream, type, state, n_envs, width, height, pass_types,
+                       flags & MG_NAV_DOORS_OPEN, rec_t, rec_n, rec_goal, ends, rec_reward, n_records,
+                       reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
+                       init_pos, T, scale, gamma, reward_out, shaping, mask);
     return tw_launched(__func__);
 }

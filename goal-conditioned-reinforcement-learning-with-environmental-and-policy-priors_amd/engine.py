@@ -431,6 +431,20 @@ class TwoarmyEngine:
                               nav.PASS_DEFAULT if pass_types is None else pass_types, age=age, init_pos=init_pos, out=out,
                               dist_out=dist_out)
 
+    def goal_shape(self, her, pos_before, pos_after, age=None, init_pos=None, pass_types=None, scale=1.0, gamma=0.99,
+                   zero_terminal=False, out=None, shaping_out=None, mask_out=None):
+        """Potential-based shaping of hindsight records under their own goals in the engine's worlds as they stand
+        (minigrid_nav.goal_shape, one launch, read from the engine's own planes) -> (reward' float32[R], F float32[R],
+        mask uint8[R]).  her: the records of ppo_ops.her_relabel (its "t", "n", "goal", "reward" and "done"); pos_before /
+        pos_after float32[T, N, 2], age int32[T, N] and init_pos float32[2] as minigrid_nav.shape takes them; pass_types
+        as in distance_field; out=her["reward"] shapes the records in place."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        return nav.goal_shape(ty, her["t"], her["n"], her["goal"], pos_before, pos_after, 17, 17, reward=her["reward"],
+                              done=her["done"], pass_types=nav.PASS_DEFAULT if pass_types is None else pass_types, age=age,
+                              init_pos=init_pos, scale=scale, gamma=gamma, zero_terminal=zero_terminal, out=out,
+                              shaping_out=shaping_out, mask_out=mask_out)
+
     def timed_goal_moves(self, her, pos, age, init_pos, avoid_risk=False, out=None, dist_out=None):
         """goal_moves over (cell, phase): the optimal-move sets of hindsight records under their own goals with the
         row-8 balls planned by their period-6 schedule (minigrid_nav.timed_goal_moves, one launch, read from the

@@ -3,8 +3,9 @@ of N grid worlds lies from the goal, and which of mg_step's four moves an agent 
 are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are int32[N] tensors, dense or the column views
 of the engine's records (TwoarmyEngine.agent_views()), read where they live.  goal_moves labels records that each name a
 goal of their own (hindsight records) without a field in memory.  timed_field / timed_moves do the same for worlds whose
-blockers move with a period (a search over (cell, phase): the expert may wait).  One launch per call, on the tensors'
-device.  No CPU fallback."""
+blockers move with a period (a search over (cell, phase): the expert may wait).  shape / goal_shape turn the distances
+into a potential and shape rewards with it, float32 with pinned rounding.  One launch per call, on the tensors' device.
+No CPU fallback."""
 import ctypes
 
 import torch
@@ -17,6 +18,7 @@ UNREACHABLE = 0xFFFF
 PASS_DEFAULT = 0x0B1B                 # mg_step's rule: types 0, 1, 3, 8, 9, 11 and open doors (bit 4)
 PASS_LAVA, PASS_BALL = 1 << 9, 1 << 6  # clear PASS_LAVA to keep out of the lava, set PASS_BALL to walk through balls
 DOORS_OPEN = 1
+SHAPE_ZERO_TERMINAL = 2               # shape / goal_shape: phi(after) = 0 where the step ended its episode
 ACTION_STAY, ACTION_NONE = 6, -1
 MOVE_STAY = 1 << 4                    # optimal_moves: the bit of a source cell (bits 0..3: left, right, up, down)
 
@@ -291,6 +293,104 @@ def timed_goal_floods(width, height, period):
     """How many of a workgroup's 8 half wavefronts flood at a time in timed_goal_moves at this size and period (8, 4, 2
     or 1: their images share 64 KiB of LDS with the staging) -- the launch's own host function."""
     return query("mg_nav_timed_goal_floods", int(width), int(height), int(period))
+
+
+def _shape_outputs(shape, dev, reward, out, shaping_out, mask_out):
+    """The three outputs of shape / goal_shape: None = a new tensor (out: only with a reward), False = not wanted, a tensor
+    = written into (out may be `reward` itself: in place).  -> (out, shaping, mask), None where not wanted."""
+    if reward is not None:
+        assert reward.shape == shape and reward.device == dev and reward.dtype == torch.float32
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev) if reward is not None else False
+    shaping_out = torch.empty(shape, dtype=torch.float32, device=dev) if shaping_out is None else shaping_out
+    mask_out = torch.empty(shape, dtype=torch.uint8, device=dev) if mask_out is None else mask_out
+    res = tuple(None if t is False else t for t in (out, shaping_out, mask_out))
+    assert res[0] is None or reward is not None, "out without a reward"
+    assert any(t is not None for t in res), "no output wanted"
+    assert all(t is None or (t.shape == shape and t.device == dev) for t in res)
+    return res
+
+
+def shape(dist, pos_before, pos_after, width, height, reward=None, age=None, init_pos=None, done=None, scale=1.0,
+          gamma=0.99, zero_terminal=False, out=None, shaping_out=None, mask_out=None):
+    """Potential-based reward shaping of a rollout from one field per env (mg_nav_shape, include/minigrid_nav.h):
+    out = reward + F, F = gamma * phi(after) - phi(before), phi = -scale * distance, float32 with one rounding per
+    operation.  dist uint16[N, H*W] as distance_field returns it or uint16[N, P, H*W] as timed_field does (the period is
+    dist's second dimension; rows may be padded); pos_before, pos_after float32[T, N, 2] = (y, x) before / after each step,
+    age int32[T, N] with init_pos float32[2] as optimal_moves takes them (required with a timed field: the age is the
+    clock); reward float32[T, N] or None; done uint8[T, N], required with zero_terminal=True (phi(after) = 0 where done).
+    -> (out float32[T, N], F float32[T, N], mask uint8[T, N]): mask 0 where either state is no cell or unreachable -- there
+    F = 0 and the reward passes through bit for bit.  out / shaping_out / mask_out: tensors to write into (out=reward
+    shapes in place), False: not wanted (None is returned for it); out needs a reward.  One launch (none for T = 0)."""
+    W, H = int(width), int(height)
+    if dist.dim() == 3:
+        assert dist.is_cuda and dist.dtype == DIST_DTYPE and dist.shape[2] == W * H
+        N, P = dist.shape[0], dist.shape[1]
+        assert dist.stride(2) == 1 or W * H == 1, "the rows must be dense"
+        dpitch = dist.stride(1) if P > 1 else (dist.stride(0) if N > 1 else W * H)
+        assert dpitch >= W * H and (N == 1 or dist.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
+        dp = _marshal_ptr(dist)
+    else:
+        dp, dpitch, N, row = rows(dist, DIST_DTYPE)
+        P = 1
+        assert row == W * H
+    dev = dist.device
+    for p in (pos_before, pos_after):
+        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
+    T = pos_before.shape[0]
+    assert pos_after.shape[0] == T
+    assert (age is None) == (init_pos is None), "age and init_pos come together"
+    assert age is not None or P == 1, "the age is the clock: age and init_pos are required with a timed field"
+    if age is not None:
+        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    assert not zero_terminal or done is not None, "zero_terminal needs done"
+    assert done is None or (done.shape == (T, N) and done.device == dev)
+    out, shaping_out, mask_out = _shape_outputs((T, N), dev, reward, out, shaping_out, mask_out)
+    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, shaping_out, mask_out
+    call("mg_nav_shape", dev, dp, int(dpitch), P, N, W, H, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
+         ptr(init_pos, torch.float32), ptr(done, torch.uint8), ptr(reward, torch.float32), T, float(scale), float(gamma),
+         SHAPE_ZERO_TERMINAL if zero_terminal else 0, ptr(out, torch.float32), ptr(shaping_out, torch.float32),
+         ptr(mask_out, torch.uint8))
+    return out, shaping_out, mask_out
+
+
+def goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width, height, reward=None, done=None,
+               pass_types=PASS_DEFAULT, age=None, init_pos=None, state=None, doors_open=False, scale=1.0, gamma=0.99,
+               zero_terminal=False, out=None, shaping_out=None, mask_out=None):
+    """shape for records that each name their own goal (mg_nav_goal_shape, include/minigrid_nav.h): the planes, the
+    records (rec_t, rec_n int32[R], rec_goal float32[R, 2] = (y, x)), age and init_pos as goal_moves takes them,
+    pos_before / pos_after float32[T, N, 2] as shape takes them; reward float32[R] (a record's own reward) or None, done
+    uint8[R], required with zero_terminal=True.  -> (out float32[R], F float32[R], mask uint8[R]): per record what shape
+    gives in the field of the record's env flooded from the record's goal cell; mask 0 (F = 0, the reward passed through)
+    for a record whose t, n, goal or either position names nothing or has no path.  out / shaping_out / mask_out as in
+    shape.  One launch (none for R = 0), no field in memory, no host synchronisation."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state is None or state.shape == (N, W * H)
+    dev = type_plane.device
+    R = rec_t.shape[0]
+    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
+    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
+    for p in (pos_before, pos_after):
+        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
+    T = pos_before.shape[0]
+    assert pos_after.shape[0] == T
+    assert (age is None) == (init_pos is None), "age and init_pos come together"
+    if age is not None:
+        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    assert not zero_terminal or done is not None, "zero_terminal needs done"
+    assert done is None or (done.shape == (R,) and done.device == dev)
+    out, shaping_out, mask_out = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)
+    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, shaping_out, mask_out
+    flags = (DOORS_OPEN if doors_open else 0) | (SHAPE_ZERO_TERMINAL if zero_terminal else 0)
+    call("mg_nav_goal_shape", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types), flags,
+         ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32), ptr(done, torch.uint8),
+         ptr(reward, torch.float32), R, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
+         ptr(init_pos, torch.float32), T, float(scale), float(gamma), ptr(out, torch.float32),
+         ptr(shaping_out, torch.float32), ptr(mask_out, torch.uint8))
+    return out, shaping_out, mask_out
 
 
 TWOARMY_PERIOD = 6

@@ -7,6 +7,7 @@ reset).  The 4-frame policy input of any (t, n) is assembled on the fly by ppo_g
 repeats the reset frame at episode starts exactly like np.tile in Env_transact.reset.
 """
 import collections
+import math
 import time
 
 import torch
@@ -104,6 +105,8 @@ class VecPPOTrainer:
         self._her_moves_of = None             # ... and the records (the dict relabel() made) they belong to
         self.bonus = None                     # BonusTracker, made by enable_bonus()
         self.reward_train = self.reward       # what targets and hindsight records use: the shaped reward when a bonus is on
+        self.shaping = None                   # potential-based shaping: {"scale", "hindsight", "timed"}, made by enable_shaping()
+        self._relabel_at = -1                 # env_steps when relabel() last ran: shape_potential() comes after it
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
         self.env_steps = 0
         self.episodes_done = 0
@@ -228,6 +231,9 @@ class VecPPOTrainer:
         4, 5, ... of the episode (`skip`), see ppo_her_relabel_window in include/twoarmy_ppo.h."""
         T, N = self.T, self.N
         skip = int(getattr(self.agent, "her_window_delay", 0))
+        if self.shaping is not None and self._shaped_at == self.env_steps:
+            raise RuntimeError("enable_shaping(): call relabel() before shape_potential(), the records copy reward_train")
+        self._relabel_at = self.env_steps
         if self.max_steps > HER_MAX_LEN:
             raise ValueError("hindsight relabelling handles episodes of up to %d steps (max_steps = %d)"
                              % (HER_MAX_LEN, self.max_steps))
@@ -489,6 +495,8 @@ class VecPPOTrainer:
         if self.bonus is not None:
             self.bonus.account(self.pos[4:4 + self.T], self.env_actions(), self.reward, self.term, dir=self.dir,
                                out=self.reward_train)
+        elif self.shaping is not None:        # enable_shaping() without a bonus: the potential is added to a copy
+            self.reward_train.copy_(self.reward)
         return self.reward_train
 
     def bonus_stats(self):
@@ -659,6 +667,92 @@ class VecPPOTrainer:
         n, hn = int(v[0]), int(v[3]) if her else 0
         return {"agree": v[1] / n if n else None, "opt_mass": v[2] / n if n else None, "labelled": n,
                 "coef": self.prior_coef(), "her_labelled": hn if her else None, "her_agree": v[4] / hn if hn else None}
+
+    # ------------------------------------------------------------------ potential-based reward shaping
+    def enable_shaping(self, scale, hindsight=True, timed=False):
+        """Shape the training reward with the distance to the goal as a potential (include/minigrid_nav.h, "Reward
+        shaping"): shape_potential() then adds F = gamma * Phi(s') - Phi(s), Phi = -scale * distance, to `reward_train`,
+        which compute_targets() and carry_over() use, while `reward` -- and with it account_episodes(), running_score(),
+        stats() and the HER switch -- stays extrinsic.  gamma is the agent's, and the terminal rule (Phi(s') = 0 at a done
+        step) follows agent.use_done_mask.  hindsight=True: the records of relabel() are shaped too, each under its own
+        goal (one mg_nav_goal_shape launch over her["reward"]).  timed=True: the rollout's potential comes from the
+        time-expanded field (TwoarmyEngine.timed_field, the age of a step being its clock); the records always use the
+        static map.  Call order in a rollout: collect() -> shape_rewards() -> relabel() -> shape_potential() ->
+        label_expert() / compute_targets() -> carry_over()."""
+        scale = float(scale)
+        if not math.isfinite(scale) or scale <= 0.0:
+            raise ValueError("enable_shaping(): scale must be a positive finite number, got %r" % scale)
+        if not isinstance(hindsight, bool) or not isinstance(timed, bool):
+            raise ValueError("enable_shaping(): hindsight and timed are booleans")
+        self.shaping = {"scale": scale, "hindsight": hindsight, "timed": timed}
+        if self.reward_train is self.reward:
+            self.reward_train = torch.zeros_like(self.reward)
+        self.shape_f = torch.zeros((self.T, self.N), dtype=torch.float32, device=self.device)
+        self.shape_mask = torch.zeros((self.T, self.N), dtype=torch.uint8, device=self.device)
+        self.shape_field = None               # uint16[N, 6, 289], made by the first shape_potential() with timed=True
+        self.her_shape_f = self.her_shape_mask = self._her_shape_of = None
+        self._shaped_at = -1
+        return self.shaping
+
+    @torch.no_grad()
+    def shape_potential(self, expect_her=False):
+        """reward_train += F of the rollout just collected, in place, under the env's goal: the static-map field of
+        account_distance() / label_expert() (reused if one of them already ran for this rollout), or with
+        enable_shaping(timed=True) TwoarmyEngine.timed_field's, and ONE mg_nav_shape launch over the positions before and
+        after each step; `shape_f` float32[T, N] and `shape_mask` uint8[T, N] afterwards.  With hindsight shaping and
+        records from relabel(): ONE mg_nav_goal_shape launch more shapes her["reward"] in place, each record under its
+        own goal on the static map -- relabel() copied reward_train into the records BEFORE the env goal's term was
+        added, so no record carries another goal's term; `her_shape_f` and `her_shape_mask` afterwards.  Call after
+        shape_rewards() and relabel(), once per rollout; expect_her=True (the caller relabels this rollout) makes a call
+        before relabel() an error.  No host synchronisation."""
+        from .. import minigrid_nav as nav
+        if self.shaping is None:
+            raise RuntimeError("shape_potential() before enable_shaping()")
+        if self._shaped_at == self.env_steps:
+            raise RuntimeError("shape_potential() ran already for this rollout: the potential would be added twice")
+        if expect_her and self.shaping["hindsight"] and self._relabel_at != self.env_steps:
+            raise RuntimeError("enable_shaping(hindsight=True): call relabel() before shape_potential()")
+        T = self.T
+        sh = self.shaping
+        before, after = self.pos[3:3 + T], self.pos[4:4 + T]
+        zero_terminal = bool(self.agent.use_done_mask)
+        done = (self.term | self.trunc).contiguous() if zero_terminal else None
+        if sh["timed"]:
+            if self.shape_field is None:
+                self.shape_field = torch.empty((self.N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
+            self.engine.timed_field(agent=False, out=self.shape_field)
+            field = self.shape_field
+        else:
+            field = self._static_field(reuse=True)
+        nav.shape(field, before, after, 17, 17, reward=self.reward_train, age=self.age[:-1], init_pos=self.init_pos,
+                  done=done, scale=sh["scale"], gamma=self.agent.gamma, zero_terminal=zero_terminal, out=self.reward_train,
+                  shaping_out=self.shape_f, mask_out=self.shape_mask)
+        self._shaped_at = self.env_steps
+        self.her_shape_f = self.her_shape_mask = self._her_shape_of = None
+        if sh["hindsight"] and self.her is not None and self.her["t"].numel():
+            _, self.her_shape_f, self.her_shape_mask = self.engine.goal_shape(
+                self.her, before, after, self.age[:-1], self.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
+                scale=sh["scale"], gamma=self.agent.gamma, zero_terminal=zero_terminal, out=self.her["reward"])
+            self._her_shape_of = self.her                     # these terms belong to these records
+        return self.reward_train
+
+    def shaping_stats(self):
+        """{"mean": mean F over the shaped steps of the last shaped rollout, "unshaped": the share of its steps left
+        unshaped, "her_mean", "her_unshaped": the same two over the hindsight records (None without shaped records)};
+        None where nothing counts.  One device-to-host copy."""
+        if self.shaping is None or self._shaped_at < 0:
+            raise RuntimeError("shaping_stats() before enable_shaping() and shape_potential()")
+        m = self.shape_mask != 0
+        sums = [m.sum().double(), torch.where(m, self.shape_f, 0.0).double().sum()]
+        her = self.her_shape_f is not None and self._her_shape_of is self.her
+        if her:
+            hm = self.her_shape_mask != 0
+            sums += [hm.sum().double(), torch.where(hm, self.her_shape_f, 0.0).double().sum()]
+        v = torch.stack(sums).cpu().tolist()
+        total, n = self.T * self.N, int(v[0])
+        hn, htotal = (int(v[2]), int(self.her_shape_f.numel())) if her else (0, 0)
+        return {"mean": v[1] / n if n else None, "unshaped": 1.0 - n / total,
+                "her_mean": v[3] / hn if hn else None, "her_unshaped": 1.0 - hn / htotal if htotal else None}
 
     def stats(self):
         done = (self.term | self.trunc) != 0

@@ -22,8 +22,13 @@ period-6 schedule and "wait one step" is a label where the gap is closed (minigr
 same two launches per rollout); off by default.
 --prior_hindsight_timed (with --prior_hindsight) labels the hindsight records by the time-expanded search too, each under
 its own goal (minigrid_nav.timed_goal_moves in place of goal_moves: still one launch per rollout); off by default.
+--shaping_scale S trains on the potential-shaped reward r + gamma * Phi(s') - Phi(s), Phi = -S * distance to the goal
+(minigrid_nav.shape, one launch per rollout; the hindsight records each under their own goal, minigrid_nav.goal_shape,
+unless --shaping_no_hindsight; --shaping_timed: the rollout's potential from the time-expanded field); appends
+`shaping mean` / `unshaped` to the log line; off by default.
 """
 import argparse
+import math
 import os
 import random
 import time
@@ -128,6 +133,17 @@ def build_parser():
                    help="with --prior_hindsight: label the hindsight records with the time-expanded expert as well, each "
                         "under its own goal (a relabelled record is no longer taught to step into a row-8 ball); "
                         "independent of --prior_timed")
+    p.add_argument("--shaping_scale", type=float, default=0.0, metavar="S",
+                   help="potential-based reward shaping: train on r + gamma * Phi(s') - Phi(s) with Phi = -S * (the "
+                        "shortest-path distance to the goal on the static map), one more launch per rollout; the logged "
+                        "rewards, the score and the HER switch stay extrinsic; appends `shaping mean` (mean term over the "
+                        "shaped steps) and `unshaped` (share of steps without a distance) to the log line; 0 = off")
+    p.add_argument("--shaping_timed", action="store_true",
+                   help="with --shaping_scale: take the rollout's potential from the time-expanded field, in which the "
+                        "row-8 balls follow their period-6 schedule; the hindsight records stay on the static map")
+    p.add_argument("--shaping_no_hindsight", action="store_true",
+                   help="with --shaping_scale: leave the hindsight records unshaped (by default each is shaped under its "
+                        "own goal, one more launch per rollout, and `her shaping mean` / `her unshaped` are logged)")
     return p
 
 
@@ -138,6 +154,16 @@ def prior_fields(ps, hindsight=False):
         " expert agree - opt_mass -"
     if hindsight:
         tail += " her agree %.3f" % ps["her_agree"] if ps["her_labelled"] else " her agree -"
+    return tail
+
+
+def shaping_fields(ss, hindsight=True):
+    """Tail of the log line with --shaping_scale (VecPPOTrainer.shaping_stats()); hindsight: unless --shaping_no_hindsight."""
+    def f(x):
+        return "-" if x is None else "%.4f" % x
+    tail = " shaping mean %s unshaped %s" % (f(ss["mean"]), f(ss["unshaped"]))
+    if hindsight:
+        tail += " her shaping mean %s her unshaped %s" % (f(ss["her_mean"]), f(ss["her_unshaped"]))
     return tail
 
 
@@ -209,6 +235,10 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--prior_hindsight_timed needs --prior_hindsight")
     if args.prior_timed and not (args.prior_coef != 0.0 or args.expert_agreement):
         raise SystemExit("--prior_timed needs --prior_coef or --expert_agreement")
+    if not (math.isfinite(args.shaping_scale) and args.shaping_scale >= 0.0):
+        raise SystemExit("--shaping_scale must be a finite number >= 0")
+    if (args.shaping_timed or args.shaping_no_hindsight) and args.shaping_scale == 0.0:
+        raise SystemExit("--shaping_timed / --shaping_no_hindsight need --shaping_scale")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -270,16 +300,21 @@ def main(argv=None, predictor=False, soa=False):
             raise SystemExit("--prior_coef / --expert_agreement: plain PPO agent only")
         trainer.enable_prior(args.prior_coef, args.prior_decay, hindsight=args.prior_hindsight, timed=args.prior_timed,
                              hindsight_timed=args.prior_hindsight_timed)
+    use_shaping = args.shaping_scale != 0.0
+    if use_shaping:
+        trainer.enable_shaping(args.shaping_scale, hindsight=not args.shaping_no_hindsight, timed=args.shaping_timed)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
         t0 = time.perf_counter()
         trainer.collect()
-        if args.bonus != "none":
+        if args.bonus != "none" or use_shaping:
             trainer.shape_rewards()
         her = trainer.her_switch(her, score)                  # train_ppo.py:128-131 of the reference
         if her and agent.gae_lambda == 0.0:
             trainer.relabel()
+        if use_shaping:                                       # behind relabel(): the records copy the unshaped reward_train
+            trainer.shape_potential(expect_her=her and agent.gae_lambda == 0.0)
         trainer.account_episodes()
         if args.visit_dir:
             trainer.account_visits(trainer.her)
@@ -297,7 +332,8 @@ def main(argv=None, predictor=False, soa=False):
         t1 = time.perf_counter()
         n_her = 0 if trainer.her is None else int(trainer.her["t"].numel())
         ps = trainer.prior_stats() if use_prior else None       # the policy that acted, before the update changes it
-        if use_prior:
+        ss = trainer.shaping_stats() if use_shaping else None   # before update() drops the records
+        if use_prior or use_shaping:
             torch.cuda.synchronize()
             t1 = time.perf_counter()                            # the statistics are not part of the update's time
         la, lv = trainer.update()
@@ -321,6 +357,8 @@ def main(argv=None, predictor=False, soa=False):
             tail += distance_fields(trainer.distance_stats())
         if use_prior:                                           # behind every other field
             tail += prior_fields(ps, args.prior_hindsight)
+        if use_shaping:                                         # behind every other field
+            tail += shaping_fields(ss, not args.shaping_no_hindsight)
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

@@ -244,6 +244,81 @@ int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state, int n_env
  * TW_E_ARG: a side <= 0 or > MG_NAV_MAX_SIDE, period outside 1..MG_NAV_MAX_PERIOD. */
 int mg_nav_timed_goal_floods(int width, int height, int period);
 
+/* ---- Reward shaping: the distance as a potential (Ng, Harada, Russell 1999).
+ *
+ * r' = r + gamma * Phi(s') - Phi(s) with Phi(s) = -scale * dist(s).  The world, moves, enterable cells, fields, visit_cell
+ * rule, acting-position rule (age <= 0 ? init_pos : pos) and phase rule (the phase of a clock, above) are the existing ones.
+ *
+ * Potential.  For a state with distance d (uint16): phi = -(scale * (float)d) in float32, with one rounding; phi = 0
+ * exactly (+0.0f) at d == 0.
+ *
+ * Shaping term.  F = (gamma * phi_after) - phi_before; out = reward + F.  Both are float32, with one IEEE rounding per
+ * operation: the kernels are compiled with fp contraction off around them, a fused multiply-add would round differently.
+ *
+ * Unshaped elements.  An element is unshaped if either state is no cell or has distance MG_NAV_UNREACHABLE (a wall
+ * dropped onto it, a cell not free at its phase).  An unshaped element has F = 0 (+0.0f), passes `reward` through bit for
+ * bit (a -0.0f or a NaN payload stays) and has mask = 0; mask = 1 elsewhere.
+ *
+ * Terminal rule.  With flag MG_NAV_SHAPE_ZERO_TERMINAL and done != 0, phi_after = 0; such an element is shaped iff the
+ * acting state is reachable.  Without the flag the terminal position's own potential is used: that matches a target
+ * r + gamma * V(s') with no done mask.
+ *
+ * Timed fields (period > 1).  The acting state is (acting cell, phase of age); the after state is (after cell, phase of
+ * (age <= 0 ? 0 : age) + 1), i.e. the phase that follows the acting one. */
+#define MG_NAV_SHAPE_ZERO_TERMINAL 2 /* flags: shares the flag space with MG_NAV_DOORS_OPEN */
+
+/* The rollout, from ONE field per env.
+ *   dist        uint16[n_envs][period][dist_pitch]: with period == 1 what mg_nav_field writes, otherwise what
+ *               mg_nav_timed_field writes (dist_pitch in elements, 0 = dense width*height)
+ *   pos_before, pos_after  float[T][n_envs][2] = (y, x) before / after step t (8-byte aligned): exactly the two streams
+ *               mg_nav_optimal_moves and mg_nav_lookup take.  The age rule applies to pos_before only.
+ *   age, init_pos  as in mg_nav_optimal_moves; nullable together when period == 1, required when period > 1
+ *   done        uint8[T][n_envs]: required with MG_NAV_SHAPE_ZERO_TERMINAL, ignored without it
+ *   reward      float[T][n_envs] (nullable; then reward_out must be NULL as well)
+ *   reward_out, shaping (F), mask (uint8)  [T][n_envs], each nullable, at least one given.  reward_out == reward (the
+ *               same pointer) is allowed and defined: the reward is shaped in place.  Any other overlap is the caller's
+ *               error.
+ * One launch covers all envs; T == 0 launches nothing.  All outputs leave as aligned 16-byte stores (4 floats, 16 mask
+ * bytes), element by element only in the first and last chunk of a workgroup's share (csrc/row_store.h); the float
+ * arrays need 4-byte alignment, mask none, and nothing outside the first T * n_envs elements of an output is written.
+ * flags: MG_NAV_SHAPE_ZERO_TERMINAL only (the doors are the field's business).
+ * TW_E_ARG: the cases of mg_nav_optimal_moves (period == 1) / mg_nav_timed_moves (period > 1) with pos_before and
+ * pos_after for pos; period outside 1..MG_NAV_MAX_PERIOD; reward, reward_out or shaping not 4-byte aligned; no output
+ * given; reward_out without reward; MG_NAV_SHAPE_ZERO_TERMINAL without done; unknown flag bits; a non-finite scale or
+ * gamma. */
+int mg_nav_shape(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                 const float *pos_before, const float *pos_after, const int32_t *age, const float *init_pos,
+                 const uint8_t *done, const float *reward, int T, float scale, float gamma, int flags,
+                 float *reward_out, float *shaping, uint8_t *mask, void *stream);
+
+/* Hindsight records, each under its OWN goal.  Per record b: let F be the field mg_nav_field computes for env rec_n[b]
+ * with visit_cell(rec_goal[b]) as its single source.  The acting state is taken exactly as in mg_nav_goal_moves (the
+ * acting position of t = rec_t[b], n = rec_n[b]); the after state is visit_cell(pos_after[t][n]); both distances are
+ * read in F and shaped as above.
+ *   rec_done    uint8[n_records]: required with MG_NAV_SHAPE_ZERO_TERMINAL, ignored without it
+ *   rec_reward  float[n_records] (nullable; then reward_out must be NULL as well)
+ *   reward_out, shaping, mask  per record, each nullable, at least one given; reward_out == rec_reward is allowed (in
+ *               place), any other overlap is the caller's error
+ * A record is unshaped (F = 0, reward passed through, mask = 0) for every reason mg_nav_goal_moves gives an empty label
+ * -- rec_t or rec_n out of range, a goal that is no cell or not enterable, an acting position that is no cell or has no
+ * path -- and also when the after state is no cell or unreachable.  No such record addresses memory outside its arrays.
+ * As in mg_nav_goal_moves: the result of record b depends on record b alone; one launch, no atomics (none for
+ * n_records == 0); a workgroup owns 1024 consecutive records and floods once per run of equal (env, goal cell); the
+ * planes are read by the over-read rule; the outputs leave by the store rule of mg_nav_shape, nothing outside the first
+ * n_records elements is written.
+ * Invariant: for records that share one goal per env the outputs equal mg_nav_field(goal_x, goal_y) followed by
+ * mg_nav_shape on the same elements.
+ * flags: MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL.
+ * TW_E_ARG: the cases of mg_nav_goal_moves (pos_before and pos_after for pos, the three outputs for moves); rec_reward,
+ * reward_out or shaping not 4-byte aligned; no output given; reward_out without rec_reward; MG_NAV_SHAPE_ZERO_TERMINAL
+ * without rec_done; unknown flag bits; a non-finite scale or gamma. */
+int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                      uint32_t pass_types, int flags, const int32_t *rec_t, const int32_t *rec_n,
+                      const float *rec_goal, const uint8_t *rec_done, const float *rec_reward, int64_t n_records,
+                      const float *pos_before, const float *pos_after, const int32_t *age, const float *init_pos,
+                      int T, float scale, float gamma, float *reward_out, float *shaping, uint8_t *mask,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
