@@ -41,6 +41,10 @@
  *   mg_nav_goal_shape_kernel   the same for records under goals of their own: the goal kernel's keys, heads and floods
  *                          (nav_goal_keys, nav_goal_heads, nav_goal_floods: written once, the labelling is a parameter),
  *                          a record also keeps its after-step cell; three float operations per record.
+ *   mg_nav_timed_goal_shape_kernel<P>   the same over (cell, phase): the timed goal kernel's flood loop
+ *                          (nav_timed_goal_floods<P>: written once, the labelling is a parameter) and the goal shaping
+ *                          kernel's after cells, label (nav_goal_shape_label, on the acting and the following phase's image)
+ *                          and stores; its staging is larger than the move sets', so it has a flood count of its own.
  *
  * Integer work only but for the shaping term (three float32 operations, each rounded once: fp contract off), no atomics:
  * the results do not depend on scheduling.
@@ -691,29 +695,23 @@ inline int nav_timed_goal_flooders(int HW, int P)
 static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + 64 + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
               "one image of the longest period and the largest world fits next to the staging");
 
-template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_timed_goal_kernel(
-    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
-    int doors_open, const uint32_t *__restrict__ blocked, int64_t bstride, const int32_t *__restrict__ rec_t,
-    const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos,
-    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves,
-    uint16_t *__restrict__ acting_dist, int flooders)
+// The flood loop of a timed goal kernel, written once (as nav_goal_floods is for the static ones): one head per flooding
+// half wavefront and round -- the head's world (kept in `fr` across heads of one env), image reset, seed, flood -- then
+// label(i, img, ok) for every record (slot i) of its run; img = the half's P images of `cells` distances each, ok = the run
+// has a result at all.  Whole wavefronts enter or skip the loop: one goes round when its first half floods, an idle second
+// half beside it with empty masks (the ballot of a round is wavefront-wide); the trip count is the workgroup's, and no
+// workgroup barrier stands inside the loop.  EVERY lane of the workgroup calls this; what label() parks in LDS is ordered
+// before the next flood; __syncthreads() before the stores.
+template <int P, typename Label> __device__ __forceinline__ void nav_timed_goal_floods(
+    const nav_goal_stage_t &st, uint16_t *images, int n_heads, int flooders, const uint8_t *__restrict__ type,
+    const uint8_t *__restrict__ state, int W, int H, uint32_t pass_types, int doors_open,
+    const uint32_t *__restrict__ blocked, int64_t bstride, Label label)
 {
-    extern __shared__ __attribute__((aligned(16))) uint16_t goal_image[];   // [flooders][P][cells]
-    __shared__ nav_goal_stage_t st;
-    __shared__ uint8_t s_phase[NAV_GOAL_SLOTS];                             // the phase of a record's clock
     const int tid = threadIdx.x, r = tid & 31, half = tid >> 5;
-    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
     const int HW = W * H, cells = nav_timed_cells(HW);
-
-    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
-    const int n_heads = nav_goal_heads(st, g);
-
-    // One head per flooding half wavefront and round.  Whole wavefronts enter or skip the loop: one goes round when its
-    // first half floods, an idle second half beside it with empty masks (the ballot of a round is wavefront-wide); the
-    // trip count is the workgroup's, and no workgroup barrier stands inside the loop.
     const bool floods = half < flooders;
     if ((half & ~1) < flooders) {
-        uint16_t *img = goal_image + (size_t)(floods ? half : 0) * P * cells;
+        uint16_t *img = images + (size_t)(floods ? half : 0) * P * cells;
         const int per = (n_heads + flooders - 1) / flooders;
         const int j_end = !floods ? 0 : (half + 1) * per < n_heads ? (half + 1) * per : n_heads;
         int cur_env = -1;
@@ -744,16 +742,36 @@ template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_time
             nav_timed_seed<P>(img, cells, r, W, src, fr, reached);          // src = 0: nothing is reached, nothing written
             nav_timed_flood<P>(img, cells, r, W, HW * P, fr, reached);
             nav_wave_sync();
-            for (int i = s0 + r; i < s1; i += 32) {
-                const int c = st.cell[i], ph = s_phase[i];
-                uint32_t d = MG_NAV_UNREACHABLE, m = 0;
-                if (env >= 0 && c != NAV_NO_CELL)
-                    m = nav_move_set<true>(img + ph * cells, img + (ph + 1 == P ? 0 : ph + 1) * cells, c, W, H, d);
-                nav_goal_label(st, g, i, m, d);
-            }
+            for (int i = s0 + r; i < s1; i += 32) label(i, img, env >= 0);
             nav_wave_sync();                                                // the labels are read before the image is reset
         }
     }
+}
+
+template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_timed_goal_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const uint32_t *__restrict__ blocked, int64_t bstride, const int32_t *__restrict__ rec_t,
+    const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos,
+    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T, uint8_t *__restrict__ moves,
+    uint16_t *__restrict__ acting_dist, int flooders)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t goal_image[];   // [flooders][P][cells]
+    __shared__ nav_goal_stage_t st;
+    __shared__ uint8_t s_phase[NAV_GOAL_SLOTS];                             // the phase of a record's clock
+    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
+    const int cells = nav_timed_cells(W * H);
+
+    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
+    const int n_heads = nav_goal_heads(st, g);
+    nav_timed_goal_floods<P>(st, goal_image, n_heads, flooders, type, state, W, H, pass_types, doors_open, blocked, bstride,
+                             [&](int i, const uint16_t *img, bool ok) {
+                                 const int c = st.cell[i], ph = s_phase[i];
+                                 uint32_t d = MG_NAV_UNREACHABLE, m = 0;
+                                 if (ok && c != NAV_NO_CELL)
+                                     m = nav_move_set<true>(img + ph * cells, img + (ph + 1 == P ? 0 : ph + 1) * cells, c, W,
+                                                            H, d);
+                                 nav_goal_label(st, g, i, m, d);
+                             });
     __syncthreads();
     nav_goal_store(st, g, M, moves, acting_dist);
 }
@@ -898,6 +916,65 @@ struct nav_goal_shape_share_t {
     int slot_lo, slot_hi;                               // 0 < slot_lo <= slot_hi <= SLOTS, or both 0: no record
 };
 
+__device__ __forceinline__ nav_goal_shape_share_t nav_goal_shape_share(const float *reward_out, const float *shaping,
+                                                                       const uint8_t *mask, int64_t M, int64_t b)
+{
+    nav_goal_shape_share_t g;
+    g.so = nav_out_span(reward_out, M, b, NAV_GOAL_ELEMS);
+    g.sf = nav_out_span(shaping, M, b, NAV_GOAL_ELEMS);
+    g.sm = nav_out_span(mask, M, b, NAV_GOAL_ELEMS);
+    g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
+    int64_t lo = M, hi = 0;                                                 // the records of this workgroup: all three spans
+    auto join = [&](const nav_out_span_t &o) {
+        if (o.has) { lo = lo < o.k.p_lo ? lo : o.k.p_lo; hi = hi > o.k.p_hi ? hi : o.k.p_hi; }
+    };
+    join(g.so); join(g.sf); join(g.sm);
+    g.slot_lo = lo < hi ? (int)(lo - g.p0) : 0;
+    g.slot_hi = lo < hi ? (int)(hi - g.p0) : 0;
+    return g;
+}
+
+// What a shaping kernel keeps of record p (slot i, element `at` or -1) besides its keys: nav_goal_keys' `more`.
+__device__ __forceinline__ void nav_goal_shape_more(nav_goal_shape_stage_t &sh, const nav_goal_shape_share_t &g, int i,
+                                                    int64_t p, int64_t at, const uint8_t *__restrict__ rec_done,
+                                                    const float *rec_reward, const float2 *__restrict__ pos_after, int W,
+                                                    int H)
+{
+    int a = NAV_NO_CELL;
+    if (at >= 0) {
+        if (rec_done != nullptr && rec_done[p] != 0) a = NAV_TERMINAL;
+        else {
+            const float2 q = pos_after[at];
+            const int c = visit_cell(q.x, q.y, W, H);
+            if (c < W * H) a = c;
+        }
+    }
+    sh.after[i] = (uint16_t)a;
+    // read before the barrier, by the workgroup that stores it: reward_out may be rec_reward
+    if (g.so.holds(p)) sh.out[(int)(p - g.so.base)] = rec_reward[p];
+}
+
+// The shaping label of the record in slot i, parked for the stores: its acting cell c is read in `before`, its after cell
+// in `after` (one image for a static field, the acting and the following phase's for a timed one); ok = the run has a result.
+__device__ __forceinline__ void nav_goal_shape_label(nav_goal_shape_stage_t &sh, const nav_goal_shape_share_t &g, int i,
+                                                     int c, const uint16_t *before, const uint16_t *after, bool ok,
+                                                     float scale, float gamma)
+{
+    const int64_t p = g.p0 + i;
+    const int a = sh.after[i];
+    float F = 0.0f;
+    bool shaped = false;
+    if (ok && c != NAV_NO_CELL && a != NAV_NO_CELL)
+        shaped = nav_shape_term(before[c], a == NAV_TERMINAL ? (uint32_t)MG_NAV_UNREACHABLE : after[a], a == NAV_TERMINAL,
+                                scale, gamma, F);
+    if (shaped && g.so.holds(p)) {
+        float &o = sh.out[(int)(p - g.so.base)];
+        o = nav_shaped(o, F);
+    }
+    if (g.sf.holds(p)) sh.f[(int)(p - g.sf.base)] = F;
+    if (g.sm.holds(p)) sh.mask[(int)(p - g.sm.base)] = shaped ? 1 : 0;
+}
+
 __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_shape_kernel(
     const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
     int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
@@ -909,60 +986,77 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_shape_kernel(
     __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
     __shared__ nav_goal_stage_t st;
     __shared__ nav_goal_shape_stage_t sh;
-    const int64_t b = blockIdx.x;
-    const int HW = W * H;
-    nav_goal_shape_share_t g;
-    g.so = nav_out_span(reward_out, M, b, NAV_GOAL_ELEMS);
-    g.sf = nav_out_span(shaping, M, b, NAV_GOAL_ELEMS);
-    g.sm = nav_out_span(mask, M, b, NAV_GOAL_ELEMS);
-    g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
-    {
-        int64_t lo = M, hi = 0;                                             // the records of this workgroup: all three spans
-        auto join = [&](const nav_out_span_t &o) {
-            if (o.has) { lo = lo < o.k.p_lo ? lo : o.k.p_lo; hi = hi > o.k.p_hi ? hi : o.k.p_hi; }
-        };
-        join(g.so); join(g.sf); join(g.sm);
-        g.slot_lo = lo < hi ? (int)(lo - g.p0) : 0;
-        g.slot_hi = lo < hi ? (int)(hi - g.p0) : 0;
-    }
+    const nav_goal_shape_share_t g = nav_goal_shape_share(reward_out, shaping, mask, M, blockIdx.x);
 
     nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos_before, age, init_pos, T,
                          [&](int i, int64_t p, int64_t at) {
-                             int a = NAV_NO_CELL;
-                             if (at >= 0) {
-                                 if (rec_done != nullptr && rec_done[p] != 0) a = NAV_TERMINAL;
-                                 else {
-                                     const float2 q = pos_after[at];
-                                     const int c = visit_cell(q.x, q.y, W, H);
-                                     if (c < HW) a = c;
-                                 }
-                             }
-                             sh.after[i] = (uint16_t)a;
-                             // read before the barrier, by the workgroup that stores it: reward_out may be rec_reward
-                             if (g.so.holds(p)) sh.out[(int)(p - g.so.base)] = rec_reward[p];
+                             nav_goal_shape_more(sh, g, i, p, at, rec_done, rec_reward, pos_after, W, H);
                          });
     const int n_heads = nav_goal_heads(st, g);
     nav_goal_floods(st, image[threadIdx.x >> 5], n_heads, type, state, W, H, pass_types, doors_open,
                     [&](int i, const uint16_t *img, bool ok) {
-                        const int64_t p = g.p0 + i;
-                        const int c = st.cell[i], a = sh.after[i];
-                        float F = 0.0f;
-                        bool shaped = false;
-                        if (ok && c != NAV_NO_CELL && a != NAV_NO_CELL)
-                            shaped = nav_shape_term(img[c], a == NAV_TERMINAL ? (uint32_t)MG_NAV_UNREACHABLE : img[a],
-                                                    a == NAV_TERMINAL, scale, gamma, F);
-                        if (shaped && g.so.holds(p)) {
-                            float &o = sh.out[(int)(p - g.so.base)];
-                            o = nav_shaped(o, F);
-                        }
-                        if (g.sf.holds(p)) sh.f[(int)(p - g.sf.base)] = F;
-                        if (g.sm.holds(p)) sh.mask[(int)(p - g.sm.base)] = shaped ? 1 : 0;
+                        nav_goal_shape_label(sh, g, i, st.cell[i], img, img, ok, scale, gamma);
                     });
     __syncthreads();
     nav_out_store(reward_out, M, g.so, sh.out, NAV_GOAL_THREADS);
     nav_out_store(shaping, M, g.sf, sh.f, NAV_GOAL_THREADS);
     nav_out_store(mask, M, g.sm, sh.mask, NAV_GOAL_THREADS);
 }
+
+// ------------------------------------------------------------------ timed shaping of records with goals of their own
+// mg_nav_goal_shape_kernel over (cell, phase): the timed goal kernel's keys, heads and floods (nav_timed_goal_floods), the
+// goal shaping kernel's after cells, label and stores.  The label reads two phase images: the acting phase's for the acting
+// cell, the following phase's for the after cell.  Its staging is larger than the move sets', so it has a host choice of
+// its own: MG_NAV_TIMED_GOAL_SHAPE_LDS is what the images share 64 KiB with (static LDS and what aligning it may cost).
+static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + sizeof(nav_goal_shape_stage_t) + 64 == MG_NAV_TIMED_GOAL_SHAPE_LDS,
+              "the header states the byte count of the formula");
+inline int nav_timed_goal_shape_flooders(int HW, int P)
+{
+    int f = NAV_GOAL_HALVES;
+    while (f > 1 && (size_t)MG_NAV_TIMED_GOAL_SHAPE_LDS + (size_t)f * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)64 * 1024)
+        f >>= 1;
+    return f;
+}
+static_assert(MG_NAV_TIMED_GOAL_SHAPE_LDS + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
+              "one image of the longest period and the largest world fits next to the shaping staging");
+
+template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_timed_goal_shape_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const uint32_t *__restrict__ blocked, int64_t bstride, const int32_t *__restrict__ rec_t,
+    const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal, const uint8_t *__restrict__ rec_done,
+    const float *rec_reward, int64_t M, const float2 *__restrict__ pos_before, const float2 *__restrict__ pos_after,
+    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T, float scale, float gamma, float *reward_out,
+    float *__restrict__ shaping, uint8_t *__restrict__ mask, int flooders)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t goal_shape_image[];   // [flooders][P][cells]
+    __shared__ nav_goal_stage_t st;
+    __shared__ nav_goal_shape_stage_t sh;
+    __shared__ uint8_t s_phase[NAV_GOAL_SLOTS];                             // the phase of a record's clock
+    const int HW = W * H, cells = nav_timed_cells(HW);
+    const nav_goal_shape_share_t g = nav_goal_shape_share(reward_out, shaping, mask, M, blockIdx.x);
+
+    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos_before, age, init_pos, T,
+                        [&](int i, int64_t p, int64_t at) {
+                            nav_goal_shape_more(sh, g, i, p, at, rec_done, rec_reward, pos_after, W, H);
+                        });
+    const int n_heads = nav_goal_heads(st, g);
+    nav_timed_goal_floods<P>(st, goal_shape_image, n_heads, flooders, type, state, W, H, pass_types, doors_open, blocked,
+                             bstride, [&](int i, const uint16_t *img, bool ok) {
+                                 const int ph = s_phase[i];                 // the after state's phase follows the acting one
+                                 nav_goal_shape_label(sh, g, i, st.cell[i], img + ph * cells,
+                                                      img + (ph + 1 == P ? 0 : ph + 1) * cells, ok, scale, gamma);
+                             });
+    __syncthreads();
+    nav_out_store(reward_out, M, g.so, sh.out, NAV_GOAL_THREADS);
+    nav_out_store(shaping, M, g.sf, sh.f, NAV_GOAL_THREADS);
+    nav_out_store(mask, M, g.sm, sh.mask, NAV_GOAL_THREADS);
+}
+
+using nav_timed_goal_shape_kernel_t = decltype(&mg_nav_timed_goal_shape_kernel<1>);
+template <int... Ps> constexpr nav_timed_goal_shape_kernel_t nav_timed_goal_shape_kernel_of[] = {
+    mg_nav_timed_goal_shape_kernel<Ps + 1>...};
+constexpr const nav_timed_goal_shape_kernel_t *nav_timed_goal_shape_kernels =   // [P - 1]
+    nav_timed_goal_shape_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
 bool nav_finite(float v) { return __builtin_isfinite(v); }
@@ -1179,5 +1273,47 @@ extern "C" int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int 
                        flags & MG_NAV_DOORS_OPEN, rec_t, rec_n, rec_goal, ends, rec_reward, n_records,
                        reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
                        init_pos, T, scale, gamma, reward_out, shaping, mask);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_timed_goal_shape_floods(int width, int height, int period)
+{
+    if (!nav_sides_ok(width, height) || period < 1 || period > NAV_MAX_PERIOD) return TW_E_ARG;
+    return nav_timed_goal_shape_flooders(width * height, period);
+}
+
+extern "C" int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                       uint32_t pass_types, int flags, const uint32_t *blocked,
+                                       int64_t blocked_env_stride, int period, const int32_t *rec_t, const int32_t *rec_n,
+                                       const float *rec_goal, const uint8_t *rec_done, const float *rec_reward,
+                                       int64_t n_records, const float *pos_before, const float *pos_after,
+                                       const int32_t *age, const float *init_pos, int T, float scale, float gamma,
+                                       float *reward_out, float *shaping, uint8_t *mask, void *stream)
+{
+    if (!type || !rec_t || !rec_n || !rec_goal || !pos_before || !pos_after || !age || !init_pos) return TW_E_ARG;
+    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
+    if (pass_types > 0xFFFFu || (flags & ~(MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL))) return TW_E_ARG;
+    if (period < 1 || period > NAV_MAX_PERIOD || !blocked || ((uintptr_t)blocked & 3u)) return TW_E_ARG;
+    if (blocked_env_stride < 0 || (blocked_env_stride != 0 && blocked_env_stride < (int64_t)period * height)) return TW_E_ARG;
+    if (((uintptr_t)pos_before & 7u) || ((uintptr_t)pos_after & 7u)) return TW_E_ARG;
+    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
+    if (((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
+    if (((uintptr_t)rec_reward & 3u) || ((uintptr_t)reward_out & 3u) || ((uintptr_t)shaping & 3u)) return TW_E_ARG;
+    if (!reward_out && !shaping && !mask) return TW_E_ARG;
+    if (reward_out && !rec_reward) return TW_E_ARG;
+    if ((flags & MG_NAV_SHAPE_ZERO_TERMINAL) && !rec_done) return TW_E_ARG;
+    if (!nav_finite(scale) || !nav_finite(gamma)) return TW_E_ARG;
+    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (n_records == 0) return TW_OK;
+    const uint8_t *ends = (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? rec_done : nullptr;
+    const int HW = width * height, flooders = nav_timed_goal_shape_flooders(HW, period);
+    const size_t lds = (size_t)flooders * period * nav_timed_cells(HW) * sizeof(uint16_t);
+    // chunks are counted from the aligned address below each output: up to 15 records more than n_records
+    hipLaunchKernelGGL(nav_timed_goal_shape_kernels[period - 1],
+                       dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)), dim3(NAV_GOAL_THREADS), lds,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       blocked, blocked_env_stride, rec_t, rec_n, rec_goal, ends, rec_reward, n_records,
+                       reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
+                       init_pos, T, scale, gamma, reward_out, shaping, mask, flooders);
     return tw_launched(__func__);
 }

@@ -463,6 +463,23 @@ class TwoarmyEngine:
         return nav.timed_goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17, self._schedule(avoid_risk, ty.device),
                                     age, init_pos, nav.PASS_DEFAULT | nav.PASS_BALL, out=out, dist_out=dist_out)
 
+    def timed_goal_shape(self, her, pos_before, pos_after, age, init_pos, avoid_risk=False, scale=1.0, gamma=0.99,
+                         zero_terminal=False, out=None, shaping_out=None, mask_out=None):
+        """goal_shape over (cell, phase): potential-based shaping of hindsight records under their own goals with the
+        row-8 balls planned by their period-6 schedule (minigrid_nav.timed_goal_shape, one launch, read from the
+        engine's own planes, no field in memory) -> (reward' float32[R], F float32[R], mask uint8[R]), as goal_shape
+        returns them.  her, pos_before, pos_after, scale, gamma, zero_terminal and the outputs as goal_shape takes them;
+        age and init_pos required: the age of a step is its clock.  Planes and schedule exactly as timed_goal_moves takes
+        them -- the schedule timed_field() caches (avoid_risk as there), the plane's own balls passable (PASS_BALL), v6's
+        blocks planned as present from the reset on, v4's caveat unchanged -- so a record's potential is the one
+        shape() reads from timed_field()'s fields for the rollout."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        return nav.timed_goal_shape(ty, her["t"], her["n"], her["goal"], pos_before, pos_after, 17, 17,
+                                    self._schedule(avoid_risk, ty.device), age, init_pos, reward=her["reward"],
+                                    done=her["done"], pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, scale=scale, gamma=gamma,
+                                    zero_terminal=zero_terminal, out=out, shaping_out=shaping_out, mask_out=mask_out)
+
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""
         ms = C.c_float()

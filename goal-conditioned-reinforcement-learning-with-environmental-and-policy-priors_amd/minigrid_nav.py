@@ -3,8 +3,8 @@ of N grid worlds lies from the goal, and which of mg_step's four moves an agent 
 are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are int32[N] tensors, dense or the column views
 of the engine's records (TwoarmyEngine.agent_views()), read where they live.  goal_moves labels records that each name a
 goal of their own (hindsight records) without a field in memory.  timed_field / timed_moves do the same for worlds whose
-blockers move with a period (a search over (cell, phase): the expert may wait).  shape / goal_shape turn the distances
-into a potential and shape rewards with it, float32 with pinned rounding.  One launch per call, on the tensors' device.
+blockers move with a period (a search over (cell, phase): the expert may wait).  shape / goal_shape / timed_goal_shape turn
+the distances into a potential and shape rewards with it, float32 with pinned rounding.  One launch per call, on the tensors' device.
 No CPU fallback."""
 import ctypes
 
@@ -391,6 +391,52 @@ def goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width,
          ptr(init_pos, torch.float32), T, float(scale), float(gamma), ptr(out, torch.float32),
          ptr(shaping_out, torch.float32), ptr(mask_out, torch.uint8))
     return out, shaping_out, mask_out
+
+
+def timed_goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width, height, blocked, age, init_pos,
+                     reward=None, done=None, pass_types=PASS_DEFAULT, state=None, doors_open=False, scale=1.0, gamma=0.99,
+                     zero_terminal=False, out=None, shaping_out=None, mask_out=None):
+    """goal_shape for a world whose blockers move with a period (mg_nav_timed_goal_shape, include/minigrid_nav.h): the
+    planes, the records, blocked, age (the clock as well) and init_pos (both required) as timed_goal_moves takes them;
+    pos_before / pos_after float32[T, N, 2], reward float32[R] or None, done uint8[R] (required with zero_terminal=True),
+    scale, gamma and the three outputs as goal_shape takes them.  -> (out float32[R], F float32[R], mask uint8[R]): per
+    record what shape gives in the time-expanded field of the record's env flooded from the record's goal cell -- the
+    acting cell at the phase of its age, the after cell at the phase that follows; mask 0 (F = 0, the reward passed
+    through) for a record whose t, n, goal or either position names nothing, whose goal cell is free at no phase, or
+    whose acting or after state is not free at its phase or has no path.  One launch (none for R = 0), no field in memory,
+    no host synchronisation."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state is None or state.shape == (N, W * H)
+    dev = type_plane.device
+    bp, bstride, P = _schedule(blocked, N, H, dev)
+    R = rec_t.shape[0]
+    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
+    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
+    for p in (pos_before, pos_after):
+        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
+    T = pos_before.shape[0]
+    assert pos_after.shape[0] == T
+    assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
+    assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    assert not zero_terminal or done is not None, "zero_terminal needs done"
+    assert done is None or (done.shape == (R,) and done.device == dev)
+    out, shaping_out, mask_out = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)
+    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, shaping_out, mask_out
+    flags = (DOORS_OPEN if doors_open else 0) | (SHAPE_ZERO_TERMINAL if zero_terminal else 0)
+    call("mg_nav_timed_goal_shape", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
+         flags, bp, bstride, P, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32),
+         ptr(done, torch.uint8), ptr(reward, torch.float32), R, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
+         ptr(init_pos, torch.float32), T, float(scale), float(gamma), ptr(out, torch.float32),
+         ptr(shaping_out, torch.float32), ptr(mask_out, torch.uint8))
+    return out, shaping_out, mask_out
+
+
+def timed_goal_shape_floods(width, height, period):
+    """How many of a workgroup's 8 half wavefronts flood at a time in timed_goal_shape at this size and period (8, 4, 2 or
+    1: their images share 64 KiB of LDS with a staging larger than timed_goal_moves') -- the launch's own host function."""
+    return query("mg_nav_timed_goal_shape_floods", int(width), int(height), int(period))
 
 
 TWOARMY_PERIOD = 6

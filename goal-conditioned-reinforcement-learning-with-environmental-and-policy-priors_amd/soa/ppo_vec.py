@@ -105,7 +105,7 @@ class VecPPOTrainer:
         self._her_moves_of = None             # ... and the records (the dict relabel() made) they belong to
         self.bonus = None                     # BonusTracker, made by enable_bonus()
         self.reward_train = self.reward       # what targets and hindsight records use: the shaped reward when a bonus is on
-        self.shaping = None                   # potential-based shaping: {"scale", "hindsight", "timed"}, made by enable_shaping()
+        self.shaping = None                   # potential-based shaping: {"scale", "hindsight", "timed", "hindsight_timed"}, made by enable_shaping()
         self._relabel_at = -1                 # env_steps when relabel() last ran: shape_potential() comes after it
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
         self.env_steps = 0
@@ -669,22 +669,27 @@ class VecPPOTrainer:
                 "coef": self.prior_coef(), "her_labelled": hn if her else None, "her_agree": v[4] / hn if hn else None}
 
     # ------------------------------------------------------------------ potential-based reward shaping
-    def enable_shaping(self, scale, hindsight=True, timed=False):
+    def enable_shaping(self, scale, hindsight=True, timed=False, hindsight_timed=False):
         """Shape the training reward with the distance to the goal as a potential (include/minigrid_nav.h, "Reward
         shaping"): shape_potential() then adds F = gamma * Phi(s') - Phi(s), Phi = -scale * distance, to `reward_train`,
         which compute_targets() and carry_over() use, while `reward` -- and with it account_episodes(), running_score(),
         stats() and the HER switch -- stays extrinsic.  gamma is the agent's, and the terminal rule (Phi(s') = 0 at a done
         step) follows agent.use_done_mask.  hindsight=True: the records of relabel() are shaped too, each under its own
         goal (one mg_nav_goal_shape launch over her["reward"]).  timed=True: the rollout's potential comes from the
-        time-expanded field (TwoarmyEngine.timed_field, the age of a step being its clock); the records always use the
-        static map.  Call order in a rollout: collect() -> shape_rewards() -> relabel() -> shape_potential() ->
+        time-expanded field (TwoarmyEngine.timed_field, the age of a step being its clock); this switch leaves the records
+        on the static map.  hindsight_timed=True (needs hindsight=True, independent of timed, as in enable_prior): the
+        records are shaped by the time-expanded search under their own goals instead (one mg_nav_timed_goal_shape launch
+        in place of the mg_nav_goal_shape one) -- with timed=True both halves of a critic batch then use one potential
+        around the balls.  Call order in a rollout: collect() -> shape_rewards() -> relabel() -> shape_potential() ->
         label_expert() / compute_targets() -> carry_over()."""
         scale = float(scale)
         if not math.isfinite(scale) or scale <= 0.0:
             raise ValueError("enable_shaping(): scale must be a positive finite number, got %r" % scale)
-        if not isinstance(hindsight, bool) or not isinstance(timed, bool):
-            raise ValueError("enable_shaping(): hindsight and timed are booleans")
-        self.shaping = {"scale": scale, "hindsight": hindsight, "timed": timed}
+        if not isinstance(hindsight, bool) or not isinstance(timed, bool) or not isinstance(hindsight_timed, bool):
+            raise ValueError("enable_shaping(): hindsight, timed and hindsight_timed are booleans")
+        if hindsight_timed and not hindsight:
+            raise ValueError("enable_shaping(hindsight_timed=True) needs hindsight=True")
+        self.shaping = {"scale": scale, "hindsight": hindsight, "timed": timed, "hindsight_timed": hindsight_timed}
         if self.reward_train is self.reward:
             self.reward_train = torch.zeros_like(self.reward)
         self.shape_f = torch.zeros((self.T, self.N), dtype=torch.float32, device=self.device)
@@ -702,7 +707,10 @@ class VecPPOTrainer:
         after each step; `shape_f` float32[T, N] and `shape_mask` uint8[T, N] afterwards.  With hindsight shaping and
         records from relabel(): ONE mg_nav_goal_shape launch more shapes her["reward"] in place, each record under its
         own goal on the static map -- relabel() copied reward_train into the records BEFORE the env goal's term was
-        added, so no record carries another goal's term; `her_shape_f` and `her_shape_mask` afterwards.  Call after
+        added, so no record carries another goal's term; `her_shape_f` and `her_shape_mask` afterwards.  With
+        enable_shaping(hindsight_timed=True) that launch is mg_nav_timed_goal_shape instead
+        (TwoarmyEngine.timed_goal_shape): the same records, positions, ages, reset position, terminal flag and in-place
+        her["reward"], the balls on their schedule.  Call after
         shape_rewards() and relabel(), once per rollout; expect_her=True (the caller relabels this rollout) makes a call
         before relabel() an error.  No host synchronisation."""
         from .. import minigrid_nav as nav
@@ -730,9 +738,14 @@ class VecPPOTrainer:
         self._shaped_at = self.env_steps
         self.her_shape_f = self.her_shape_mask = self._her_shape_of = None
         if sh["hindsight"] and self.her is not None and self.her["t"].numel():
-            _, self.her_shape_f, self.her_shape_mask = self.engine.goal_shape(
-                self.her, before, after, self.age[:-1], self.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
-                scale=sh["scale"], gamma=self.agent.gamma, zero_terminal=zero_terminal, out=self.her["reward"])
+            if sh["hindsight_timed"]:
+                _, self.her_shape_f, self.her_shape_mask = self.engine.timed_goal_shape(
+                    self.her, before, after, self.age[:-1], self.init_pos, scale=sh["scale"], gamma=self.agent.gamma,
+                    zero_terminal=zero_terminal, out=self.her["reward"])
+            else:
+                _, self.her_shape_f, self.her_shape_mask = self.engine.goal_shape(
+                    self.her, before, after, self.age[:-1], self.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
+                    scale=sh["scale"], gamma=self.agent.gamma, zero_terminal=zero_terminal, out=self.her["reward"])
             self._her_shape_of = self.her                     # these terms belong to these records
         return self.reward_train
 

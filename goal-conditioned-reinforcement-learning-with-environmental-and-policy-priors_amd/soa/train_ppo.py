@@ -26,6 +26,9 @@ its own goal (minigrid_nav.timed_goal_moves in place of goal_moves: still one la
 (minigrid_nav.shape, one launch per rollout; the hindsight records each under their own goal, minigrid_nav.goal_shape,
 unless --shaping_no_hindsight; --shaping_timed: the rollout's potential from the time-expanded field); appends
 `shaping mean` / `unshaped` to the log line; off by default.
+--shaping_hindsight_timed (with --shaping_scale, not with --shaping_no_hindsight) shapes the hindsight records by the
+time-expanded search too, each under its own goal (minigrid_nav.timed_goal_shape in place of goal_shape: still one launch
+per rollout), so that with --shaping_timed both halves of a critic batch use one potential; off by default.
 """
 import argparse
 import math
@@ -140,7 +143,12 @@ def build_parser():
                         "shaped steps) and `unshaped` (share of steps without a distance) to the log line; 0 = off")
     p.add_argument("--shaping_timed", action="store_true",
                    help="with --shaping_scale: take the rollout's potential from the time-expanded field, in which the "
-                        "row-8 balls follow their period-6 schedule; the hindsight records stay on the static map")
+                        "row-8 balls follow their period-6 schedule; the hindsight records stay on the static map unless "
+                        "--shaping_hindsight_timed is given")
+    p.add_argument("--shaping_hindsight_timed", action="store_true",
+                   help="with --shaping_scale: shape the hindsight records by the time-expanded search as well, each "
+                        "under its own goal (a relabelled record is no longer rewarded for stepping into a row-8 ball); "
+                        "independent of --shaping_timed, not with --shaping_no_hindsight")
     p.add_argument("--shaping_no_hindsight", action="store_true",
                    help="with --shaping_scale: leave the hindsight records unshaped (by default each is shaped under its "
                         "own goal, one more launch per rollout, and `her shaping mean` / `her unshaped` are logged)")
@@ -239,6 +247,10 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--shaping_scale must be a finite number >= 0")
     if (args.shaping_timed or args.shaping_no_hindsight) and args.shaping_scale == 0.0:
         raise SystemExit("--shaping_timed / --shaping_no_hindsight need --shaping_scale")
+    if args.shaping_hindsight_timed and args.shaping_scale == 0.0:
+        raise SystemExit("--shaping_hindsight_timed needs --shaping_scale")
+    if args.shaping_hindsight_timed and args.shaping_no_hindsight:
+        raise SystemExit("--shaping_hindsight_timed shapes the hindsight records: not with --shaping_no_hindsight")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -302,7 +314,8 @@ def main(argv=None, predictor=False, soa=False):
                              hindsight_timed=args.prior_hindsight_timed)
     use_shaping = args.shaping_scale != 0.0
     if use_shaping:
-        trainer.enable_shaping(args.shaping_scale, hindsight=not args.shaping_no_hindsight, timed=args.shaping_timed)
+        trainer.enable_shaping(args.shaping_scale, hindsight=not args.shaping_no_hindsight, timed=args.shaping_timed,
+                               hindsight_timed=args.shaping_hindsight_timed)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):

@@ -319,6 +319,58 @@ int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int n_envs, int
                       int T, float scale, float gamma, float *reward_out, float *shaping, uint8_t *mask,
                       void *stream);
 
+/* mg_nav_goal_shape over (cell, phase): hindsight records, each under its OWN goal, shaped with the potential of a world
+ * whose blockers move -- the potential mg_nav_shape uses with a timed field, so that a rollout and its hindsight records
+ * agree around the blockers.  Nothing here is new: every rule is one of the blocks above.
+ *   type, state, n_envs, width, height, pass_types: the world exactly as in mg_nav_field (state nullable)
+ *   blocked, blocked_env_stride, period: the schedule; free cells, transition, distance and phase from the clock exactly
+ *                 as in the "time-expanded fields" block
+ *   rec_t, rec_n, rec_goal, n_records, pos_before, age, init_pos, T: the records and the acting positions exactly as in
+ *                 mg_nav_timed_goal_moves (pos_before for pos); age and init_pos are REQUIRED, age[t][n] is also the clock
+ *   pos_after, rec_done, rec_reward, scale, gamma, reward_out, shaping, mask: exactly as in mg_nav_goal_shape
+ * Per record b, with t = rec_t[b], n = rec_n[b]: let F be what mg_nav_timed_field computes for env n with
+ * visit_cell(rec_goal[b]) as its single source -- a source is 0 in every phase in which it is free.  The acting state is
+ * the acting cell of mg_nav_timed_goal_moves (age[t][n] <= 0 ? init_pos : pos_before[t][n], by the rule of the visit
+ * counters) at the phase of age[t][n]; the after state is visit_cell(pos_after[t][n]) at the phase that follows (the
+ * "Timed fields" paragraph of the shaping block).  Both distances are read in F; phi, the shaping term, out, the unshaped
+ * rule (F = +0.0f, the reward passed through bit for bit, mask = 0) and the terminal rule (MG_NAV_SHAPE_ZERO_TERMINAL
+ * with rec_done) are exactly those of mg_nav_goal_shape.
+ * A record is unshaped for every reason mg_nav_timed_goal_moves gives an empty label -- rec_t or rec_n out of range, a
+ * goal that is no cell or free at no phase, an acting state that is no cell, not free at its phase or without a path --
+ * and also when the after state is no cell, not free at its phase (a ball that moved onto the agent) or unreachable,
+ * unless the terminal rule applies.  No such record addresses memory outside its arrays.
+ * Invariants: (a) for records that share one goal per env the outputs equal mg_nav_timed_field(goal_x, goal_y) followed
+ * by mg_nav_shape with that period on the same elements; (b) with period = 1 and an all-zero schedule the outputs equal
+ * mg_nav_goal_shape's; (c) mask[b] != 0 implies that mg_nav_timed_goal_moves gives record b a non-empty move set, with
+ * the acting_dist the shaping used.
+ * As in mg_nav_timed_goal_moves: the result of record b depends on record b alone; one launch, no atomics (none for
+ * n_records == 0); a workgroup owns 1024 consecutive records and floods once per run of equal (env, goal cell) -- the
+ * phase is no part of the key; a flood ends after at most width*height*P rounds; every (width, height, period) the
+ * limits allow works (mg_nav_timed_goal_shape_floods).  The planes are read by the over-read rule; the outputs leave by
+ * the store rule of mg_nav_shape, nothing outside the first n_records elements is written.
+ * flags: MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL.
+ * TW_E_ARG: the cases of mg_nav_timed_goal_moves (pos_before and pos_after for pos, the three outputs for moves) and
+ * those of mg_nav_goal_shape: NULL age or init_pos; period outside 1..MG_NAV_MAX_PERIOD; NULL or misaligned blocked;
+ * blocked_env_stride < 0 or 0 < blocked_env_stride < P*height; rec_reward, reward_out or shaping not 4-byte aligned; no
+ * output given; reward_out without rec_reward; MG_NAV_SHAPE_ZERO_TERMINAL without rec_done; unknown flag bits; a
+ * non-finite scale or gamma. */
+int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                            uint32_t pass_types, int flags, const uint32_t *blocked, int64_t blocked_env_stride,
+                            int period, const int32_t *rec_t, const int32_t *rec_n, const float *rec_goal,
+                            const uint8_t *rec_done, const float *rec_reward, int64_t n_records, const float *pos_before,
+                            const float *pos_after, const int32_t *age, const float *init_pos, int T, float scale,
+                            float gamma, float *reward_out, float *shaping, uint8_t *mask, void *stream);
+
+/* Host only, no launch: how many floods a workgroup of mg_nav_timed_goal_shape runs at a time at this size and period.
+ * With cells = width*height rounded up to a multiple of 8 (whole 16-byte chunks per phase image), it is the largest f of
+ * 8, 4, 2, 1 with  MG_NAV_TIMED_GOAL_SHAPE_LDS + f * period * cells * 2 <= 65536,  and 1 if none is (one image always
+ * fits: 32 x 32 with P = 16 gives 1).  MG_NAV_TIMED_GOAL_SHAPE_LDS is the workgroup's staging in bytes -- the move sets'
+ * keys and heads, a phase byte per record, the three outputs on their way out, and 64 bytes for aligning them -- which is
+ * larger than that of mg_nav_timed_goal_moves, so the two counts differ.
+ * TW_E_ARG: a side <= 0 or > MG_NAV_MAX_SIDE, period outside 1..MG_NAV_MAX_PERIOD. */
+#define MG_NAV_TIMED_GOAL_SHAPE_LDS 25968
+int mg_nav_timed_goal_shape_floods(int width, int height, int period);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,22 @@ ht_s = timed(lambda: h_eng.timed_goal_moves(her, h_pos, h_age, h_tr.init_pos, ou
 report("mg_nav_timed_goal_moves (the same %d records, %d heads, P = 6)" % (R, n_heads),
        R * (4 + 4 + 8 + 8 + 4 + 1 + 2) + N * 289, ht_s,
        "one launch; %.1f floods per us, %.2f x mg_nav_goal_moves" % (n_heads / (ht_s * 1e6), ht_s / h_s))
+# Shaping of the same records under their own goals: on the static map, and over (cell, phase).  The yardsticks of the
+# timed launch are the two rows it is made of: mg_nav_goal_shape (its staging and stores) and mg_nav_timed_goal_moves (its
+# floods), taken in the same process on the same records.
+h_after = h_tr.pos[4:4 + T]
+hs_out, hs_f = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+hs_mask = torch.empty(R, dtype=torch.uint8, device=dev)
+hs_s = timed(lambda: h_eng.goal_shape(her, h_pos, h_after, h_age, h_tr.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
+                                      scale=0.05, gamma=0.99, out=hs_out, shaping_out=hs_f, mask_out=hs_mask))
+report("mg_nav_goal_shape (the same %d records, %d heads)" % (R, n_heads),
+       R * (4 + 4 + 8 + 8 + 8 + 4 + 4 + 4 + 4 + 1) + N * 289, hs_s, "one launch; %.2f x mg_nav_goal_moves" % (hs_s / h_s))
+for _ in range(3):                                             # three windows: the spread of the number below
+    hts_s = timed(lambda: h_eng.timed_goal_shape(her, h_pos, h_after, h_age, h_tr.init_pos, scale=0.05, gamma=0.99,
+                                                 out=hs_out, shaping_out=hs_f, mask_out=hs_mask))
+    report("mg_nav_timed_goal_shape (the same %d records, %d heads, P = 6)" % (R, n_heads),
+           R * (4 + 4 + 8 + 8 + 8 + 4 + 4 + 4 + 4 + 1) + N * 289, hts_s,
+           "one launch; %.2f x mg_nav_timed_goal_moves, %.2f x mg_nav_goal_shape" % (hts_s / ht_s, hts_s / hs_s))
 h_eng.close()
 del h_tr, h_eng, her
 mv_flat = torch.randint(0, 32, (T * N,), generator=g, dtype=torch.uint8).to(dev)
