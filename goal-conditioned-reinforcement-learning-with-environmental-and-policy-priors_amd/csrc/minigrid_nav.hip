@@ -28,8 +28,8 @@
  *                          the round before; one ballot per round decides "nothing new in any phase".  The image is
  *                          P * W*H distances per env in dynamic LDS, and the envs per workgroup (8, 4 or 2) follow from it.
  *                          The moves kernel serves the timed fields too (TIMED: the phase comes from the element's age).
- *   mg_nav_timed_goal_kernel<P>   the goal kernel over (cell, phase): its staging, heads and stores (nav_goal_* below) and
- *                          the timed field kernel's seed and round (nav_timed_*).  A record also keeps one phase byte; the
+ *   mg_nav_timed_goal_kernel<P>   the goal kernel over (cell, phase): its staging, heads and stores and the timed field
+ *                          kernel's seed and round.  A record also keeps one phase byte; the
  *                          phase is no part of a run's key, one flood serves every phase.  A flooding half wavefront owns
  *                          an image of P * W*H distances in dynamic LDS, and as many halves flood at a time (8, 4, 2 or 1)
  *                          as fit 64 KiB next to the staging; the other wavefronts skip the flood loop whole.
@@ -38,13 +38,15 @@
  *                          the acting and the after-step state from the env's field, parks shaped reward, shaping term and
  *                          mask in LDS and stores each as the chunks of its own alignment.  It reads `reward` for the
  *                          elements it stores only, before the barrier: shaping in place is safe.
- *   mg_nav_goal_shape_kernel   the same for records under goals of their own: the goal kernel's keys, heads and floods
- *                          (nav_goal_keys, nav_goal_heads, nav_goal_floods: written once, the labelling is a parameter),
+ *   mg_nav_goal_shape_kernel   the same for records under goals of their own: the goal kernel's keys, heads and floods,
  *                          a record also keeps its after-step cell; three float operations per record.
- *   mg_nav_timed_goal_shape_kernel<P>   the same over (cell, phase): the timed goal kernel's flood loop
- *                          (nav_timed_goal_floods<P>: written once, the labelling is a parameter) and the goal shaping
+ *   mg_nav_timed_goal_shape_kernel<P>   the same over (cell, phase): the timed goal kernel's flood loop and the goal shaping
  *                          kernel's after cells, label (nav_goal_shape_label, on the acting and the following phase's image)
  *                          and stores; its staging is larger than the move sets', so it has a flood count of its own.
+ *
+ * Shared: nav_image_clear, nav_dilate, nav_move_set<WAIT>; nav_out_span_t / nav_out_span / nav_out_store (one output of a
+ * workgroup, any element type: the goal kernel and the shaping kernels; the moves and the timed goal kernel measured slower
+ * on them and keep their own); nav_goal_records, _keys, _heads, _floods; on the host one nav_*_ok per argument rule.
  *
  * Integer work only but for the shaping term (three float32 operations, each rounded once: fp contract off), no atomics:
  * the results do not depend on scheduling.
@@ -97,10 +99,10 @@ __device__ __forceinline__ void nav_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Every cell of a 32 x 32 image starts unreachable: the 32 lanes of a half wavefront, then nav_wave_sync().
-__device__ __forceinline__ void nav_image_clear(uint16_t *img, int r)
+// Every distance of `chunks` 16-byte chunks starts unreachable: the 32 lanes of a half wavefront, then nav_wave_sync().
+__device__ __forceinline__ void nav_image_clear(uint16_t *img, int r, int chunks)
 {
-    for (int c = r; c < NAV_CELLS / 8; c += 32)
+    for (int c = r; c < chunks; c += 32)
         reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
 }
 
@@ -125,6 +127,16 @@ __device__ __forceinline__ uint32_t nav_open_row(const uint8_t *__restrict__ typ
     return open | doors;
 }
 
+// reached | its four neighbours, before the mask of enterable cells: the step of every flood (a timed one may wait)
+__device__ __forceinline__ uint32_t nav_dilate(uint32_t reached, int r)
+{
+    const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
+    uint32_t next = reached | reached << 1 | reached >> 1;
+    if (r > 0) next |= up;
+    if (r < 31) next |= dn;
+    return next;
+}
+
 // The flood of one half wavefront's world from the cells in `reached` (lane r holds row r; rows outside the world have
 // open = 0): cells reached in step k get k written into img.  The exit ballot is wavefront-wide, so EVERY lane of the
 // wavefront calls this together; a half with reached = 0 floods nothing.  At most cap steps whatever the input.
@@ -134,15 +146,35 @@ __device__ __forceinline__ void nav_flood(uint16_t *img, int r, int W, int cap, 
     for (int k = 0;; ++k) {
         for (uint32_t m = fresh; m != 0u; m &= m - 1u) img[r * W + (__ffs(m) - 1)] = (uint16_t)k;
         if (k >= cap) break;
-        const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
-        uint32_t next = reached | reached << 1 | reached >> 1;
-        if (r > 0) next |= up;
-        if (r < 31) next |= dn;
-        fresh = next & open & ~reached;
+        fresh = nav_dilate(reached, r) & open & ~reached;
         reached |= fresh;
         if (__ballot(fresh != 0u) == 0ull) break;                           // wavefront-uniform: both worlds are done
     }
 }
+
+// The optimal moves on cell c of a field row (minigrid_nav.h): bit k = neighbour k lies one move nearer; 0x10 on a source.
+// `next` is the row the move arrives in: `row` itself for a static field, the next phase's for a timed one, where staying
+// on c may be a move nearer too (WAIT: the stay bit then joins the others).
+template <bool WAIT = false>
+__device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ row, const uint16_t *__restrict__ next, int c,
+                                                 int W, int H, uint32_t &d)
+{
+    d = row[c];
+    if (d == 0u) return 0x10u;
+    if (d == (uint32_t)MG_NAV_UNREACHABLE) return 0u;
+    const int y = c / W, x = c - y * W;
+    const uint32_t want = d - 1u;
+    uint32_t m = 0;
+    if (x > 0 && next[c - 1] == want) m |= 1u;
+    if (x < W - 1 && next[c + 1] == want) m |= 2u;
+    if (y > 0 && next[c - W] == want) m |= 4u;
+    if (y < H - 1 && next[c + W] == want) m |= 8u;
+    if (WAIT && next[c] == want) m |= 0x10u;
+    return m;
+}
+
+// The phase of a clock value (minigrid_nav.h): 0 up to the episode's first step, the clock mod P after it.
+__device__ __forceinline__ int nav_phase(int clock, int P) { return clock <= 0 ? 0 : clock % P; }
 
 __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
@@ -158,7 +190,7 @@ __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     const bool row = e < N && r < H;                                        // this lane holds a row of the world
     uint16_t *img = image[slot];
 
-    nav_image_clear(img, r);                                                // every cell starts unreachable
+    nav_image_clear(img, r, NAV_CELLS / 8);                                 // every cell starts unreachable
     nav_wave_sync();                                                        // before other lanes write steps into it
 
     uint32_t open = 0, goals = 0;
@@ -182,27 +214,13 @@ __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     nav_wave_sync();
 
     if (e >= N) return;                                                     // a whole half wavefront at once
-    if (agent_dist != nullptr || agent_action != nullptr || (error != nullptr && agent_x != nullptr)) {
-        if (r == 0) {
-            const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride];
-            int d = MG_NAV_UNREACHABLE, a = MG_NAV_ACTION_NONE;
-            if (ax < 0 || ax >= W || ay < 0 || ay >= H) {
-                if (err == 0) err = 3;
-            } else {
-                const int c = ay * W + ax;
-                d = img[c];
-                if (d == 0) a = MG_NAV_ACTION_STAY;
-                else if (d != MG_NAV_UNREACHABLE) {
-                    const int want = d - 1;
-                    if (ax > 0 && img[c - 1] == want) a = 0;
-                    else if (ax < W - 1 && img[c + 1] == want) a = 1;
-                    else if (ay > 0 && img[c - W] == want) a = 2;
-                    else if (ay < H - 1 && img[c + W] == want) a = 3;
-                }
-            }
-            if (agent_dist) agent_dist[e] = d;
-            if (agent_action) agent_action[e] = a;
-        }
+    if ((agent_dist != nullptr || agent_action != nullptr || (error != nullptr && agent_x != nullptr)) && r == 0) {
+        const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride];
+        uint32_t d = MG_NAV_UNREACHABLE, m = 0;
+        if (ax >= 0 && ax < W && ay >= 0 && ay < H) m = nav_move_set(img, img, ay * W + ax, W, H, d);
+        else if (err == 0) err = 3;
+        if (agent_dist) agent_dist[e] = (int)d;                             // the lowest move: left, right, up, down
+        if (agent_action) agent_action[e] = m == 0u ? MG_NAV_ACTION_NONE : m == 0x10u ? MG_NAV_ACTION_STAY : __ffs(m) - 1;
     }
     if (error != nullptr && r == 0) error[e] = err;
     if (dist != nullptr) {
@@ -234,29 +252,33 @@ constexpr int NAV_MOVES_ELEMS = 2048;                  // elements per workgroup
 constexpr int NAV_MOVES_ROUNDS = (NAV_MOVES_ELEMS + 16 + NAV_MOVES_THREADS - 1) / NAV_MOVES_THREADS;
 static_assert(NAV_MOVES_ELEMS % 16 == 0, "whole chunks of both outputs");
 
-// The optimal moves on cell c of a field row (minigrid_nav.h): bit k = neighbour k lies one move nearer; 0x10 on a source.
-// `next` is the row the move arrives in: `row` itself for a static field, the next phase's for a timed one, where staying
-// on c may be a move nearer too (WAIT: the stay bit then joins the others).
-template <bool WAIT = false>
-__device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ row, const uint16_t *__restrict__ next, int c,
-                                                 int W, int H, uint32_t &d)
+// One output of a workgroup that owns `elems` consecutive elements (E per 16-byte chunk): its chunks of it, the elements
+// they hold -- within [elems * b - 15, elems * (b + 1)) and inside [0, M) -- and the element of slot 0 of its LDS staging.
+struct nav_out_span_t {
+    mg_row_span_t<int64_t> k;
+    int64_t base;
+    bool has;                                           // the output is given and the workgroup holds some of it
+    __device__ __forceinline__ bool holds(int64_t p) const { return has && p >= k.p_lo && p < k.p_hi; }
+};
+template <typename T> __device__ __forceinline__ nav_out_span_t nav_out_span(const T *out, int64_t M, int64_t b, int elems)
 {
-    d = row[c];
-    if (d == 0u) return 0x10u;
-    if (d == (uint32_t)MG_NAV_UNREACHABLE) return 0u;
-    const int y = c / W, x = c - y * W;
-    const uint32_t want = d - 1u;
-    uint32_t m = 0;
-    if (x > 0 && next[c - 1] == want) m |= 1u;
-    if (x < W - 1 && next[c + 1] == want) m |= 2u;
-    if (y > 0 && next[c - W] == want) m |= 4u;
-    if (y < H - 1 && next[c + W] == want) m |= 8u;
-    if (WAIT && next[c] == want) m |= 0x10u;
-    return m;
+    constexpr int E = 16 / sizeof(T);
+    const int s = out ? mg_row_misalign(out, E) : 0;
+    nav_out_span_t o;
+    o.k = mg_row_span<int64_t>(s, M, b, elems / E, E);
+    o.base = E * o.k.c0 - s;
+    o.has = out != nullptr && o.k.c0 < o.k.c1;
+    return o;
 }
-
-// The phase of a clock value (minigrid_nav.h): 0 up to the episode's first step, the clock mod P after it.
-__device__ __forceinline__ int nav_phase(int clock, int P) { return clock <= 0 ? 0 : clock % P; }
+// the staged elements leave through the aligned row store; after a __syncthreads()
+template <typename T> __device__ __forceinline__ void nav_out_store(T *__restrict__ out, int64_t M, const nav_out_span_t &o,
+                                                                    const T *staged, int threads)
+{
+    if (!o.has) return;
+    for (int64_t c = o.k.c0 + threadIdx.x; c < o.k.c1; c += threads)
+        mg_row_store(out, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(staged + (int)(p - o.base)); },
+                     [&](int64_t q) { return staged[(int)(q - o.base)]; });
+}
 
 // TIMED: dist holds P fields per env, age is given and is the clock of the element (mg_nav_timed_moves).
 template <bool TIMED> __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_moves_kernel(
@@ -268,7 +290,7 @@ template <bool TIMED> __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_na
     __shared__ __attribute__((aligned(16))) uint16_t s_dist[NAV_MOVES_ELEMS];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    // this workgroup's chunks of either output and the positions they hold: both within [ELEMS * b - 15, ELEMS * (b + 1))
+    // its two spans by hand, as before nav_out_span_t: on that the launch measured 0.9 % slower
     const int sm = mg_row_misalign(moves, 16), sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
     const mg_row_span_t<int64_t> km = mg_row_span<int64_t>(sm, M, b, NAV_MOVES_ELEMS / 16, 16);
     const mg_row_span_t<int64_t> kd = mg_row_span<int64_t>(sd, M, b, NAV_MOVES_ELEMS / 8, 8);
@@ -333,35 +355,24 @@ struct nav_goal_stage_t {
     int count[NAV_GOAL_ROUNDS][NAV_GOAL_THREADS / 64];
 };
 
-// A workgroup's chunks of either output and the records they hold, as in mg_nav_moves_kernel.
-struct nav_goal_share_t {
-    int sm, sd;
-    mg_row_span_t<int64_t> km, kd;
-    int64_t bm, bd;                                     // record of LDS slot 0 of either image
+// The records of workgroup b: those that the spans of its outputs hold between them.
+struct nav_goal_records_t {
     int64_t p0;                                         // record of slot 0 of the key arrays
-    bool has_m, has_d;
     int slot_lo, slot_hi;                               // 0 < slot_lo <= slot_hi <= SLOTS, or both 0: no record
 };
-
-__device__ __forceinline__ nav_goal_share_t nav_goal_share(const uint8_t *moves, const uint16_t *acting_dist, int64_t M,
-                                                           int64_t b)
+template <typename... Spans>
+__device__ __forceinline__ nav_goal_records_t nav_goal_records(int64_t M, int64_t b, const Spans &...spans)
 {
-    nav_goal_share_t g;
-    g.sm = mg_row_misalign(moves, 16);
-    g.sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
-    g.km = mg_row_span<int64_t>(g.sm, M, b, NAV_GOAL_ELEMS / 16, 16);
-    g.kd = mg_row_span<int64_t>(g.sd, M, b, NAV_GOAL_ELEMS / 8, 8);
-    g.bm = 16 * g.km.c0 - g.sm;
-    g.bd = 8 * g.kd.c0 - g.sd;
-    g.has_m = g.km.c0 < g.km.c1;
-    g.has_d = acting_dist != nullptr && g.kd.c0 < g.kd.c1;
+    nav_goal_records_t g;
     g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
-    int64_t lo = 0, hi = 0;                                                 // the records of this workgroup: both spans
-    if (g.has_m) { lo = g.km.p_lo; hi = g.km.p_hi; }
-    if (g.has_d) { lo = g.has_m && lo < g.kd.p_lo ? lo : g.kd.p_lo; hi = g.has_m && hi > g.kd.p_hi ? hi : g.kd.p_hi; }
-    // a workgroup that holds neither span (the last one may) has no slots
-    g.slot_lo = g.has_m || g.has_d ? (int)(lo - g.p0) : 0;
-    g.slot_hi = g.has_m || g.has_d ? (int)(hi - g.p0) : 0;
+    int64_t lo = M, hi = 0;
+    auto join = [&](const nav_out_span_t &o) {
+        if (o.has) { lo = lo < o.k.p_lo ? lo : o.k.p_lo; hi = hi > o.k.p_hi ? hi : o.k.p_hi; }
+    };
+    (join(spans), ...);
+    // a workgroup that holds no span (the last one may) has no slots
+    g.slot_lo = lo < hi ? (int)(lo - g.p0) : 0;
+    g.slot_hi = lo < hi ? (int)(hi - g.p0) : 0;
     return g;
 }
 
@@ -441,27 +452,12 @@ template <typename G> __device__ __forceinline__ int nav_goal_heads(nav_goal_sta
     return n_heads;
 }
 
-// the label of the record in slot i, parked for the stores
-__device__ __forceinline__ void nav_goal_label(nav_goal_stage_t &st, const nav_goal_share_t &g, int i, uint32_t m, uint32_t d)
+// the label of record p, parked for the stores of `moves` (sm) and `acting_dist` (sd)
+__device__ __forceinline__ void nav_goal_label(nav_goal_stage_t &st, const nav_out_span_t &sm, const nav_out_span_t &sd,
+                                               int64_t p, uint32_t m, uint32_t d)
 {
-    const int64_t p = g.p0 + i;
-    if (g.has_m && p >= g.km.p_lo && p < g.km.p_hi) st.moves[(int)(p - g.bm)] = (uint8_t)m;
-    if (g.has_d && p >= g.kd.p_lo && p < g.kd.p_hi) st.dist[(int)(p - g.bd)] = (uint16_t)d;
-}
-
-// both outputs leave as the moves kernel's do; after a __syncthreads()
-__device__ __forceinline__ void nav_goal_store(const nav_goal_stage_t &st, const nav_goal_share_t &g, int64_t M,
-                                               uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
-{
-    const int tid = threadIdx.x;
-    for (int64_t c = g.km.c0 + tid; c < g.km.c1; c += NAV_GOAL_THREADS)
-        mg_row_store(moves, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(st.moves + (int)(p - g.bm)); },
-                     [&](int64_t q) { return st.moves[(int)(q - g.bm)]; });
-    if (acting_dist != nullptr)
-        for (int64_t c = g.kd.c0 + tid; c < g.kd.c1; c += NAV_GOAL_THREADS)
-            mg_row_store(acting_dist, M, c,
-                         [&](int64_t p) { return *reinterpret_cast<const uint4 *>(st.dist + (int)(p - g.bd)); },
-                         [&](int64_t q) { return st.dist[(int)(q - g.bd)]; });
+    if (sm.holds(p)) st.moves[(int)(p - sm.base)] = (uint8_t)m;
+    if (sd.holds(p)) st.dist[(int)(p - sd.base)] = (uint16_t)d;
 }
 
 // One head per half wavefront and round: flood its goal into the half's image `img`, then label(i, img, ok) every record
@@ -493,7 +489,7 @@ template <typename Label> __device__ __forceinline__ void nav_goal_floods(
             }
             const int gc = st.goal[s0], gy = gc / W;
             if (r == gy) reached = (1u << (gc - gy * W)) & open;
-            nav_image_clear(img, r);
+            nav_image_clear(img, r, NAV_CELLS / 8);
         }
         nav_wave_sync();                                                    // before other lanes write steps into it
         nav_flood(img, r, W, HW, env >= 0 ? open : 0u, reached);
@@ -511,7 +507,9 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
 {
     __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
     __shared__ nav_goal_stage_t st;
-    const nav_goal_share_t g = nav_goal_share(moves, acting_dist, M, blockIdx.x);
+    const nav_out_span_t sm = nav_out_span(moves, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sd = nav_out_span(acting_dist, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_goal_records_t g = nav_goal_records(M, blockIdx.x, sm, sd);
 
     nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
     const int n_heads = nav_goal_heads(st, g);
@@ -520,10 +518,11 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
                         const int c = st.cell[i];
                         uint32_t d = MG_NAV_UNREACHABLE, m = 0;
                         if (ok && c != NAV_NO_CELL) m = nav_move_set(img, img, c, W, H, d);
-                        nav_goal_label(st, g, i, m, d);
+                        nav_goal_label(st, sm, sd, g.p0 + i, m, d);
                     });
     __syncthreads();
-    nav_goal_store(st, g, M, moves, acting_dist);
+    nav_out_store(moves, M, sm, st.moves, NAV_GOAL_THREADS);
+    nav_out_store(acting_dist, M, sd, st.dist, NAV_GOAL_THREADS);
 }
 
 // ------------------------------------------------------------------ time-expanded fields: blockers that move with period P
@@ -531,23 +530,15 @@ constexpr int NAV_MAX_PERIOD = MG_NAV_MAX_PERIOD;
 constexpr int NAV_TIMED_LDS = 48 * 1024;               // the image of a workgroup where 4 or 8 envs share one: 3 fit on a CU
 // uint16 elements of one phase's image: whole 16-byte chunks, so that every env's images start on one
 __host__ __device__ inline int nav_timed_cells(int HW) { return (HW + 7) & ~7; }
+// the dynamic LDS of a launch: `images` times P phase images
+inline size_t nav_timed_bytes(int images, int HW, int P) { return (size_t)images * P * nav_timed_cells(HW) * sizeof(uint16_t); }
 // Envs of a workgroup: 8 as in the field kernel while their images fit NAV_TIMED_LDS, else 4, else 2 (one wavefront; at
 // P = 16 and 32 x 32 cells that is 64 KiB, the most a launch asks for).
 inline int nav_timed_envs(int HW, int P)
 {
     int envs = NAV_ENVS;
-    while (envs > 2 && (size_t)envs * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)NAV_TIMED_LDS) envs >>= 1;
+    while (envs > 2 && nav_timed_bytes(envs, HW, P) > (size_t)NAV_TIMED_LDS) envs >>= 1;
     return envs;
-}
-
-// reached | its four neighbours, before the mask of free cells: the field kernel's step plus the row itself (waiting)
-__device__ __forceinline__ uint32_t nav_dilate(uint32_t reached, int r)
-{
-    const uint32_t up = __shfl_up(reached, 1, 32), dn = __shfl_down(reached, 1, 32);
-    uint32_t next = reached | reached << 1 | reached >> 1;
-    if (r > 0) next |= up;
-    if (r < 31) next |= dn;
-    return next;
 }
 
 // The sources of a timed flood: the cells of `src` in every phase in which they are free, at distance 0.  -> the row's
@@ -609,8 +600,7 @@ template <int P> __global__ __launch_bounds__(NAV_THREADS) void mg_nav_timed_fie
     const bool row = e < N && r < H;                                        // this lane holds a row of the world
     uint16_t *img = timed_image + (size_t)slot * P * cells;
 
-    for (int c = r; c < P * cells / 8; c += 32)                             // every state starts unreachable
-        reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    nav_image_clear(img, r, P * cells / 8);                                 // every state starts unreachable
     nav_wave_sync();                                                        // before other lanes write rounds into it
 
     uint32_t open = 0, goals = 0;
@@ -638,6 +628,7 @@ template <int P> __global__ __launch_bounds__(NAV_THREADS) void mg_nav_timed_fie
     nav_wave_sync();
 
     if (e >= N) return;                                                     // a whole half wavefront at once
+    // The agent, as this kernel had it before nav_move_set: on that and on shared helpers it measured 0.6 % slower.
     if (agent_dist != nullptr || agent_action != nullptr || (error != nullptr && agent_x != nullptr)) {
         if (r == 0) {
             const int ax = agent_x[(int64_t)e * astride], ay = agent_y[(int64_t)e * astride];
@@ -735,8 +726,7 @@ template <int P, typename Label> __device__ __forceinline__ void nav_timed_goal_
                 }
                 const int gc = st.goal[s0], gy = gc / W;
                 if (r == gy) src = 1u << (gc - gy * W);
-                for (int c = r; c < P * cells / 8; c += 32)                 // every state starts unreachable
-                    reinterpret_cast<uint4 *>(img)[c] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+                nav_image_clear(img, r, P * cells / 8);                     // every state starts unreachable
             }
             nav_wave_sync();                                                // before other lanes write rounds into it
             nav_timed_seed<P>(img, cells, r, W, src, fr, reached);          // src = 0: nothing is reached, nothing written
@@ -746,6 +736,63 @@ template <int P, typename Label> __device__ __forceinline__ void nav_timed_goal_
             nav_wave_sync();                                                // the labels are read before the image is reset
         }
     }
+}
+
+// mg_nav_timed_goal_kernel keeps the two spans of its outputs as it had them before nav_out_span_t served every kernel:
+// on nav_out_span / nav_out_store it measured 0.9 % slower.  At P = 6 that form has 2034 instructions
+// for 2029: 3 v_cmp_lt_i64, 4 s_cselect_b32, 2 v_mov_b64 more, 3 v_writelane and 5 v_readlane fewer; same registers.
+struct nav_goal_share_t {
+    int sm, sd;
+    mg_row_span_t<int64_t> km, kd;
+    int64_t bm, bd;                                     // record of LDS slot 0 of either image
+    int64_t p0;                                         // record of slot 0 of the key arrays
+    bool has_m, has_d;
+    int slot_lo, slot_hi;                               // 0 < slot_lo <= slot_hi <= SLOTS, or both 0: no record
+};
+
+__device__ __forceinline__ nav_goal_share_t nav_goal_share(const uint8_t *moves, const uint16_t *acting_dist, int64_t M,
+                                                           int64_t b)
+{
+    nav_goal_share_t g;
+    g.sm = mg_row_misalign(moves, 16);
+    g.sd = acting_dist ? mg_row_misalign(acting_dist, 8) : 0;
+    g.km = mg_row_span<int64_t>(g.sm, M, b, NAV_GOAL_ELEMS / 16, 16);
+    g.kd = mg_row_span<int64_t>(g.sd, M, b, NAV_GOAL_ELEMS / 8, 8);
+    g.bm = 16 * g.km.c0 - g.sm;
+    g.bd = 8 * g.kd.c0 - g.sd;
+    g.has_m = g.km.c0 < g.km.c1;
+    g.has_d = acting_dist != nullptr && g.kd.c0 < g.kd.c1;
+    g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
+    int64_t lo = 0, hi = 0;                                                 // the records of this workgroup: both spans
+    if (g.has_m) { lo = g.km.p_lo; hi = g.km.p_hi; }
+    if (g.has_d) { lo = g.has_m && lo < g.kd.p_lo ? lo : g.kd.p_lo; hi = g.has_m && hi > g.kd.p_hi ? hi : g.kd.p_hi; }
+    // a workgroup that holds neither span (the last one may) has no slots
+    g.slot_lo = g.has_m || g.has_d ? (int)(lo - g.p0) : 0;
+    g.slot_hi = g.has_m || g.has_d ? (int)(hi - g.p0) : 0;
+    return g;
+}
+
+// the label of the record in slot i, parked for the stores
+__device__ __forceinline__ void nav_goal_label(nav_goal_stage_t &st, const nav_goal_share_t &g, int i, uint32_t m, uint32_t d)
+{
+    const int64_t p = g.p0 + i;
+    if (g.has_m && p >= g.km.p_lo && p < g.km.p_hi) st.moves[(int)(p - g.bm)] = (uint8_t)m;
+    if (g.has_d && p >= g.kd.p_lo && p < g.kd.p_hi) st.dist[(int)(p - g.bd)] = (uint16_t)d;
+}
+
+// both outputs leave through the aligned row store; after a __syncthreads()
+__device__ __forceinline__ void nav_goal_store(const nav_goal_stage_t &st, const nav_goal_share_t &g, int64_t M,
+                                               uint8_t *__restrict__ moves, uint16_t *__restrict__ acting_dist)
+{
+    const int tid = threadIdx.x;
+    for (int64_t c = g.km.c0 + tid; c < g.km.c1; c += NAV_GOAL_THREADS)
+        mg_row_store(moves, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(st.moves + (int)(p - g.bm)); },
+                     [&](int64_t q) { return st.moves[(int)(q - g.bm)]; });
+    if (acting_dist != nullptr)
+        for (int64_t c = g.kd.c0 + tid; c < g.kd.c1; c += NAV_GOAL_THREADS)
+            mg_row_store(acting_dist, M, c,
+                         [&](int64_t p) { return *reinterpret_cast<const uint4 *>(st.dist + (int)(p - g.bd)); },
+                         [&](int64_t q) { return st.dist[(int)(q - g.bd)]; });
 }
 
 template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_timed_goal_kernel(
@@ -810,34 +857,6 @@ __device__ __forceinline__ bool nav_shape_term(uint32_t d_before, uint32_t d_aft
     if (d_before == (uint32_t)MG_NAV_UNREACHABLE || (!terminal && d_after == (uint32_t)MG_NAV_UNREACHABLE)) return false;
     F = nav_shaping(gamma, terminal ? 0.0f : nav_phi(scale, d_after), nav_phi(scale, d_before));
     return true;
-}
-
-// One output of a shaping kernel (E elements per 16-byte chunk): a workgroup's chunks of it, the elements they hold and
-// the element of slot 0 of its LDS staging, as mg_nav_moves_kernel keeps them for `moves` and `acting_dist`.
-struct nav_out_span_t {
-    mg_row_span_t<int64_t> k;
-    int64_t base;
-    bool has;                                           // the output is given and the workgroup holds some of it
-    __device__ __forceinline__ bool holds(int64_t p) const { return has && p >= k.p_lo && p < k.p_hi; }
-};
-template <typename T> __device__ __forceinline__ nav_out_span_t nav_out_span(const T *out, int64_t M, int64_t b, int elems)
-{
-    constexpr int E = 16 / sizeof(T);
-    const int s = out ? mg_row_misalign(out, E) : 0;
-    nav_out_span_t o;
-    o.k = mg_row_span<int64_t>(s, M, b, elems / E, E);
-    o.base = E * o.k.c0 - s;
-    o.has = out != nullptr && o.k.c0 < o.k.c1;
-    return o;
-}
-// the staged elements leave through the aligned row store; after a __syncthreads()
-template <typename T> __device__ __forceinline__ void nav_out_store(T *__restrict__ out, int64_t M, const nav_out_span_t &o,
-                                                                    const T *staged, int threads)
-{
-    if (!o.has) return;
-    for (int64_t c = o.k.c0 + threadIdx.x; c < o.k.c1; c += threads)
-        mg_row_store(out, M, c, [&](int64_t p) { return *reinterpret_cast<const uint4 *>(staged + (int)(p - o.base)); },
-                     [&](int64_t q) { return staged[(int)(q - o.base)]; });
 }
 
 static_assert(NAV_MOVES_ELEMS % 16 == 0 && NAV_MOVES_ELEMS % 4 == 0, "whole chunks of the float outputs and of the mask");
@@ -909,34 +928,9 @@ static_assert(NAV_CELLS < NAV_TERMINAL, "the two marks are no cells");
 static_assert(sizeof(nav_goal_stage_t) + sizeof(nav_goal_shape_stage_t) + NAV_GOAL_HALVES * NAV_CELLS * sizeof(uint16_t) + 64
                   <= 64 * 1024, "the staging of a shaping workgroup fits 64 KiB next to its 8 images");
 
-// a shaping workgroup's records: those of its three spans (nav_goal_keys, nav_goal_heads)
-struct nav_goal_shape_share_t {
-    nav_out_span_t so, sf, sm;
-    int64_t p0;                                         // record of slot 0 of the key arrays
-    int slot_lo, slot_hi;                               // 0 < slot_lo <= slot_hi <= SLOTS, or both 0: no record
-};
-
-__device__ __forceinline__ nav_goal_shape_share_t nav_goal_shape_share(const float *reward_out, const float *shaping,
-                                                                       const uint8_t *mask, int64_t M, int64_t b)
-{
-    nav_goal_shape_share_t g;
-    g.so = nav_out_span(reward_out, M, b, NAV_GOAL_ELEMS);
-    g.sf = nav_out_span(shaping, M, b, NAV_GOAL_ELEMS);
-    g.sm = nav_out_span(mask, M, b, NAV_GOAL_ELEMS);
-    g.p0 = (int64_t)NAV_GOAL_ELEMS * b - 16;
-    int64_t lo = M, hi = 0;                                                 // the records of this workgroup: all three spans
-    auto join = [&](const nav_out_span_t &o) {
-        if (o.has) { lo = lo < o.k.p_lo ? lo : o.k.p_lo; hi = hi > o.k.p_hi ? hi : o.k.p_hi; }
-    };
-    join(g.so); join(g.sf); join(g.sm);
-    g.slot_lo = lo < hi ? (int)(lo - g.p0) : 0;
-    g.slot_hi = lo < hi ? (int)(hi - g.p0) : 0;
-    return g;
-}
-
 // What a shaping kernel keeps of record p (slot i, element `at` or -1) besides its keys: nav_goal_keys' `more`.
-__device__ __forceinline__ void nav_goal_shape_more(nav_goal_shape_stage_t &sh, const nav_goal_shape_share_t &g, int i,
-                                                    int64_t p, int64_t at, const uint8_t *__restrict__ rec_done,
+__device__ __forceinline__ void nav_goal_shape_more(nav_goal_shape_stage_t &sh, const nav_out_span_t &so, int i, int64_t p,
+                                                    int64_t at, const uint8_t *__restrict__ rec_done,
                                                     const float *rec_reward, const float2 *__restrict__ pos_after, int W,
                                                     int H)
 {
@@ -951,28 +945,28 @@ __device__ __forceinline__ void nav_goal_shape_more(nav_goal_shape_stage_t &sh, 
     }
     sh.after[i] = (uint16_t)a;
     // read before the barrier, by the workgroup that stores it: reward_out may be rec_reward
-    if (g.so.holds(p)) sh.out[(int)(p - g.so.base)] = rec_reward[p];
+    if (so.holds(p)) sh.out[(int)(p - so.base)] = rec_reward[p];
 }
 
-// The shaping label of the record in slot i, parked for the stores: its acting cell c is read in `before`, its after cell
+// The shaping label of record p in slot i, parked for the stores: its acting cell c is read in `before`, its after cell
 // in `after` (one image for a static field, the acting and the following phase's for a timed one); ok = the run has a result.
-__device__ __forceinline__ void nav_goal_shape_label(nav_goal_shape_stage_t &sh, const nav_goal_shape_share_t &g, int i,
+__device__ __forceinline__ void nav_goal_shape_label(nav_goal_shape_stage_t &sh, const nav_out_span_t &so,
+                                                     const nav_out_span_t &sf, const nav_out_span_t &sm, int64_t p, int i,
                                                      int c, const uint16_t *before, const uint16_t *after, bool ok,
                                                      float scale, float gamma)
 {
-    const int64_t p = g.p0 + i;
     const int a = sh.after[i];
     float F = 0.0f;
     bool shaped = false;
     if (ok && c != NAV_NO_CELL && a != NAV_NO_CELL)
         shaped = nav_shape_term(before[c], a == NAV_TERMINAL ? (uint32_t)MG_NAV_UNREACHABLE : after[a], a == NAV_TERMINAL,
                                 scale, gamma, F);
-    if (shaped && g.so.holds(p)) {
-        float &o = sh.out[(int)(p - g.so.base)];
+    if (shaped && so.holds(p)) {
+        float &o = sh.out[(int)(p - so.base)];
         o = nav_shaped(o, F);
     }
-    if (g.sf.holds(p)) sh.f[(int)(p - g.sf.base)] = F;
-    if (g.sm.holds(p)) sh.mask[(int)(p - g.sm.base)] = shaped ? 1 : 0;
+    if (sf.holds(p)) sh.f[(int)(p - sf.base)] = F;
+    if (sm.holds(p)) sh.mask[(int)(p - sm.base)] = shaped ? 1 : 0;
 }
 
 __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_shape_kernel(
@@ -986,21 +980,24 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_shape_kernel(
     __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
     __shared__ nav_goal_stage_t st;
     __shared__ nav_goal_shape_stage_t sh;
-    const nav_goal_shape_share_t g = nav_goal_shape_share(reward_out, shaping, mask, M, blockIdx.x);
+    const nav_out_span_t so = nav_out_span(reward_out, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sf = nav_out_span(shaping, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sm = nav_out_span(mask, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_goal_records_t g = nav_goal_records(M, blockIdx.x, so, sf, sm);
 
     nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos_before, age, init_pos, T,
                          [&](int i, int64_t p, int64_t at) {
-                             nav_goal_shape_more(sh, g, i, p, at, rec_done, rec_reward, pos_after, W, H);
+                             nav_goal_shape_more(sh, so, i, p, at, rec_done, rec_reward, pos_after, W, H);
                          });
     const int n_heads = nav_goal_heads(st, g);
     nav_goal_floods(st, image[threadIdx.x >> 5], n_heads, type, state, W, H, pass_types, doors_open,
                     [&](int i, const uint16_t *img, bool ok) {
-                        nav_goal_shape_label(sh, g, i, st.cell[i], img, img, ok, scale, gamma);
+                        nav_goal_shape_label(sh, so, sf, sm, g.p0 + i, i, st.cell[i], img, img, ok, scale, gamma);
                     });
     __syncthreads();
-    nav_out_store(reward_out, M, g.so, sh.out, NAV_GOAL_THREADS);
-    nav_out_store(shaping, M, g.sf, sh.f, NAV_GOAL_THREADS);
-    nav_out_store(mask, M, g.sm, sh.mask, NAV_GOAL_THREADS);
+    nav_out_store(reward_out, M, so, sh.out, NAV_GOAL_THREADS);
+    nav_out_store(shaping, M, sf, sh.f, NAV_GOAL_THREADS);
+    nav_out_store(mask, M, sm, sh.mask, NAV_GOAL_THREADS);
 }
 
 // ------------------------------------------------------------------ timed shaping of records with goals of their own
@@ -1033,23 +1030,26 @@ template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_time
     __shared__ nav_goal_shape_stage_t sh;
     __shared__ uint8_t s_phase[NAV_GOAL_SLOTS];                             // the phase of a record's clock
     const int HW = W * H, cells = nav_timed_cells(HW);
-    const nav_goal_shape_share_t g = nav_goal_shape_share(reward_out, shaping, mask, M, blockIdx.x);
+    const nav_out_span_t so = nav_out_span(reward_out, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sf = nav_out_span(shaping, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sm = nav_out_span(mask, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_goal_records_t g = nav_goal_records(M, blockIdx.x, so, sf, sm);
 
     nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos_before, age, init_pos, T,
                         [&](int i, int64_t p, int64_t at) {
-                            nav_goal_shape_more(sh, g, i, p, at, rec_done, rec_reward, pos_after, W, H);
+                            nav_goal_shape_more(sh, so, i, p, at, rec_done, rec_reward, pos_after, W, H);
                         });
     const int n_heads = nav_goal_heads(st, g);
     nav_timed_goal_floods<P>(st, goal_shape_image, n_heads, flooders, type, state, W, H, pass_types, doors_open, blocked,
                              bstride, [&](int i, const uint16_t *img, bool ok) {
                                  const int ph = s_phase[i];                 // the after state's phase follows the acting one
-                                 nav_goal_shape_label(sh, g, i, st.cell[i], img + ph * cells,
+                                 nav_goal_shape_label(sh, so, sf, sm, g.p0 + i, i, st.cell[i], img + ph * cells,
                                                       img + (ph + 1 == P ? 0 : ph + 1) * cells, ok, scale, gamma);
                              });
     __syncthreads();
-    nav_out_store(reward_out, M, g.so, sh.out, NAV_GOAL_THREADS);
-    nav_out_store(shaping, M, g.sf, sh.f, NAV_GOAL_THREADS);
-    nav_out_store(mask, M, g.sm, sh.mask, NAV_GOAL_THREADS);
+    nav_out_store(reward_out, M, so, sh.out, NAV_GOAL_THREADS);
+    nav_out_store(shaping, M, sf, sh.f, NAV_GOAL_THREADS);
+    nav_out_store(mask, M, sm, sh.mask, NAV_GOAL_THREADS);
 }
 
 using nav_timed_goal_shape_kernel_t = decltype(&mg_nav_timed_goal_shape_kernel<1>);
@@ -1058,9 +1058,70 @@ template <int... Ps> constexpr nav_timed_goal_shape_kernel_t nav_timed_goal_shap
 constexpr const nav_timed_goal_shape_kernel_t *nav_timed_goal_shape_kernels =   // [P - 1]
     nav_timed_goal_shape_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
+// ------------------------------------------------------------------ the argument rules of minigrid_nav.h, each once
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
-bool nav_finite(float v) { return __builtin_isfinite(v); }
+bool nav_period_ok(int P) { return P >= 1 && P <= NAV_MAX_PERIOD; }
+bool nav_flags_ok(int flags, int allowed) { return (flags & ~allowed) == 0; }
+bool nav_aligned(const void *p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }       // NULL is aligned
+bool nav_count_ok(int64_t count) { return count >= 0 && count < ((int64_t)1 << 40); }     // elements or records of a launch
 
+bool nav_world_ok(const uint8_t *type, int n_envs, int W, int H, uint32_t pass_types, int flags, int allowed)
+{
+    return type && n_envs > 0 && nav_sides_ok(W, H) && pass_types <= 0xFFFFu && nav_flags_ok(flags, allowed);
+}
+
+// fields in memory: rows of W * H distances, dist_pitch elements apart (0: dense); required: dist is no option
+bool nav_field_ok(const uint16_t *dist, int64_t dist_pitch, int n_envs, int W, int H, bool required)
+{
+    return (dist || !required) && nav_aligned(dist, 2) && n_envs > 0 && nav_sides_ok(W, H) &&
+           (dist_pitch == 0 || dist_pitch >= (int64_t)W * H);
+}
+int64_t nav_pitch(int64_t dist_pitch, int W, int H) { return dist_pitch ? dist_pitch : (int64_t)W * H; }
+
+// the schedule: period * height words per env, blocked_env_stride words apart (0: one schedule for all envs)
+bool nav_schedule_ok(const uint32_t *blocked, int64_t blocked_env_stride, int period, int height)
+{
+    return nav_period_ok(period) && blocked && nav_aligned(blocked, 4) &&
+           (blocked_env_stride == 0 || blocked_env_stride >= (int64_t)period * height);
+}
+
+// goals and agents: x and y come together, each pair with a positive stride; wanted: an output or the clock asks for the agent
+bool nav_agents_ok(const int32_t *goal_x, const int32_t *goal_y, int goal_stride, const int32_t *agent_x,
+                   const int32_t *agent_y, int agent_stride, bool wanted)
+{
+    return (goal_x == nullptr) == (goal_y == nullptr) && (agent_x == nullptr) == (agent_y == nullptr) &&
+           (agent_x || !wanted) && (!goal_x || goal_stride > 0) && (!agent_x || agent_stride > 0);
+}
+
+bool nav_records_ok(const int32_t *rec_t, const int32_t *rec_n, const float *rec_goal, int64_t n_records)
+{
+    return rec_t && rec_n && rec_goal && nav_aligned(rec_t, 4) && nav_aligned(rec_n, 4) && nav_aligned(rec_goal, 4) &&
+           nav_count_ok(n_records);
+}
+
+bool nav_rollout_ok(const float *pos, int T) { return pos && nav_aligned(pos, 8) && T >= 0; }
+
+// the clock: age comes with init_pos; required: the age is the clock of a timed field, both must be given
+bool nav_clock_ok(const int32_t *age, const float *init_pos, bool required)
+{
+    return (required ? age && init_pos : !age || init_pos) && nav_aligned(age, 4) && nav_aligned(init_pos, 4);
+}
+
+bool nav_moves_out_ok(const uint8_t *moves, const uint16_t *acting_dist) { return moves && nav_aligned(acting_dist, 2); }
+// shaping: an output at least, reward_out with a reward, the terminal flag with done, finite scale and gamma
+bool nav_shaping_ok(const float *reward, const uint8_t *done, int flags, float scale, float gamma, const float *reward_out,
+                    const float *shaping, const uint8_t *mask)
+{
+    return (reward_out || shaping || mask) && (!reward_out || reward) && (!(flags & MG_NAV_SHAPE_ZERO_TERMINAL) || done) &&
+           nav_aligned(reward, 4) && nav_aligned(reward_out, 4) && nav_aligned(shaping, 4) && __builtin_isfinite(scale) &&
+           __builtin_isfinite(gamma);
+}
+const uint8_t *nav_ends(const uint8_t *done, int flags) { return (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? done : nullptr; }
+
+// workgroups of `elems` elements: chunks are counted from the aligned address below each output, up to 15 more than count
+dim3 nav_grid(int64_t count, int elems) { return dim3((unsigned)((count + 15 + elems - 1) / elems)); }
+
+const float2 *nav_f2(const float *pos) { return reinterpret_cast<const float2 *>(pos); }
 }  // namespace
 
 extern "C" int mg_nav_field(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
@@ -1068,34 +1129,28 @@ extern "C" int mg_nav_field(const uint8_t *type, const uint8_t *state, int n_env
                             const int32_t *agent_x, const int32_t *agent_y, int agent_stride, uint16_t *dist,
                             int64_t dist_pitch, int32_t *agent_dist, int32_t *agent_action, int32_t *error, void *stream)
 {
-    if (!type || n_envs <= 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
-    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
-    if ((uintptr_t)dist & 1u) return TW_E_ARG;
-    if ((goal_x == nullptr) != (goal_y == nullptr) || (agent_x == nullptr) != (agent_y == nullptr)) return TW_E_ARG;
-    if ((agent_dist || agent_action) && !agent_x) return TW_E_ARG;
-    if ((goal_x && goal_stride <= 0) || (agent_x && agent_stride <= 0)) return TW_E_ARG;
-    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
+        !nav_field_ok(dist, dist_pitch, n_envs, width, height, false) ||
+        !nav_agents_ok(goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, agent_dist || agent_action))
+        return TW_E_ARG;
     hipLaunchKernelGGL(mg_nav_field_kernel, dim3((n_envs + NAV_ENVS - 1) / NAV_ENVS), dim3(NAV_THREADS), 0,
                        (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
-                       goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, dist, pitch, agent_dist, agent_action,
-                       error);
+                       goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, dist,
+                       nav_pitch(dist_pitch, width, height), agent_dist, agent_action, error);
     return tw_launched(__func__);
 }
 
 extern "C" int mg_nav_lookup(const uint16_t *dist, int64_t dist_pitch, int n_envs, int width, int height, const float *pos,
                              int T, uint16_t *out, void *stream)
 {
-    if (!dist || !pos || !out || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
-    if (((uintptr_t)dist & 1u) || ((uintptr_t)out & 1u) || ((uintptr_t)pos & 7u)) return TW_E_ARG;
     const int64_t M = (int64_t)T * n_envs;
-    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_rollout_ok(pos, T) || !out ||
+        !nav_aligned(out, 2) || !nav_count_ok(M))
+        return TW_E_ARG;
     if (M == 0) return TW_OK;
-    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
     hipLaunchKernelGGL(mg_nav_lookup_kernel, dim3((unsigned)((M + NAV_LOOKUP_THREADS - 1) / NAV_LOOKUP_THREADS)),
-                       dim3(NAV_LOOKUP_THREADS), 0, (hipStream_t)stream, dist, pitch, n_envs, width, height,
-                       reinterpret_cast<const float2 *>(pos), M, out);
+                       dim3(NAV_LOOKUP_THREADS), 0, (hipStream_t)stream, dist, nav_pitch(dist_pitch, width, height), n_envs,
+                       width, height, nav_f2(pos), M, out);
     return tw_launched(__func__);
 }
 
@@ -1103,18 +1158,14 @@ extern "C" int mg_nav_optimal_moves(const uint16_t *dist, int64_t dist_pitch, in
                                     const float *pos, const int32_t *age, const float *init_pos, int T, uint8_t *moves,
                                     uint16_t *acting_dist, void *stream)
 {
-    if (!dist || !pos || !moves || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
-    if (((uintptr_t)dist & 1u) || ((uintptr_t)acting_dist & 1u) || ((uintptr_t)pos & 7u)) return TW_E_ARG;
-    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
     const int64_t M = (int64_t)T * n_envs;
-    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, false) || !nav_moves_out_ok(moves, acting_dist) || !nav_count_ok(M))
+        return TW_E_ARG;
     if (M == 0) return TW_OK;
-    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
-    // chunks are counted from the aligned address below either output: up to 15 positions more than M
-    hipLaunchKernelGGL(mg_nav_moves_kernel<false>, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
-                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, 1, n_envs, width, height,
-                       reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
+    hipLaunchKernelGGL(mg_nav_moves_kernel<false>, nav_grid(M, NAV_MOVES_ELEMS), dim3(NAV_MOVES_THREADS), 0,
+                       (hipStream_t)stream, dist, nav_pitch(dist_pitch, width, height), 1, n_envs, width, height,
+                       nav_f2(pos), age, init_pos, M, moves, acting_dist);
     return tw_launched(__func__);
 }
 
@@ -1123,19 +1174,14 @@ extern "C" int mg_nav_goal_moves(const uint8_t *type, const uint8_t *state, int 
                                  const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                                  const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream)
 {
-    if (!type || !rec_t || !rec_n || !rec_goal || !pos || !moves) return TW_E_ARG;
-    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
-    if (((uintptr_t)pos & 7u) || ((uintptr_t)acting_dist & 1u)) return TW_E_ARG;
-    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
-    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
-    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
+        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, false) || !nav_moves_out_ok(moves, acting_dist))
+        return TW_E_ARG;
     if (n_records == 0) return TW_OK;
-    // chunks are counted from the aligned address below either output: up to 15 records more than n_records
-    hipLaunchKernelGGL(mg_nav_goal_kernel, dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)),
-                       dim3(NAV_GOAL_THREADS), 0, (hipStream_t)stream, type, state, n_envs, width, height, pass_types,
-                       flags & MG_NAV_DOORS_OPEN, rec_t, rec_n, rec_goal, n_records,
-                       reinterpret_cast<const float2 *>(pos), age, init_pos, T, moves, acting_dist);
+    hipLaunchKernelGGL(mg_nav_goal_kernel, nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS), 0,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       rec_t, rec_n, rec_goal, n_records, nav_f2(pos), age, init_pos, T, moves, acting_dist);
     return tw_launched(__func__);
 }
 
@@ -1146,22 +1192,17 @@ extern "C" int mg_nav_timed_field(const uint8_t *type, const uint8_t *state, int
                                   int agent_stride, uint16_t *dist, int64_t dist_pitch, int32_t *agent_dist,
                                   int32_t *agent_action, int32_t *error, void *stream)
 {
-    if (!type || n_envs <= 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
-    if (period < 1 || period > NAV_MAX_PERIOD || !blocked || ((uintptr_t)blocked & 3u)) return TW_E_ARG;
-    if (blocked_env_stride < 0 || (blocked_env_stride != 0 && blocked_env_stride < (int64_t)period * height)) return TW_E_ARG;
-    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
-    if ((uintptr_t)dist & 1u) return TW_E_ARG;
-    if ((goal_x == nullptr) != (goal_y == nullptr) || (agent_x == nullptr) != (agent_y == nullptr)) return TW_E_ARG;
-    if ((agent_dist || agent_action || agent_clock) && !agent_x) return TW_E_ARG;
-    if ((goal_x && goal_stride <= 0) || (agent_x && agent_stride <= 0)) return TW_E_ARG;
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
+        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
+        !nav_field_ok(dist, dist_pitch, n_envs, width, height, false) ||
+        !nav_agents_ok(goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, agent_dist || agent_action || agent_clock))
+        return TW_E_ARG;
     const int HW = width * height, envs = nav_timed_envs(HW, period);
-    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)HW;
-    const size_t lds = (size_t)envs * period * nav_timed_cells(HW) * sizeof(uint16_t);
-    hipLaunchKernelGGL(nav_timed_kernels[period - 1], dim3((n_envs + envs - 1) / envs), dim3(32 * envs), lds,
-                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
-                       blocked, blocked_env_stride, goal_x, goal_y, goal_stride, agent_x, agent_y, agent_clock,
-                       agent_stride, dist, pitch, agent_dist, agent_action, error);
+    hipLaunchKernelGGL(nav_timed_kernels[period - 1], dim3((n_envs + envs - 1) / envs), dim3(32 * envs),
+                       nav_timed_bytes(envs, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
+                       pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, goal_x, goal_y, goal_stride,
+                       agent_x, agent_y, agent_clock, agent_stride, dist, nav_pitch(dist_pitch, width, height), agent_dist,
+                       agent_action, error);
     return tw_launched(__func__);
 }
 
@@ -1169,24 +1210,20 @@ extern "C" int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int 
                                   const float *pos, const int32_t *age, const float *init_pos, int T, uint8_t *moves,
                                   uint16_t *acting_dist, void *stream)
 {
-    if (!dist || !pos || !moves || !age || !init_pos || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (period < 1 || period > NAV_MAX_PERIOD) return TW_E_ARG;
-    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
-    if (((uintptr_t)dist & 1u) || ((uintptr_t)acting_dist & 1u) || ((uintptr_t)pos & 7u)) return TW_E_ARG;
-    if (((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
     const int64_t M = (int64_t)T * n_envs;
-    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, true) || !nav_moves_out_ok(moves, acting_dist) || !nav_count_ok(M))
+        return TW_E_ARG;
     if (M == 0) return TW_OK;
-    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
-    hipLaunchKernelGGL(mg_nav_moves_kernel<true>, dim3((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS)),
-                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, pitch, period, n_envs, width, height,
-                       reinterpret_cast<const float2 *>(pos), age, init_pos, M, moves, acting_dist);
+    hipLaunchKernelGGL(mg_nav_moves_kernel<true>, nav_grid(M, NAV_MOVES_ELEMS), dim3(NAV_MOVES_THREADS), 0,
+                       (hipStream_t)stream, dist, nav_pitch(dist_pitch, width, height), period, n_envs, width, height,
+                       nav_f2(pos), age, init_pos, M, moves, acting_dist);
     return tw_launched(__func__);
 }
 
 extern "C" int mg_nav_timed_goal_floods(int width, int height, int period)
 {
-    if (!nav_sides_ok(width, height) || period < 1 || period > NAV_MAX_PERIOD) return TW_E_ARG;
+    if (!nav_sides_ok(width, height) || !nav_period_ok(period)) return TW_E_ARG;
     return nav_timed_goal_flooders(width * height, period);
 }
 
@@ -1196,24 +1233,17 @@ extern "C" int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state
                                        const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                                        const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream)
 {
-    if (!type || !rec_t || !rec_n || !rec_goal || !pos || !moves || !age || !init_pos) return TW_E_ARG;
-    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (pass_types > 0xFFFFu || (flags & ~MG_NAV_DOORS_OPEN)) return TW_E_ARG;
-    if (period < 1 || period > NAV_MAX_PERIOD || !blocked || ((uintptr_t)blocked & 3u)) return TW_E_ARG;
-    if (blocked_env_stride < 0 || (blocked_env_stride != 0 && blocked_env_stride < (int64_t)period * height)) return TW_E_ARG;
-    if (((uintptr_t)pos & 7u) || ((uintptr_t)acting_dist & 1u)) return TW_E_ARG;
-    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
-    if (((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
-    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
+        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
+        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, true) || !nav_moves_out_ok(moves, acting_dist))
+        return TW_E_ARG;
     if (n_records == 0) return TW_OK;
     const int HW = width * height, flooders = nav_timed_goal_flooders(HW, period);
-    const size_t lds = (size_t)flooders * period * nav_timed_cells(HW) * sizeof(uint16_t);
-    // chunks are counted from the aligned address below either output: up to 15 records more than n_records
-    hipLaunchKernelGGL(nav_timed_goal_kernels[period - 1],
-                       dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)), dim3(NAV_GOAL_THREADS), lds,
-                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
-                       blocked, blocked_env_stride, rec_t, rec_n, rec_goal, n_records,
-                       reinterpret_cast<const float2 *>(pos), age, init_pos, T, moves, acting_dist, flooders);
+    hipLaunchKernelGGL(nav_timed_goal_kernels[period - 1], nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
+                       nav_timed_bytes(flooders, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
+                       pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
+                       n_records, nav_f2(pos), age, init_pos, T, moves, acting_dist, flooders);
     return tw_launched(__func__);
 }
 
@@ -1222,27 +1252,17 @@ extern "C" int mg_nav_shape(const uint16_t *dist, int64_t dist_pitch, int period
                             const uint8_t *done, const float *reward, int T, float scale, float gamma, int flags,
                             float *reward_out, float *shaping, uint8_t *mask, void *stream)
 {
-    if (!dist || !pos_before || !pos_after || n_envs <= 0 || T < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (period < 1 || period > NAV_MAX_PERIOD || (period > 1 && (!age || !init_pos))) return TW_E_ARG;
-    if (dist_pitch < 0 || (dist_pitch != 0 && dist_pitch < (int64_t)width * height)) return TW_E_ARG;
-    if (((uintptr_t)dist & 1u) || ((uintptr_t)pos_before & 7u) || ((uintptr_t)pos_after & 7u)) return TW_E_ARG;
-    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
-    if (((uintptr_t)reward & 3u) || ((uintptr_t)reward_out & 3u) || ((uintptr_t)shaping & 3u)) return TW_E_ARG;
-    if (!reward_out && !shaping && !mask) return TW_E_ARG;
-    if (reward_out && !reward) return TW_E_ARG;
-    if ((flags & ~MG_NAV_SHAPE_ZERO_TERMINAL) || ((flags & MG_NAV_SHAPE_ZERO_TERMINAL) && !done)) return TW_E_ARG;
-    if (!nav_finite(scale) || !nav_finite(gamma)) return TW_E_ARG;
     const int64_t M = (int64_t)T * n_envs;
-    if (M >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) ||
+        !nav_rollout_ok(pos_before, T) || !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, period > 1) ||
+        !nav_flags_ok(flags, MG_NAV_SHAPE_ZERO_TERMINAL) ||     // no MG_NAV_DOORS_OPEN: the doors are the field's business
+        !nav_shaping_ok(reward, done, flags, scale, gamma, reward_out, shaping, mask) || !nav_count_ok(M))
+        return TW_E_ARG;
     if (M == 0) return TW_OK;
-    const int64_t pitch = dist_pitch ? dist_pitch : (int64_t)width * height;
-    const uint8_t *ends = (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? done : nullptr;
-    // chunks are counted from the aligned address below each output: up to 15 positions more than M
-    const dim3 grid((unsigned)((M + 15 + NAV_MOVES_ELEMS - 1) / NAV_MOVES_ELEMS));
-    hipLaunchKernelGGL(period > 1 ? mg_nav_shape_kernel<true> : mg_nav_shape_kernel<false>, grid, dim3(NAV_MOVES_THREADS), 0,
-                       (hipStream_t)stream, dist, pitch, period, n_envs, width, height,
-                       reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
-                       init_pos, ends, reward, M, scale, gamma, reward_out, shaping, mask);
+    hipLaunchKernelGGL(period > 1 ? mg_nav_shape_kernel<true> : mg_nav_shape_kernel<false>, nav_grid(M, NAV_MOVES_ELEMS),
+                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, nav_pitch(dist_pitch, width, height), period,
+                       n_envs, width, height, nav_f2(pos_before), nav_f2(pos_after), age, init_pos, nav_ends(done, flags),
+                       reward, M, scale, gamma, reward_out, shaping, mask);
     return tw_launched(__func__);
 }
 
@@ -1253,32 +1273,22 @@ extern "C" int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int 
                                  const float *init_pos, int T, float scale, float gamma, float *reward_out, float *shaping,
                                  uint8_t *mask, void *stream)
 {
-    if (!type || !rec_t || !rec_n || !rec_goal || !pos_before || !pos_after) return TW_E_ARG;
-    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (pass_types > 0xFFFFu || (flags & ~(MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL))) return TW_E_ARG;
-    if (((uintptr_t)pos_before & 7u) || ((uintptr_t)pos_after & 7u)) return TW_E_ARG;
-    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
-    if ((age && !init_pos) || ((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
-    if (((uintptr_t)rec_reward & 3u) || ((uintptr_t)reward_out & 3u) || ((uintptr_t)shaping & 3u)) return TW_E_ARG;
-    if (!reward_out && !shaping && !mask) return TW_E_ARG;
-    if (reward_out && !rec_reward) return TW_E_ARG;
-    if ((flags & MG_NAV_SHAPE_ZERO_TERMINAL) && !rec_done) return TW_E_ARG;
-    if (!nav_finite(scale) || !nav_finite(gamma)) return TW_E_ARG;
-    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL) ||
+        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos_before, T) ||
+        !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, false) ||
+        !nav_shaping_ok(rec_reward, rec_done, flags, scale, gamma, reward_out, shaping, mask))
+        return TW_E_ARG;
     if (n_records == 0) return TW_OK;
-    const uint8_t *ends = (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? rec_done : nullptr;
-    // chunks are counted from the aligned address below each output: up to 15 records more than n_records
-    hipLaunchKernelGGL(mg_nav_goal_shape_kernel, dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)),
-                       dim3(NAV_GOAL_THREADS), 0, (hipStream_t)stream, type, state, n_envs, width, height, pass_types,
-                       flags & MG_NAV_DOORS_OPEN, rec_t, rec_n, rec_goal, ends, rec_reward, n_records,
-                       reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
-                       init_pos, T, scale, gamma, reward_out, shaping, mask);
+    hipLaunchKernelGGL(mg_nav_goal_shape_kernel, nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS), 0,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       rec_t, rec_n, rec_goal, nav_ends(rec_done, flags), rec_reward, n_records, nav_f2(pos_before),
+                       nav_f2(pos_after), age, init_pos, T, scale, gamma, reward_out, shaping, mask);
     return tw_launched(__func__);
 }
 
 extern "C" int mg_nav_timed_goal_shape_floods(int width, int height, int period)
 {
-    if (!nav_sides_ok(width, height) || period < 1 || period > NAV_MAX_PERIOD) return TW_E_ARG;
+    if (!nav_sides_ok(width, height) || !nav_period_ok(period)) return TW_E_ARG;
     return nav_timed_goal_shape_flooders(width * height, period);
 }
 
@@ -1290,30 +1300,18 @@ extern "C" int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state
                                        const int32_t *age, const float *init_pos, int T, float scale, float gamma,
                                        float *reward_out, float *shaping, uint8_t *mask, void *stream)
 {
-    if (!type || !rec_t || !rec_n || !rec_goal || !pos_before || !pos_after || !age || !init_pos) return TW_E_ARG;
-    if (n_envs <= 0 || T < 0 || n_records < 0 || !nav_sides_ok(width, height)) return TW_E_ARG;
-    if (pass_types > 0xFFFFu || (flags & ~(MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL))) return TW_E_ARG;
-    if (period < 1 || period > NAV_MAX_PERIOD || !blocked || ((uintptr_t)blocked & 3u)) return TW_E_ARG;
-    if (blocked_env_stride < 0 || (blocked_env_stride != 0 && blocked_env_stride < (int64_t)period * height)) return TW_E_ARG;
-    if (((uintptr_t)pos_before & 7u) || ((uintptr_t)pos_after & 7u)) return TW_E_ARG;
-    if (((uintptr_t)rec_t & 3u) || ((uintptr_t)rec_n & 3u) || ((uintptr_t)rec_goal & 3u)) return TW_E_ARG;
-    if (((uintptr_t)age & 3u) || ((uintptr_t)init_pos & 3u)) return TW_E_ARG;
-    if (((uintptr_t)rec_reward & 3u) || ((uintptr_t)reward_out & 3u) || ((uintptr_t)shaping & 3u)) return TW_E_ARG;
-    if (!reward_out && !shaping && !mask) return TW_E_ARG;
-    if (reward_out && !rec_reward) return TW_E_ARG;
-    if ((flags & MG_NAV_SHAPE_ZERO_TERMINAL) && !rec_done) return TW_E_ARG;
-    if (!nav_finite(scale) || !nav_finite(gamma)) return TW_E_ARG;
-    if (n_records >= ((int64_t)1 << 40)) return TW_E_ARG;
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL) ||
+        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
+        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos_before, T) ||
+        !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, true) ||
+        !nav_shaping_ok(rec_reward, rec_done, flags, scale, gamma, reward_out, shaping, mask))
+        return TW_E_ARG;
     if (n_records == 0) return TW_OK;
-    const uint8_t *ends = (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? rec_done : nullptr;
     const int HW = width * height, flooders = nav_timed_goal_shape_flooders(HW, period);
-    const size_t lds = (size_t)flooders * period * nav_timed_cells(HW) * sizeof(uint16_t);
-    // chunks are counted from the aligned address below each output: up to 15 records more than n_records
-    hipLaunchKernelGGL(nav_timed_goal_shape_kernels[period - 1],
-                       dim3((unsigned)((n_records + 15 + NAV_GOAL_ELEMS - 1) / NAV_GOAL_ELEMS)), dim3(NAV_GOAL_THREADS), lds,
-                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
-                       blocked, blocked_env_stride, rec_t, rec_n, rec_goal, ends, rec_reward, n_records,
-                       reinterpret_cast<const float2 *>(pos_before), reinterpret_cast<const float2 *>(pos_after), age,
+    hipLaunchKernelGGL(nav_timed_goal_shape_kernels[period - 1], nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
+                       nav_timed_bytes(flooders, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
+                       pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
+                       nav_ends(rec_done, flags), rec_reward, n_records, nav_f2(pos_before), nav_f2(pos_after), age,
                        init_pos, T, scale, gamma, reward_out, shaping, mask, flooders);
     return tw_launched(__func__);
 }

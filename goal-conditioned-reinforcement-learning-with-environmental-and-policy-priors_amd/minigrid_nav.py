@@ -10,7 +10,7 @@ import ctypes
 
 import torch
 
-from ._marshal import agent_arrays, call, ptr, query, rows
+from ._marshal import agent_arrays, call, inner, ptr, query, rows
 
 MAX_SIDE = 32
 MAX_PERIOD = 16                       # timed_field: phases of a schedule
@@ -26,6 +26,64 @@ MOVE_STAY = 1 << 4                    # optimal_moves: the bit of a source cell 
 DIST_DTYPE = torch.uint16
 
 
+def _planes(type_plane, state, width, height):
+    """(N, W, H, device) of the world planes uint8[N, H*W]."""
+    N, W, H = type_plane.shape[0], int(width), int(height)
+    assert type_plane.shape == (N, W * H)
+    assert state is None or state.shape == (N, W * H)
+    return N, W, H, type_plane.device
+
+
+def _records(rec_t, rec_n, rec_goal, dev):
+    """R of the records t[R], n[R], goal[R, 2]."""
+    R = rec_t.shape[0]
+    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
+    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
+    return R
+
+
+def _positions(N, dev, *pos):
+    """T of one or two rollout position tensors float32[T, N, 2]."""
+    for p in pos:
+        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
+    T = pos[0].shape[0]
+    assert pos[-1].shape[0] == T
+    return T
+
+
+def _clock(age, init_pos, T, N, dev, required=False):
+    """age int32[T, N] comes with init_pos float32[2]; required: the age is the clock of a timed field."""
+    if required:
+        assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
+    else:
+        assert (age is None) == (init_pos is None), "age and init_pos come together"
+    if age is not None:
+        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+
+
+def _moves_outputs(shape, dev, out, dist_out):
+    """(out, dist_out) of a moves launch: None = a new tensor, dist_out False = no distances (None is returned)."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    assert out.shape == shape and out.device == dev
+    if dist_out is None:
+        dist_out = torch.empty(shape, dtype=DIST_DTYPE, device=dev)
+    elif dist_out is False:
+        dist_out = None
+    assert dist_out is None or (dist_out.shape == shape and dist_out.device == dev)
+    return out, dist_out
+
+
+def _timed_rows(dist, W, H):
+    """(pointer, pitch in elements, N, P) of fields uint16[N, P, H*W] whose rows are dense but may be padded."""
+    assert dist.is_cuda and dist.dtype == DIST_DTYPE and dist.dim() == 3 and dist.shape[2] == W * H
+    N, P = dist.shape[0], dist.shape[1]
+    inner(dist, 2)
+    dpitch = dist.stride(1) if P > 1 else (dist.stride(0) if N > 1 else W * H)
+    assert dpitch >= W * H and (N == 1 or dist.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
+    return ctypes.c_void_p(dist.data_ptr()), int(dpitch), N, P
+
+
 def distance_field(type_plane, state_plane, width, height, pass_types=PASS_DEFAULT, goal=None, agent=None, out=None,
                    doors_open=False, want_field=True, want_error=True, agent_out=None, error_out=None):
     """-> (dist, agent_dist, agent_action, error).
@@ -35,10 +93,7 @@ def distance_field(type_plane, state_plane, width, height, pass_types=PASS_DEFAU
     (0 left, 1 right, 2 up, 3 down, 6 stay on a source, -1 unreachable), else None.  error int32[N]: 0 ok, 1 no source,
     2 source outside the world, 3 agent outside the world.  agent_out = (agent_dist, agent_action) and error_out:
     contiguous int32[N] tensors to write into, so that a call per step allocates nothing."""
-    N, W, H = type_plane.shape[0], int(width), int(height)
-    assert type_plane.shape == (N, W * H)
-    assert state_plane is None or state_plane.shape == (N, W * H)
-    dev = type_plane.device
+    N, W, H, dev = _planes(type_plane, state_plane, width, height)
     dp, dpitch = None, 0
     if out is not None or want_field:
         if out is None:
@@ -101,19 +156,9 @@ def optimal_moves(dist, pos, width, height, age=None, init_pos=None, out=None, d
     dp, dpitch, N, row = rows(dist, DIST_DTYPE)
     assert row == W * H
     dev = dist.device
-    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
-    T = pos.shape[0]
-    assert (age is None) == (init_pos is None), "age and init_pos come together"
-    if age is not None:
-        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
-    if out is None:
-        out = torch.empty((T, N), dtype=torch.uint8, device=dev)
-    assert out.shape == (T, N) and out.device == dev
-    if dist_out is None:
-        dist_out = torch.empty((T, N), dtype=DIST_DTYPE, device=dev)
-    elif dist_out is False:
-        dist_out = None
-    assert dist_out is None or (dist_out.shape == (T, N) and dist_out.device == dev)
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev)
+    out, dist_out = _moves_outputs((T, N), dev, out, dist_out)
     call("mg_nav_optimal_moves", dev, dp, dpitch, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
          ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
     return out, dist_out
@@ -128,26 +173,11 @@ def goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, pass_type
     gives in the field of the record's env flooded from the record's goal cell; 0 / UNREACHABLE for a record whose t,
     n, goal or acting position names nothing.  out / dist_out: tensors to write into; dist_out=False: no distances
     (None is returned for them).  One launch (none for R = 0), no host synchronisation."""
-    N, W, H = type_plane.shape[0], int(width), int(height)
-    assert type_plane.shape == (N, W * H)
-    assert state is None or state.shape == (N, W * H)
-    dev = type_plane.device
-    R = rec_t.shape[0]
-    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
-    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
-    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
-    T = pos.shape[0]
-    assert (age is None) == (init_pos is None), "age and init_pos come together"
-    if age is not None:
-        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
-    if out is None:
-        out = torch.empty((R,), dtype=torch.uint8, device=dev)
-    assert out.shape == (R,) and out.device == dev
-    if dist_out is None:
-        dist_out = torch.empty((R,), dtype=DIST_DTYPE, device=dev)
-    elif dist_out is False:
-        dist_out = None
-    assert dist_out is None or (dist_out.shape == (R,) and dist_out.device == dev)
+    N, W, H, dev = _planes(type_plane, state, width, height)
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev)
+    out, dist_out = _moves_outputs((R,), dev, out, dist_out)
     if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
         return out, dist_out
     call("mg_nav_goal_moves", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
@@ -177,20 +207,14 @@ def timed_field(type_plane, state_plane, width, height, blocked, pass_types=PASS
     [N, P, H*W] tensor whose rows may be padded; want_field=False: None).  agent = (x, y) int32[N] with clock int32[N]
     sharing their stride (None: phase 0): the agent's phase is clock <= 0 ? 0 : clock % P.  agent_action: 0..3 a move, 6
     stay on a source OR wait for the blockers, -1 unreachable.  Everything else as distance_field takes and returns it."""
-    N, W, H = type_plane.shape[0], int(width), int(height)
-    assert type_plane.shape == (N, W * H)
-    assert state_plane is None or state_plane.shape == (N, W * H)
-    dev = type_plane.device
+    N, W, H, dev = _planes(type_plane, state_plane, width, height)
     bp, bstride, P = _schedule(blocked, N, H, dev)
     dp, dpitch = None, 0
     if out is not None or want_field:
         if out is None:
             out = torch.empty((N, P, W * H), dtype=DIST_DTYPE, device=dev)
-        assert out.dim() == 3 and out.shape == (N, P, W * H) and out.device == dev and out.dtype == DIST_DTYPE
-        assert out.stride(2) == 1 or W * H == 1, "the rows must be dense"
-        dpitch = out.stride(1) if P > 1 else (out.stride(0) if N > 1 else W * H)
-        assert dpitch >= W * H and (N == 1 or out.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
-        dp = _marshal_ptr(out)
+        dp, dpitch, No, Po = _timed_rows(out, W, H)
+        assert (No, Po) == (N, P) and out.device == dev
     gx = gy = ax = ay = cp = None
     gstride = astride = 1
     if goal is not None:
@@ -211,12 +235,6 @@ def timed_field(type_plane, state_plane, width, height, blocked, pass_types=PASS
     return out, adist, aact, err
 
 
-def _marshal_ptr(t):
-    """Address of a device tensor whose (padded) layout the caller has checked."""
-    assert t.is_cuda
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def timed_moves(dist, pos, width, height, age, init_pos, out=None, dist_out=None):
     """optimal_moves for a timed field (mg_nav_timed_moves, include/minigrid_nav.h): dist uint16[N, P, H*W] as
     timed_field returns it (rows may be padded), pos float32[T, N, 2] = (y, x) BEFORE each step, age int32[T, N] (the
@@ -224,27 +242,14 @@ def timed_moves(dist, pos, width, height, age, init_pos, out=None, dist_out=None
     -> (moves uint8[T, N], acting_dist uint16[T, N]): bits 0..3 = the move leads one transition nearer, MOVE_STAY = on a
     source, or waiting is optimal; 0 on an unreachable state or outside the world.  out / dist_out as in optimal_moves."""
     W, H = int(width), int(height)
-    assert dist.is_cuda and dist.dtype == DIST_DTYPE and dist.dim() == 3 and dist.shape[2] == W * H
-    N, P = dist.shape[0], dist.shape[1]
-    assert dist.stride(2) == 1 or W * H == 1, "the rows must be dense"
-    dpitch = dist.stride(1) if P > 1 else (dist.stride(0) if N > 1 else W * H)
-    assert dpitch >= W * H and (N == 1 or dist.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
+    dp, dpitch, N, P = _timed_rows(dist, W, H)
     dev = dist.device
-    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
-    T = pos.shape[0]
-    assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
-    assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
-    if out is None:
-        out = torch.empty((T, N), dtype=torch.uint8, device=dev)
-    assert out.shape == (T, N) and out.device == dev
-    if dist_out is None:
-        dist_out = torch.empty((T, N), dtype=DIST_DTYPE, device=dev)
-    elif dist_out is False:
-        dist_out = None
-    assert dist_out is None or (dist_out.shape == (T, N) and dist_out.device == dev)
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev, required=True)
+    out, dist_out = _moves_outputs((T, N), dev, out, dist_out)
     if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
         return out, dist_out
-    call("mg_nav_timed_moves", dev, _marshal_ptr(dist), int(dpitch), P, N, W, H, ptr(pos), ptr(age, torch.int32),
+    call("mg_nav_timed_moves", dev, dp, dpitch, P, N, W, H, ptr(pos), ptr(age, torch.int32),
          ptr(init_pos, torch.float32), T, ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
     return out, dist_out
 
@@ -260,26 +265,12 @@ def timed_goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blo
     the goal, or waiting is optimal; 0 / UNREACHABLE for a record whose t, n, goal or acting position names nothing,
     whose goal cell is free at no phase or whose state has no path.  out / dist_out as in goal_moves.  One launch (none
     for R = 0), no field in memory, no host synchronisation."""
-    N, W, H = type_plane.shape[0], int(width), int(height)
-    assert type_plane.shape == (N, W * H)
-    assert state is None or state.shape == (N, W * H)
-    dev = type_plane.device
+    N, W, H, dev = _planes(type_plane, state, width, height)
     bp, bstride, P = _schedule(blocked, N, H, dev)
-    R = rec_t.shape[0]
-    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
-    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
-    assert pos.dtype == torch.float32 and pos.dim() == 3 and pos.is_contiguous() and pos.shape[1:] == (N, 2) and pos.device == dev
-    T = pos.shape[0]
-    assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
-    assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
-    if out is None:
-        out = torch.empty((R,), dtype=torch.uint8, device=dev)
-    assert out.shape == (R,) and out.device == dev
-    if dist_out is None:
-        dist_out = torch.empty((R,), dtype=DIST_DTYPE, device=dev)
-    elif dist_out is False:
-        dist_out = None
-    assert dist_out is None or (dist_out.shape == (R,) and dist_out.device == dev)
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev, required=True)
+    out, dist_out = _moves_outputs((R,), dev, out, dist_out)
     if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
         return out, dist_out
     call("mg_nav_timed_goal_moves", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
@@ -324,25 +315,15 @@ def shape(dist, pos_before, pos_after, width, height, reward=None, age=None, ini
     shapes in place), False: not wanted (None is returned for it); out needs a reward.  One launch (none for T = 0)."""
     W, H = int(width), int(height)
     if dist.dim() == 3:
-        assert dist.is_cuda and dist.dtype == DIST_DTYPE and dist.shape[2] == W * H
-        N, P = dist.shape[0], dist.shape[1]
-        assert dist.stride(2) == 1 or W * H == 1, "the rows must be dense"
-        dpitch = dist.stride(1) if P > 1 else (dist.stride(0) if N > 1 else W * H)
-        assert dpitch >= W * H and (N == 1 or dist.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
-        dp = _marshal_ptr(dist)
+        dp, dpitch, N, P = _timed_rows(dist, W, H)
     else:
         dp, dpitch, N, row = rows(dist, DIST_DTYPE)
         P = 1
         assert row == W * H
     dev = dist.device
-    for p in (pos_before, pos_after):
-        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
-    T = pos_before.shape[0]
-    assert pos_after.shape[0] == T
-    assert (age is None) == (init_pos is None), "age and init_pos come together"
+    T = _positions(N, dev, pos_before, pos_after)
+    _clock(age, init_pos, T, N, dev)
     assert age is not None or P == 1, "the age is the clock: age and init_pos are required with a timed field"
-    if age is not None:
-        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
     assert not zero_terminal or done is not None, "zero_terminal needs done"
     assert done is None or (done.shape == (T, N) and done.device == dev)
     out, shaping_out, mask_out = _shape_outputs((T, N), dev, reward, out, shaping_out, mask_out)
@@ -365,20 +346,10 @@ def goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width,
     gives in the field of the record's env flooded from the record's goal cell; mask 0 (F = 0, the reward passed through)
     for a record whose t, n, goal or either position names nothing or has no path.  out / shaping_out / mask_out as in
     shape.  One launch (none for R = 0), no field in memory, no host synchronisation."""
-    N, W, H = type_plane.shape[0], int(width), int(height)
-    assert type_plane.shape == (N, W * H)
-    assert state is None or state.shape == (N, W * H)
-    dev = type_plane.device
-    R = rec_t.shape[0]
-    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
-    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
-    for p in (pos_before, pos_after):
-        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
-    T = pos_before.shape[0]
-    assert pos_after.shape[0] == T
-    assert (age is None) == (init_pos is None), "age and init_pos come together"
-    if age is not None:
-        assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    N, W, H, dev = _planes(type_plane, state, width, height)
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, pos_before, pos_after)
+    _clock(age, init_pos, T, N, dev)
     assert not zero_terminal or done is not None, "zero_terminal needs done"
     assert done is None or (done.shape == (R,) and done.device == dev)
     out, shaping_out, mask_out = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)
@@ -405,20 +376,11 @@ def timed_goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, 
     through) for a record whose t, n, goal or either position names nothing, whose goal cell is free at no phase, or
     whose acting or after state is not free at its phase or has no path.  One launch (none for R = 0), no field in memory,
     no host synchronisation."""
-    N, W, H = type_plane.shape[0], int(width), int(height)
-    assert type_plane.shape == (N, W * H)
-    assert state is None or state.shape == (N, W * H)
-    dev = type_plane.device
+    N, W, H, dev = _planes(type_plane, state, width, height)
     bp, bstride, P = _schedule(blocked, N, H, dev)
-    R = rec_t.shape[0]
-    assert rec_t.shape == (R,) and rec_n.shape == (R,) and rec_goal.shape == (R, 2), "expected t[R], n[R], goal[R, 2]"
-    assert rec_t.device == dev and rec_n.device == dev and rec_goal.device == dev
-    for p in (pos_before, pos_after):
-        assert p.dtype == torch.float32 and p.dim() == 3 and p.is_contiguous() and p.shape[1:] == (N, 2) and p.device == dev
-    T = pos_before.shape[0]
-    assert pos_after.shape[0] == T
-    assert age is not None and init_pos is not None, "the age is the clock: age and init_pos are required"
-    assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, pos_before, pos_after)
+    _clock(age, init_pos, T, N, dev, required=True)
     assert not zero_terminal or done is not None, "zero_terminal needs done"
     assert done is None or (done.shape == (R,) and done.device == dev)
     out, shaping_out, mask_out = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)

@@ -9,6 +9,7 @@ import torch
 import nav_ref
 import visit_ref
 from golden_util import load_traces
+from nav_util import dev, host, u16_full
 
 pytestmark = pytest.mark.gpu
 _, SEED = load_traces()
@@ -20,20 +21,6 @@ U = nav_ref.UNREACHABLE
 def nav():
     from twoarmy_amd import minigrid_nav
     return minigrid_nav
-
-
-def dev(x):
-    return torch.from_numpy(np.array(x)).to(DEV)                          # a copy: the shared cases are read-only
-
-
-def u16_full(shape, byte=0xA5):
-    """A uint16 device tensor with every byte = `byte` (torch's uint16 has views and copies, little else)."""
-    n = int(np.prod(shape))
-    return torch.full((2 * n,), byte, dtype=torch.uint8, device=DEV).view(torch.uint16).view(shape)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def worlds(seed, N, W, H, goals="random"):
@@ -474,7 +461,7 @@ def test_bad_arguments_launch_nothing():
                                  C.c_void_p(a["out"]), None)
     for kw in [dict(dist=None), dict(pos=None), dict(out=None), dict(n=0), dict(T=-1), dict(W=0), dict(H=33),
                dict(pitch=W * H - 1), dict(pitch=-3), dict(dist=dist.data_ptr() + 1), dict(out=look.data_ptr() + 1),
-               dict(pos=pos.data_ptr() + 4)]:
+               dict(pos=pos.data_ptr() + 4), dict(n=1 << 20, T=1 << 20)]:
         assert lookup(**kw) == -1, kw
     assert lookup(T=0) == 0
     torch.cuda.synchronize()

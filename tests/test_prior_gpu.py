@@ -11,6 +11,7 @@ import torch
 import nav_ref
 import prior_ref
 import visit_ref
+from nav_util import dev, host
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,14 +28,6 @@ def nav():
 def ops():
     from twoarmy_amd import ppo_ops
     return ppo_ops
-
-
-def dev(x):
-    return torch.from_numpy(np.array(x)).to(DEV)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------ labels

@@ -10,16 +10,13 @@ import torch
 import goal_moves_ref
 import nav_ref
 import prior_ref
+from nav_util import host
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 U = nav_ref.UNREACHABLE
 N, T, MAX_STEPS, MB = 64, 16, 12, 512
 STATIC = nav_ref.PASS_DEFAULT | (1 << 6)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def _trainer(variant, state=None):

@@ -11,6 +11,7 @@ import torch
 import nav_ref
 import shape_ref
 import timed_nav_ref as tref
+from nav_util import Boxed, bits, dev, host, same
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -24,23 +25,6 @@ ARITH = [(1.0, 0.125), (0.99, 0.01)]                                  # (gamma, 
 def nav():
     from twoarmy_amd import minigrid_nav
     return minigrid_nav
-
-
-def dev(x):
-    return None if x is None else torch.from_numpy(np.array(x)).to(DEV)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
-
-
-def bits(a):
-    a = np.asarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(got, want):
-    return got.shape == want.shape and np.array_equal(bits(got), bits(want))
 
 
 # ------------------------------------------------------------------------------------------------ worlds and fields
@@ -131,24 +115,6 @@ def rollout(c, T, seed):
     age.reshape(-1)[:: max(1, M // 7)] = 0
     init = np.array([H - 0.5, 0.25], np.float32)
     return dict(before=before, after=after, age=age, init=init, done=done, reward=reward, T=T)
-
-
-class Boxed:
-    """A device tensor of `n` elements at element offset `off` from a 16-byte boundary inside a 0xA5-filled buffer."""
-
-    def __init__(self, n, dtype, off=0, shape=None):
-        size = torch.empty(0, dtype=dtype).element_size()
-        self.buf = torch.full(((16 // size + off + n) * size + 48,), 0xA5, dtype=torch.uint8, device=DEV)
-        self.lo, self.hi = 16 + off * size, 16 + (off + n) * size
-        self.view = self.buf[self.lo:self.hi].view(dtype).view(shape if shape is not None else (n,))
-        assert self.buf.data_ptr() % 16 == 0 and (n == 0 or self.view.data_ptr() % 16 == (off * size) % 16)
-
-    def borders_intact(self):
-        b = host(self.buf)
-        return bool((b[:self.lo] == 0xA5).all() and (b[self.hi:] == 0xA5).all())
-
-    def untouched(self):
-        return bool((host(self.buf) == 0xA5).all())
 
 
 def run_shape(c, r, period, gamma, scale, flags, want=(True, True, True), off=(0, 0, 0), in_place=False, pad=0,
@@ -439,7 +405,8 @@ def test_bad_arguments_launch_nothing():
                   dict(flags=4), dict(flags=8 | ZT), dict(flags=-1),                     # unknown flag bits
                   dict(scale=nan), dict(scale=inf), dict(scale=-inf), dict(gamma=nan), dict(gamma=inf)]
     bad_shape = bad_common + [dict(dist=None), dict(dist=good["dist"] + 1), dict(pitch=-1), dict(pitch=W * H - 1),
-                              dict(P=0), dict(P=17), dict(P=-1), dict(P=2, age=None, init=None), dict(T=1 << 30, n=1 << 10),
+                              dict(P=0), dict(P=17), dict(P=-1), dict(P=2, age=None, init=None), dict(P=2, age=None),
+                              dict(T=1 << 30, n=1 << 10),
                               dict(flags=1), dict(flags=3)]                              # the doors are the field's business
     for kw in bad_shape:
         assert shape(dict(good, **kw)) == -1, kw

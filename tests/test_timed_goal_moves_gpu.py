@@ -14,6 +14,7 @@ import nav_ref
 import prior_ref
 import timed_goal_moves_ref as tgref
 import timed_nav_ref as tref
+from nav_util import dev, host, random_records, runs_to_records
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,14 +34,6 @@ PERIODS = [1, 2, 6, 16]
 def nav():
     from twoarmy_amd import minigrid_nav
     return minigrid_nav
-
-
-def dev(x):
-    return torch.from_numpy(np.array(x)).to(DEV)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 _CASES = {}
@@ -74,26 +67,6 @@ def positions(rng, T, N, W, H):
         for i, s in enumerate(special):
             pos[(i * 5 + 2) % (T * N)] = s
     return pos.reshape(T, N, 2)
-
-
-def runs_to_records(rng, c, runs, T):
-    """runs = [(env, goal cell, length)] -> (t, n, goal): consecutive steps inside a run, as ppo_her_relabel emits them."""
-    W = c["W"]
-    t = np.concatenate([(rng.integers(0, T) + np.arange(L)) % T for _, _, L in runs]).astype(np.int32)
-    n = np.concatenate([np.full(L, e) for e, _, L in runs]).astype(np.int32)
-    g = np.concatenate([np.full(L, gc) for _, gc, L in runs])
-    goal = (np.stack([g // W, g % W], 1) + rng.choice([0.0, 0.25, 0.999], (len(g), 2))).astype(np.float32)
-    return t, n, goal
-
-
-def random_records(rng, c, R, T, mean_run=9):
-    runs, left = [], R
-    while left:
-        L = int(min(left, 1 + rng.integers(0, 2 * mean_run)))
-        e = int(rng.integers(0, c["N"]))
-        runs.append((e, int(c["pool"][e][rng.integers(0, 3)]), L))
-        left -= L
-    return runs_to_records(rng, c, runs, T)
 
 
 def raw_call(lib, a):

@@ -17,6 +17,7 @@ import timed_goal_moves_ref as tgref
 import timed_goal_shape_ref as tsref
 import timed_nav_ref as tref
 import visit_ref
+from nav_util import Boxed, all_same, bits, dev, host, same
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -34,50 +35,11 @@ def nav():
     return minigrid_nav
 
 
-def dev(x):
-    return None if x is None else torch.from_numpy(np.array(x)).to(DEV)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
-
-
-def bits(a):
-    a = np.asarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def same(got, want):
-    return got.shape == want.shape and np.array_equal(bits(got), bits(want))
-
-
-def all_same(got, want):
-    return all(same(g, w) for g, w in zip(got, want))
-
-
 def floods(W, H, P):
     """The header's formula from the header's byte count."""
     fixed = int(re.search(r"#define MG_NAV_TIMED_GOAL_SHAPE_LDS (\d+)", open(os.path.join(ROOT, "include", "minigrid_nav.h")).read()).group(1))
     cells = (W * H + 7) & ~7
     return next((f for f in (8, 4, 2) if fixed + f * P * cells * 2 <= 65536), 1)
-
-
-class Boxed:
-    """A device tensor of `n` elements at element offset `off` from a 16-byte boundary inside a 0xA5-filled buffer."""
-
-    def __init__(self, n, dtype, off=0):
-        size = torch.empty(0, dtype=dtype).element_size()
-        self.buf = torch.full(((16 // size + off + n) * size + 48,), 0xA5, dtype=torch.uint8, device=DEV)
-        self.lo, self.hi = 16 + off * size, 16 + (off + n) * size
-        self.view = self.buf[self.lo:self.hi].view(dtype)
-        assert self.buf.data_ptr() % 16 == 0 and (n == 0 or self.view.data_ptr() % 16 == (off * size) % 16)
-
-    def borders_intact(self):
-        b = host(self.buf)
-        return bool((b[:self.lo] == 0xA5).all() and (b[self.hi:] == 0xA5).all())
-
-    def untouched(self):
-        return bool((host(self.buf) == 0xA5).all())
 
 
 # ------------------------------------------------------------------------------------------------ worlds, rollouts, records

@@ -10,6 +10,7 @@ import torch
 import nav_ref
 import timed_nav_ref as tref
 import visit_ref
+from nav_util import dev, host, u16_full
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,21 +26,8 @@ def nav():
     return minigrid_nav
 
 
-def dev(x):
-    return torch.from_numpy(np.array(x)).to(DEV)
-
-
 def sched(b):
     return dev(np.asarray(b, np.uint32).view(np.int32))
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
-
-
-def u16_full(shape, byte=0xA5):
-    n = int(np.prod(shape))
-    return torch.full((2 * n,), byte, dtype=torch.uint8, device=DEV).view(torch.uint16).view(shape)
 
 
 def check(got, want):
@@ -279,7 +267,7 @@ def test_rejected_calls_launch_nothing():
     for kw in [dict(dist=None), dict(pos=None), dict(mv=None), dict(age=None), dict(init=None), dict(age=None, init=None),
                dict(n=0), dict(T=-1), dict(W=0), dict(H=33), dict(pitch=W * H - 1), dict(pitch=-3), dict(P=0), dict(P=17),
                dict(dist=dist.data_ptr() + 1), dict(ad=ad.data_ptr() + 1), dict(pos=pos.data_ptr() + 4),
-               dict(age=age.data_ptr() + 2), dict(init=init.data_ptr() + 2)]:
+               dict(age=age.data_ptr() + 2), dict(init=init.data_ptr() + 2), dict(n=1 << 20, T=1 << 20)]:
         assert moves(**kw) == -1, kw
     assert moves(T=0) == 0
     torch.cuda.synchronize()
