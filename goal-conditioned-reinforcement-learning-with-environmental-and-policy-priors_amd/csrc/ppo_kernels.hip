@@ -8,6 +8,8 @@
 #include <float.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "launch.h"
 #include "philox.h"
 #include "twoarmy.h"
@@ -17,6 +19,58 @@ namespace {
 
 constexpr float CAT_EPS = FLT_EPSILON;          // torch.finfo(float32).eps used by probs_to_logits
 
+// ------------------------------------------------------------------ pieces the kernels below share
+// One row of Categorical(probs = p): p[k] = row[k], returns S = sum p in ascending k; q = p / S is the caller's.
+template <int A> __device__ __forceinline__ float cat_row(const float *__restrict__ row, float (&p)[A]) {
+    float S = 0.f;
+#pragma unroll
+    for (int k = 0; k < A; ++k) { p[k] = row[k]; S += p[k]; }
+    return S;
+}
+__device__ __forceinline__ float cat_log(float q) { return logf(fminf(fmaxf(q, CAT_EPS), 1.0f - CAT_EPS)); }
+
+// Sum of K values per thread over a 256-thread workgroup: the tree 128, 64, ... 1 on lds[K][256], every level adding
+// element tid + s to element tid (a fixed shape: the sums' bits are part of the contract).  v holds the sums afterwards.
+template <typename T, int K> __device__ __forceinline__ void block_sum(T (&v)[K], T *lds) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) lds[k * 256 + tid] = v[k];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) lds[k * 256 + tid] += lds[k * 256 + tid + s];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = lds[k * 256];
+}
+
+__device__ __forceinline__ float4 relu4(float4 v) {
+    return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+}
+__device__ __forceinline__ float4 mask4(float4 g, float4 y) {       // g where y > 0 (ReLU backward)
+    return make_float4(y.x > 0.f ? g.x : 0.f, y.y > 0.f ? g.y : 0.f, y.z > 0.f ? g.z : 0.f, y.w > 0.f ? g.w : 0.f);
+}
+__device__ __forceinline__ void add4(float4 &acc, const float4 &o) { acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w; }
+__device__ __forceinline__ float4 fma4(float x, float4 w, float4 acc) {
+    return make_float4(fmaf(x, w.x, acc.x), fmaf(x, w.y, acc.y), fmaf(x, w.z, acc.z), fmaf(x, w.w, acc.w));
+}
+
+// red[rows][stride] holds one float4 per pixel slot and channel quad: slot 0 plus slots 1 .. rows - 1, in that order.
+__device__ __forceinline__ float4 slot_sum4(const float4 *red, int rows, int stride, int cq) {
+    float4 sum = red[cq];
+    for (int r = 1; r < rows; ++r) add4(sum, red[r * stride + cq]);
+    return sum;
+}
+
+// "the episode ends at step i", non-zero for either flag
+__device__ __forceinline__ uint32_t done_at(const uint8_t *__restrict__ terminated, const uint8_t *__restrict__ truncated,
+                                            size_t i) {
+    return (uint32_t)(terminated[i] | truncated[i]);
+}
+
 // ------------------------------------------------------------------ categorical sample
 template <int A>
 __global__ void ppo_sample_kernel(const float *__restrict__ probs, int B, const float *__restrict__ uniforms,
@@ -25,9 +79,7 @@ __global__ void ppo_sample_kernel(const float *__restrict__ probs, int B, const 
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float p[A];
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < A; ++k) { p[k] = probs[(size_t)b * A + k]; sum += p[k]; }
+    const float sum = cat_row<A>(probs + (size_t)b * A, p);
     float u;
     if (uniforms) u = uniforms[b];
     else {
@@ -51,7 +103,7 @@ __global__ void ppo_sample_kernel(const float *__restrict__ probs, int B, const 
 #pragma unroll
     for (int k = 0; k < A; ++k) if (k == a) qa = p[k] / sum;
     action[b] = a;
-    logp[b] = logf(fminf(fmaxf(qa, CAT_EPS), 1.0f - CAT_EPS));
+    logp[b] = cat_log(qa);
 }
 
 // ------------------------------------------------------------------ conv epilogues (channels-last activations)
@@ -64,10 +116,8 @@ __global__ __launch_bounds__(256) void ppo_bias_relu_kernel(float4 *__restrict__
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 v = y[i];
-        const float4 b = bias[i % c4];
-        v.x = fmaxf(v.x + b.x, 0.f); v.y = fmaxf(v.y + b.y, 0.f);
-        v.z = fmaxf(v.z + b.z, 0.f); v.w = fmaxf(v.w + b.w, 0.f);
-        y[i] = v;
+        add4(v, bias[i % c4]);
+        y[i] = relu4(v);
     }
 }
 
@@ -88,23 +138,14 @@ __global__ __launch_bounds__(256) void ppo_relu_bwd_bias_grad_kernel(const float
     if (row < rows) {
         for (size_t px = p0 + row; px < p1; px += rows) {
             const size_t i = px * c4 + cq;
-            const float4 g = gy[i], v = y[i];
-            float4 o;
-            o.x = v.x > 0.f ? g.x : 0.f; o.y = v.y > 0.f ? g.y : 0.f;
-            o.z = v.z > 0.f ? g.z : 0.f; o.w = v.w > 0.f ? g.w : 0.f;
+            const float4 o = mask4(gy[i], y[i]);
             gx[i] = o;
-            acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
+            add4(acc, o);
         }
     }
     red[threadIdx.x] = acc;
     __syncthreads();
-    if (row == 0) {
-        for (int r = 1; r < rows; ++r) {
-            const float4 o = red[r * c4 + cq];
-            acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
-        }
-        partial[(size_t)blockIdx.x * c4 + cq] = acc;
-    }
+    if (row == 0) partial[(size_t)blockIdx.x * c4 + cq] = slot_sum4(red, rows, c4, cq);
 }
 
 // ------------------------------------------------------------------ conv1 of TINet, fused with its input upsampling
@@ -116,18 +157,22 @@ __global__ __launch_bounds__(256) void ppo_relu_bwd_bias_grad_kernel(const float
 // Folded weights wf[py][px][ty][tx][c][64] (taps that a parity does not have carry zeros) come from the caller.
 // Block = 256 threads = 16 channel quads x 16 pixel slots, one sample per block; per parity phase the thread keeps its
 // 4 taps x F x float4 weights in registers and walks the phase's pixels; x values are LDS broadcasts.
-template <int F, int CQ>                           // F input channels, CQ = output channels / 4 (16 for TINet, 4 for Net_Encoder)
-__global__ __launch_bounds__(256) void ppo_conv1_up4_kernel(const float *__restrict__ frames, const float4 *__restrict__ wf,
-                                                            const float4 *__restrict__ bias, float4 *__restrict__ out, int B) {
-    __shared__ float xs[F * 18 * 18];                  // [c][18][18]: row / column 17 = zero pad for the (unused) far taps
-    constexpr int SLOTS = 256 / CQ;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int cq = tid % CQ, slot = tid / CQ;
-    const float *src = frames + (size_t)b * F * 289;
+// One sample's frames src[F][17][17] -> xs[F][18][18]: row / column 17 = zero pad for the (unused) far taps.
+template <int F> __device__ __forceinline__ void conv1_stage_frame(float *xs, const float *__restrict__ src, int tid) {
     for (int i = tid; i < F * 324; i += 256) {
         const int c = i / 324, r = i - c * 324, y = r / 18, x = r - y * 18;
         xs[i] = (y < 17 && x < 17) ? src[c * 289 + y * 17 + x] : 0.f;
     }
+}
+
+template <int F, int CQ>                           // F input channels, CQ = output channels / 4 (16 for TINet, 4 for Net_Encoder)
+__global__ __launch_bounds__(256) void ppo_conv1_up4_kernel(const float *__restrict__ frames, const float4 *__restrict__ wf,
+                                                            const float4 *__restrict__ bias, float4 *__restrict__ out, int B) {
+    __shared__ float xs[F * 18 * 18];
+    constexpr int SLOTS = 256 / CQ;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int cq = tid % CQ, slot = tid / CQ;
+    conv1_stage_frame<F>(xs, frames + (size_t)b * F * 289, tid);
     __syncthreads();
     const float4 bv = bias[cq];
     float4 *dst = out + (size_t)b * 1089 * CQ;
@@ -145,15 +190,9 @@ __global__ __launch_bounds__(256) void ppo_conv1_up4_kernel(const float *__restr
             for (int t = 0; t < 4; ++t) {
                 const int ty = t >> 1, tx = t & 1;
 #pragma unroll
-                for (int c = 0; c < F; ++c) {
-                    const float xv = xs[c * 324 + (m + ty) * 18 + n + tx];
-                    const float4 ww = w[t * F + c];
-                    acc.x = fmaf(xv, ww.x, acc.x); acc.y = fmaf(xv, ww.y, acc.y);
-                    acc.z = fmaf(xv, ww.z, acc.z); acc.w = fmaf(xv, ww.w, acc.w);
-                }
+                for (int c = 0; c < F; ++c) acc = fma4(xs[c * 324 + (m + ty) * 18 + n + tx], w[t * F + c], acc);
             }
-            acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
-            dst[((2 * m + py) * 33 + 2 * n + px) * CQ + cq] = acc;
+            dst[((2 * m + py) * 33 + 2 * n + px) * CQ + cq] = relu4(acc);
         }
     }
 }
@@ -180,30 +219,19 @@ __global__ __launch_bounds__(256) void ppo_conv1_up4_bwd_kernel(const float *__r
     float4 accb = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
         __syncthreads();                                    // the previous sample's xs is no longer read
-        const float *src = frames + (size_t)b * F * 289;
-        for (int i = tid; i < F * 324; i += 256) {
-            const int c = i / 324, r = i - c * 324, yy = r / 18, xx = r - yy * 18;
-            xs[i] = (yy < 17 && xx < 17) ? src[c * 289 + yy * 17 + xx] : 0.f;
-        }
+        conv1_stage_frame<F>(xs, frames + (size_t)b * F * 289, tid);
         __syncthreads();
         const size_t base = (size_t)b * 1089 * 16;
         for (int q = slot; q < ny * nx; q += 16) {
             const int m = q / nx, n = q - m * nx;
             const size_t o = base + (size_t)((2 * m + py) * 33 + 2 * n + px) * 16 + cq;
-            const float4 gv = gy[o], yv = y[o];
-            float4 g;
-            g.x = yv.x > 0.f ? gv.x : 0.f; g.y = yv.y > 0.f ? gv.y : 0.f;
-            g.z = yv.z > 0.f ? gv.z : 0.f; g.w = yv.w > 0.f ? gv.w : 0.f;
-            accb.x += g.x; accb.y += g.y; accb.z += g.z; accb.w += g.w;
+            const float4 g = mask4(gy[o], y[o]);
+            add4(accb, g);
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int ty = t >> 1, tx = t & 1;
 #pragma unroll
-                for (int c = 0; c < F; ++c) {
-                    const float xv = xs[c * 324 + (m + ty) * 18 + n + tx];
-                    float4 &a = acc[t * F + c];
-                    a.x = fmaf(xv, g.x, a.x); a.y = fmaf(xv, g.y, a.y); a.z = fmaf(xv, g.z, a.z); a.w = fmaf(xv, g.w, a.w);
-                }
+                for (int c = 0; c < F; ++c) acc[t * F + c] = fma4(xs[c * 324 + (m + ty) * 18 + n + tx], g, acc[t * F + c]);
             }
         }
     }
@@ -215,11 +243,7 @@ __global__ __launch_bounds__(256) void ppo_conv1_up4_bwd_kernel(const float *__r
         red[tid] = k < 4 * F ? acc[k < 4 * F ? k : 0] : accb;
         __syncthreads();
         if (slot == 0) {
-            float4 sum = red[cq];
-            for (int r = 1; r < 16; ++r) {
-                const float4 o = red[r * 16 + cq];
-                sum.x += o.x; sum.y += o.y; sum.z += o.z; sum.w += o.w;
-            }
+            const float4 sum = slot_sum4(red, 16, 16, cq);
             if (k < 4 * F) gw_part[wbase + (size_t)k * 16 + cq] = sum;
             else gb_part[((size_t)blockIdx.x * 4 + ph) * 16 + cq] = sum;
         }
@@ -297,34 +321,26 @@ __global__ __launch_bounds__(256) void ppo_gae_kernel(const float *__restrict__ 
 
 // ------------------------------------------------------------------ advantage normalisation
 __global__ __launch_bounds__(256) void ppo_moments_kernel(const float *__restrict__ x, int64_t n, double *__restrict__ ws) {
-    __shared__ double s1[256], s2[256];
-    double a = 0.0, b = 0.0;
+    __shared__ double lds[2 * 256];
+    double m[2] = {0.0, 0.0};                                                      // sum x, sum x^2
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double v = (double)x[i];
-        a += v; b += v * v;
+        m[0] += v; m[1] += v * v;
     }
-    s1[threadIdx.x] = a; s2[threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { s1[threadIdx.x] += s1[threadIdx.x + s]; s2[threadIdx.x] += s2[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { ws[2 * blockIdx.x] = s1[0]; ws[2 * blockIdx.x + 1] = s2[0]; }
+    block_sum(m, lds);
+    if (threadIdx.x == 0) { ws[2 * blockIdx.x] = m[0]; ws[2 * blockIdx.x + 1] = m[1]; }
 }
 
 __global__ __launch_bounds__(256) void ppo_normalise_kernel(float *__restrict__ x, int64_t n, float eps,
                                                             const double *__restrict__ ws, int nblocks) {
     __shared__ float s_mean, s_inv;
-    __shared__ double r1[256], r2[256];
-    r1[threadIdx.x] = (int)threadIdx.x < nblocks ? ws[2 * threadIdx.x] : 0.0;      // nblocks <= 256 partial sums
-    r2[threadIdx.x] = (int)threadIdx.x < nblocks ? ws[2 * threadIdx.x + 1] : 0.0;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {                                            // fixed-order tree: deterministic
-        if ((int)threadIdx.x < s) { r1[threadIdx.x] += r1[threadIdx.x + s]; r2[threadIdx.x] += r2[threadIdx.x + s]; }
-        __syncthreads();
-    }
+    __shared__ double lds[2 * 256];
+    double m[2];                                                                   // nblocks <= 256 partial sums
+    m[0] = (int)threadIdx.x < nblocks ? ws[2 * threadIdx.x] : 0.0;
+    m[1] = (int)threadIdx.x < nblocks ? ws[2 * threadIdx.x + 1] : 0.0;
+    block_sum(m, lds);                                                             // fixed-order tree: deterministic
     if (threadIdx.x == 0) {
-        const double a = r1[0], b = r2[0];
+        const double a = m[0], b = m[1];
         const double mean = a / (double)n;
         double var = n > 1 ? (b - (double)n * mean * mean) / (double)(n - 1) : 0.0;  // unbiased
         if (var < 0.0) var = 0.0;
@@ -345,7 +361,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float *__restrict__
                                                        int B, int n_valid, float clip, float ent_coef,
                                                        float *__restrict__ grad_probs, float *__restrict__ grad_value,
                                                        float *__restrict__ ws) {
-    __shared__ float sa[256], sv[256];
+    __shared__ float lds[2 * 256];
     const int b = blockIdx.x * 256 + threadIdx.x;
     float la = 0.f, lv = 0.f;
     if (b >= n_valid && b < B) {                      // padding rows of a fixed-shape minibatch: no loss, no gradient
@@ -357,15 +373,13 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float *__restrict__
         const float invB = 1.0f / (float)n_valid;
         float p[A], q[A], l[A];
         bool inside[A];
-        float S = 0.f;
-#pragma unroll
-        for (int k = 0; k < A; ++k) { p[k] = probs[(size_t)b * A + k]; S += p[k]; }
+        const float S = cat_row<A>(probs + (size_t)b * A, p);
         float H = 0.f;
 #pragma unroll
         for (int k = 0; k < A; ++k) {
             q[k] = p[k] / S;
             inside[k] = q[k] >= CAT_EPS && q[k] <= 1.0f - CAT_EPS;        // clamp passes gradient inside (inclusive)
-            l[k] = logf(fminf(fmaxf(q[k], CAT_EPS), 1.0f - CAT_EPS));
+            l[k] = cat_log(q[k]);
             H -= q[k] * l[k];
         }
         const int a = action[b];
@@ -402,13 +416,9 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float *__restrict__
         lv = ab < 1.0f ? 0.5f * d * d : ab - 0.5f;
         grad_value[b] = (ab < 1.0f ? d : (d > 0.f ? 1.f : -1.f)) * invB;
     }
-    sa[threadIdx.x] = la; sv[threadIdx.x] = lv;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sv[threadIdx.x] += sv[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { ws[2 * blockIdx.x] = sa[0]; ws[2 * blockIdx.x + 1] = sv[0]; }
+    float sums[2] = {la, lv};
+    block_sum(sums, lds);
+    if (threadIdx.x == 0) { ws[2 * blockIdx.x] = sums[0]; ws[2 * blockIdx.x + 1] = sums[1]; }
 }
 
 __global__ void ppo_loss_finalize_kernel(const float *__restrict__ ws, int nblocks, int B, float *__restrict__ losses) {
@@ -427,9 +437,8 @@ __global__ void ppo_loss_finalize_kernel(const float *__restrict__ ws, int nbloc
 template <int A> struct prior_row_t { float S, m, rest; int top; };
 template <int A> __device__ __forceinline__ prior_row_t<A> prior_row(const float *__restrict__ p, uint32_t mask)
 {
-    float v[A], S = 0.f;
-#pragma unroll
-    for (int k = 0; k < A; ++k) { v[k] = p[k]; S += v[k]; }
+    float v[A];
+    const float S = cat_row<A>(p, v);
     prior_row_t<A> r = {S, 0.f, 0.f, 0};
     float best = 0.f;
 #pragma unroll
@@ -442,36 +451,34 @@ template <int A> __device__ __forceinline__ prior_row_t<A> prior_row(const float
 }
 
 // pass 1: per-workgroup partial sums {loss, mass} and counts {labelled, arg-max in the mask} -> ws[4 * block]
+struct prior_sums_t {
+    float l, m;
+    int lab, agree;
+    __device__ __forceinline__ prior_sums_t &operator+=(const prior_sums_t &o) {
+        l += o.l; m += o.m; lab += o.lab; agree += o.agree;
+        return *this;
+    }
+};
+
 template <int A>
 __global__ __launch_bounds__(256) void ppo_prior_partial_kernel(const float *__restrict__ probs,
                                                                 const uint8_t *__restrict__ moves, int n_valid,
                                                                 float *__restrict__ ws) {
-    __shared__ float sl[256], sm[256];
-    __shared__ int sc[256], sg[256];
+    __shared__ prior_sums_t lds[256];
     const int b = blockIdx.x * 256 + threadIdx.x;
-    float l = 0.f, m = 0.f;
-    int lab = 0, agree = 0;
+    prior_sums_t s[1] = {{0.f, 0.f, 0, 0}};
     const uint32_t mask = b < n_valid ? (uint32_t)moves[b] & ((1u << A) - 1u) : 0u;
     if (mask != 0u) {
         const prior_row_t<A> r = prior_row<A>(probs + (size_t)b * A, mask);
-        const float mc = r.rest < CAT_EPS ? 1.0f - CAT_EPS : fminf(fmaxf(r.m, CAT_EPS), 1.0f - CAT_EPS);
-        l = -logf(mc);
-        m = r.m;
-        lab = 1;
-        agree = (int)((mask >> r.top) & 1u);
+        s[0].l = -cat_log(r.rest < CAT_EPS ? 1.0f - CAT_EPS : r.m);            // 1 - eps passes the clamp as it is
+        s[0].m = r.m;
+        s[0].lab = 1;
+        s[0].agree = (int)((mask >> r.top) & 1u);
     }
-    sl[threadIdx.x] = l; sm[threadIdx.x] = m; sc[threadIdx.x] = lab; sg[threadIdx.x] = agree;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            sl[threadIdx.x] += sl[threadIdx.x + s]; sm[threadIdx.x] += sm[threadIdx.x + s];
-            sc[threadIdx.x] += sc[threadIdx.x + s]; sg[threadIdx.x] += sg[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    block_sum(s, lds);
     if (threadIdx.x == 0) {
-        ws[4 * blockIdx.x] = sl[0]; ws[4 * blockIdx.x + 1] = sm[0];
-        ws[4 * blockIdx.x + 2] = __int_as_float(sc[0]); ws[4 * blockIdx.x + 3] = __int_as_float(sg[0]);
+        ws[4 * blockIdx.x] = s[0].l; ws[4 * blockIdx.x + 1] = s[0].m;
+        ws[4 * blockIdx.x + 2] = __int_as_float(s[0].lab); ws[4 * blockIdx.x + 3] = __int_as_float(s[0].agree);
     }
 }
 
@@ -593,7 +600,7 @@ __global__ __launch_bounds__(64) void ppo_her_kernel(const float *__restrict__ p
     int start = age0[n] == 0 ? 0 : -1;               // an episode already running at t = 0 is not relabelled
     for (int c0 = 0; c0 < T; c0 += 64) {
         const int tl = c0 + lane;
-        const bool d = tl < T && (terminated[(size_t)tl * N + n] | truncated[(size_t)tl * N + n]) != 0;
+        const bool d = tl < T && done_at(terminated, truncated, (size_t)tl * N + n) != 0;
         unsigned long long dm = __ballot(d);
         while (dm) {
             const int t1 = c0 + __builtin_ctzll(dm);
@@ -667,7 +674,7 @@ __global__ void ppo_age_scan_kernel(const uint8_t *__restrict__ terminated, cons
     age[n] = a;
     for (int t = 0; t < T; ++t) {
         const size_t i = (size_t)t * N + n;
-        a = (terminated[i] | truncated[i]) ? 0 : a + 1;
+        a = done_at(terminated, truncated, i) ? 0 : a + 1;
         age[(size_t)(t + 1) * N + n] = a;
     }
 }
@@ -696,7 +703,7 @@ __global__ __launch_bounds__(64) void ppo_episode_scan_kernel(const float *__res
     for (int j = 0; j < EP_ROWS; ++j) {
         const size_t i = (size_t)j * N + n;
         r[j] = j < T ? reward[i] : 0.f;
-        d[j] = j < T ? (uint32_t)(terminated[i] | truncated[i]) : 0u;
+        d[j] = j < T ? (uint32_t)(terminated[i] | truncated[i]) : 0u;      // not done_at: DESIGN.md 6.20
     }
     for (int t0 = 0; t0 < T; t0 += EP_ROWS) {
 #pragma unroll
@@ -893,11 +900,6 @@ __global__ __launch_bounds__(64) void ppo_episode_finalize_kernel(const double *
     }
 }
 
-__host__ int ep_summary_blocks(int64_t M) {
-    const int64_t want = (M + EP_BLOCK_ELEMS - 1) / EP_BLOCK_ELEMS;
-    return (int)(want < EP_MAX_BLOCKS ? want : EP_MAX_BLOCKS);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // World-model decoder, inference only (Net_Decoder, all_net.py:100-137): latent float[64][4][4] per frame ->
 //   ConvTranspose2d(64->16, k2, s2) + ReLU  -> a1[8][8][16]
@@ -963,16 +965,11 @@ __global__ __launch_bounds__(256) void ppo_decoder_frames_kernel(const float *__
                     const float *a = &a1s[(iy * 8 + ix) * 16];
                     const float *w = &W2s[(ky * 5 + kx) * 16 + q * 4];
 #pragma unroll
-                    for (int ci = 0; ci < 16; ++ci) {
-                        const float av = a[ci];
-                        const float4 wv = *reinterpret_cast<const float4 *>(w + ci * 400);
-                        acc.x = fmaf(av, wv.x, acc.x); acc.y = fmaf(av, wv.y, acc.y);
-                        acc.z = fmaf(av, wv.z, acc.z); acc.w = fmaf(av, wv.w, acc.w);
-                    }
+                    for (int ci = 0; ci < 16; ++ci)
+                        acc = fma4(a[ci], *reinterpret_cast<const float4 *>(w + ci * 400), acc);
                 }
             }
-            acc.x = fmaxf(acc.x, 0.0f); acc.y = fmaxf(acc.y, 0.0f); acc.z = fmaxf(acc.z, 0.0f); acc.w = fmaxf(acc.w, 0.0f);
-            *reinterpret_cast<float4 *>(&a2s[pix * 16 + q * 4]) = acc;
+            *reinterpret_cast<float4 *>(&a2s[pix * 16 + q * 4]) = relu4(acc);
         }
         __syncthreads();
         // ---- stage 3: last transposed conv + 4x4 average pooling = 3x3 / stride 2 / pad 1 over a2
@@ -1018,6 +1015,7 @@ __global__ __launch_bounds__(256) void ppo_lstm_cell_kernel(const float4 *__rest
         const float4 *g = ga + (size_t)b * 4 * H4;
         gi = g[j]; gf = g[H4 + j]; gg = g[2 * H4 + j]; go = g[3 * H4 + j];
     }
+    // its own add4, not the shared one, which costs 6 VGPRs and 0.1 us here
     auto add4 = [](float4 &a, const float4 &v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; };
     if (gb) {
         const float4 *q = gb + (size_t)b * ldb4;
@@ -1035,6 +1033,43 @@ __global__ __launch_bounds__(256) void ppo_lstm_cell_kernel(const float4 *__rest
     h[i] = hv;
 }
 
+// ------------------------------------------------------------------ host: argument rules, grids, dispatch
+template <typename... P> bool all_set(const P *...p) { return (... && (p != nullptr)); }
+template <typename... P> bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15u) == 0; }     // NULL counts as aligned
+int blocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
+int blocks_capped(int64_t n, int per, int cap) { return (int)((n + per - 1) / per < cap ? (n + per - 1) / per : cap); }
+int ep_summary_blocks(int64_t M) { return blocks_capped(M, EP_BLOCK_ELEMS, EP_MAX_BLOCKS); }
+float4 *f4(float *p) { return reinterpret_cast<float4 *>(p); }
+const float4 *f4(const float *p) { return reinterpret_cast<const float4 *>(p); }
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// The action counts the templated kernels are built for, stated once: the rule, and runtime A -> fn(int_c<A>).
+#define PPO_ACTION_COUNTS(X) X(5) X(2) X(3) X(4) X(7)
+bool ppo_actions_ok(int A) {
+#define PPO_IS(V) if (A == V) return true;
+    PPO_ACTION_COUNTS(PPO_IS)
+#undef PPO_IS
+    return false;
+}
+template <typename Fn> void ppo_with_actions(int A, Fn &&fn) {      // A has passed ppo_actions_ok
+    switch (A) {
+#define PPO_CASE(V) case V: fn(int_c<V>{}); break;
+    PPO_ACTION_COUNTS(PPO_CASE)
+#undef PPO_CASE
+    }
+}
+
+template <typename FT>
+int gather_stack(const char *what, const FT *frames, int frame_pitch, const float *pos_frames, int N, const int32_t *k_idx,
+                 const int32_t *n_idx, const int32_t *age, const float *init_frame, const float *init_pos, int B,
+                 float *out, float *pos_out, void *stream) {
+    if (!all_set(frames, k_idx, n_idx, age, init_frame, out) || B <= 0 || frame_pitch < TW_CELLS) return TW_E_ARG;
+    if (pos_out && !all_set(pos_frames, init_pos)) return TW_E_ARG;
+    hipLaunchKernelGGL(ppo_gather_stack_kernel<FT>, dim3(blocks(B, 4)), dim3(256), 0, (hipStream_t)stream, frames, frame_pitch,
+                       pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out);
+    return tw_launched(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1046,42 +1081,32 @@ int ppo_sample(const float *probs, int B, int A, const float *uniforms, uint64_t
 
 int ppo_sample_dev(const float *probs, int B, int A, const float *uniforms, uint64_t seed, uint64_t offset,
                    const uint64_t *offset_dev, int32_t *action, float *logp, void *stream) {
-    if (!probs || !action || !logp || B <= 0) return TW_E_ARG;
-    const dim3 grid((B + 255) / 256), block(256);
+    if (!all_set(probs, action, logp) || B <= 0 || !ppo_actions_ok(A)) return TW_E_ARG;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    hipStream_t st = (hipStream_t)stream;
-#define PPO_SAMPLE_LAUNCH(AA) \
-    hipLaunchKernelGGL(ppo_sample_kernel<AA>, grid, block, 0, st, probs, B, uniforms, k0, k1, offset, offset_dev, action, logp)
-    switch (A) {
-    case 5: PPO_SAMPLE_LAUNCH(5); break;
-    case 2: PPO_SAMPLE_LAUNCH(2); break;
-    case 3: PPO_SAMPLE_LAUNCH(3); break;
-    case 4: PPO_SAMPLE_LAUNCH(4); break;
-    case 7: PPO_SAMPLE_LAUNCH(7); break;
-    default: return TW_E_ARG;
-    }
-#undef PPO_SAMPLE_LAUNCH
+    ppo_with_actions(A, [&](auto a) {
+        hipLaunchKernelGGL(ppo_sample_kernel<decltype(a)::value>, dim3(blocks(B, 256)), dim3(256), 0, (hipStream_t)stream,
+                           probs, B, uniforms, k0, k1, offset, offset_dev, action, logp);
+    });
     return tw_launched(__func__);
 }
 
 int ppo_gae(const float *reward, const float *value, const float *next_value, const uint8_t *done, float gamma,
             float lambda, int use_done_mask, int T, int N, float *adv, float *target, float *ret, void *stream) {
-    if (!reward || !value || !next_value || T <= 0 || N <= 0 || (use_done_mask && !done)) return TW_E_ARG;
-    if (N >= 16384)
-        hipLaunchKernelGGL(ppo_gae_kernel<64>, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, reward, value,
-                           next_value, done, gamma, lambda, use_done_mask, T, N, adv, target, ret);
-    else
-        hipLaunchKernelGGL(ppo_gae_kernel<16>, dim3((N + 15) / 16), dim3(256), 0, (hipStream_t)stream, reward, value,
-                           next_value, done, gamma, lambda, use_done_mask, T, N, adv, target, ret);
+    if (!all_set(reward, value, next_value) || T <= 0 || N <= 0 || (use_done_mask && !done)) return TW_E_ARG;
+    auto launch = [&](auto gn) {                             // envs per workgroup
+        hipLaunchKernelGGL(ppo_gae_kernel<decltype(gn)::value>, dim3(blocks(N, decltype(gn)::value)), dim3(256), 0,
+                           (hipStream_t)stream, reward, value, next_value, done, gamma, lambda, use_done_mask, T, N, adv,
+                           target, ret);
+    };
+    if (N >= 16384) launch(int_c<64>{});
+    else launch(int_c<16>{});
     return tw_launched(__func__);
 }
 
 int ppo_adv_norm(float *adv, int64_t n, float eps, double *workspace, void *stream) {
-    if (!adv || n <= 0 || !workspace) return TW_E_ARG;
-    int nblocks = (int)((n + 1023) / 1024);                  // partial sums: one workgroup per CU at most
-    if (nblocks > 256) nblocks = 256;
-    int nblocks2 = (int)((n + 255) / 256);
-    if (nblocks2 > 2048) nblocks2 = 2048;
+    if (!all_set(adv, workspace) || n <= 0) return TW_E_ARG;
+    const int nblocks = blocks_capped(n, 1024, 256);         // partial sums: one workgroup per CU at most
+    const int nblocks2 = blocks_capped(n, 256, 2048);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_moments_kernel, dim3(nblocks), dim3(256), 0, st, adv, n, workspace);
     hipLaunchKernelGGL(ppo_normalise_kernel, dim3(nblocks2), dim3(256), 0, st, adv, n, eps, workspace, nblocks);
@@ -1099,10 +1124,10 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
                             const float *value, const float *target_v, int B, int n_valid, int A, float clip,
                             float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
                             void *stream) {
-    if (!probs || !action || !old_logp || !adv || !value || !target_v || !losses || !grad_probs || !grad_value ||
-        !workspace || B <= 0 || A != 5 || n_valid <= 0 || n_valid > B)
+    if (!all_set(probs, action, old_logp, adv, value, target_v, losses, grad_probs, grad_value, workspace) || B <= 0 ||
+        A != 5 || n_valid <= 0 || n_valid > B)              // the reference's policy has five actions: the one width built
         return TW_E_ARG;
-    const int nblocks = (B + 255) / 256;
+    const int nblocks = blocks(B, 256);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_loss_kernel<5>, dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
                        target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace);
@@ -1112,55 +1137,43 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
 
 int ppo_prior_loss_fwd_bwd(const float *probs, const uint8_t *moves, int B, int n_valid, int A, float coef, float *out,
                            int32_t *counts, float *grad_probs, float *workspace, void *stream) {
-    if (!probs || !moves || !out || !counts || !grad_probs || !workspace || B <= 0 || n_valid < 0 || n_valid > B)
+    if (!all_set(probs, moves, out, counts, grad_probs, workspace) || B <= 0 || n_valid < 0 || n_valid > B ||
+        !ppo_actions_ok(A))
         return TW_E_ARG;
-    const int nblocks = (B + 255) / 256;
+    const int nblocks = blocks(B, 256);
     hipStream_t st = (hipStream_t)stream;
-#define PPO_PRIOR_LAUNCH(AA) do { \
-        hipLaunchKernelGGL(ppo_prior_partial_kernel<AA>, dim3(nblocks), dim3(256), 0, st, probs, moves, n_valid, workspace); \
-        hipLaunchKernelGGL(ppo_prior_grad_kernel<AA>, dim3(nblocks), dim3(256), 0, st, probs, moves, B, n_valid, coef, \
-                           workspace, nblocks, out, counts, grad_probs); } while (0)
-    switch (A) {
-    case 5: PPO_PRIOR_LAUNCH(5); break;
-    case 2: PPO_PRIOR_LAUNCH(2); break;
-    case 3: PPO_PRIOR_LAUNCH(3); break;
-    case 4: PPO_PRIOR_LAUNCH(4); break;
-    case 7: PPO_PRIOR_LAUNCH(7); break;
-    default: return TW_E_ARG;
-    }
-#undef PPO_PRIOR_LAUNCH
+    ppo_with_actions(A, [&](auto a) {
+        hipLaunchKernelGGL(ppo_prior_partial_kernel<decltype(a)::value>, dim3(nblocks), dim3(256), 0, st, probs, moves, n_valid,
+                           workspace);
+        hipLaunchKernelGGL(ppo_prior_grad_kernel<decltype(a)::value>, dim3(nblocks), dim3(256), 0, st, probs, moves, B, n_valid,
+                           coef, workspace, nblocks, out, counts, grad_probs);
+    });
     return tw_launched(__func__);
 }
 
 int ppo_gather_stack(const float *frames, int frame_pitch, const float *pos_frames, int N, const int32_t *k_idx,
                      const int32_t *n_idx, const int32_t *age, const float *init_frame, const float *init_pos, int B,
                      float *out, float *pos_out, void *stream) {
-    if (!frames || !k_idx || !n_idx || !age || !init_frame || !out || B <= 0 || frame_pitch < TW_CELLS) return TW_E_ARG;
-    if (pos_out && (!pos_frames || !init_pos)) return TW_E_ARG;
-    hipLaunchKernelGGL(ppo_gather_stack_kernel<float>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, frames, frame_pitch,
-                       pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out);
-    return tw_launched(__func__);
+    return gather_stack(__func__, frames, frame_pitch, pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out,
+                        stream);
 }
 
 int ppo_gather_stack_u8(const uint8_t *frames, int frame_pitch, const float *pos_frames, int N, const int32_t *k_idx,
                         const int32_t *n_idx, const int32_t *age, const float *init_frame, const float *init_pos, int B,
                         float *out, float *pos_out, void *stream) {
-    if (!frames || !k_idx || !n_idx || !age || !init_frame || !out || B <= 0 || frame_pitch < TW_CELLS) return TW_E_ARG;
-    if (pos_out && (!pos_frames || !init_pos)) return TW_E_ARG;
-    hipLaunchKernelGGL(ppo_gather_stack_kernel<uint8_t>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, frames,
-                       frame_pitch, pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out);
-    return tw_launched(__func__);
+    return gather_stack(__func__, frames, frame_pitch, pos_frames, N, k_idx, n_idx, age, init_frame, init_pos, B, out, pos_out,
+                        stream);
 }
 
 int ppo_her_relabel_window(const float *pos, const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0,
                            const float *reward, const int32_t *choices, uint64_t seed, uint32_t env_id0, uint32_t step0,
                            int T, int N, int max_goals, int skip, const int64_t *offsets, int32_t *counts, int32_t *out_t,
                            int32_t *out_n, float *out_goal, float *out_reward, uint8_t *out_done, void *stream) {
-    if (!pos || !terminated || !truncated || !age0 || !reward || T <= 0 || N <= 0 || max_goals < 0) return TW_E_ARG;
+    if (!all_set(pos, terminated, truncated, age0, reward) || T <= 0 || N <= 0 || max_goals < 0) return TW_E_ARG;
     if (max_goals > 4) return TW_E_ARG;                                  // 4 pick columns / one Philox call
     if (skip < 0 || skip >= HER_MAX_LEN) return TW_E_ARG;
     if (!offsets && !counts) return TW_E_ARG;
-    if (offsets && (!out_t || !out_n || !out_goal || !out_reward || !out_done)) return TW_E_ARG;
+    if (offsets && !all_set(out_t, out_n, out_goal, out_reward, out_done)) return TW_E_ARG;
     hipLaunchKernelGGL(ppo_her_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, pos, terminated, truncated, age0,
                        reward, choices, (uint32_t)seed, (uint32_t)(seed >> 32), env_id0, step0, T, N, max_goals, skip,
                        offsets, counts, out_t, out_n, out_goal, out_reward, out_done);
@@ -1177,16 +1190,16 @@ int ppo_her_relabel(const float *pos, const uint8_t *terminated, const uint8_t *
 
 int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0, int T, int N, int32_t *age,
                  void *stream) {
-    if (!terminated || !truncated || !age0 || !age || T <= 0 || N <= 0) return TW_E_ARG;
-    hipLaunchKernelGGL(ppo_age_scan_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, terminated,
+    if (!all_set(terminated, truncated, age0, age) || T <= 0 || N <= 0) return TW_E_ARG;
+    hipLaunchKernelGGL(ppo_age_scan_kernel, dim3(blocks(N, 256)), dim3(256), 0, (hipStream_t)stream, terminated,
                        truncated, age0, T, N, age);
     return tw_launched(__func__);
 }
 
 int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
                      double *carry_return, int32_t *carry_length, double *ep_return, int32_t *ep_length, void *stream) {
-    if (!reward || !terminated || !truncated || !carry_return || !carry_length || T <= 0 || N <= 0) return TW_E_ARG;
-    hipLaunchKernelGGL(ppo_episode_scan_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, reward, terminated,
+    if (!all_set(reward, terminated, truncated, carry_return, carry_length) || T <= 0 || N <= 0) return TW_E_ARG;
+    hipLaunchKernelGGL(ppo_episode_scan_kernel, dim3(blocks(N, 64)), dim3(64), 0, (hipStream_t)stream, reward, terminated,
                        truncated, T, N, carry_return, carry_length, ep_return, ep_length);
     return tw_launched(__func__);
 }
@@ -1200,15 +1213,14 @@ int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const
                         const uint8_t *truncated, const float *reward, const int32_t *action, int A, int T, int N,
                         double keep, double gain, double *score, double *summary, int64_t *action_hist,
                         int64_t *reward_hist, double *workspace, void *stream) {
-    if (!ep_return || !ep_length || !terminated || !truncated || !reward || !summary || !reward_hist || !workspace ||
-        T <= 0 || N <= 0)
+    if (!all_set(ep_return, ep_length, terminated, truncated, reward, summary, reward_hist, workspace) || T <= 0 || N <= 0 ||
+        !ppo_actions_ok(A))
         return TW_E_ARG;
-    if (A != 2 && A != 3 && A != 4 && A != 5 && A != 7) return TW_E_ARG;      // the action counts ppo_sample accepts
     const int64_t M = (int64_t)T * N;
     if (M > ((int64_t)1 << 40)) return TW_E_ARG;                              // per-thread run length stays an int
     const int nblocks = ep_summary_blocks(M);
     const int64_t per_block = (M + nblocks - 1) / nblocks;
-    const int per_thread = (int)((per_block + 255) / 256);
+    const int per_thread = blocks(per_block, 256);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_episode_partial_kernel, dim3(nblocks), dim3(256), 0, st, ep_return, ep_length, terminated,
                        truncated, reward, action, M, per_block, per_thread, keep, gain, workspace);
@@ -1218,29 +1230,25 @@ int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const
 }
 
 int ppo_bias_relu_nhwc(float *y, const float *bias, int64_t n_pixels, int C, void *stream) {
-    if (!y || !bias || n_pixels <= 0 || C <= 0 || (C & 3) || ((uintptr_t)y & 15u) || ((uintptr_t)bias & 15u)) return TW_E_ARG;
+    if (!all_set(y, bias) || n_pixels <= 0 || C <= 0 || (C & 3) || !aligned16(y, bias)) return TW_E_ARG;
     const size_t n4 = (size_t)n_pixels * (C / 4);
-    const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-    hipLaunchKernelGGL(ppo_bias_relu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4 *>(y),
-                       reinterpret_cast<const float4 *>(bias), n4, C / 4);
+    hipLaunchKernelGGL(ppo_bias_relu_kernel, dim3(blocks_capped((int64_t)n4, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                       f4(y), f4(bias), n4, C / 4);
     return tw_launched(__func__);
 }
 
 int ppo_relu_bwd_bias_grad_nhwc_blocks(int64_t n_pixels, int C) {
     if (n_pixels <= 0 || C <= 0 || (C & 3) || C > 256) return TW_E_ARG;
-    const int64_t want = (n_pixels + 511) / 512;              // >= 512 pixels per block
-    return (int)(want < 4096 ? want : 4096);
+    return blocks_capped(n_pixels, 512, 4096);                // >= 512 pixels per block
 }
 
 int ppo_relu_bwd_bias_grad_nhwc(const float *gy, const float *y, float *gx, float *partial, int64_t n_pixels, int C,
                                 void *stream) {
-    const int blocks = ppo_relu_bwd_bias_grad_nhwc_blocks(n_pixels, C);
-    if (blocks <= 0 || !gy || !y || !gx || !partial || (((uintptr_t)gy | (uintptr_t)y | (uintptr_t)gx | (uintptr_t)partial) & 15u))
-        return TW_E_ARG;
-    const int ppb = (int)((n_pixels + blocks - 1) / blocks);
-    hipLaunchKernelGGL(ppo_relu_bwd_bias_grad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4 *>(gy), reinterpret_cast<const float4 *>(y),
-                       reinterpret_cast<float4 *>(gx), reinterpret_cast<float4 *>(partial), (size_t)n_pixels, C / 4, ppb);
+    const int nb = ppo_relu_bwd_bias_grad_nhwc_blocks(n_pixels, C);
+    if (nb <= 0 || !all_set(gy, y, gx, partial) || !aligned16(gy, y, gx, partial)) return TW_E_ARG;
+    const int ppb = blocks(n_pixels, nb);                     // pixels per block
+    hipLaunchKernelGGL(ppo_relu_bwd_bias_grad_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, f4(gy), f4(y), f4(gx),
+                       f4(partial), (size_t)n_pixels, C / 4, ppb);
     return tw_launched(__func__);
 }
 
@@ -1251,49 +1259,39 @@ int ppo_conv1_up4_bias_relu(const float *frames, int B, int F, const float *fold
 
 int ppo_conv1_up4_bias_relu_c(const float *frames, int B, int F, int C_out, const float *folded_w, const float *bias,
                               float *out, void *stream) {
-    if (!frames || !folded_w || !bias || !out || B <= 0 || ((uintptr_t)out & 15u) || ((uintptr_t)folded_w & 15u) ||
-        ((uintptr_t)bias & 15u))
-        return TW_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-#define PPO_CONV1_LAUNCH(FF, CQQ)                                                                                        \
-    hipLaunchKernelGGL((ppo_conv1_up4_kernel<FF, CQQ>), dim3(B), dim3(256), 0, st, frames,                               \
-                       reinterpret_cast<const float4 *>(folded_w), reinterpret_cast<const float4 *>(bias),               \
-                       reinterpret_cast<float4 *>(out), B)
-    if (F == 4 && C_out == 64) PPO_CONV1_LAUNCH(4, 16);
-    else if (F == 8 && C_out == 64) PPO_CONV1_LAUNCH(8, 16);
-    else if (F == 1 && C_out == 16) PPO_CONV1_LAUNCH(1, 4);
+    if (!all_set(frames, folded_w, bias, out) || B <= 0 || !aligned16(out, folded_w, bias)) return TW_E_ARG;
+    auto launch = [&](auto f, auto cq) {
+        hipLaunchKernelGGL((ppo_conv1_up4_kernel<decltype(f)::value, decltype(cq)::value>), dim3(B), dim3(256), 0,
+                           (hipStream_t)stream, frames, f4(folded_w), f4(bias), f4(out), B);
+    };
+    if (F == 4 && C_out == 64) launch(int_c<4>{}, int_c<16>{});
+    else if (F == 8 && C_out == 64) launch(int_c<8>{}, int_c<16>{});
+    else if (F == 1 && C_out == 16) launch(int_c<1>{}, int_c<4>{});
     else return TW_E_ARG;
-#undef PPO_CONV1_LAUNCH
     return tw_launched(__func__);
 }
 
-int ppo_conv1_up4_bwd_groups(int B) { return B <= 0 ? TW_E_ARG : (B < 256 ? B : 256); }
+int ppo_conv1_up4_bwd_groups(int B) { return B <= 0 ? TW_E_ARG : blocks_capped(B, 1, 256); }
 
 int ppo_conv1_up4_bwd(const float *frames, int B, int F, const float *gy, const float *y, float *gw_partial,
                       float *gb_partial, void *stream) {
     const int groups = ppo_conv1_up4_bwd_groups(B);
-    if (groups <= 0 || !frames || !gy || !y || !gw_partial || !gb_partial ||
-        (((uintptr_t)gy | (uintptr_t)y | (uintptr_t)gw_partial | (uintptr_t)gb_partial) & 15u))
+    if (groups <= 0 || !all_set(frames, gy, y, gw_partial, gb_partial) || !aligned16(gy, y, gw_partial, gb_partial))
         return TW_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(groups, 4), block(256);
-    if (F == 4)
-        hipLaunchKernelGGL(ppo_conv1_up4_bwd_kernel<4>, grid, block, 0, st, frames, reinterpret_cast<const float4 *>(gy),
-                           reinterpret_cast<const float4 *>(y), reinterpret_cast<float4 *>(gw_partial),
-                           reinterpret_cast<float4 *>(gb_partial), B);
-    else if (F == 8)
-        hipLaunchKernelGGL(ppo_conv1_up4_bwd_kernel<8>, grid, block, 0, st, frames, reinterpret_cast<const float4 *>(gy),
-                           reinterpret_cast<const float4 *>(y), reinterpret_cast<float4 *>(gw_partial),
-                           reinterpret_cast<float4 *>(gb_partial), B);
-    else
-        return TW_E_ARG;
+    auto launch = [&](auto f) {
+        hipLaunchKernelGGL(ppo_conv1_up4_bwd_kernel<decltype(f)::value>, dim3(groups, 4), dim3(256), 0, (hipStream_t)stream,
+                           frames, f4(gy), f4(y), f4(gw_partial), f4(gb_partial), B);
+    };
+    if (F == 4) launch(int_c<4>{});
+    else if (F == 8) launch(int_c<8>{});
+    else return TW_E_ARG;
     return tw_launched(__func__);
 }
 
 int ppo_decoder_frames(const float *z, int n_frames, const float *w1, const float *b1, const float *w2, const float *b2,
                        const float *kfold, float b3, float *frames, void *stream) {
-    if (!z || !w1 || !b1 || !w2 || !b2 || !kfold || !frames || n_frames <= 0) return TW_E_ARG;
-    const int grid = n_frames < 512 ? n_frames : 512;          // 120 KB of LDS: one workgroup per CU, two rounds of them
+    if (!all_set(z, w1, b1, w2, b2, kfold, frames) || n_frames <= 0) return TW_E_ARG;
+    const int grid = blocks_capped(n_frames, 1, 512);          // 120 KB of LDS: one workgroup per CU, two rounds of them
     hipLaunchKernelGGL(ppo_decoder_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, z, n_frames, w1, b1, w2,
                        b2, kfold, b3, frames);
     return tw_launched(__func__);
@@ -1301,17 +1299,13 @@ int ppo_decoder_frames(const float *z, int n_frames, const float *w1, const floa
 
 int ppo_lstm_cell(const float *gates_a, const float *gates_b, long long ldb, const float *bias, float *c, float *h, int B,
                   int H, void *stream) {
-    if ((!gates_a && !gates_b) || !c || !h || B <= 0 || H <= 0 || (H & 3) ||
-        (((uintptr_t)gates_a | (uintptr_t)c | (uintptr_t)h) & 15u))
+    if ((!gates_a && !gates_b) || !all_set(c, h) || B <= 0 || H <= 0 || (H & 3) || !aligned16(gates_a, gates_b, bias, c, h))
         return TW_E_ARG;
-    if (gates_b && ((((uintptr_t)gates_b) & 15u) || (ldb & 3) || ldb < 4LL * H)) return TW_E_ARG;
-    if (bias && (((uintptr_t)bias) & 15u)) return TW_E_ARG;
+    if (gates_b && ((ldb & 3) || ldb < 4LL * H)) return TW_E_ARG;
     const long long n = (long long)B * (H / 4);
     if (n > 0x7fffffffLL) return TW_E_ARG;
-    hipLaunchKernelGGL(ppo_lstm_cell_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4 *>(gates_a), reinterpret_cast<const float4 *>(gates_b), ldb / 4,
-                       reinterpret_cast<const float4 *>(bias), reinterpret_cast<float4 *>(c), reinterpret_cast<float4 *>(h),
-                       B, H / 4);
+    hipLaunchKernelGGL(ppo_lstm_cell_kernel, dim3(blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, f4(gates_a),
+                       f4(gates_b), ldb / 4, f4(bias), f4(c), f4(h), B, H / 4);
     return tw_launched(__func__);
 }
 

@@ -9,6 +9,19 @@ from ._marshal import call as _call, ptr as _p, query as _query
 _CL = torch.channels_last
 
 
+def _pf(t):
+    """Pointer to t detached, contiguous and checked to be fp32 (a parameter or a view goes in as it is)."""
+    return _p(t.detach().contiguous(), torch.float32)
+
+
+def _step_outputs(out, want_steps, T, N, dtypes, device):
+    """The per-step output pair of a scan: the caller's `out`, fresh [T,N] tensors, or (None, None)."""
+    if out is None:
+        return tuple(torch.empty((T, N), dtype=d, device=device) if want_steps else None for d in dtypes)
+    assert out[0].shape == (T, N) and out[1].shape == (T, N)
+    return out
+
+
 def sample(probs, uniforms=None, seed=0, offset=0, offset_dev=None):
     """Categorical(probs).sample() + log_prob (reference soa/agent/PPO.py:86-88) -> (int32[B], float[B]).
     offset_dev: int64[1] device tensor added to the Philox row counter at run time (graph-captured launches)."""
@@ -123,13 +136,7 @@ def episode_scan(reward, terminated, truncated, carry_return, carry_length, want
     want_steps=False; out = (ep_return, ep_length) reuses buffers of the caller."""
     T, N = reward.shape
     assert terminated.shape == (T, N) and truncated.shape == (T, N) and carry_return.shape == (N,) and carry_length.shape == (N,)
-    ep_return = ep_length = None
-    if out is not None:
-        ep_return, ep_length = out
-        assert ep_return.shape == (T, N) and ep_length.shape == (T, N)
-    elif want_steps:
-        ep_return = torch.empty((T, N), dtype=torch.float64, device=reward.device)
-        ep_length = torch.empty((T, N), dtype=torch.int32, device=reward.device)
+    ep_return, ep_length = _step_outputs(out, want_steps, T, N, (torch.float64, torch.int32), reward.device)
     _call("ppo_episode_scan", reward, _p(reward, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
           T, N, _p(carry_return, torch.float64), _p(carry_length, torch.int32), _p(ep_return, torch.float64),
           _p(ep_length, torch.int32))
@@ -173,13 +180,7 @@ def visit_scan(pos, terminated, truncated, carry, width=17, height=17, want_step
     ep_cells i32[T,N]), or (None, None) with want_steps=False; out = (first_visit, ep_cells) reuses the caller's buffers."""
     T, N = terminated.shape
     assert pos.shape == (T, N, 2) and truncated.shape == (T, N) and carry.numel() == visit_carry_words(width, height, N)
-    first_visit = ep_cells = None
-    if out is not None:
-        first_visit, ep_cells = out
-        assert first_visit.shape == (T, N) and ep_cells.shape == (T, N)
-    elif want_steps:
-        first_visit = torch.empty((T, N), dtype=torch.uint8, device=pos.device)
-        ep_cells = torch.empty((T, N), dtype=torch.int32, device=pos.device)
+    first_visit, ep_cells = _step_outputs(out, want_steps, T, N, (torch.uint8, torch.int32), pos.device)
     _call("ppo_visit_scan", pos, _p(pos, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8), T, N,
           int(width), int(height), _p(carry, torch.int32), _p(first_visit, torch.uint8), _p(ep_cells, torch.int32))
     return first_visit, ep_cells
@@ -289,7 +290,7 @@ class _ConvBiasReLU(torch.autograd.Function):
         y = torch.ops.aten.convolution(x, w, None, list(stride), [0, 0], [1, 1], False, [0, 0], 1)
         assert y.is_contiguous(memory_format=torch.channels_last), "conv epilogue kernels need channels-last activations"
         B, Cc, H, W = y.shape
-        _call("ppo_bias_relu_nhwc", y, _p(y, None, _CL), _p(b.detach(), torch.float32), B * H * W, Cc)
+        _call("ppo_bias_relu_nhwc", y, _p(y, None, _CL), _pf(b), B * H * W, Cc)
         ctx.save_for_backward(x, w, y)
         ctx.stride = list(stride)
         return y
@@ -338,8 +339,7 @@ def conv1_up4_bias_relu_infer(frames, weight, bias):
     Cout = weight.shape[0]
     y = torch.empty((B, Cout, 33, 33), dtype=torch.float32, device=frames.device, memory_format=torch.channels_last)
     wf = fold_conv1_weights(weight)
-    _call("ppo_conv1_up4_bias_relu_c", y, _p(frames.contiguous(), torch.float32), B, F, Cout, _p(wf),
-          _p(bias.contiguous(), torch.float32), _p(y, None, _CL))
+    _call("ppo_conv1_up4_bias_relu_c", y, _pf(frames), B, F, Cout, _p(wf), _pf(bias), _p(y, None, _CL))
     return y
 
 
@@ -356,8 +356,7 @@ class _Conv1Up4(torch.autograd.Function):
         if wf is None:
             wf = fold_conv1_weights(w)
         fr = frames.contiguous()
-        _call("ppo_conv1_up4_bias_relu", y, _p(fr, torch.float32), B, F, _p(wf), _p(b.detach().contiguous()),
-              _p(y, None, _CL))
+        _call("ppo_conv1_up4_bias_relu", y, _p(fr, torch.float32), B, F, _p(wf), _pf(b), _p(y, None, _CL))
         ctx.save_for_backward(fr, w, y)
         return y
 
@@ -409,9 +408,8 @@ def decoder_frames(z, w1, b1, w2, b2, w3, b3):
     n = z.shape[0]
     out = torch.empty((n, 289), dtype=torch.float32, device=z.device)
     if n:
-        _call("ppo_decoder_frames", z, _p(z), n, _p(w1.detach().contiguous(), torch.float32),
-              _p(b1.detach().contiguous(), torch.float32), _p(w2.detach().contiguous(), torch.float32),
-              _p(b2.detach().contiguous(), torch.float32), _p(fold_decoder_tail(w3.detach())), 0.0, _p(out))
+        _call("ppo_decoder_frames", z, _p(z), n, _pf(w1), _pf(b1), _pf(w2), _pf(b2), _p(fold_decoder_tail(w3.detach())), 0.0,
+              _p(out))
         out += b3.detach().view(1, 1)            # the bias as a device-side add: no host synchronisation in the rollout
     return out
 

@@ -6,15 +6,10 @@ import torch
 
 import her_oracle
 import twoarmy_oracle as orc
+from ppo_util import DEV, ops as _ops
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 SEED = 9981
-
-
-def _ops():
-    from twoarmy_amd import ppo_ops
-    return ppo_ops
 
 
 def _dev(rec):

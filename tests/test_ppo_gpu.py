@@ -5,15 +5,10 @@ import pytest
 import torch
 
 import ppo_oracle as po
+from ppo_util import DEV, ops as _ops
 from test_ppo_common import det_weights, load_ppo_golden
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _ops():
-    from twoarmy_amd import ppo_ops
-    return ppo_ops
 
 
 def _rand_probs(rs, B, A=5, extreme=False):

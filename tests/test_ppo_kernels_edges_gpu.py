@@ -9,29 +9,17 @@ import numpy as np
 import pytest
 import torch
 
+from ppo_util import DEV, accepted, dev as _dev, lib_module as _libmod, ops as _ops, ptr as _P, rejected
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 EPS32 = float(np.finfo(np.float32).eps)          # 2^-23
 U_MAX = 1.0 - 2.0 ** -24                          # largest uniform of the Philox path: (2^24 - 1) * 2^-24
-
-
-def _ops():
-    from twoarmy_amd import ppo_ops
-    return ppo_ops
-
-
-def _lib():
-    from twoarmy_amd import _lib
-    return _lib
+CANARY = -55.5                                    # what the outputs of a rejected call are filled with
 
 
 def _marshal():
     from twoarmy_amd import _marshal
     return _marshal
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
 # ------------------------------------------------------------------------------------------------------------ sampler
@@ -136,7 +124,7 @@ def test_sample_offset_dev_equals_plain_offset(A):
 @pytest.mark.parametrize("A", [1, 6, 8, 9])
 def test_sample_unsupported_width_raises(A):
     p = torch.full((4, A), 1.0 / A, device=DEV)
-    with pytest.raises(_lib().TwoarmyLibraryError):
+    with pytest.raises(_libmod().TwoarmyLibraryError):
         _ops().sample(p, None)
 
 
@@ -442,7 +430,7 @@ def test_bias_relu_grid_stride_vs_float64(C):
     y = _dyadic(rs, (npix, C), 64, 4)
     b = _dyadic(rs, (C,), 64, 2)
     t, tb = _dev(y), _dev(b)
-    _lib().check(_lib().lib().ppo_bias_relu_nhwc(_marshal().ptr(t), _marshal().ptr(tb), npix, C, _marshal().stream(t)),
+    _libmod().check(_libmod().lib().ppo_bias_relu_nhwc(_marshal().ptr(t), _marshal().ptr(tb), npix, C, _marshal().stream(t)),
                  "ppo_bias_relu_nhwc")
     ref = np.maximum(y.astype(np.float64) + b.astype(np.float64), 0.0)      # exact in fp32 (multiples of 1/64, < 8)
     assert np.array_equal(t.cpu().numpy().astype(np.float64), ref)
@@ -450,13 +438,13 @@ def test_bias_relu_grid_stride_vs_float64(C):
 
 def _relu_bwd(gy, y, C):
     npix = gy.shape[0]
-    lib = _lib().lib()
+    lib = _libmod().lib()
     blocks = lib.ppo_relu_bwd_bias_grad_nhwc_blocks(npix, C)
     tg, ty = _dev(gy), _dev(y)
     gx = torch.empty_like(tg)
     part = torch.empty((max(blocks, 1), C), dtype=torch.float32, device=DEV)
     m = _marshal()
-    _lib().check(lib.ppo_relu_bwd_bias_grad_nhwc(m.ptr(tg), m.ptr(ty), m.ptr(gx), m.ptr(part), npix, C, m.stream(tg)),
+    _libmod().check(lib.ppo_relu_bwd_bias_grad_nhwc(m.ptr(tg), m.ptr(ty), m.ptr(gx), m.ptr(part), npix, C, m.stream(tg)),
                  "ppo_relu_bwd_bias_grad_nhwc")
     return blocks, gx, part
 
@@ -476,9 +464,9 @@ def test_relu_bwd_bias_grad_vs_float64(npix, C):
 
 
 def test_relu_bwd_bias_grad_rejects_more_than_256_channels():
-    assert _lib().lib().ppo_relu_bwd_bias_grad_nhwc_blocks(100, 260) < 0
+    assert _libmod().lib().ppo_relu_bwd_bias_grad_nhwc_blocks(100, 260) < 0
     gy = np.zeros((8, 260), np.float32)
-    with pytest.raises(_lib().TwoarmyLibraryError):
+    with pytest.raises(_libmod().TwoarmyLibraryError):
         _relu_bwd(gy, gy, 260)
 
 
@@ -524,3 +512,117 @@ def test_conv1_up4_infer_one_frame_sixteen_channels_vs_float64():
     b = _dyadic(rs, (16,), 64, 1)
     y = _ops().conv1_up4_bias_relu_infer(_dev(frames), _dev(w), _dev(b))    # exact: as in the F = 4 / 8 forward
     assert torch.equal(y.double().cpu(), _conv1_ref64(frames, w, b))
+
+
+# ------------------------------------------------------------------------------------------------------------ rejections
+# Every argument rule of these entry points violated alone, by a raw call past the front end: TW_E_ARG, and after a
+# synchronise every output still holds its fill value -- nothing was launched.  The same call with the rule kept is
+# accepted.  The shapes are the smallest at which each rule can still be misread.
+def _fill(n, dtype=torch.float32, value=CANARY):
+    """n elements of `value` with 4 spare ones behind them, so that the same buffer can be passed 4 bytes further on."""
+    t = torch.full((n + 4,), value, dtype=dtype, device=DEV)
+    assert t.data_ptr() % 16 == 0
+    return t
+
+
+def _each_rejected(fn, good, bad, outs, value=CANARY):
+    """bad: (argument position, value) pairs, each put alone into the accepted argument list `good`."""
+    canaries = [(t, value) for t in outs]
+    for i, v in bad:
+        args = list(good)
+        args[i] = v
+        assert rejected(fn, args, canaries), (fn, i, getattr(v, "value", v))
+    assert accepted(fn, good), fn
+    assert not all(bool((t == value).all()) for t in outs), fn                  # the accepted call does write
+
+
+def test_gae_rejections_launch_nothing():
+    T, N = 5, 9
+    r, v, nv = (_dev(np.ones((T, N), np.float32)) for _ in range(3))
+    done = torch.zeros((T, N), dtype=torch.uint8, device=DEV)
+    outs = [_fill(T * N) for _ in range(3)]
+    good = [_P(r), _P(v), _P(nv), _P(done), 0.99, 0.95, 1, T, N] + [_P(o) for o in outs]
+    bad = [(0, None), (1, None), (2, None), (3, None), (7, 0), (7, -1), (8, 0), (8, -1)]    # (3, None): mask without done
+    _each_rejected("ppo_gae", good, bad, outs)
+
+
+def test_adv_norm_rejections_launch_nothing():
+    n = 9
+    adv = _fill(n)
+    ws = _fill(4096, torch.float64)
+    good = [_P(adv), n, 1e-8, _P(ws)]
+    _each_rejected("ppo_adv_norm", good, [(0, None), (1, 0), (1, -1), (3, None)], [adv, ws])
+
+
+def test_loss_rejections_launch_nothing():
+    B, A = 3, 5
+    probs = torch.full((B, A), 0.2, device=DEV)
+    action = torch.zeros(B, dtype=torch.int32, device=DEV)
+    old, adv, value, target = (torch.full((B,), x, device=DEV) for x in (-1.6, 1.0, 0.5, 0.0))
+    outs = [_fill(2), _fill(B * A), _fill(B), _fill(2)]                         # losses, grad_probs, grad_value, workspace
+    good = [_P(x) for x in (probs, action, old, adv, value, target)] + [B, B, A, 0.1, 0.01] + [_P(o) for o in outs]
+    bad = [(i, None) for i in (0, 1, 2, 3, 4, 5, 11, 12, 13, 14)]
+    bad += [(8, a) for a in (2, 3, 4, 6, 7)] + [(7, 0), (7, B + 1)]
+    _each_rejected("ppo_loss_fwd_bwd_masked", good, bad, outs)
+
+
+def test_prior_loss_and_episode_summary_reject_unbuilt_action_counts():
+    B = 3
+    probs = torch.full((B, 8), 0.125, device=DEV)
+    moves = torch.ones(B, dtype=torch.uint8, device=DEV)
+    outs = [_fill(2), _fill(2, torch.int32, -7), _fill(B * 8), _fill(4)]        # out, counts, grad_probs, workspace
+    good = [_P(probs), _P(moves), B, B, 5, 1.0] + [_P(o) for o in outs]
+    for a in (1, 6, 8):
+        args = list(good)
+        args[4] = a
+        assert rejected("ppo_prior_loss_fwd_bwd", args, [(outs[0], CANARY), (outs[1], -7), (outs[2], CANARY),
+                                                         (outs[3], CANARY)]), a
+    T, N = 5, 9
+    ep_r = torch.ones((T, N), dtype=torch.float64, device=DEV)
+    ep_l = torch.ones((T, N), dtype=torch.int32, device=DEV)
+    term = torch.ones((T, N), dtype=torch.uint8, device=DEV)
+    trunc = torch.zeros((T, N), dtype=torch.uint8, device=DEV)
+    rew = torch.ones((T, N), device=DEV)
+    act = torch.zeros((T, N), dtype=torch.int32, device=DEV)
+    score, summary, ws = _fill(1, torch.float64), _fill(8, torch.float64), _fill(24, torch.float64)
+    ah, rh = _fill(7, torch.int64, -7), _fill(6, torch.int64, -7)
+    good = [_P(x) for x in (ep_r, ep_l, term, trunc, rew, act)] + [5, T, N, 0.99, 0.01] + [_P(x) for x in (score, summary, ah, rh, ws)]
+    can = [(score, CANARY), (summary, CANARY), (ws, CANARY), (ah, -7), (rh, -7)]
+    args = list(good)
+    args[6] = 6
+    assert rejected("ppo_episode_summary", args, can)
+    assert accepted("ppo_episode_summary", good) and not bool((summary[:8] == CANARY).any())
+
+
+def test_bias_relu_rejections_launch_nothing():
+    npix, Cc = 2, 8
+    y, bias = _fill(npix * Cc), _fill(Cc)
+    good = [_P(y), _P(bias), npix, Cc]
+    _each_rejected("ppo_bias_relu_nhwc", good, [(3, 6), (0, _P(y, 4)), (1, _P(bias, 4))], [y])
+
+
+def test_relu_bwd_bias_grad_rejects_each_misaligned_pointer():
+    npix, Cc = 2, 8
+    gy, y = _fill(npix * Cc, value=1.0), _fill(npix * Cc, value=1.0)
+    gx, part = _fill(npix * Cc), _fill(Cc)
+    good = [_P(gy), _P(y), _P(gx), _P(part), npix, Cc]
+    bad = [(i, _P(t, 4)) for i, t in enumerate((gy, y, gx, part))]
+    _each_rejected("ppo_relu_bwd_bias_grad_nhwc", good, bad, [gx, part])
+
+
+def test_conv1_up4_rejections_launch_nothing():
+    B, F = 2, 4
+    frames = torch.ones(B * 8 * 289, device=DEV)                                # room for F = 8 as well
+    wf, bias, out = _fill(16 * 8 * 64, value=0.5), _fill(64, value=0.5), _fill(B * 1089 * 64)
+    good = [_P(frames), B, F, 64, _P(wf), _P(bias), _P(out)]
+    bad = [(4, _P(wf, 4)), (5, _P(bias, 4)), (6, _P(out, 4))]
+    for f, c in ((4, 16), (1, 64), (2, 64)):                                    # two arguments make one rule here
+        args = list(good)
+        args[2], args[3] = f, c
+        assert rejected("ppo_conv1_up4_bias_relu_c", args, [(out, CANARY)]), (f, c)
+    _each_rejected("ppo_conv1_up4_bias_relu_c", good, bad, [out])
+    gy, y = _fill(B * 1089 * 64, value=1.0), _fill(B * 1089 * 64, value=1.0)
+    gw, gb = _fill(B * 16 * 8 * 64), _fill(B * 4 * 64)
+    good = [_P(frames), B, F, _P(gy), _P(y), _P(gw), _P(gb)]
+    bad = [(2, 1), (1, 0)] + [(i + 3, _P(t, 4)) for i, t in enumerate((gy, y, gw, gb))]
+    _each_rejected("ppo_conv1_up4_bwd", good, bad, [gw, gb])

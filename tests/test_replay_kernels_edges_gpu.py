@@ -3,8 +3,6 @@ ppo_decoder_frames) at their edges: episode lengths around HER_MAX_LEN and `skip
 chunks, Philox counters that wrap, ragged batches, every age around the episode start, odd pitches, the ABI's NULL /
 range rejections.  Index kernels are compared bit for bit with the CPU oracles; the decoder with float64 under a derived
 rounding bound (tests/replay_ref.py).  Every rejected call is refused on the host before anything is launched."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -12,33 +10,10 @@ import torch
 import her_oracle
 import ppo_oracle as po
 import replay_ref as rr
+from ppo_util import DEV, TW_E_ARG, dev as _d, lib as _lib, ops as _ops, ptr as _P, stream as _stream
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-TW_E_ARG = -1
 KEYS = ("counts", "t", "n", "goal", "reward", "done")
-
-
-def _ops():
-    from twoarmy_amd import ppo_ops
-    return ppo_ops
-
-
-def _lib():
-    from twoarmy_amd import _lib
-    return _lib.lib()
-
-
-def _d(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def _P(t, off=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + off)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ====================================================================================================== hindsight

@@ -74,6 +74,69 @@ carry_r, carry_l = torch.zeros(N, dtype=torch.float64, device=dev), torch.zeros(
 ep_r, ep_l = ppo_ops.episode_scan(rw5, term, trunc, carry_r, carry_l)
 report("ppo_episode_scan (per-step outputs)", T * N * (4 + 1 + 1 + 8 + 4),
        timed(lambda: ppo_ops.episode_scan(rw5, term, trunc, carry_r, carry_l, out=(ep_r, ep_l))), "latency-bound: one lane per env")
+mv_flat = torch.randint(0, 32, (T * N,), generator=g, dtype=torch.uint8).to(dev)
+report("ppo_prior_loss_fwd_bwd (524288 x 5)", T * N * (A * 4 + 1) * 2 + T * N * A * 4,
+       timed(lambda: ppo_ops.prior_loss(probs, mv_flat, 0.1)), "two launches, probs and moves read twice; includes 5 allocations")
+ep_score = torch.zeros(1, dtype=torch.float64, device=dev)
+ep_out = (torch.empty(8, dtype=torch.float64, device=dev), torch.empty(A, dtype=torch.int64, device=dev),
+          torch.empty(6, dtype=torch.int64, device=dev),
+          torch.empty(ppo_ops.episode_summary_workspace(T, N), dtype=torch.float64, device=dev))
+n_done = int(((term | trunc) != 0).sum())
+report("ppo_episode_summary (partials + ordered final pass)", T * N * (4 + 1 + 1 + 4) + n_done * 12,
+       timed(lambda: ppo_ops.episode_summary(ep_r, ep_l, term, trunc, rw5, act_tn, A, 0.99, 0.01, ep_score, *ep_out)),
+       "two launches")
+p2 = torch.randint(1, 16, (T, N, 2), generator=g).float().to(dev)
+rw = torch.randn(T, N, generator=g).to(dev)
+report("ppo_her_relabel (count + scan + emit, one host sync)", T * N * (8 + 1 + 1 + 4) * 2,
+       timed(lambda: ppo_ops.her_relabel(p2, term, trunc, age0, rw, seed=1), iters=5), "includes the record-count sync")
+
+
+def update_path_rows():
+    """The kernels around the update's convolutions at 4096 samples of 4 frames (33 x 33 x 64 activations, 1.1 GB), the
+    decoder at 4096 frames and the LSTM cell at 4096 x 256: raw C ABI calls on buffers made once."""
+    from twoarmy_amd._marshal import call, ptr, query
+    CL = torch.channels_last
+    Bc, F, H = 4096, 4, 256
+    act_bytes = Bc * 1089 * 64 * 4
+    y = torch.randn(Bc, 64, 33, 33, generator=g).to(dev).contiguous(memory_format=CL)
+    gy = torch.randn(Bc, 64, 33, 33, generator=g).to(dev).contiguous(memory_format=CL)
+    gx = torch.empty_like(y)
+    bias = torch.randn(64, generator=g).to(dev)
+    report("ppo_bias_relu_nhwc (4096 x 33 x 33 x 64)", 2 * act_bytes,
+           timed(lambda: call("ppo_bias_relu_nhwc", y, ptr(y, None, CL), ptr(bias), Bc * 1089, 64)))
+    blocks = query("ppo_relu_bwd_bias_grad_nhwc_blocks", Bc * 1089, 64)
+    part = torch.empty((blocks, 64), device=dev)
+    report("ppo_relu_bwd_bias_grad_nhwc (4096 x 33 x 33 x 64)", 3 * act_bytes,
+           timed(lambda: call("ppo_relu_bwd_bias_grad_nhwc", y, ptr(gy, None, CL), ptr(y, None, CL), ptr(gx, None, CL),
+                              ptr(part), Bc * 1089, 64)))
+    frames4 = torch.randn(Bc, F, 289, generator=g).to(dev)
+    wf = ppo_ops.fold_conv1_weights(torch.randn(64, F, 4, 4, generator=g).to(dev) * 0.2)
+    report("ppo_conv1_up4_bias_relu (4096 x 4 frames -> 33 x 33 x 64)", act_bytes + Bc * F * 289 * 4,
+           timed(lambda: call("ppo_conv1_up4_bias_relu", y, ptr(frames4), Bc, F, ptr(wf), ptr(bias), ptr(y, None, CL))))
+    groups = query("ppo_conv1_up4_bwd_groups", Bc)
+    gw_part, gb_part = torch.empty((groups, 16, F, 64), device=dev), torch.empty((groups, 4, 64), device=dev)
+    report("ppo_conv1_up4_bwd (4096 x 4 frames)", 2 * act_bytes + 4 * Bc * F * 289 * 4,
+           timed(lambda: call("ppo_conv1_up4_bwd", y, ptr(frames4), Bc, F, ptr(gy, None, CL), ptr(y, None, CL), ptr(gw_part),
+                              ptr(gb_part))))
+    z = torch.randn(Bc, 64, 4, 4, generator=g).to(dev)
+    w1, b1 = (torch.randn(64, 16, 2, 2, generator=g) * 0.2).to(dev), torch.randn(16, generator=g).to(dev)
+    w2, b2 = (torch.randn(16, 16, 5, 5, generator=g) * 0.2).to(dev), torch.randn(16, generator=g).to(dev)
+    kfold = ppo_ops.fold_decoder_tail((torch.randn(16, 1, 4, 4, generator=g) * 0.2).to(dev))
+    dec_out = torch.empty((Bc, 289), device=dev)
+    report("ppo_decoder_frames (4096 frames)", Bc * (1024 + 289) * 4,
+           timed(lambda: call("ppo_decoder_frames", z, ptr(z), Bc, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(kfold), 0.0,
+                              ptr(dec_out))), "compute-bound: activations stay in LDS")
+    gates, xin = torch.randn(Bc, 4 * H, generator=g).to(dev), torch.randn(Bc, 2, 4 * H, generator=g).to(dev)
+    lb, c = torch.randn(4 * H, generator=g).to(dev), torch.randn(Bc, H, generator=g).to(dev)
+    report("ppo_lstm_cell (4096 x 256, gates + gates_b + bias)", Bc * H * 4 * (4 + 4 + 3) + 4 * H * 4,
+           timed(lambda: ppo_ops.lstm_cell_(gates, c, gates_b=xin[:, 1], bias=lb)))
+    report("ppo_lstm_cell (4096 x 256, gates alone)", Bc * H * 4 * (4 + 3), timed(lambda: ppo_ops.lstm_cell_(gates, c)))
+
+
+update_path_rows()
+if "--ppo" in sys.argv[1:]:            # the rows of csrc/ppo_kernels.hip alone: none of the sections below
+    sys.exit(0)
+
 # Shortest-path prior: the label launch over a whole rollout (one field per env, every acting state) and the set-valued
 # imitation loss with its gradient over the same 524 288 rows; ppo_episode_scan above is the yardstick.
 from twoarmy_amd import minigrid_nav as nav  # noqa: E402
@@ -137,21 +200,6 @@ for _ in range(3):                                             # three windows: 
            "one launch; %.2f x mg_nav_timed_goal_moves, %.2f x mg_nav_goal_shape" % (hts_s / ht_s, hts_s / hs_s))
 h_eng.close()
 del h_tr, h_eng, her
-mv_flat = torch.randint(0, 32, (T * N,), generator=g, dtype=torch.uint8).to(dev)
-report("ppo_prior_loss_fwd_bwd (524288 x 5)", T * N * (A * 4 + 1) * 2 + T * N * A * 4,
-       timed(lambda: ppo_ops.prior_loss(probs, mv_flat, 0.1)), "two launches, probs and moves read twice; includes 5 allocations")
-ep_score = torch.zeros(1, dtype=torch.float64, device=dev)
-ep_out = (torch.empty(8, dtype=torch.float64, device=dev), torch.empty(A, dtype=torch.int64, device=dev),
-          torch.empty(6, dtype=torch.int64, device=dev),
-          torch.empty(ppo_ops.episode_summary_workspace(T, N), dtype=torch.float64, device=dev))
-n_done = int(((term | trunc) != 0).sum())
-report("ppo_episode_summary (partials + ordered final pass)", T * N * (4 + 1 + 1 + 4) + n_done * 12,
-       timed(lambda: ppo_ops.episode_summary(ep_r, ep_l, term, trunc, rw5, act_tn, A, 0.99, 0.01, ep_score, *ep_out)),
-       "two launches")
-p2 = torch.randint(1, 16, (T, N, 2), generator=g).float().to(dev)
-rw = torch.randn(T, N, generator=g).to(dev)
-report("ppo_her_relabel (count + scan + emit, one host sync)", T * N * (8 + 1 + 1 + 4) * 2,
-       timed(lambda: ppo_ops.her_relabel(p2, term, trunc, age0, rw, seed=1), iters=5), "includes the record-count sync")
 
 # Visited cells (csrc/visitation.hip): the scan, the three dense histograms a VisitTracker.account() launches and an
 # indexed one over 100 000 hindsight records, on positions as concentrated as a rollout's (every env walks away from one
