@@ -43,8 +43,14 @@
  *   mg_nav_timed_goal_shape_kernel<P>   the same over (cell, phase): the timed goal kernel's flood loop and the goal shaping
  *                          kernel's after cells, label (nav_goal_shape_label, on the acting and the following phase's image)
  *                          and stores; its staging is larger than the move sets', so it has a flood count of its own.
+ *   mg_nav_ahead_kernel    where a shortest path leads in 1..3 steps (minigrid_nav.h, "Look-ahead"): the moves kernel's shape
+ *                          with a uint64 label per element (two per 16-byte chunk).  A lane walks the set bits of its
+ *                          frontier word and takes nav_move_set of each cell on the env's field (nav_ahead_label, at most 19
+ *                          cells); TIMED advances the phase per step.
+ *   mg_nav_goal_ahead_kernel   the same labels for records under goals of their own: the goal kernel's keys, heads and
+ *                          floods, nav_ahead_label on the half wavefront's image, 8 KiB of staged labels of its own.
  *
- * Shared: nav_image_clear, nav_dilate, nav_move_set<WAIT>; nav_out_span_t / nav_out_span / nav_out_store (one output of a
+ * Shared: nav_image_clear, nav_dilate, nav_move_set<WAIT>, nav_ahead_expand / nav_ahead_label; nav_out_span_t / nav_out_span / nav_out_store (one output of a
  * workgroup, any element type: the goal kernel and the shaping kernels; the moves and the timed goal kernel measured slower
  * on them and keep their own); nav_goal_records, _keys, _heads, _floods; on the host one nav_*_ok per argument rule.
  *
@@ -175,6 +181,45 @@ __device__ __forceinline__ uint32_t nav_move_set(const uint16_t *__restrict__ ro
 
 // The phase of a clock value (minigrid_nav.h): 0 up to the episode's first step, the clock mod P after it.
 __device__ __forceinline__ int nav_phase(int clock, int P) { return clock <= 0 ? 0 : clock % P; }
+
+// One step of the look-ahead (minigrid_nav.h, "Look-ahead") from the frontier cell behind bit b of a label whose origin is
+// cell c0: the bits of its successors -- the members of its move set on `row`, arriving in `next`.  A frontier lies within
+// Manhattan radius 2 of c0 when it is expanded, so b - 1, b + 1, b - 7 and b + 7 stay inside the 7 x 7 window, and every
+// member lies inside the world because nav_move_set puts only such cells into a set.
+template <bool WAIT>
+__device__ __forceinline__ uint64_t nav_ahead_expand(const uint16_t *__restrict__ row, const uint16_t *__restrict__ next,
+                                                     int c0, int b, int W, int H)
+{
+    const int by = b / MG_NAV_AHEAD_SIDE;
+    const int c = c0 + (by - 3) * W + (b - by * MG_NAV_AHEAD_SIDE - 3);
+    uint32_t d;
+    const uint64_t m = nav_move_set<WAIT>(row, next, c, W, H, d);
+    return (m & 1u) << (b - 1) | ((m >> 1) & 1u) << (b + 1) | ((m >> 2) & 1u) << (b - MG_NAV_AHEAD_SIDE) |
+           ((m >> 3) & 1u) << (b + MG_NAV_AHEAD_SIDE) | ((m >> 4) & 1u) << b;
+}
+
+// The look-ahead label of the acting state (c0, ph) in the P fields at f, `stride` elements apart (P = 1: one field), d = its
+// distance.  All members of a frontier share one distance, max(d - j, 0): after min(steps, d) expansions every member has
+// ended its episode and stays.  At most `steps` rounds of at most 49 cells each, whatever the input.
+template <bool WAIT>
+__device__ __forceinline__ uint64_t nav_ahead_label(const uint16_t *__restrict__ f, int64_t stride, int P, int ph, int c0,
+                                                    int W, int H, int steps, uint32_t &d)
+{
+    d = f[ph * stride + c0];
+    if (d == (uint32_t)MG_NAV_UNREACHABLE) return 0ull;
+    uint64_t front = 1ull << (3 * MG_NAV_AHEAD_SIDE + 3);
+    const int rounds = (uint32_t)steps < d ? steps : (int)d;
+    for (int j = 0; j < rounds; ++j) {
+        const int nph = ph + 1 >= P ? 0 : ph + 1;
+        const uint16_t *row = f + ph * stride, *next = f + nph * stride;
+        uint64_t out = 0;
+        for (uint64_t m = front & ((1ull << (MG_NAV_AHEAD_SIDE * MG_NAV_AHEAD_SIDE)) - 1ull); m != 0ull; m &= m - 1ull)
+            out |= nav_ahead_expand<WAIT>(row, next, c0, __ffsll((unsigned long long)m) - 1, W, H);
+        front = out;
+        ph = nph;
+    }
+    return front;
+}
 
 __global__ __launch_bounds__(NAV_THREADS) void mg_nav_field_kernel(
     const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
@@ -332,6 +377,47 @@ template <bool TIMED> __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_na
             mg_row_store(acting_dist, M, c,
                          [&](int64_t p) { return *reinterpret_cast<const uint4 *>(s_dist + (int)(p - bd)); },
                          [&](int64_t q) { return s_dist[(int)(q - bd)]; });
+}
+
+// ------------------------------------------------------------------ look-ahead labels of a rollout's acting states
+// The moves kernel's shape with a uint64 label per element: two labels per 16-byte chunk.
+template <bool TIMED> __global__ __launch_bounds__(NAV_MOVES_THREADS) void mg_nav_ahead_kernel(
+    const uint16_t *__restrict__ dist, int64_t pitch, int P, int N, int W, int H, const float2 *__restrict__ pos,
+    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int64_t M, int steps,
+    unsigned long long *__restrict__ ahead, uint16_t *__restrict__ acting_dist)
+{
+    __shared__ __attribute__((aligned(16))) unsigned long long s_ahead[NAV_MOVES_ELEMS];
+    __shared__ __attribute__((aligned(16))) uint16_t s_dist[NAV_MOVES_ELEMS];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const nav_out_span_t sa = nav_out_span(ahead, M, b, NAV_MOVES_ELEMS);
+    const nav_out_span_t sd = nav_out_span(acting_dist, M, b, NAV_MOVES_ELEMS);
+    const int HW = W * H;
+    float2 init = make_float2(0.f, 0.f);
+    if (age != nullptr) init = make_float2(init_pos[0], init_pos[1]);
+
+    const int64_t p0 = (int64_t)NAV_MOVES_ELEMS * b - 16;
+#pragma unroll 1
+    for (int k = 0; k < NAV_MOVES_ROUNDS; ++k) {
+        const int64_t p = p0 + k * NAV_MOVES_THREADS + tid;
+        const bool in_a = sa.holds(p), in_d = sd.holds(p);
+        if (!(in_a || in_d)) continue;                                      // both spans lie inside [0, M)
+        float2 q = pos[p];
+        const int clock = age != nullptr ? age[p] : 1;
+        if (clock <= 0) q = init;
+        const int c = visit_cell(q.x, q.y, W, H);
+        uint32_t d = MG_NAV_UNREACHABLE;
+        uint64_t a = 0;
+        if (c < HW) {
+            if (TIMED) a = nav_ahead_label<true>(dist + (int64_t)(p % N) * P * pitch, pitch, P, nav_phase(clock, P), c, W, H, steps, d);
+            else a = nav_ahead_label<false>(dist + (int64_t)(p % N) * pitch, 0, 1, 0, c, W, H, steps, d);
+        }
+        if (in_a) s_ahead[(int)(p - sa.base)] = a;
+        if (in_d) s_dist[(int)(p - sd.base)] = (uint16_t)d;
+    }
+    __syncthreads();
+    nav_out_store(ahead, M, sa, s_ahead, NAV_MOVES_THREADS);
+    nav_out_store(acting_dist, M, sd, s_dist, NAV_MOVES_THREADS);
 }
 
 // ------------------------------------------------------------------ optimal-move sets of records with goals of their own
@@ -522,6 +608,46 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_kernel(
                     });
     __syncthreads();
     nav_out_store(moves, M, sm, st.moves, NAV_GOAL_THREADS);
+    nav_out_store(acting_dist, M, sd, st.dist, NAV_GOAL_THREADS);
+}
+
+// ------------------------------------------------------------------ look-ahead labels of records with goals of their own
+// The goal kernel with a uint64 label per record: the labels on their way out have a struct of their own, so that
+// nav_goal_stage_t (from which mg_nav_timed_goal_moves sizes its floods) stays as it is.
+struct nav_goal_ahead_stage_t {
+    alignas(16) unsigned long long ahead[NAV_GOAL_ELEMS];
+};
+static_assert(sizeof(nav_goal_stage_t) + sizeof(nav_goal_ahead_stage_t) + NAV_GOAL_HALVES * NAV_CELLS * sizeof(uint16_t) + 64
+                  <= 64 * 1024, "the staging of a look-ahead workgroup fits 64 KiB next to its 8 images");
+
+__global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_ahead_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const int32_t *__restrict__ rec_t, const int32_t *__restrict__ rec_n,
+    const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos, const int32_t *__restrict__ age,
+    const float *__restrict__ init_pos, int T, int steps, unsigned long long *__restrict__ ahead,
+    uint16_t *__restrict__ acting_dist)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t image[NAV_GOAL_HALVES][NAV_CELLS];
+    __shared__ nav_goal_stage_t st;
+    __shared__ nav_goal_ahead_stage_t sh;
+    const nav_out_span_t sa = nav_out_span(ahead, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sd = nav_out_span(acting_dist, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_goal_records_t g = nav_goal_records(M, blockIdx.x, sa, sd);
+
+    nav_goal_keys<false>(st, nullptr, g, N, W, H, 1, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
+    const int n_heads = nav_goal_heads(st, g);
+    nav_goal_floods(st, image[threadIdx.x >> 5], n_heads, type, state, W, H, pass_types, doors_open,
+                    [&](int i, const uint16_t *img, bool ok) {
+                        const int c = st.cell[i];
+                        const int64_t p = g.p0 + i;
+                        uint32_t d = MG_NAV_UNREACHABLE;
+                        uint64_t a = 0;
+                        if (ok && c != NAV_NO_CELL) a = nav_ahead_label<false>(img, 0, 1, 0, c, W, H, steps, d);
+                        if (sa.holds(p)) sh.ahead[(int)(p - sa.base)] = a;
+                        if (sd.holds(p)) st.dist[(int)(p - sd.base)] = (uint16_t)d;
+                    });
+    __syncthreads();
+    nav_out_store(ahead, M, sa, sh.ahead, NAV_GOAL_THREADS);
     nav_out_store(acting_dist, M, sd, st.dist, NAV_GOAL_THREADS);
 }
 
@@ -1108,6 +1234,10 @@ bool nav_clock_ok(const int32_t *age, const float *init_pos, bool required)
 }
 
 bool nav_moves_out_ok(const uint8_t *moves, const uint16_t *acting_dist) { return moves && nav_aligned(acting_dist, 2); }
+bool nav_ahead_out_ok(int steps, const uint64_t *ahead, const uint16_t *acting_dist)
+{
+    return steps >= 1 && steps <= MG_NAV_AHEAD_MAX_STEPS && ahead && nav_aligned(ahead, 8) && nav_aligned(acting_dist, 2);
+}
 // shaping: an output at least, reward_out with a reward, the terminal flag with done, finite scale and gamma
 bool nav_shaping_ok(const float *reward, const uint8_t *done, int flags, float scale, float gamma, const float *reward_out,
                     const float *shaping, const uint8_t *mask)
@@ -1313,5 +1443,39 @@ extern "C" int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state
                        pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
                        nav_ends(rec_done, flags), rec_reward, n_records, nav_f2(pos_before), nav_f2(pos_after), age,
                        init_pos, T, scale, gamma, reward_out, shaping, mask, flooders);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_ahead(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                            const float *pos, const int32_t *age, const float *init_pos, int T, int steps, uint64_t *ahead,
+                            uint16_t *acting_dist, void *stream)
+{
+    const int64_t M = (int64_t)T * n_envs;
+    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, period > 1) || !nav_ahead_out_ok(steps, ahead, acting_dist) || !nav_count_ok(M))
+        return TW_E_ARG;
+    if (M == 0) return TW_OK;
+    hipLaunchKernelGGL(period > 1 ? mg_nav_ahead_kernel<true> : mg_nav_ahead_kernel<false>, nav_grid(M, NAV_MOVES_ELEMS),
+                       dim3(NAV_MOVES_THREADS), 0, (hipStream_t)stream, dist, nav_pitch(dist_pitch, width, height), period,
+                       n_envs, width, height, nav_f2(pos), age, init_pos, M, steps,
+                       reinterpret_cast<unsigned long long *>(ahead), acting_dist);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                 uint32_t pass_types, int flags, const int32_t *rec_t, const int32_t *rec_n,
+                                 const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
+                                 const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist,
+                                 void *stream)
+{
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
+        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, false) || !nav_ahead_out_ok(steps, ahead, acting_dist))
+        return TW_E_ARG;
+    if (n_records == 0) return TW_OK;
+    hipLaunchKernelGGL(mg_nav_goal_ahead_kernel, nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS), 0,
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
+                       rec_t, rec_n, rec_goal, n_records, nav_f2(pos), age, init_pos, T, steps,
+                       reinterpret_cast<unsigned long long *>(ahead), acting_dist);
     return tw_launched(__func__);
 }

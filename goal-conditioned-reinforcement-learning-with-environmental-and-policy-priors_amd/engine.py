@@ -431,6 +431,17 @@ class TwoarmyEngine:
                               nav.PASS_DEFAULT if pass_types is None else pass_types, age=age, init_pos=init_pos, out=out,
                               dist_out=dist_out)
 
+    def goal_ahead(self, her, pos, age=None, init_pos=None, steps=3, pass_types=None, out=None, dist_out=None):
+        """Look-ahead labels of hindsight records under their own goals in the engine's worlds as they stand
+        (minigrid_nav.goal_ahead, one launch, read from the engine's own planes) -> (labels int64[R], acting_dist
+        uint16[R]): where a shortest path to the record's goal stands `steps` steps after the record's acting state.
+        her, pos, age, init_pos and pass_types as goal_moves takes them."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        return nav.goal_ahead(ty, her["t"], her["n"], her["goal"], pos, 17, 17, steps=steps,
+                              pass_types=nav.PASS_DEFAULT if pass_types is None else pass_types, age=age,
+                              init_pos=init_pos, out=out, dist_out=dist_out)
+
     def goal_shape(self, her, pos_before, pos_after, age=None, init_pos=None, pass_types=None, scale=1.0, gamma=0.99,
                    zero_terminal=False, out=None, shaping_out=None, mask_out=None):
         """Potential-based shaping of hindsight records under their own goals in the engine's worlds as they stand

@@ -401,6 +401,102 @@ def timed_goal_shape_floods(width, height, period):
     return query("mg_nav_timed_goal_shape_floods", int(width), int(height), int(period))
 
 
+AHEAD_SIDE = 7                        # ahead: displacements -3..3 per axis, bit (dy + 3) * 7 + (dx + 3) of a label
+AHEAD_MAX_STEPS = 3
+AHEAD_DTYPE = torch.int64             # a uint64 label; bits 49..63 are 0, so the sign bit never is set
+
+
+def _ahead_outputs(shape, dev, out, dist_out):
+    """(out, dist_out) of a look-ahead launch, as _moves_outputs makes them, the labels int64."""
+    if out is None:
+        out = torch.empty(shape, dtype=AHEAD_DTYPE, device=dev)
+    assert out.shape == shape and out.device == dev
+    if dist_out is None:
+        dist_out = torch.empty(shape, dtype=DIST_DTYPE, device=dev)
+    elif dist_out is False:
+        dist_out = None
+    assert dist_out is None or (dist_out.shape == shape and dist_out.device == dev)
+    return out, dist_out
+
+
+def ahead(field, pos, width, height, steps=3, age=None, init_pos=None, out=None, dist_out=None):
+    """Where a shortest path leads in `steps` (1..3) steps from every acting state of a rollout (mg_nav_ahead,
+    include/minigrid_nav.h, "Look-ahead").  field uint16[N, H*W] as distance_field returns it or uint16[N, P, H*W] as
+    timed_field does (a 3-D field means timed, as in shape; rows may be padded); pos float32[T, N, 2] = (y, x) BEFORE each
+    step, age int32[T, N] with init_pos float32[2] as optimal_moves takes them (required with a timed field: the age is
+    the clock).  -> (labels int64[T, N], acting_dist uint16[T, N]): bit (dy + 3) * 7 + (dx + 3) of a label = some shortest
+    path stands at displacement (dy, dx) after `steps` steps (at the goal it stays); 0 on an unreachable state or outside
+    the world.  out / dist_out as in optimal_moves.  One launch (none for T = 0)."""
+    W, H = int(width), int(height)
+    if field.dim() == 3:
+        dp, dpitch, N, P = _timed_rows(field, W, H)
+    else:
+        dp, dpitch, N, row = rows(field, DIST_DTYPE)
+        P = 1
+        assert row == W * H
+    dev = field.device
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev)
+    assert age is not None or P == 1, "the age is the clock: age and init_pos are required with a timed field"
+    out, dist_out = _ahead_outputs((T, N), dev, out, dist_out)
+    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, dist_out
+    call("mg_nav_ahead", dev, dp, int(dpitch), P, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
+         int(steps), ptr(out, AHEAD_DTYPE), ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+def goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps=3, pass_types=PASS_DEFAULT, age=None,
+               init_pos=None, state=None, doors_open=False, out=None, dist_out=None):
+    """ahead for records that each name their own goal (mg_nav_goal_ahead, include/minigrid_nav.h): the planes, the
+    records, pos, age and init_pos as goal_moves takes them.  -> (labels int64[R], acting_dist uint16[R]): per record what
+    ahead gives in the field of the record's env flooded from the record's goal cell; 0 / UNREACHABLE for a record whose
+    t, n, goal or acting position names nothing.  out / dist_out as in goal_moves.  One launch (none for R = 0), no field
+    in memory, no host synchronisation."""
+    N, W, H, dev = _planes(type_plane, state, width, height)
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev)
+    out, dist_out = _ahead_outputs((R,), dev, out, dist_out)
+    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, dist_out
+    call("mg_nav_goal_ahead", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
+         DOORS_OPEN if doors_open else 0, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32),
+         R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, int(steps), ptr(out, AHEAD_DTYPE),
+         ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+def ahead_bits(labels):
+    """Look-ahead labels int64[...] -> bool[..., 7, 7]: [..., i, j] = displacement (dy, dx) = (i - 3, j - 3) is in the
+    label -- the classes of the orientation head's two 7-way distributions.  A torch op on any device."""
+    assert labels.dtype == AHEAD_DTYPE
+    sh = torch.arange(AHEAD_SIDE * AHEAD_SIDE, dtype=torch.int64, device=labels.device)
+    return (((labels.unsqueeze(-1) >> sh) & 1) != 0).view(*labels.shape, AHEAD_SIDE, AHEAD_SIDE)
+
+
+def ahead_loss(p0, p1, labels, coef, n_valid=None):
+    """The set-valued prior of the orientation head, plain torch like the head's own NLL.  p0, p1 [B, 7]: the head's two
+    distributions (any positive scale: they are normalised here), labels int64[B].  With q0, q1 the normalised
+    probabilities, m[b] = sum_ij bits[b, i, j] * q0[b, i] * q1[b, j] is the mass the head puts on the label and
+    l = -log(clamp(m, eps, 1 - eps)), eps = float32's;  term = coef * the mean of l over the rows below n_valid (None: all)
+    with a non-zero label, 0 without such a row.  -> (term, stats): stats = {"rows": labelled rows, "mass": their summed m},
+    detached 0-d tensors.  No host synchronisation."""
+    B = labels.shape[0]
+    assert p0.shape == (B, AHEAD_SIDE) and p1.shape == (B, AHEAD_SIDE)
+    q0, q1 = p0 / p0.sum(-1, keepdim=True), p1 / p1.sum(-1, keepdim=True)
+    bits = ahead_bits(labels).to(q0.dtype)
+    m = ((bits * q1.unsqueeze(1)).sum(-1) * q0).sum(-1)
+    eps = torch.finfo(torch.float32).eps
+    lab = labels != 0
+    if n_valid is not None:
+        lab = lab & (torch.arange(B, device=labels.device) < int(n_valid))
+    loss = -torch.log(m.clamp(eps, 1.0 - eps))
+    rows_ = lab.sum()
+    term = float(coef) * torch.where(lab, loss, torch.zeros_like(loss)).sum() / rows_.clamp(min=1).to(loss.dtype)
+    return term, {"rows": rows_.detach(), "mass": torch.where(lab, m, torch.zeros_like(m)).sum().detach()}
+
+
 TWOARMY_PERIOD = 6
 _TWOARMY_BALL_X0 = (7, 8, 7, 6, 6, 6)      # x of the first of the three row-8 balls by step_move % 6 (twoarmy_v6.py:96-109)
 _TWOARMY_V6_BLOCKS = ((4, 11), (5, 11), (4, 12), (5, 12), (8, 11), (8, 12), (9, 11), (9, 12))   # twoarmy_v6.py:186-197

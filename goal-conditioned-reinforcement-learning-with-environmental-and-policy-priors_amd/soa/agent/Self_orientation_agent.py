@@ -141,14 +141,30 @@ class self_orinetation_agent(ppo_predictor):
             self.scheduler_actor.step()
             self.scheduler_critic.step()
 
-    def orientation_step(self, x8, p4, goal, displacement, n_valid=None):
-        """One optimiser step of the orientation head: NLL of the realised displacement (+3 -> class), :266-281.
-        n_valid: only the first n_valid rows are samples, the rest pads the minibatch to a fixed shape (no loss)."""
-        p0, p1 = self.orient_probs(x8, p4, goal)
+    @staticmethod
+    def orientation_nll(p0, p1, displacement, n_valid=None, nll_rows=None):
+        """Mean NLL of the realised displacement (+3 -> class) under the head's two distributions, :266-281, over the first
+        n_valid rows (None: all); nll_rows bool[B]: only these rows carry an NLL, the mean is over them."""
         cls = (displacement + 3).long()
         nll = (-Categorical(probs=p0).log_prob(cls[:, 0]).view(-1, 1)
                - Categorical(probs=p1).log_prob(cls[:, 1]).view(-1, 1))
-        loss = nll.mean() if n_valid is None else nll[:n_valid].sum() / float(n_valid)
+        if nll_rows is None:
+            return nll.mean() if n_valid is None else nll[:n_valid].sum() / float(n_valid)
+        w = nll_rows.to(nll.dtype).view(-1, 1)
+        if n_valid is not None:
+            w = w * (torch.arange(w.shape[0], device=w.device) < int(n_valid)).to(nll.dtype).view(-1, 1)
+        return (nll * w).sum() / w.sum().clamp(min=1.0)
+
+    def orientation_step(self, x8, p4, goal, displacement, n_valid=None, ahead=None, prior_coef=0.0, nll_rows=None):
+        """One optimiser step of the orientation head: NLL of the realised displacement (+3 -> class), :266-281.
+        n_valid: only the first n_valid rows are samples, the rest pads the minibatch to a fixed shape (no loss).
+        ahead int64[B] with prior_coef > 0: the look-ahead labels of the rows (minigrid_nav.ahead); prior_coef times
+        minigrid_nav.ahead_loss over the labelled rows joins the loss.  nll_rows bool[B]: rows without it are prior-only."""
+        p0, p1 = self.orient_probs(x8, p4, goal)
+        loss = self.orientation_nll(p0, p1, displacement, n_valid, nll_rows)
+        if ahead is not None and prior_coef > 0.0:
+            from ... import minigrid_nav as nav
+            loss = loss + nav.ahead_loss(p0, p1, ahead, prior_coef, n_valid)[0]
         bucket = self.grad_sync_orient if hasattr(self.grad_sync_orient, "reduce_async") else None
         if bucket is not None:                       # dist.GradBucket: gradients accumulate straight into the bucket
             bucket.zero()

@@ -29,6 +29,13 @@ unless --shaping_no_hindsight; --shaping_timed: the rollout's potential from the
 --shaping_hindsight_timed (with --shaping_scale, not with --shaping_no_hindsight) shapes the hindsight records by the
 time-expanded search too, each under its own goal (minigrid_nav.timed_goal_shape in place of goal_shape: still one launch
 per rollout), so that with --shaping_timed both halves of a critic batch use one potential; off by default.
+--orient_prior_coef C [--orient_prior_decay D] [--orient_prior_steps K] (train_SoA.py, the self-orientation agent only) adds
+C * D^update times the set-valued look-ahead prior to the NLL of every orientation minibatch: the mass the orientation head
+puts on the displacements a shortest path reaches in K (default 3) steps (minigrid_nav.ahead, one launch per rollout);
+--orient_agreement only labels and reports.  Both append `orient agree` to the log line.  --orient_prior_timed takes the
+labels from the time-expanded field, --orient_prior_hindsight labels the hindsight records too, each under its own goal
+(minigrid_nav.goal_ahead, one more launch; appends `her realised`), --orient_prior_every_state adds every rollout step that
+is no success sample as a prior-only row; all off by default.
 """
 import argparse
 import math
@@ -152,7 +159,38 @@ def build_parser():
     p.add_argument("--shaping_no_hindsight", action="store_true",
                    help="with --shaping_scale: leave the hindsight records unshaped (by default each is shaped under its "
                         "own goal, one more launch per rollout, and `her shaping mean` / `her unshaped` are logged)")
+    p.add_argument("--orient_prior_coef", type=float, default=0.0, metavar="C",
+                   help="self-orientation agent: add C * (the mean of -log of the orientation head's mass on the "
+                        "displacements a shortest path reaches in --orient_prior_steps steps) to the NLL of every "
+                        "orientation minibatch; one label launch per rollout; 0 = off")
+    p.add_argument("--orient_prior_decay", type=float, default=1.0, help="with --orient_prior_coef: the coefficient of update u is C * D^u")
+    p.add_argument("--orient_prior_steps", type=int, default=3, metavar="K", help="steps of the look-ahead, 1..3 (the head predicts 3 ahead)")
+    p.add_argument("--orient_prior_timed", action="store_true",
+                   help="with --orient_prior_coef / --orient_agreement: labels from the time-expanded field (the row-8 "
+                        "balls on their period-6 schedule, the age of a step being its clock)")
+    p.add_argument("--orient_prior_hindsight", action="store_true",
+                   help="with --orient_prior_coef / --orient_agreement: label the hindsight records too, each under its "
+                        "own goal on the static map (one more launch per rollout), and append `her realised` (share of "
+                        "the labelled hindsight samples whose realised displacement lies in the label)")
+    p.add_argument("--orient_prior_every_state", action="store_true",
+                   help="with --orient_prior_coef: every rollout step that is no success sample joins the orientation "
+                        "minibatches as a prior-only row under the env's goal (no NLL)")
+    p.add_argument("--orient_agreement", action="store_true",
+                   help="self-orientation agent: label every rollout with the look-ahead and append `orient agree` (share of "
+                        "the labelled steps whose drawn orientation sample lies in the label) to the log line, without "
+                        "training on it; implied by --orient_prior_coef")
     return p
+
+
+def orient_fields(os_, hindsight=False):
+    """Tail of the log line with --orient_prior_coef / --orient_agreement (VecSoATrainer.orientation_prior_stats());
+    hindsight: with --orient_prior_hindsight."""
+    def f(x):
+        return "-" if x is None else "%.3f" % x
+    tail = " orient agree %s" % f(os_["agree"])
+    if hindsight:
+        tail += " her realised %s" % f(os_["her_realised"])
+    return tail
 
 
 def prior_fields(ps, hindsight=False):
@@ -251,6 +289,15 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--shaping_hindsight_timed needs --shaping_scale")
     if args.shaping_hindsight_timed and args.shaping_no_hindsight:
         raise SystemExit("--shaping_hindsight_timed shapes the hindsight records: not with --shaping_no_hindsight")
+    use_orient = args.orient_prior_coef != 0.0 or args.orient_agreement
+    if not (math.isfinite(args.orient_prior_coef) and args.orient_prior_coef >= 0.0):
+        raise SystemExit("--orient_prior_coef must be a finite number >= 0")
+    if (use_orient or args.orient_prior_timed or args.orient_prior_hindsight or args.orient_prior_every_state) and not soa:
+        raise SystemExit("--orient_prior_* / --orient_agreement: self-orientation agent only")
+    if (args.orient_prior_timed or args.orient_prior_hindsight or args.orient_prior_every_state) and not use_orient:
+        raise SystemExit("--orient_prior_timed / _hindsight / _every_state need --orient_prior_coef or --orient_agreement")
+    if not 1 <= args.orient_prior_steps <= 3:
+        raise SystemExit("--orient_prior_steps must be 1, 2 or 3")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -316,6 +363,10 @@ def main(argv=None, predictor=False, soa=False):
     if use_shaping:
         trainer.enable_shaping(args.shaping_scale, hindsight=not args.shaping_no_hindsight, timed=args.shaping_timed,
                                hindsight_timed=args.shaping_hindsight_timed)
+    if use_orient:
+        trainer.enable_orientation_prior(args.orient_prior_coef, args.orient_prior_decay, steps=args.orient_prior_steps,
+                                         timed=args.orient_prior_timed, hindsight=args.orient_prior_hindsight,
+                                         every_state=args.orient_prior_every_state)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
@@ -335,6 +386,8 @@ def main(argv=None, predictor=False, soa=False):
             trainer.account_distance()
         if use_prior:
             trainer.label_expert()
+        if use_orient:                                        # behind relabel(): its records are labelled too
+            trainer.label_ahead()
         es = None
         if args.score == "episode":
             es = trainer.episode_stats()
@@ -346,7 +399,8 @@ def main(argv=None, predictor=False, soa=False):
         n_her = 0 if trainer.her is None else int(trainer.her["t"].numel())
         ps = trainer.prior_stats() if use_prior else None       # the policy that acted, before the update changes it
         ss = trainer.shaping_stats() if use_shaping else None   # before update() drops the records
-        if use_prior or use_shaping:
+        ots = trainer.orientation_prior_stats() if use_orient else None   # before update() drops the records
+        if use_prior or use_shaping or use_orient:
             torch.cuda.synchronize()
             t1 = time.perf_counter()                            # the statistics are not part of the update's time
         la, lv = trainer.update()
@@ -372,6 +426,8 @@ def main(argv=None, predictor=False, soa=False):
             tail += prior_fields(ps, args.prior_hindsight)
         if use_shaping:                                         # behind every other field
             tail += shaping_fields(ss, not args.shaping_no_hindsight)
+        if use_orient:                                          # behind every other field
+            tail += orient_fields(ots, args.orient_prior_hindsight)
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

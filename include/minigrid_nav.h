@@ -371,6 +371,65 @@ int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state, int n_env
 #define MG_NAV_TIMED_GOAL_SHAPE_LDS 25968
 int mg_nav_timed_goal_shape_floods(int width, int height, int period);
 
+/* ---- Look-ahead: where a shortest path leads in k steps (the k-step counterpart of the move sets).
+ *
+ * The world, moves, fields, visit_cell rule, acting-position rule (age <= 0 ? init_pos : pos) and phase rule are the
+ * existing ones.  1 <= steps <= MG_NAV_AHEAD_MAX_STEPS.
+ *
+ * Label.  A uint64_t: bit (dy + 3) * MG_NAV_AHEAD_SIDE + (dx + 3) stands for the displacement (dy, dx) = (y' - y, x' - x)
+ * from the acting cell (x, y) -- the order of `pos` and of the classes displacement + 3 of the orientation head.  Bit 24 is
+ * "same cell"; bits 49..63 are always 0.
+ *
+ * Look-ahead of an acting state s0 = (c, phase) with distance d in a field, for steps = k:
+ *   S_0 = {s0};  S_(j+1) = the union of the successors of the states in S_j;  the label = { c' - c : (c', .) in S_k }.
+ *   Successors.  A state at distance 0 has itself as its only successor: the episode has ended there, and the position
+ *   stays (the rule pos[min(t + k, end + 1)] of a realised trajectory) -- whether or not the cell is free at the next phase.
+ *   Any other state has exactly the members of its move set (mg_nav_optimal_moves / mg_nav_timed_moves): a neighbour inside
+ *   the world whose distance, read in the row the move arrives in, is one less, and the cell itself where waiting is
+ *   optimal in a timed field.  The row the move arrives in is the same row for period 1, the row of phase + 1 mod P otherwise.
+ *   The label is 0 where the acting position is no cell or its state is MG_NAV_UNREACHABLE.
+ * Two consequences: all members of S_j share one phase and one distance, max(d - j, 0), so the expansion simply stops after
+ * min(k, d) steps; and S_j lies within Manhattan radius j <= 3, so one 64-bit word holds every frontier.
+ *
+ * Invariants.  (a) At steps = 1 the label is the image of the move set: left -> bit 23, right -> 25, up -> 17, down -> 31,
+ * stay -> 24.  (b) Every cell of the label has distance max(d - k, 0) -- at phase + k for a timed field -- unless d < k.
+ * (c) The label at k is the union, over the cells of the label at k - 1, of their labels at 1 at the phase that follows;
+ * cells at distance 0 are carried over.  (d) label != 0 iff acting_dist != MG_NAV_UNREACHABLE.  (b) - (d) hold on fields the
+ * field kernels wrote; on an array of distances that is no field (no neighbour one nearer) a label can be 0 at a reachable
+ * acting_dist: the frontier then simply dies, and nothing is read outside the arrays either way. */
+#define MG_NAV_AHEAD_MAX_STEPS 3
+#define MG_NAV_AHEAD_SIDE 7
+
+/* The rollout, from ONE field per env.
+ *   dist, dist_pitch, period, age, init_pos: exactly as mg_nav_shape takes them (period 1 = what mg_nav_field writes, age and
+ *               init_pos nullable together; period > 1 = what mg_nav_timed_field writes, age is the clock, both required)
+ *   pos         float[T][n_envs][2] = (y, x) BEFORE step t (8-byte aligned), as in mg_nav_optimal_moves
+ *   ahead       uint64[T][n_envs], 8-byte aligned;  acting_dist uint16[T][n_envs] (nullable): as in mg_nav_optimal_moves
+ * One launch, no atomics; T == 0 launches nothing.  Both outputs leave as aligned 16-byte stores (2 labels, 8 distances),
+ * element by element only in the first and last chunk of a workgroup's share (csrc/row_store.h); nothing outside the first
+ * T * n_envs elements of either output is written, and nothing outside the arrays is read for any position, NaN included.
+ * TW_E_ARG: the cases of mg_nav_optimal_moves (period == 1) / mg_nav_timed_moves (period > 1) with ahead for moves; period
+ * outside 1..MG_NAV_MAX_PERIOD; steps outside 1..MG_NAV_AHEAD_MAX_STEPS; ahead not 8-byte aligned. */
+int mg_nav_ahead(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                 const float *pos, const int32_t *age, const float *init_pos, int T, int steps, uint64_t *ahead,
+                 uint16_t *acting_dist, void *stream);
+
+/* Hindsight records, each under its OWN goal, on the static map.  Per record b: let F be the field mg_nav_field computes for
+ * env rec_n[b] with visit_cell(rec_goal[b]) as its single source; ahead[b] and acting_dist[b] are what mg_nav_ahead gives
+ * for the record's acting cell in F.  The records, the acting positions, the records that name nothing (label 0,
+ * MG_NAV_UNREACHABLE, no access outside the arrays), the independence of a record from its neighbours and their order, the
+ * workgroup's 1024 records and its one flood per run of equal (env, goal cell), the reads and the store rule are those of
+ * mg_nav_goal_moves.
+ *   ahead uint64[n_records], 8-byte aligned;  acting_dist uint16[n_records] (nullable)
+ * Invariant: for records that share one goal per env the outputs equal mg_nav_field(goal_x, goal_y) followed by mg_nav_ahead
+ * on the same positions.  One launch, no atomics; n_records == 0 returns 0 and launches nothing.
+ * TW_E_ARG: the cases of mg_nav_goal_moves with ahead for moves; steps outside 1..MG_NAV_AHEAD_MAX_STEPS; ahead not 8-byte
+ * aligned. */
+int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                      uint32_t pass_types, int flags, const int32_t *rec_t, const int32_t *rec_n,
+                      const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
+                      const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,35 @@ h_s = timed(lambda: h_eng.goal_moves(her, h_pos, h_age, h_tr.init_pos, pass_type
 report("mg_nav_goal_moves (%d hindsight records of a 4096 x 128 rollout, %d heads)" % (R, n_heads),
        R * (4 + 4 + 8 + 8 + 4 + 1 + 2) + N * 289, h_s,
        "one launch; %d records, %d heads, %.1f floods per us" % (R, n_heads, n_heads / (h_s * 1e6)))
+# Look-ahead labels of that rollout (mg_nav_ahead, steps 3) next to the move sets of the same elements, on REAL fields -- the
+# engine's static field and its six-phase one -- and the rollout's own positions and ages: on a random field hardly any
+# neighbour is one nearer and the frontier dies after one round.  Three windows each, the spread of the number.
+r_field = h_tr._static_field(reuse=False)
+r_field6 = torch.empty((N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=dev)
+h_eng.timed_field(agent=False, out=r_field6)
+ah_out = torch.empty((T, N), dtype=torch.int64, device=dev)
+rom_s = timed(lambda: nav.optimal_moves(r_field, h_pos, 17, 17, age=h_age, init_pos=h_tr.init_pos, out=mv_out, dist_out=ad_out))
+report("mg_nav_optimal_moves (the rollout on its static field)", T * N * (8 + 4 + 1 + 2) + N * 578, rom_s, "one launch")
+rtm_s = timed(lambda: nav.timed_moves(r_field6, h_pos, 17, 17, h_age, h_tr.init_pos, out=mv_out, dist_out=ad_out))
+report("mg_nav_timed_moves (the rollout on its timed field, P = 6)", T * N * (8 + 4 + 1 + 2) + N * 6 * 578, rtm_s, "one launch")
+ah_cells = None
+for _ in range(3):
+    a_s = timed(lambda: nav.ahead(r_field, h_pos, 17, 17, steps=3, age=h_age, init_pos=h_tr.init_pos, out=ah_out, dist_out=ad_out))
+    if ah_cells is None:                                       # the mean size of a final frontier: the work is real
+        ah_cells = float(nav.ahead_bits(ah_out).sum()) / float((ah_out != 0).sum().clamp(min=1))
+    report("mg_nav_ahead (the rollout, steps 3, static)", T * N * (8 + 4 + 8 + 2) + N * 578, a_s,
+           "one launch; %.2f x mg_nav_optimal_moves; %.2f cells per non-empty label" % (a_s / rom_s, ah_cells))
+for _ in range(3):
+    a_s = timed(lambda: nav.ahead(r_field6, h_pos, 17, 17, steps=3, age=h_age, init_pos=h_tr.init_pos, out=ah_out, dist_out=ad_out))
+    report("mg_nav_ahead (the rollout, steps 3, P = 6)", T * N * (8 + 4 + 8 + 2) + N * 6 * 578, a_s,
+           "one launch; %.2f x mg_nav_timed_moves" % (a_s / rtm_s))
+# The records' look-ahead labels (mg_nav_goal_ahead, steps 3): the same floods, a frontier walk per record and 8-byte labels.
+ha_out = torch.empty(R, dtype=torch.int64, device=dev)
+for _ in range(3):                                             # three windows: the spread of the number below
+    ha_s = timed(lambda: h_eng.goal_ahead(her, h_pos, h_age, h_tr.init_pos, steps=3, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
+                                          out=ha_out, dist_out=hd_out))
+    report("mg_nav_goal_ahead (the same %d records, %d heads, steps 3)" % (R, n_heads),
+           R * (4 + 4 + 8 + 8 + 4 + 8 + 2) + N * 289, ha_s, "one launch; %.2f x mg_nav_goal_moves" % (ha_s / h_s))
 # The same records labelled over (cell, phase): six phases per flood, the balls on their schedule.  The row above, taken
 # in the same process on the same records, is the yardstick.
 ht_s = timed(lambda: h_eng.timed_goal_moves(her, h_pos, h_age, h_tr.init_pos, out=hm_out, dist_out=hd_out))
