@@ -49,13 +49,18 @@
  *                          cells); TIMED advances the phase per step.
  *   mg_nav_goal_ahead_kernel   the same labels for records under goals of their own: the goal kernel's keys, heads and
  *                          floods, nav_ahead_label on the half wavefront's image, 8 KiB of staged labels of its own.
+ *   mg_nav_path_scan_kernel    path efficiency per episode (minigrid_nav.h, "Path efficiency"): a lane per env walks the
+ *                          rollout in step order with four integer carries, the shaping kernel's two distances per step
+ *                          gathered eight rows ahead of the chain; plain coalesced stores, no LDS.
+ *   mg_nav_path_partial_kernel, mg_nav_path_finalize_kernel   the summary over the done steps, in ppo_episode_summary's
+ *                          fixed order: runs per thread, lanes as a tree, wavefronts and workgroups in index order.
  *
  * Shared: nav_image_clear, nav_dilate, nav_move_set<WAIT>, nav_ahead_expand / nav_ahead_label; nav_out_span_t / nav_out_span / nav_out_store (one output of a
  * workgroup, any element type: the goal kernel and the shaping kernels; the moves and the timed goal kernel measured slower
  * on them and keep their own); nav_goal_records, _keys, _heads, _floods; on the host one nav_*_ok per argument rule.
  *
- * Integer work only but for the shaping term (three float32 operations, each rounded once: fp contract off), no atomics:
- * the results do not depend on scheduling.
+ * Integer work only but for the shaping term (three float32 operations, each rounded once: fp contract off) and the two
+ * quotient sums of the path summary (float64, combined in a fixed order), no atomics: the results do not depend on scheduling.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1184,6 +1189,174 @@ template <int... Ps> constexpr nav_timed_goal_shape_kernel_t nav_timed_goal_shap
 constexpr const nav_timed_goal_shape_kernel_t *nav_timed_goal_shape_kernels =   // [P - 1]
     nav_timed_goal_shape_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
+// ------------------------------------------------------------------ path efficiency per episode
+// The scan of minigrid_nav.h ("Path efficiency"): ppo_episode_scan's shape, a lane per env over coalesced rows [t][n].  The
+// dependent chain is four integer operations per step; what costs is the two gathers per step from the env's field, so the
+// loads and gathers of NAV_PATH_ROWS rows are issued together, ahead of the chain (rows past T repeat row T - 1 and are
+// dropped: every load of a batch is unconditional).  TIMED: dist holds P fields per env, the phases come from the age.
+constexpr int NAV_PATH_THREADS = 64, NAV_PATH_ROWS = 8;
+
+template <bool TIMED> __global__ __launch_bounds__(NAV_PATH_THREADS) void mg_nav_path_scan_kernel(
+    const uint16_t *__restrict__ dist, int64_t pitch, int P, int N, int W, int H, const float2 *__restrict__ pos_before,
+    const float2 *__restrict__ pos_after, const int32_t *__restrict__ age, const float *__restrict__ init_pos,
+    const uint8_t *__restrict__ terminated, const uint8_t *__restrict__ truncated, int T,
+    uint16_t *__restrict__ carry_start, uint16_t *__restrict__ carry_best, int32_t *__restrict__ carry_off,
+    int32_t *__restrict__ carry_steps, uint16_t *__restrict__ ep_start, uint16_t *__restrict__ ep_best,
+    int32_t *__restrict__ ep_off, int32_t *__restrict__ ep_steps)
+{
+    const int n = blockIdx.x * NAV_PATH_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const int HW = W * H;
+    const uint16_t *f = dist + (int64_t)n * P * pitch;
+    float2 init = make_float2(0.f, 0.f);
+    if (age != nullptr) init = make_float2(init_pos[0], init_pos[1]);
+    uint32_t start = carry_start[n], best = carry_best[n];
+    int off = carry_off[n], steps = carry_steps[n];
+    for (int t0 = 0; t0 < T; t0 += NAV_PATH_ROWS) {
+        uint32_t db[NAV_PATH_ROWS], da[NAV_PATH_ROWS], dn[NAV_PATH_ROWS];
+#pragma unroll
+        for (int j = 0; j < NAV_PATH_ROWS; ++j) {
+            const int t = t0 + j < T ? t0 + j : T - 1;
+            const int64_t i = (int64_t)t * N + n;
+            float2 q = pos_before[i];
+            const float2 qa = pos_after[i];
+            const int clock = age != nullptr ? age[i] : 1;
+            if (clock <= 0) q = init;
+            const int cb = visit_cell(q.x, q.y, W, H), ca = visit_cell(qa.x, qa.y, W, H);
+            const uint16_t *fb = f, *fa = f;
+            if (TIMED) {                                                    // as mg_nav_shape_kernel takes its two rows
+                const int ph = nav_phase(clock, P);
+                fb += ph * pitch;
+                fa += (ph + 1 >= P ? 0 : ph + 1) * pitch;
+            }
+            db[j] = cb < HW ? fb[cb] : (uint32_t)MG_NAV_UNREACHABLE;
+            da[j] = ca < HW ? fa[ca] : (uint32_t)MG_NAV_UNREACHABLE;
+            dn[j] = (uint32_t)(terminated[i] | truncated[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < NAV_PATH_ROWS; ++j) {
+            const int t = t0 + j;
+            if (t < T) {
+                const int64_t i = (int64_t)t * N + n;
+                if (steps == 0) { start = best = db[j]; off = 0; }
+                steps += 1;
+                const bool on_path = db[j] != (uint32_t)MG_NAV_UNREACHABLE && db[j] >= 1u && da[j] == db[j] - 1u;
+                off += on_path ? 0 : 1;
+                best = da[j] < best ? da[j] : best;
+                if (ep_start) ep_start[i] = (uint16_t)start;
+                if (ep_best) ep_best[i] = (uint16_t)best;
+                if (ep_off) ep_off[i] = off;
+                if (ep_steps) ep_steps[i] = steps;
+                if (dn[j]) steps = 0;
+            }
+        }
+    }
+    carry_start[n] = (uint16_t)start;
+    carry_best[n] = (uint16_t)best;
+    carry_off[n] = off;
+    carry_steps[n] = steps;
+}
+
+// The summary of minigrid_nav.h: ppo_episode_summary's two kernels and its order of combination (ppo_kernels.hip) on a
+// partial of NAV_PATH_NV doubles -- every entry a sum but the last, a minimum.  Counts and integer sums are kept as integers
+// per thread and are exact as doubles from there on (far below 2^53).
+constexpr int NAV_PATH_NV = MG_NAV_PATH_SUMMARY, NAV_PATH_MIN = NAV_PATH_NV - 1;
+constexpr int NAV_PATH_BLOCK_ELEMS = 2048, NAV_PATH_MAX_BLOCKS = 256, NAV_PATH_SUM_THREADS = 256;
+
+__device__ __forceinline__ void nav_path_combine(double (&v)[NAV_PATH_NV], const double (&w)[NAV_PATH_NV])
+{
+#pragma unroll
+    for (int k = 0; k < NAV_PATH_MIN; ++k) v[k] += w[k];
+    v[NAV_PATH_MIN] = fmin(v[NAV_PATH_MIN], w[NAV_PATH_MIN]);
+}
+
+// Ordered over the 64 lanes: after step s a lane whose index is a multiple of 2s holds lanes [lane, lane + 2s) in lane order.
+__device__ __forceinline__ void nav_path_wave_reduce(double (&v)[NAV_PATH_NV])
+{
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        double w[NAV_PATH_NV];
+#pragma unroll
+        for (int k = 0; k < NAV_PATH_NV; ++k) w[k] = __shfl_down(v[k], s, 64);
+        nav_path_combine(v, w);
+    }
+}
+
+__global__ __launch_bounds__(NAV_PATH_SUM_THREADS) void mg_nav_path_partial_kernel(
+    const uint16_t *__restrict__ ep_start, const uint16_t *__restrict__ ep_best, const int32_t *__restrict__ ep_off,
+    const int32_t *__restrict__ ep_steps, const uint8_t *__restrict__ terminated, const uint8_t *__restrict__ truncated,
+    int64_t M, int64_t per_block, int per_thread, double *__restrict__ ws)
+{
+    __shared__ double sh[NAV_PATH_SUM_THREADS / 64][NAV_PATH_NV];
+    const int64_t block_lo = (int64_t)blockIdx.x * per_block;
+    const int64_t block_hi = block_lo + per_block < M ? block_lo + per_block : M;
+    const int64_t lo = block_lo + (int64_t)threadIdx.x * per_thread;
+    const int64_t hi = lo + per_thread < block_hi ? lo + per_thread : block_hi;
+    long long episodes = 0, successes = 0, rated = 0, sum_start = 0, sum_best = 0, sum_off = 0, sum_steps = 0;
+    uint32_t min_best = MG_NAV_UNREACHABLE;                                 // of the rated: reachable, so below this
+    double spl = 0.0, progress = 0.0;
+    for (int64_t i = lo; i < hi; ++i) {
+        const uint32_t te = terminated[i];
+        if (!(te | truncated[i])) continue;                                 // an episode ends here
+        const uint32_t s = ep_start[i], b = ep_best[i];
+        const int st = ep_steps[i];
+        episodes += 1;
+        successes += te ? 1 : 0;
+        sum_off += ep_off[i];
+        sum_steps += st;
+        if (s == (uint32_t)MG_NAV_UNREACHABLE) continue;
+        rated += 1;
+        sum_start += s;
+        sum_best += b;
+        min_best = b < min_best ? b : min_best;
+        if (te) spl += (double)s / (double)(st > (int)s ? st : (int)s);
+        if (s >= 1u) progress += (double)((int)s - (int)b) / (double)s;      // the scan keeps best <= start
+    }
+    double v[NAV_PATH_NV] = {(double)episodes, (double)successes, (double)rated, spl, (double)sum_start, (double)sum_best,
+                             progress, (double)sum_off, (double)sum_steps,
+                             rated ? (double)min_best : (double)INFINITY};
+    nav_path_wave_reduce(v);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NAV_PATH_NV; ++k) sh[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < NAV_PATH_SUM_THREADS / 64; ++w) {               // wavefronts in index order
+            double o[NAV_PATH_NV];
+#pragma unroll
+            for (int k = 0; k < NAV_PATH_NV; ++k) o[k] = sh[w][k];
+            nav_path_combine(v, o);
+        }
+#pragma unroll
+        for (int k = 0; k < NAV_PATH_NV; ++k) ws[(size_t)blockIdx.x * NAV_PATH_NV + k] = v[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void mg_nav_path_finalize_kernel(const double *__restrict__ ws, int nblocks,
+                                                                  double *__restrict__ summary)
+{
+    const int lane = threadIdx.x;
+    const int per_lane = (nblocks + 63) / 64;                               // nblocks <= NAV_PATH_MAX_BLOCKS: at most 4 each
+    double v[NAV_PATH_NV] = {};
+    v[NAV_PATH_MIN] = (double)INFINITY;
+    for (int j = 0; j < per_lane; ++j) {                                    // lane l: blocks [l * per_lane, (l + 1) * per_lane)
+        const int blk = lane * per_lane + j;
+        if (blk < nblocks) {
+            double o[NAV_PATH_NV];
+#pragma unroll
+            for (int k = 0; k < NAV_PATH_NV; ++k) o[k] = ws[(size_t)blk * NAV_PATH_NV + k];
+            nav_path_combine(v, o);
+        }
+    }
+    nav_path_wave_reduce(v);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NAV_PATH_NV; ++k) summary[k] = v[k];
+    }
+}
+
 // ------------------------------------------------------------------ the argument rules of minigrid_nav.h, each once
 bool nav_sides_ok(int W, int H) { return W >= 1 && W <= NAV_SIDE && H >= 1 && H <= NAV_SIDE; }
 bool nav_period_ok(int P) { return P >= 1 && P <= NAV_MAX_PERIOD; }
@@ -1247,6 +1420,18 @@ bool nav_shaping_ok(const float *reward, const uint8_t *done, int flags, float s
            __builtin_isfinite(gamma);
 }
 const uint8_t *nav_ends(const uint8_t *done, int flags) { return (flags & MG_NAV_SHAPE_ZERO_TERMINAL) ? done : nullptr; }
+// path efficiency: the two flag arrays, and (start, best, off, steps) as carries or as per-step arrays -- required: all four
+bool nav_flags_given(const uint8_t *terminated, const uint8_t *truncated) { return terminated && truncated; }
+bool nav_path_arrays_ok(const uint16_t *start, const uint16_t *best, const int32_t *off, const int32_t *steps, bool required)
+{
+    return (required ? start && best && off && steps : start || best || off || steps) && nav_aligned(start, 2) &&
+           nav_aligned(best, 2) && nav_aligned(off, 4) && nav_aligned(steps, 4);
+}
+int nav_path_blocks(int64_t M)
+{
+    const int64_t b = (M + NAV_PATH_BLOCK_ELEMS - 1) / NAV_PATH_BLOCK_ELEMS;
+    return (int)(b < NAV_PATH_MAX_BLOCKS ? b : NAV_PATH_MAX_BLOCKS);
+}
 
 // workgroups of `elems` elements: chunks are counted from the aligned address below each output, up to 15 more than count
 dim3 nav_grid(int64_t count, int elems) { return dim3((unsigned)((count + 15 + elems - 1) / elems)); }
@@ -1477,5 +1662,50 @@ extern "C" int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int 
                        (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
                        rec_t, rec_n, rec_goal, n_records, nav_f2(pos), age, init_pos, T, steps,
                        reinterpret_cast<unsigned long long *>(ahead), acting_dist);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_path_scan(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                                const float *pos_before, const float *pos_after, const int32_t *age, const float *init_pos,
+                                const uint8_t *terminated, const uint8_t *truncated, int T, uint16_t *carry_start,
+                                uint16_t *carry_best, int32_t *carry_off, int32_t *carry_steps, uint16_t *ep_start,
+                                uint16_t *ep_best, int32_t *ep_off, int32_t *ep_steps, void *stream)
+{
+    const int64_t M = (int64_t)T * n_envs;
+    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) ||
+        !nav_rollout_ok(pos_before, T) || !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, period > 1) ||
+        !nav_flags_given(terminated, truncated) || !nav_path_arrays_ok(carry_start, carry_best, carry_off, carry_steps, true) ||
+        !nav_path_arrays_ok(ep_start, ep_best, ep_off, ep_steps, false) || !nav_count_ok(M))
+        return TW_E_ARG;
+    if (M == 0) return TW_OK;
+    hipLaunchKernelGGL(period > 1 ? mg_nav_path_scan_kernel<true> : mg_nav_path_scan_kernel<false>,
+                       dim3((n_envs + NAV_PATH_THREADS - 1) / NAV_PATH_THREADS), dim3(NAV_PATH_THREADS), 0,
+                       (hipStream_t)stream, dist, nav_pitch(dist_pitch, width, height), period, n_envs, width, height,
+                       nav_f2(pos_before), nav_f2(pos_after), age, init_pos, terminated, truncated, T, carry_start,
+                       carry_best, carry_off, carry_steps, ep_start, ep_best, ep_off, ep_steps);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_path_summary_workspace(int T, int N)
+{
+    if (T <= 0 || N <= 0 || !nav_count_ok((int64_t)T * N)) return TW_E_ARG;
+    return nav_path_blocks((int64_t)T * N) * NAV_PATH_NV;
+}
+
+extern "C" int mg_nav_path_summary(const uint16_t *ep_start, const uint16_t *ep_best, const int32_t *ep_off,
+                                   const int32_t *ep_steps, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
+                                   double *summary, double *workspace, void *stream)
+{
+    const int64_t M = (int64_t)T * N;
+    if (!nav_path_arrays_ok(ep_start, ep_best, ep_off, ep_steps, true) || !nav_flags_given(terminated, truncated) ||
+        T <= 0 || N <= 0 || !nav_count_ok(M) || !summary || !workspace || !nav_aligned(summary, 8) ||
+        !nav_aligned(workspace, 8))
+        return TW_E_ARG;
+    const int nblocks = nav_path_blocks(M);
+    const int64_t per_block = (M + nblocks - 1) / nblocks;
+    const int per_thread = (int)((per_block + NAV_PATH_SUM_THREADS - 1) / NAV_PATH_SUM_THREADS);
+    hipLaunchKernelGGL(mg_nav_path_partial_kernel, dim3(nblocks), dim3(NAV_PATH_SUM_THREADS), 0, (hipStream_t)stream,
+                       ep_start, ep_best, ep_off, ep_steps, terminated, truncated, M, per_block, per_thread, workspace);
+    hipLaunchKernelGGL(mg_nav_path_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, workspace, nblocks, summary);
     return tw_launched(__func__);
 }

@@ -4,7 +4,9 @@ are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are in
 of the engine's records (TwoarmyEngine.agent_views()), read where they live.  goal_moves labels records that each name a
 goal of their own (hindsight records) without a field in memory.  timed_field / timed_moves do the same for worlds whose
 blockers move with a period (a search over (cell, phase): the expert may wait).  shape / goal_shape / timed_goal_shape turn
-the distances into a potential and shape rewards with it, float32 with pinned rounding.  One launch per call, on the tensors' device.
+the distances into a potential and shape rewards with it, float32 with pinned rounding.  path_scan / path_summary / PathTracker
+rate every episode against the field: success weighted by path length, progress, steps off a shortest path.  One launch per
+call (path_summary: two), on the tensors' device.
 No CPU fallback."""
 import ctypes
 
@@ -495,6 +497,138 @@ def ahead_loss(p0, p1, labels, coef, n_valid=None):
     rows_ = lab.sum()
     term = float(coef) * torch.where(lab, loss, torch.zeros_like(loss)).sum() / rows_.clamp(min=1).to(loss.dtype)
     return term, {"rows": rows_.detach(), "mass": torch.where(lab, m, torch.zeros_like(m)).sum().detach()}
+
+
+PATH_SUMMARY = ("episodes", "successes", "rated", "spl_sum", "start_sum", "best_sum", "progress_sum", "off_sum",
+                "steps_sum", "best_min")              # the ten entries of mg_nav_path_summary
+_PATH_DTYPES = (DIST_DTYPE, DIST_DTYPE, torch.int32, torch.int32)       # start, best, off, steps
+
+
+def _u16_zeros(shape, dev):
+    """A zeroed uint16 tensor (torch's uint16 has views and copies, little else: made as int16)."""
+    return torch.zeros(shape, dtype=torch.int16, device=dev).view(DIST_DTYPE)
+
+
+def _field_rows(field, W, H):
+    """(pointer, pitch in elements, N, P) of a static field uint16[N, H*W] or a timed one uint16[N, P, H*W]."""
+    if field.dim() == 3:
+        return _timed_rows(field, W, H)
+    dp, dpitch, N, row = rows(field, DIST_DTYPE)
+    assert row == W * H
+    return dp, dpitch, N, 1
+
+
+def path_scan(field, pos_before, pos_after, width, height, terminated, truncated, carry, age=None, init_pos=None, out=None):
+    """Path efficiency per episode, one step after the other (mg_nav_path_scan, include/minigrid_nav.h, "Path
+    efficiency").  field uint16[N, H*W] as distance_field returns it or uint16[N, P, H*W] as timed_field does (rows may be
+    padded); pos_before, pos_after float32[T, N, 2], age int32[T, N] and init_pos float32[2] as shape takes them (required
+    with a timed field); terminated, truncated uint8[T, N]; carry = (start uint16[N], best uint16[N], off int32[N], steps
+    int32[N]), updated in place -- all zero: no episode is running.  -> (ep_start uint16[T, N], ep_best uint16[T, N],
+    ep_off int32[T, N], ep_steps int32[T, N]): at a done step the distance the ending episode started at, the least it
+    stood at, its steps off a shortest path and its length.  out: a 4-tuple of tensors to write into, None = a new one,
+    False = not wanted (None is returned for it); at least one is wanted.  One launch (none for T = 0)."""
+    W, H = int(width), int(height)
+    dp, dpitch, N, P = _field_rows(field, W, H)
+    dev = field.device
+    T = _positions(N, dev, pos_before, pos_after)
+    _clock(age, init_pos, T, N, dev)
+    assert age is not None or P == 1, "the age is the clock: age and init_pos are required with a timed field"
+    for f in (terminated, truncated):
+        assert f.shape == (T, N) and f.device == dev
+    for c, dt in zip(carry, _PATH_DTYPES):
+        assert c.shape == (N,) and c.device == dev and c.dtype == dt
+    outs = []
+    for o, dt in zip(out if out is not None else (None,) * 4, _PATH_DTYPES):
+        o = torch.empty((T, N), dtype=dt, device=dev) if o is None else (None if o is False else o)
+        assert o is None or (o.shape == (T, N) and o.device == dev and o.dtype == dt)
+        outs.append(o)
+    assert any(o is not None for o in outs), "no output wanted"
+    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return tuple(outs)
+    call("mg_nav_path_scan", dev, dp, int(dpitch), P, N, W, H, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
+         ptr(init_pos, torch.float32), ptr(terminated, torch.uint8), ptr(truncated, torch.uint8), T,
+         *(ptr(c) for c in carry), *(ptr(o) for o in outs))
+    return tuple(outs)
+
+
+def path_summary_workspace(T, N):
+    """Doubles of workspace path_summary needs for a [T, N] rollout -- the launch's own host function."""
+    return query("mg_nav_path_summary_workspace", int(T), int(N))
+
+
+def path_summary(ep_start, ep_best, ep_off, ep_steps, terminated, truncated, summary=None, workspace=None):
+    """The episodes that ended in a rollout (mg_nav_path_summary): path_scan's four outputs and the flags, all [T, N] with
+    T >= 1 -> summary float64[10] in the order of PATH_SUMMARY: episodes, successes, rated episodes (reachable start), the
+    sums over the rated of SPL = success ? start / max(steps, start) : 0, of start, of best and of (start - best) / start,
+    the sums of off and steps over all episodes, and the least best (+inf without a rated episode).  Deterministic: a
+    fixed grid and order for a given (T, N).  summary / workspace: tensors to write into.  No host synchronisation."""
+    T, N = terminated.shape
+    dev = terminated.device
+    for t, dt in zip((ep_start, ep_best, ep_off, ep_steps), _PATH_DTYPES):
+        assert t.shape == (T, N) and t.device == dev and t.dtype == dt
+    assert truncated.shape == (T, N) and truncated.device == dev
+    if summary is None:
+        summary = torch.empty(len(PATH_SUMMARY), dtype=torch.float64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(path_summary_workspace(T, N), dtype=torch.float64, device=dev)
+    assert summary.shape == (len(PATH_SUMMARY),) and workspace.numel() >= path_summary_workspace(T, N)
+    call("mg_nav_path_summary", dev, ptr(ep_start), ptr(ep_best), ptr(ep_off), ptr(ep_steps), ptr(terminated, torch.uint8),
+         ptr(truncated, torch.uint8), T, N, ptr(summary, torch.float64), ptr(workspace, torch.float64))
+    return summary
+
+
+class PathTracker:
+    """Path efficiency of the episodes of N envs, carried across rollouts, in the style of EpisodeTracker / VisitTracker:
+    account() per rollout (mg_nav_path_scan, mg_nav_path_summary: two calls, no host synchronisation), read() for the
+    numbers of the last accounted rollout."""
+
+    def __init__(self, num_envs, device, width, height, period=1):
+        self.N, self.device = int(num_envs), torch.device(device)
+        self.width, self.height, self.period = int(width), int(height), int(period)
+        assert 1 <= self.period <= MAX_PERIOD
+        d = self.device
+        self.carry = (_u16_zeros(self.N, d), _u16_zeros(self.N, d), torch.zeros(self.N, dtype=torch.int32, device=d),
+                      torch.zeros(self.N, dtype=torch.int32, device=d))         # start, best, off, steps
+        self.summary = torch.zeros(len(PATH_SUMMARY), dtype=torch.float64, device=d)
+        self.summary[-1] = float("inf")                                     # nothing accounted yet: no rated episode
+        self.steps = self._workspace = None                                 # sized by the first account()
+
+    def reset(self):
+        """Forget the running episodes (envs were reset); the last summary stays."""
+        for c in self.carry:
+            c.view(torch.int16 if c.dtype == DIST_DTYPE else c.dtype).zero_()
+
+    def account(self, field, pos_before, pos_after, terminated, truncated, age=None, init_pos=None):
+        """Account one rollout: field uint16[N, H*W] (period 1) or uint16[N, P, H*W], the positions [T, N, 2] before and
+        after each step, the flags [T, N], age [T, N] with init_pos (required with period > 1) as path_scan takes them.
+        Afterwards `steps` = (ep_start, ep_best, ep_off, ep_steps) [T, N] hold the scan's outputs and `summary` the ten
+        sums over the episodes that ended in this rollout."""
+        T, N = terminated.shape
+        assert N == self.N, "tracker made for %d envs, got %d" % (self.N, N)
+        assert (field.shape[1] if field.dim() == 3 else 1) == self.period, "tracker made for period %d" % self.period
+        if self.steps is None or self.steps[0].shape[0] != T:
+            self.steps = tuple(torch.empty((T, N), dtype=dt, device=self.device) for dt in _PATH_DTYPES)
+            self._workspace = torch.empty(path_summary_workspace(T, N), dtype=torch.float64, device=self.device)
+        path_scan(field, pos_before, pos_after, self.width, self.height, terminated, truncated, self.carry, age=age,
+                  init_pos=init_pos, out=self.steps)
+        path_summary(*self.steps, terminated, truncated, summary=self.summary, workspace=self._workspace)
+
+    def read(self):
+        """The last account()'s summary as Python numbers (one device-to-host copy: the one sync): the entries of
+        PATH_SUMMARY (best_min +inf without a rated episode) plus spl = spl_sum / rated, success_rate = successes /
+        episodes, progress = progress_sum / rated and off_path_rate = off_sum / steps_sum, each None where its denominator
+        is 0."""
+        host = self.summary.cpu().tolist()
+        out = dict(zip(PATH_SUMMARY, host))
+        for k in ("episodes", "successes", "rated", "start_sum", "best_sum", "off_sum", "steps_sum"):
+            out[k] = int(out[k])
+        E, R, S = out["episodes"], out["rated"], out["steps_sum"]
+        out["best_min"] = int(out["best_min"]) if R else float("inf")
+        out["spl"] = out["spl_sum"] / R if R else None
+        out["success_rate"] = out["successes"] / E if E else None
+        out["progress"] = out["progress_sum"] / R if R else None
+        out["off_path_rate"] = out["off_sum"] / S if S else None
+        return out
 
 
 TWOARMY_PERIOD = 6

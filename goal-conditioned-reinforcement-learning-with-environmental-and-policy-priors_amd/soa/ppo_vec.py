@@ -99,6 +99,7 @@ class VecPPOTrainer:
         self.visits = None                    # VisitTracker, made by the first account_visits()
         self.nav_field = self.goal_dist = None  # made by the first account_distance()
         self._nav_field_at = -1               # env_steps when nav_field was last computed: one field per rollout
+        self.paths = self.path_field = None   # PathTracker and its timed field, made by the first account_paths()
         self.prior = None                     # shortest-path prior: {"coef", "decay", "updates"}, made by enable_prior()
         self.expert_moves = self.expert_dist = self.act_probs = None   # made by enable_prior() / label_expert()
         self.her_moves = self.her_dist = None # labels of the hindsight records (enable_prior(hindsight=True)) ...
@@ -563,6 +564,37 @@ class VecPPOTrainer:
                          (~ok).sum()]).cpu().tolist()
         return {"end_mean": v[1] / v[0] if v[0] else None, "end_min": v[2] if v[0] else None,
                 "mean": v[4] / v[3] if v[3] else None, "cut_off": v[5]}
+
+    # ------------------------------------------------------------------ path efficiency per episode
+    def account_paths(self, timed=False):
+        """Rate the episodes of the rollout just collected against the shortest paths (call after collect(), before
+        carry_over(), outside the rollout's graph capture; include/minigrid_nav.h, "Path efficiency"): the static-map field
+        exactly as account_distance() / label_expert() take it (reused if one of them already ran for this rollout), or with
+        timed=True TwoarmyEngine.timed_field's (the row-8 balls on their schedule, the age of a step being its clock),
+        then PathTracker.account() over the positions before and after each step, episode starts at the reset position.
+        The field is the map as it stands when the rollout ends; an episode that spans a rollout boundary keeps the start
+        distance it got from the earlier rollout's field.  A field launch and the tracker's two calls, no host
+        synchronisation."""
+        from .. import minigrid_nav as nav
+        T, timed = self.T, bool(timed)
+        if self.paths is None:
+            self.paths = nav.PathTracker(self.N, self.device, 17, 17, period=nav.TWOARMY_PERIOD if timed else 1)
+        if timed != (self.paths.period > 1):
+            raise RuntimeError("account_paths(timed=%s) after account_paths(timed=%s): one tracker, one field" % (timed, not timed))
+        if timed:
+            if self.path_field is None:
+                self.path_field = torch.empty((self.N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
+            self.engine.timed_field(agent=False, out=self.path_field)
+            field = self.path_field
+        else:
+            field = self._static_field(reuse=True)
+        self.paths.account(field, self.pos[3:3 + T], self.pos[4:4 + T], self.term, self.trunc, self.age[:-1], self.init_pos)
+
+    def path_stats(self):
+        """PathTracker.read() of the last accounted rollout."""
+        if self.paths is None:
+            raise RuntimeError("path_stats() before account_paths()")
+        return self.paths.read()
 
     # ------------------------------------------------------------------ shortest-path prior
     def enable_prior(self, coef, decay=1.0, hindsight=False, timed=False, hindsight_timed=False):

@@ -121,6 +121,15 @@ def build_parser():
                    help="once per rollout: the shortest-path distance to the goal on the static map (balls and patrols "
                         "passable) at every step, one field and one lookup launch on the device; adds `goal_dist end "
                         "mean/min` over the finished episodes and `goal_dist mean` over all steps to the log line; off by default")
+    p.add_argument("--path_stats", action="store_true",
+                   help="once per rollout: rate every episode against the shortest paths of the static map (balls and "
+                        "patrols passable), exactly and across rollout boundaries, on the device; appends `spl` (success "
+                        "weighted by path length over the episodes that ended), `progress` (the share of the start distance "
+                        "they made good) and `off_path` (the share of their steps off a shortest path) to the log line; off "
+                        "by default")
+    p.add_argument("--path_stats_timed", action="store_true",
+                   help="with --path_stats: rate against the time-expanded field instead, in which the row-8 balls follow "
+                        "their period-6 schedule: waiting for the gap is on the path, walking into a ball is not")
     p.add_argument("--prior_coef", type=float, default=0.0,
                    help="shortest-path prior: add C * (the mean of -log of the policy's mass on the optimal moves of the "
                         "static map) to the actor's loss of every minibatch; rewards, returns and the critic are untouched; "
@@ -221,6 +230,13 @@ def distance_fields(ds):
                                                                f(ds["mean"], "%.2f"))
 
 
+def path_fields(ps):
+    """Tail of the log line with --path_stats (VecPPOTrainer.path_stats())."""
+    def f(x):
+        return "-" if x is None else "%.4f" % x
+    return " spl %s progress %s off_path %s" % (f(ps["spl"]), f(ps["progress"]), f(ps["off_path_rate"]))
+
+
 def dump_bonus(bs, path, update, rank):
     os.makedirs(path, exist_ok=True)
     maps = {k: bs[k] for k in ("state", "action") if k in bs}
@@ -289,6 +305,8 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--shaping_hindsight_timed needs --shaping_scale")
     if args.shaping_hindsight_timed and args.shaping_no_hindsight:
         raise SystemExit("--shaping_hindsight_timed shapes the hindsight records: not with --shaping_no_hindsight")
+    if args.path_stats_timed and not args.path_stats:
+        raise SystemExit("--path_stats_timed needs --path_stats")
     use_orient = args.orient_prior_coef != 0.0 or args.orient_agreement
     if not (math.isfinite(args.orient_prior_coef) and args.orient_prior_coef >= 0.0):
         raise SystemExit("--orient_prior_coef must be a finite number >= 0")
@@ -384,6 +402,8 @@ def main(argv=None, predictor=False, soa=False):
             trainer.account_visits(trainer.her)
         if args.goal_distance:
             trainer.account_distance()
+        if args.path_stats:
+            trainer.account_paths(timed=args.path_stats_timed)
         if use_prior:
             trainer.label_expert()
         if use_orient:                                        # behind relabel(): its records are labelled too
@@ -428,6 +448,8 @@ def main(argv=None, predictor=False, soa=False):
             tail += shaping_fields(ss, not args.shaping_no_hindsight)
         if use_orient:                                          # behind every other field
             tail += orient_fields(ots, args.orient_prior_hindsight)
+        if args.path_stats:                                     # behind every other field
+            tail += path_fields(trainer.path_stats())
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

@@ -430,6 +430,75 @@ int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int
                       const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                       const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist, void *stream);
 
+/* ---- Path efficiency: how good a trajectory was, per episode (success weighted by path length, steps off the path).
+ *
+ * The world, the fields (dist uint16[n_envs][period][dist_pitch], period 1 = what mg_nav_field writes), the visit_cell
+ * rule, the acting-position rule (age <= 0 ? init_pos : pos) and the phase rule (the phase of a clock) are the existing ones.
+ *
+ * Per step.  d_before and d_after are the two distances mg_nav_shape reads WITHOUT MG_NAV_SHAPE_ZERO_TERMINAL: d_before is
+ * the acting state's, at the phase of age; d_after is the after cell's, in the one field at period 1 and in the field of the
+ * phase that follows the acting one otherwise ("Reward shaping", "Timed fields").  A done step is no exception: the terminal
+ * position's own distance is d_after.  A position that is no cell has distance MG_NAV_UNREACHABLE.
+ * A step is ON PATH iff d_before is reachable, d_before >= 1 and d_after == d_before - 1.  In a timed field an optimal wait
+ * is therefore on path; walking into a blocker, or being hit by one (the after state is not free: unreachable), is not.
+ *
+ * Episodes.  An episode ends with a step whose terminated | truncated is set; the next step of that env opens a new one.
+ * Per env four carries hold the running episode: start (d_before of its first step), best (the least distance it has
+ * stood at), off (its steps that were not on path) and steps (its steps so far).  steps == 0 means that no episode is
+ * running -- all-zero carries are the state after a reset -- and the other three carries are then meaningless.
+ *
+ * Everything is integer: the results do not depend on scheduling or on how a rollout is cut into launches. */
+
+/* The scan, one launch for all envs (none for T == 0), no atomics.  For every env n, for t = 0 .. T - 1 in this order:
+ *     if (steps == 0) { start = best = d_before; off = 0; }
+ *     steps += 1;   off += 1 unless the step is on path;   best = min(best, d_after);
+ *     ep_start[t][n] = start, ep_best[t][n] = best, ep_off[t][n] = off, ep_steps[t][n] = steps;
+ *     if (terminated[t][n] | truncated[t][n]) steps = 0;
+ * and the four carries are written back afterwards (start, best and off as they stand, also behind a done step).
+ * MG_NAV_UNREACHABLE is the largest uint16, so an unreachable d_after never lowers best, and an episode that starts on an
+ * unreachable state has start = MG_NAV_UNREACHABLE until it ends.  At a done step the four outputs describe the episode that
+ * ends there, wherever -- in this launch or in an earlier one -- it began.  T launches of one step each give the bits of
+ * one launch of T steps, carries included.
+ *   dist, dist_pitch, period, pos_before, pos_after, age, init_pos: exactly as mg_nav_shape takes them (age and init_pos
+ *               nullable together when period == 1, required when period > 1)
+ *   terminated, truncated  uint8[T][n_envs]
+ *   carry_start, carry_best  uint16[n_envs];  carry_off, carry_steps  int32[n_envs]: in and out
+ *   ep_start, ep_best  uint16[T][n_envs];  ep_off, ep_steps  int32[T][n_envs]: each nullable, at least one given
+ * A lane owns an env; the rows [t][.] are read and written coalesced, element by element.  Nothing outside the first
+ * T * n_envs elements of an output or outside the n_envs elements of a carry is written, and nothing outside the arrays
+ * is read for any position, NaN included.
+ * TW_E_ARG: the cases of mg_nav_shape that concern dist, dist_pitch, period, n_envs, width, height, pos_before, pos_after,
+ * age, init_pos and T; NULL terminated / truncated / carry; a uint16 array not 2-byte aligned, an int32 array not 4-byte
+ * aligned; no output given. */
+int mg_nav_path_scan(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int width, int height,
+                     const float *pos_before, const float *pos_after, const int32_t *age, const float *init_pos,
+                     const uint8_t *terminated, const uint8_t *truncated, int T, uint16_t *carry_start,
+                     uint16_t *carry_best, int32_t *carry_off, int32_t *carry_steps, uint16_t *ep_start,
+                     uint16_t *ep_best, int32_t *ep_off, int32_t *ep_steps, void *stream);
+
+/* What the episodes that ended in a rollout looked like: summary double[MG_NAV_PATH_SUMMARY] over the done steps of the
+ * scan's four outputs [T][N] (all four required).  An episode is RATED iff its start is reachable.
+ *   0  episodes                                   1  successes (terminated != 0)
+ *   2  rated episodes                             3  the sum of SPL over the rated: terminated ? start / max(steps, start) : 0
+ *   4  the sum of start over the rated            5  the sum of best over the rated
+ *   6  the sum of (start - best) / start over the rated with start >= 1
+ *   7  the sum of off over all episodes           8  the sum of steps over all episodes
+ *   9  the least best over the rated, +inf when there is none
+ * The two quotients are float64 divisions of the integers.  Deterministic in the way of ppo_episode_summary (twoarmy_ppo.h):
+ * the grid depends on (T, N) alone, a thread folds a contiguous run of the row-major (t, then n) index range in order, lanes,
+ * wavefronts and workgroups are combined in index order -- lanes as a binary tree -- each workgroup leaves one partial of
+ * MG_NAV_PATH_SUMMARY doubles in `workspace`, and one wavefront of a second kernel combines the partials in block order.
+ * Entries 0 - 2, 4, 5 and 7 - 9 are exact (integers below 2^53, a minimum); 3 and 6 are that tree of float64 additions.
+ *   workspace   double[mg_nav_path_summary_workspace(T, N)], 8-byte aligned like summary
+ * mg_nav_path_summary_workspace: host only, the number of doubles.
+ * TW_E_ARG: a NULL array; T <= 0 or N <= 0; T * N >= 2^40; ep_start or ep_best not 2-byte aligned, ep_off or ep_steps not
+ * 4-byte aligned, summary or workspace not 8-byte aligned. */
+#define MG_NAV_PATH_SUMMARY 10
+int mg_nav_path_summary_workspace(int T, int N);
+int mg_nav_path_summary(const uint16_t *ep_start, const uint16_t *ep_best, const int32_t *ep_off, const int32_t *ep_steps,
+                        const uint8_t *terminated, const uint8_t *truncated, int T, int N, double *summary,
+                        double *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,21 @@ for _ in range(3):
     a_s = timed(lambda: nav.ahead(r_field6, h_pos, 17, 17, steps=3, age=h_age, init_pos=h_tr.init_pos, out=ah_out, dist_out=ad_out))
     report("mg_nav_ahead (the rollout, steps 3, P = 6)", T * N * (8 + 4 + 8 + 2) + N * 6 * 578, a_s,
            "one launch; %.2f x mg_nav_timed_moves" % (a_s / rtm_s))
+# Path efficiency of that rollout (PathTracker.account: mg_nav_path_scan + mg_nav_path_summary) on the same two fields, next
+# to the nearest existing thing on the rollout's own flags: ppo_episode_scan + ppo_episode_summary (EpisodeTracker.account).
+h_after = h_tr.pos[4:4 + T]
+h_ep = ppo_ops.episode_scan(h_tr.reward, h_tr.term, h_tr.trunc, carry_r, carry_l)
+ep_s = timed(lambda: (ppo_ops.episode_scan(h_tr.reward, h_tr.term, h_tr.trunc, carry_r, carry_l, out=h_ep),
+                      ppo_ops.episode_summary(*h_ep, h_tr.term, h_tr.trunc, h_tr.reward, h_tr.action, A, 0.99, 0.01, ep_score,
+                                              *ep_out)))
+report("ppo_episode_scan + ppo_episode_summary (the rollout)", T * N * (4 + 1 + 1 + 8 + 4) + T * N * (4 + 1 + 1 + 4), ep_s,
+       "three launches")
+for p_field, p_name in ((r_field, "static"), (r_field6, "P = 6")):
+    p_tr = nav.PathTracker(N, dev, 17, 17, period=1 if p_field.dim() == 2 else nav.TWOARMY_PERIOD)
+    p_s = timed(lambda: p_tr.account(p_field, h_pos, h_after, h_tr.term, h_tr.trunc, h_age, h_tr.init_pos))
+    report("PathTracker.account (the rollout, %s): mg_nav_path_scan + mg_nav_path_summary" % p_name,
+           T * N * (8 + 8 + 4 + 1 + 1 + 2 + 2 + 4 + 4) + T * N * (1 + 1) + p_field.numel() * 2, p_s,
+           "three launches; %.2f x ppo_episode_scan + ppo_episode_summary" % (p_s / ep_s))
 # The records' look-ahead labels (mg_nav_goal_ahead, steps 3): the same floods, a frontier walk per record and 8-byte labels.
 ha_out = torch.empty(R, dtype=torch.int64, device=dev)
 for _ in range(3):                                             # three windows: the spread of the number below
@@ -214,7 +229,6 @@ report("mg_nav_timed_goal_moves (the same %d records, %d heads, P = 6)" % (R, n_
 # Shaping of the same records under their own goals: on the static map, and over (cell, phase).  The yardsticks of the
 # timed launch are the two rows it is made of: mg_nav_goal_shape (its staging and stores) and mg_nav_timed_goal_moves (its
 # floods), taken in the same process on the same records.
-h_after = h_tr.pos[4:4 + T]
 hs_out, hs_f = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
 hs_mask = torch.empty(R, dtype=torch.uint8, device=dev)
 hs_s = timed(lambda: h_eng.goal_shape(her, h_pos, h_after, h_age, h_tr.init_pos, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL,
