@@ -62,6 +62,20 @@ def call(name, dev, *args):
         _lib.check(getattr(_lib.lib(), name)(*args, stream(dev)), name)
 
 
+_constants = {}
+
+
+def constant(key, values, dtype, device):
+    """A small device constant made from Python numbers, once per (key, dtype, device) and kept: making it is a
+    pageable host-to-device copy, which blocks the host and cannot be captured in a graph, so no call after the first
+    makes one.  The copy is complete when the first call returns; the tensor is read-only to every user."""
+    device = torch.device(device)
+    k = (key, dtype, device)
+    if k not in _constants:
+        _constants[k] = torch.tensor(values, dtype=dtype, device=device)
+    return _constants[k]
+
+
 def query(name, *args):
     """lib.<name>(*args) of a size query: the value, or the error a negative one stands for."""
     n = getattr(_lib.lib(), name)(*args)

@@ -1626,6 +1626,7 @@ struct tw_engine {
     int parity;
     int envs_per_wave;              // 0 = auto
     int pipeline;                   // 1 = use the pipelined kernel when eligible (TW_PIPELINE=0 disables)
+    int pinned;                     // 1 = the state stays in its buffers: a pipelined launch copies back instead of swapping
     int *fb_count;                  // device counter: pipelined launches re-run by the sequential fallback
     uint32_t *pipe_tab;             // constant tables of the pipelined kernel (static image, per-lane emission constants)
     int last[8];                    // what the most recent tw_step / tw_rollout launched (tw_last_launch; enum below)
@@ -1717,6 +1718,20 @@ int launch_sequential(tw_engine *e, const Params &p, hipStream_t st) {
     return TW_OK;
 }
 
+// A captured launch is replayed with the pointers it was recorded with, so the state must stay where the capture found
+// it.  The pipelined launch writes the ping-pong partner; an engine that is not pinned swaps the two on the host (once per
+// call, not once per replay), a pinned one copies the partner back on the stream and clears its flag there.  An engine
+// pins itself for good at the first pipelined launch on a capturing stream, or with tw_set_pipeline(e, 2).  A query that
+// fails counts as capturing: the copy is right on any stream.
+bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &status) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+
 int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *draws, uint8_t *obs, int obs_pitch,
                    float *matrix, int mat_pitch, float *pos, float *reward, uint8_t *term, uint8_t *trunc, int flags,
                    hipStream_t st) {
@@ -1731,6 +1746,7 @@ int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *
                p.obs_pitch >= REC_OBS_OFF + ((((e->view * e->view * 3) + 15) >> 4) << 4);
     const bool pipe = e->pipeline && T >= PIPE_MIN_T && (flags & TW_F_AUTORESET) && params_fast(e, p, true);
     if (!pipe) return launch_sequential(e, p, st);
+    if (!e->pinned && stream_is_capturing(st)) e->pinned = 1;      // asked on launches of >= 8 steps only, never per step
     // pipelined launch: cur -> next, with the sequential kernel as a flag-gated fallback from the same input
     p.type_out = e->type2; p.colour_out = e->colour2; p.rec_out = e->rec2;
     p.abnormal = e->abnormal + e->parity;
@@ -1753,6 +1769,13 @@ int launch_rollout(tw_engine *e, int T, const int32_t *actions, const uint32_t *
     const int rc = launch_sequential(e, p, st);
     if (rc != TW_OK) return rc;
     e->last[LL_PIPELINED] = 1; e->last[LL_PG] = pg; e->last[LL_LAYOUT] = layout; e->last[LL_PIPE_GRID] = grid;
+    if (e->pinned) {                       // next -> cur on the stream; the flag is cleared here, whichever parity a replay uses
+        HIP_TRY(hipMemcpyAsync(e->type, e->type2, (size_t)e->n_envs * NC, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(e->colour, e->colour2, (size_t)e->n_envs * NC, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(e->rec, e->rec2, (size_t)e->n_envs * REC * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(p.abnormal, 0, sizeof(int), st));
+        return TW_OK;
+    }
     uint8_t *t8; int32_t *t32;
     t8 = e->type; e->type = e->type2; e->type2 = t8;
     t8 = e->colour; e->colour = e->colour2; e->colour2 = t8;
@@ -1775,6 +1798,7 @@ int tw_create(tw_engine **out, int variant, int n_envs, int view_size, int devic
     e->seed = seed; e->env_id0 = env_id0;
     const char *pl = getenv("TW_PIPELINE");
     e->pipeline = pl ? atoi(pl) : 1;
+    e->pinned = e->pipeline == 2;
     hipError_t rr[8];
     rr[0] = hipMalloc((void **)&e->type, (size_t)n_envs * NC);
     rr[1] = hipMalloc((void **)&e->colour, (size_t)n_envs * NC);
@@ -1837,6 +1861,7 @@ int tw_last_launch(const tw_engine *e, int *info) {
 int tw_set_pipeline(tw_engine *e, int enable) {
     if (!e) return TW_E_ARG;
     e->pipeline = enable ? 1 : 0;
+    if (enable == 2) e->pinned = 1;
     return TW_OK;
 }
 

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._marshal import inner, ptr, stream
+from ._marshal import constant, inner, ptr, stream
 from ._lib import (FIELDS, TW_CELLS, TW_DRAW_WORDS, TW_F_AUTORESET, TW_F_MATRIX_CODE, TW_F_POLICY_IDX, TW_F_SLAB_HIPMALLOC,
                    TW_REC_WORDS)
 
@@ -135,7 +135,17 @@ class TwoarmyEngine:
             pass
 
     def set_pipeline(self, enable):
-        _lib.check(_lib.lib().tw_set_pipeline(self._h, int(bool(enable))), "tw_set_pipeline")
+        """False: the sequential kernel only; True: the pipelined kernel where eligible; 2: the same, with the state
+        pinned (pin_state)."""
+        _lib.check(_lib.lib().tw_set_pipeline(self._h, 2 if enable == 2 else int(bool(enable))), "tw_set_pipeline")
+
+    def pin_state(self):
+        """Keep the state where it is for good (tw_set_pipeline(e, 2), include/twoarmy.h): pipelined rollouts then copy
+        the ping-pong partner back on the stream instead of swapping the buffers, so graphs that hold a launch of this
+        engine, and the views of plane_views() / agent_views(), stay valid across them.  A captured pipelined rollout
+        pins the engine by itself; pin before capturing step(), reset() or gen_obs() of an engine that also runs eager
+        pipelined rollouts."""
+        self.set_pipeline(2)
 
     def fallback_count(self):
         """Pipelined launches re-run by the sequential fallback so far (0 in normal play)."""
@@ -258,7 +268,7 @@ class TwoarmyEngine:
     @staticmethod
     def decode_matrix(codes):
         """uint8 code frames -> the float matrix of Env_transact.matrix_env (env_buffer.py:300-336)."""
-        lut = torch.tensor(MATRIX_CODE_VALUES, dtype=torch.float32, device=codes.device)
+        lut = constant("matrix_code_values", MATRIX_CODE_VALUES, torch.float32, codes.device)
         return lut[codes.long()]
 
     def _out_args(self, lead, out, flags):
@@ -288,6 +298,8 @@ class TwoarmyEngine:
         return self._launch(_lib.lib().tw_step, "tw_step", (self.num_envs,), None, actions, draws, out, flags)
 
     def rollout(self, T, out, actions=None, draws=None, autoreset=True, policy_idx=True):
+        """T steps in one launch on the current stream.  May be captured in a graph: a pipelined launch (T >= 8 with
+        auto-reset) on a capturing stream pins the state (pin_state) and copies it back on the stream from then on."""
         flags = (TW_F_AUTORESET if autoreset else 0) | (TW_F_POLICY_IDX if policy_idx else 0)
         if actions is not None:
             assert actions.shape == (T, self.num_envs)

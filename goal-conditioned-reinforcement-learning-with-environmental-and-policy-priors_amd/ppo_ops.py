@@ -4,7 +4,7 @@ import ctypes as C
 
 import torch
 
-from ._marshal import call as _call, ptr as _p, query as _query
+from ._marshal import call as _call, constant as _constant, ptr as _p, query as _query
 
 _CL = torch.channels_last
 
@@ -376,7 +376,7 @@ class _Conv1Up4(torch.autograd.Function):
 def unfold_conv1_grad(gwf):
     """Gradient w.r.t. the folded weights [py][px][ty][tx][F][O] -> gradient w.r.t. W[O][F][4][4] (transpose of
     fold_conv1_weights: row r of W feeds tap 0 of parity 0 and tap r // 2 of parity 1; columns alike)."""
-    ty = torch.tensor([[0, 0, 0, 0], [0, 0, 1, 1]], device=gwf.device)              # [py][r]
+    ty = _constant("conv1_tap_of_row", [[0, 0, 0, 0], [0, 0, 1, 1]], torch.int64, gwf.device)   # [py][r]
     out = None
     for py in (0, 1):
         for px in (0, 1):
@@ -396,7 +396,7 @@ def fold_decoder_tail(w3):
     """ConvTranspose2d(16 -> 1, k4, s2) followed by AvgPool2d(4) (Net_Decoder, all_net.py:100-137) as ONE 3x3 / stride-2 /
     pad-1 convolution: pooled cell y averages image rows 4y..4y+3, row 4y+d of the transposed conv reads input row 2y+u
     through tap row d-2u, so input row 2y-1 contributes tap rows {2,3}, row 2y all four, row 2y+1 rows {0,1}."""
-    m = torch.tensor([[0., 0., 1., 1.], [1., 1., 1., 1.], [1., 1., 0., 0.]], dtype=w3.dtype, device=w3.device)
+    m = _constant("decoder_tail_rows", [[0., 0., 1., 1.], [1., 1., 1., 1.], [1., 1., 0., 0.]], w3.dtype, w3.device)
     return torch.einsum("ur,crs,vs->cuv", m, w3[:, 0], m).mul_(1.0 / 16.0).contiguous()
 
 

@@ -120,7 +120,14 @@ int tw_set_envs_per_wave(tw_engine *e, int envs_per_wave);
 
 /* Rollouts of >= 8 steps with auto-reset, native layouts and Philox draws use the pipelined kernel
  * (one logic wave + 15 emission waves per 16 envs) with the sequential kernel as in-stream fallback;
- * enable = 0 forces the sequential kernel (also TW_PIPELINE=0). */
+ * enable = 0 forces the sequential kernel (also TW_PIPELINE=0).
+ * Where the state lives: a pipelined launch writes the state's ping-pong partner and swaps the two on the host, so the
+ * addresses of tw_state_ptrs, and those recorded in a HIP graph that holds ANY launch of this engine, change with it.
+ * enable = 2 (also TW_PIPELINE=2) PINS the engine for good: pipelined launches then copy the partner back on the stream
+ * (three device-to-device copies and a 4-byte memset behind the kernels) and the state never moves.  An engine pins
+ * itself at its first pipelined launch on a capturing stream, so a captured tw_rollout replays correctly.  Graphs that
+ * hold only tw_step / tw_reset / tw_gen_obs / shorter rollouts of an engine that also runs eager pipelined rollouts
+ * need the pin set BEFORE they are captured. */
 int tw_set_pipeline(tw_engine *e, int enable);
 
 /* Statistic: how many of this engine's pipelined launches so far left normal play (illegal action, injected / drifted
