@@ -133,6 +133,9 @@ _SIGS.update({
     "mg_nav_ahead": (C.c_int, [_vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "mg_nav_goal_ahead": (C.c_int, [_vp, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _vp,
                                     _vp, _vp]),
+    "mg_nav_timed_goal_ahead": (C.c_int, [_vp, _vp, _i, _i, _i, C.c_uint32, _i, _vp, _i64, _i, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp, _i, _i, _vp, _vp, _vp]),
+    "mg_nav_timed_goal_ahead_floods": (C.c_int, [_i, _i, _i]),
     "mg_nav_path_scan": (C.c_int, [_vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
     "mg_nav_path_summary_workspace": (C.c_int, [_i, _i]),

@@ -1189,6 +1189,62 @@ template <int... Ps> constexpr nav_timed_goal_shape_kernel_t nav_timed_goal_shap
 constexpr const nav_timed_goal_shape_kernel_t *nav_timed_goal_shape_kernels =   // [P - 1]
     nav_timed_goal_shape_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
+// ------------------------------------------------------------------ timed look-ahead labels of records with goals of their own
+// mg_nav_goal_ahead_kernel over (cell, phase): the timed goal kernel's keys, heads and floods (nav_timed_goal_floods), the
+// look-ahead kernel's label, staging and stores.  The label walks the half wavefront's P images, `cells` apart, from the
+// record's phase on.  Its staging is the move sets' plus the 8 KiB of labels, so it has a host choice of its own:
+// MG_NAV_TIMED_GOAL_AHEAD_LDS is what the images share 64 KiB with (static LDS and what aligning it may cost).
+static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + sizeof(nav_goal_ahead_stage_t) + 64 == MG_NAV_TIMED_GOAL_AHEAD_LDS,
+              "the header states the byte count of the formula");
+inline int nav_timed_goal_ahead_flooders(int HW, int P)
+{
+    int f = NAV_GOAL_HALVES;
+    while (f > 1 && (size_t)MG_NAV_TIMED_GOAL_AHEAD_LDS + (size_t)f * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)64 * 1024)
+        f >>= 1;
+    return f;
+}
+static_assert(MG_NAV_TIMED_GOAL_AHEAD_LDS + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
+              "one image of the longest period and the largest world fits next to the look-ahead staging");
+
+template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_timed_goal_ahead_kernel(
+    const uint8_t *__restrict__ type, const uint8_t *__restrict__ state, int N, int W, int H, uint32_t pass_types,
+    int doors_open, const uint32_t *__restrict__ blocked, int64_t bstride, const int32_t *__restrict__ rec_t,
+    const int32_t *__restrict__ rec_n, const float *__restrict__ rec_goal, int64_t M, const float2 *__restrict__ pos,
+    const int32_t *__restrict__ age, const float *__restrict__ init_pos, int T, int steps,
+    unsigned long long *__restrict__ ahead, uint16_t *__restrict__ acting_dist, int flooders)
+{
+    extern __shared__ __attribute__((aligned(16))) uint16_t goal_ahead_image[];   // [flooders][P][cells]
+    __shared__ nav_goal_stage_t st;
+    __shared__ nav_goal_ahead_stage_t sh;
+    __shared__ uint8_t s_phase[NAV_GOAL_SLOTS];                             // the phase of a record's clock
+    const int cells = nav_timed_cells(W * H);
+    const nav_out_span_t sa = nav_out_span(ahead, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_out_span_t sd = nav_out_span(acting_dist, M, blockIdx.x, NAV_GOAL_ELEMS);
+    const nav_goal_records_t g = nav_goal_records(M, blockIdx.x, sa, sd);
+
+    nav_goal_keys<true>(st, s_phase, g, N, W, H, P, rec_t, rec_n, rec_goal, pos, age, init_pos, T, nav_goal_no_more);
+    const int n_heads = nav_goal_heads(st, g);
+    nav_timed_goal_floods<P>(st, goal_ahead_image, n_heads, flooders, type, state, W, H, pass_types, doors_open, blocked,
+                             bstride, [&](int i, const uint16_t *img, bool ok) {
+                                 const int c = st.cell[i], ph = s_phase[i];
+                                 const int64_t p = g.p0 + i;
+                                 uint32_t d = MG_NAV_UNREACHABLE;
+                                 uint64_t a = 0;
+                                 if (ok && c != NAV_NO_CELL) a = nav_ahead_label<true>(img, cells, P, ph, c, W, H, steps, d);
+                                 if (sa.holds(p)) sh.ahead[(int)(p - sa.base)] = a;
+                                 if (sd.holds(p)) st.dist[(int)(p - sd.base)] = (uint16_t)d;
+                             });
+    __syncthreads();
+    nav_out_store(ahead, M, sa, sh.ahead, NAV_GOAL_THREADS);
+    nav_out_store(acting_dist, M, sd, st.dist, NAV_GOAL_THREADS);
+}
+
+using nav_timed_goal_ahead_kernel_t = decltype(&mg_nav_timed_goal_ahead_kernel<1>);
+template <int... Ps> constexpr nav_timed_goal_ahead_kernel_t nav_timed_goal_ahead_kernel_of[] = {
+    mg_nav_timed_goal_ahead_kernel<Ps + 1>...};
+constexpr const nav_timed_goal_ahead_kernel_t *nav_timed_goal_ahead_kernels =   // [P - 1]
+    nav_timed_goal_ahead_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
+
 // ------------------------------------------------------------------ path efficiency per episode
 // The scan of minigrid_nav.h ("Path efficiency"): ppo_episode_scan's shape, a lane per env over coalesced rows [t][n].  The
 // dependent chain is four integer operations per step; what costs is the two gathers per step from the env's field, so the
@@ -1662,6 +1718,34 @@ extern "C" int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int 
                        (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN,
                        rec_t, rec_n, rec_goal, n_records, nav_f2(pos), age, init_pos, T, steps,
                        reinterpret_cast<unsigned long long *>(ahead), acting_dist);
+    return tw_launched(__func__);
+}
+
+extern "C" int mg_nav_timed_goal_ahead_floods(int width, int height, int period)
+{
+    if (!nav_sides_ok(width, height) || !nav_period_ok(period)) return TW_E_ARG;
+    return nav_timed_goal_ahead_flooders(width * height, period);
+}
+
+extern "C" int mg_nav_timed_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                                       uint32_t pass_types, int flags, const uint32_t *blocked,
+                                       int64_t blocked_env_stride, int period, const int32_t *rec_t, const int32_t *rec_n,
+                                       const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
+                                       const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist,
+                                       void *launch_stream)
+{
+    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
+        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
+        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
+        !nav_clock_ok(age, init_pos, true) || !nav_ahead_out_ok(steps, ahead, acting_dist))
+        return TW_E_ARG;
+    if (n_records == 0) return TW_OK;
+    const int HW = width * height, flooders = nav_timed_goal_ahead_flooders(HW, period);
+    hipLaunchKernelGGL(nav_timed_goal_ahead_kernels[period - 1], nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
+                       nav_timed_bytes(flooders, HW, period), (hipStream_t)launch_stream, type, state, n_envs, width,
+                       height, pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
+                       n_records, nav_f2(pos), age, init_pos, T, steps, reinterpret_cast<unsigned long long *>(ahead),
+                       acting_dist, flooders);
     return tw_launched(__func__);
 }
 

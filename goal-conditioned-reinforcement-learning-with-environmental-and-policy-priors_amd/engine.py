@@ -486,6 +486,21 @@ class TwoarmyEngine:
         return nav.timed_goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17, self._schedule(avoid_risk, ty.device),
                                     age, init_pos, nav.PASS_DEFAULT | nav.PASS_BALL, out=out, dist_out=dist_out)
 
+    def timed_goal_ahead(self, her, pos, age, init_pos, steps=3, avoid_risk=False, out=None, dist_out=None):
+        """goal_ahead over (cell, phase): the look-ahead labels of hindsight records under their own goals with the
+        row-8 balls planned by their period-6 schedule (minigrid_nav.timed_goal_ahead, one launch, read from the engine's
+        own planes, no field in memory) -> (labels int64[R], acting_dist uint16[R]).  her, pos, age, init_pos and steps as
+        goal_ahead takes them, age and init_pos required: the age of a step is its clock.  Bit 24 off the goal means
+        "wait here".  Planes and schedule exactly as timed_goal_moves takes them -- the schedule timed_field() caches
+        (avoid_risk as there), the plane's own balls passable (PASS_BALL), v6's blocks planned as present from the reset
+        on, v4's caveat unchanged -- so a record's label is the one minigrid_nav.ahead reads from timed_field()'s fields
+        for the rollout."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        return nav.timed_goal_ahead(ty, her["t"], her["n"], her["goal"], pos, 17, 17, self._schedule(avoid_risk, ty.device),
+                                    age, init_pos, steps=steps, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, out=out,
+                                    dist_out=dist_out)
+
     def timed_goal_shape(self, her, pos_before, pos_after, age, init_pos, avoid_risk=False, scale=1.0, gamma=0.99,
                          zero_terminal=False, out=None, shaping_out=None, mask_out=None):
         """goal_shape over (cell, phase): potential-based shaping of hindsight records under their own goals with the

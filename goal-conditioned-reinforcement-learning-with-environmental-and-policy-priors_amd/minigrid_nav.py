@@ -4,7 +4,8 @@ are uint8[N, H*W] with cell (x, y) at y*W + x; goal and agent coordinates are in
 of the engine's records (TwoarmyEngine.agent_views()), read where they live.  goal_moves labels records that each name a
 goal of their own (hindsight records) without a field in memory.  timed_field / timed_moves do the same for worlds whose
 blockers move with a period (a search over (cell, phase): the expert may wait).  shape / goal_shape / timed_goal_shape turn
-the distances into a potential and shape rewards with it, float32 with pinned rounding.  path_scan / path_summary / PathTracker
+the distances into a potential and shape rewards with it, float32 with pinned rounding.  ahead / goal_ahead /
+timed_goal_ahead say where a shortest path leads in up to three steps, as a set of displacements.  path_scan / path_summary / PathTracker
 rate every episode against the field: success weighted by path length, progress, steps off a shortest path.  One launch per
 call (path_summary: two), on the tensors' device.
 No CPU fallback."""
@@ -467,6 +468,36 @@ def goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps=3, 
          R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, int(steps), ptr(out, AHEAD_DTYPE),
          ptr(dist_out, DIST_DTYPE))
     return out, dist_out
+
+
+def timed_goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blocked, age, init_pos, steps=3,
+                     pass_types=PASS_DEFAULT, state=None, doors_open=False, out=None, dist_out=None):
+    """goal_ahead for a world whose blockers move with a period (mg_nav_timed_goal_ahead, include/minigrid_nav.h): the
+    planes, the records, pos, blocked, age (the clock as well) and init_pos (both required) as timed_goal_moves takes them.
+    -> (labels int64[R], acting_dist uint16[R]): per record what ahead gives in the time-expanded field of the record's env
+    flooded from the record's goal cell, from the acting cell at the phase of its age -- the expert waits where the
+    blockers make it; 0 / UNREACHABLE for a record whose t, n, goal or acting position names nothing, whose goal cell is
+    free at no phase or whose state has no path.  out / dist_out as in goal_moves.  One launch (none for R = 0), no field
+    in memory, no host synchronisation."""
+    N, W, H, dev = _planes(type_plane, state, width, height)
+    bp, bstride, P = _schedule(blocked, N, H, dev)
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, pos)
+    _clock(age, init_pos, T, N, dev, required=True)
+    out, dist_out = _ahead_outputs((R,), dev, out, dist_out)
+    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
+        return out, dist_out
+    call("mg_nav_timed_goal_ahead", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
+         DOORS_OPEN if doors_open else 0, bp, bstride, P, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32),
+         ptr(rec_goal, torch.float32), R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, int(steps),
+         ptr(out, AHEAD_DTYPE), ptr(dist_out, DIST_DTYPE))
+    return out, dist_out
+
+
+def timed_goal_ahead_floods(width, height, period):
+    """How many of a workgroup's 8 half wavefronts flood at a time in timed_goal_ahead at this size and period (8, 4, 2 or
+    1: their images share 64 KiB of LDS with a staging larger than timed_goal_moves') -- the launch's own host function."""
+    return query("mg_nav_timed_goal_ahead_floods", int(width), int(height), int(period))
 
 
 def ahead_bits(labels):

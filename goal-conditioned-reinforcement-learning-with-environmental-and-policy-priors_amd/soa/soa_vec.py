@@ -165,7 +165,8 @@ class VecSoATrainer(VecPPOTrainer):
             self._replay.popleft()
 
     # ------------------------------------------------------------------ look-ahead prior of the orientation head
-    def enable_orientation_prior(self, coef, decay=1.0, steps=3, timed=False, hindsight=False, every_state=False):
+    def enable_orientation_prior(self, coef, decay=1.0, steps=3, timed=False, hindsight=False, every_state=False,
+                                 hindsight_timed=False):
         """Train the orientation head with the look-ahead prior: update_orientation adds coef * decay^(updates done) times
         minigrid_nav.ahead_loss -- minus the log of the mass the head's two 7-way distributions put on the displacements a
         shortest path reaches in `steps` steps -- to the NLL of every minibatch, over the labels label_ahead() makes.  The
@@ -173,6 +174,9 @@ class VecSoATrainer(VecPPOTrainer):
         labels come from the time-expanded field (TwoarmyEngine.timed_field, the age of a step being its clock).
         hindsight=True: the hindsight records of relabel() are labelled too, each under its own goal on the static map (one
         mg_nav_goal_ahead launch in label_ahead()); without it a hindsight sample has no label and no prior term.
+        hindsight_timed=True (needs hindsight=True): that one launch is mg_nav_timed_goal_ahead instead -- the records are
+        labelled over (cell, phase) with the schedule of timed=True's field, so that they wait for the balls as the rollout's
+        labels do.
         every_state=True (with coef > 0): every rollout step that is no success sample joins the sample set as a prior-only
         row under the env's goal; it carries no NLL, and the NLL mean stays over the NLL rows.  From here on the success
         FIFO remembers the label of every sample."""
@@ -181,8 +185,11 @@ class VecSoATrainer(VecPPOTrainer):
             raise ValueError("enable_orientation_prior(): coef must be a finite number >= 0, got %r" % coef)
         if not 1 <= steps <= 3:
             raise ValueError("enable_orientation_prior(): steps must be 1, 2 or 3, got %r" % steps)
+        if hindsight_timed and not hindsight:
+            raise ValueError("enable_orientation_prior(): hindsight_timed=True needs hindsight=True")
         self.orient_prior = {"coef": coef, "decay": decay, "updates": 0, "steps": steps, "timed": bool(timed),
-                             "hindsight": bool(hindsight), "every_state": bool(every_state) and coef > 0.0}
+                             "hindsight": bool(hindsight), "every_state": bool(every_state) and coef > 0.0,
+                             "hindsight_timed": bool(hindsight_timed)}
         self.expert_ahead = self.ahead_dist = self.ahead_field = None
         self.her_ahead = self.her_ahead_dist = self._her_ahead_of = None
         self._her_sample_rec = None
@@ -202,8 +209,9 @@ class VecSoATrainer(VecPPOTrainer):
         for this rollout), or with timed=True TwoarmyEngine.timed_field's, and ONE mg_nav_ahead launch over the positions
         before each step, episode starts at the reset position; `expert_ahead` int64[T, N] and `ahead_dist` uint16[T, N]
         afterwards.  With hindsight=True and records from relabel(): ONE mg_nav_goal_ahead launch more, on the engine's
-        planes as they stand and the same static map; `her_ahead` int64[R] and `her_ahead_dist` uint16[R] afterwards.  No
-        host synchronisation."""
+        planes as they stand and the same static map -- with hindsight_timed=True ONE mg_nav_timed_goal_ahead launch in its
+        place, over (cell, phase) with the age of a record's step as its clock; `her_ahead` int64[R] and `her_ahead_dist`
+        uint16[R] afterwards.  No host synchronisation."""
         from .. import minigrid_nav as nav
         op = self.orient_prior
         if op is None:
@@ -224,9 +232,13 @@ class VecSoATrainer(VecPPOTrainer):
         self._ahead_at = self.env_steps
         self.her_ahead = self.her_ahead_dist = self._her_ahead_of = None
         if op["hindsight"] and self.her is not None and self.her["t"].numel():
-            self.her_ahead, self.her_ahead_dist = self.engine.goal_ahead(
-                self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos, steps=op["steps"],
-                pass_types=nav.PASS_DEFAULT | nav.PASS_BALL)
+            if op["hindsight_timed"]:
+                self.her_ahead, self.her_ahead_dist = self.engine.timed_goal_ahead(
+                    self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos, steps=op["steps"])
+            else:
+                self.her_ahead, self.her_ahead_dist = self.engine.goal_ahead(
+                    self.her, self.pos[3:3 + T], self.age[:-1], self.init_pos, steps=op["steps"],
+                    pass_types=nav.PASS_DEFAULT | nav.PASS_BALL)
             self._her_ahead_of = self.her                     # these labels belong to these records
         return self.expert_ahead
 

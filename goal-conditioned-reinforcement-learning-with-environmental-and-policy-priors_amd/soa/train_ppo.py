@@ -34,8 +34,10 @@ C * D^update times the set-valued look-ahead prior to the NLL of every orientati
 puts on the displacements a shortest path reaches in K (default 3) steps (minigrid_nav.ahead, one launch per rollout);
 --orient_agreement only labels and reports.  Both append `orient agree` to the log line.  --orient_prior_timed takes the
 labels from the time-expanded field, --orient_prior_hindsight labels the hindsight records too, each under its own goal
-(minigrid_nav.goal_ahead, one more launch; appends `her realised`), --orient_prior_every_state adds every rollout step that
-is no success sample as a prior-only row; all off by default.
+(minigrid_nav.goal_ahead, one more launch; appends `her realised`), --orient_prior_hindsight_timed (with
+--orient_prior_hindsight) labels them by the time-expanded search (minigrid_nav.timed_goal_ahead in its place, so that with
+--orient_prior_timed both kinds of sample wait for the balls), --orient_prior_every_state adds every rollout step that is no
+success sample as a prior-only row; all off by default.
 """
 import argparse
 import math
@@ -181,6 +183,9 @@ def build_parser():
                    help="with --orient_prior_coef / --orient_agreement: label the hindsight records too, each under its "
                         "own goal on the static map (one more launch per rollout), and append `her realised` (share of "
                         "the labelled hindsight samples whose realised displacement lies in the label)")
+    p.add_argument("--orient_prior_hindsight_timed", action="store_true",
+                   help="with --orient_prior_hindsight: label the hindsight records by the time-expanded search too, each "
+                        "under its own goal (minigrid_nav.timed_goal_ahead in place of goal_ahead: still one launch)")
     p.add_argument("--orient_prior_every_state", action="store_true",
                    help="with --orient_prior_coef: every rollout step that is no success sample joins the orientation "
                         "minibatches as a prior-only row under the env's goal (no NLL)")
@@ -314,6 +319,8 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--orient_prior_* / --orient_agreement: self-orientation agent only")
     if (args.orient_prior_timed or args.orient_prior_hindsight or args.orient_prior_every_state) and not use_orient:
         raise SystemExit("--orient_prior_timed / _hindsight / _every_state need --orient_prior_coef or --orient_agreement")
+    if args.orient_prior_hindsight_timed and not args.orient_prior_hindsight:
+        raise SystemExit("--orient_prior_hindsight_timed needs --orient_prior_hindsight")
     if not 1 <= args.orient_prior_steps <= 3:
         raise SystemExit("--orient_prior_steps must be 1, 2 or 3")
     from .. import dist as twdist
@@ -384,7 +391,8 @@ def main(argv=None, predictor=False, soa=False):
     if use_orient:
         trainer.enable_orientation_prior(args.orient_prior_coef, args.orient_prior_decay, steps=args.orient_prior_steps,
                                          timed=args.orient_prior_timed, hindsight=args.orient_prior_hindsight,
-                                         every_state=args.orient_prior_every_state)
+                                         every_state=args.orient_prior_every_state,
+                                         hindsight_timed=args.orient_prior_hindsight_timed)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):

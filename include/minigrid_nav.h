@@ -430,6 +430,39 @@ int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int
                       const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                       const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist, void *stream);
 
+/* mg_nav_goal_ahead over (cell, phase): the look-ahead labels of hindsight records, each under its OWN goal, in a world whose
+ * blockers move -- the labels mg_nav_ahead gives a rollout from a timed field, so that a rollout and its hindsight records
+ * agree around the blockers.  Nothing here is new: every rule is one of the blocks above.  Per record b: let F be what
+ * mg_nav_timed_field computes for env rec_n[b] with visit_cell(rec_goal[b]) as its single source; ahead[b] and acting_dist[b]
+ * are what mg_nav_ahead gives, with that period and `steps`, for the record's acting cell in F -- age[t][n] <= 0 ? init_pos :
+ * pos[t][n], at the phase of age[t][n].  The world, the schedule, the records, the REQUIRED age and init_pos, the records that
+ * name nothing (label 0, MG_NAV_UNREACHABLE, no access outside the arrays), the independence of a record from its neighbours
+ * and their order, the one launch without atomics, the workgroup's 1024 records, its one flood per run of equal (env, goal
+ * cell) for every phase, the at most width*height*P rounds of a flood and the reads are those of mg_nav_timed_goal_moves; the
+ * outputs and the store rule are those of mg_nav_goal_ahead.
+ *   ahead uint64[n_records], 8-byte aligned;  acting_dist uint16[n_records] (nullable)
+ * Invariants: (a) for records that share one goal per env the outputs equal mg_nav_timed_field(goal_x, goal_y) followed by
+ * mg_nav_ahead with that period on the same positions; (b) with period = 1 and an all-zero schedule they equal
+ * mg_nav_goal_ahead's; (c) at steps = 1 the label is the image of mg_nav_timed_goal_moves' move set (invariant (a) of the
+ * look-ahead block), with the same acting_dist; (d) ahead[b] != 0 iff acting_dist[b] != MG_NAV_UNREACHABLE.
+ * n_records == 0 returns 0 and launches nothing.
+ * launch_stream is the `stream` of every other entry, spelt apart because its two stream checks live with its own GPU tests.
+ * TW_E_ARG: the cases of mg_nav_timed_goal_moves with ahead for moves; steps outside 1..MG_NAV_AHEAD_MAX_STEPS; ahead not
+ * 8-byte aligned. */
+int mg_nav_timed_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
+                            uint32_t pass_types, int flags, const uint32_t *blocked, int64_t blocked_env_stride,
+                            int period, const int32_t *rec_t, const int32_t *rec_n, const float *rec_goal,
+                            int64_t n_records, const float *pos, const int32_t *age, const float *init_pos, int T,
+                            int steps, uint64_t *ahead, uint16_t *acting_dist, void *launch_stream);
+
+/* Host only, no launch: how many floods a workgroup of mg_nav_timed_goal_ahead runs at a time at this size and period: by the
+ * formula of mg_nav_timed_goal_shape_floods with MG_NAV_TIMED_GOAL_AHEAD_LDS, the workgroup's staging in bytes -- the move
+ * sets' keys and heads, a phase byte per record, 8 bytes of label per record on their way out, and 64 bytes for aligning
+ * them (32 x 32 with P = 16 gives 1).
+ * TW_E_ARG: a side <= 0 or > MG_NAV_MAX_SIDE, period outside 1..MG_NAV_MAX_PERIOD. */
+#define MG_NAV_TIMED_GOAL_AHEAD_LDS 22864
+int mg_nav_timed_goal_ahead_floods(int width, int height, int period);
+
 /* ---- Path efficiency: how good a trajectory was, per episode (success weighted by path length, steps off the path).
  *
  * The world, the fields (dist uint16[n_envs][period][dist_pitch], period 1 = what mg_nav_field writes), the visit_cell

@@ -226,6 +226,13 @@ ht_s = timed(lambda: h_eng.timed_goal_moves(her, h_pos, h_age, h_tr.init_pos, ou
 report("mg_nav_timed_goal_moves (the same %d records, %d heads, P = 6)" % (R, n_heads),
        R * (4 + 4 + 8 + 8 + 4 + 1 + 2) + N * 289, ht_s,
        "one launch; %.1f floods per us, %.2f x mg_nav_goal_moves" % (n_heads / (ht_s * 1e6), ht_s / h_s))
+# The records' look-ahead labels over (cell, phase) (mg_nav_timed_goal_ahead, steps 3): the floods of the row above, the frontier
+# walk and 8-byte labels of mg_nav_goal_ahead.  Both yardsticks are taken in the same process on the same records.
+for _ in range(3):                                             # three windows: the spread of the number below
+    hta_s = timed(lambda: h_eng.timed_goal_ahead(her, h_pos, h_age, h_tr.init_pos, steps=3, out=ha_out, dist_out=hd_out))
+    report("mg_nav_timed_goal_ahead (the same %d records, %d heads, P = 6, steps 3)" % (R, n_heads),
+           R * (4 + 4 + 8 + 8 + 4 + 8 + 2) + N * 289, hta_s,
+           "one launch; %.2f x mg_nav_timed_goal_moves, %.2f x mg_nav_goal_ahead" % (hta_s / ht_s, hta_s / ha_s))
 # Shaping of the same records under their own goals: on the static map, and over (cell, phase).  The yardsticks of the
 # timed launch are the two rows it is made of: mg_nav_goal_shape (its staging and stores) and mg_nav_timed_goal_moves (its
 # floods), taken in the same process on the same records.
