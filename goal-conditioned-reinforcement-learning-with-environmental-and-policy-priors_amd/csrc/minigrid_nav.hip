@@ -57,13 +57,21 @@
  *
  * Shared: nav_image_clear, nav_dilate, nav_move_set<WAIT>, nav_ahead_expand / nav_ahead_label; nav_out_span_t / nav_out_span / nav_out_store (one output of a
  * workgroup, any element type: the goal kernel and the shaping kernels; the moves and the timed goal kernel measured slower
- * on them and keep their own); nav_goal_records, _keys, _heads, _floods; on the host one nav_*_ok per argument rule.
+ * on them and keep their own); nav_goal_records, _keys, _heads, _floods; nav_timed_goal_flooders(fixed, HW, P), the one
+ * count of flooding halves for the three timed record launches and their queries.  On the host: nav_period_kernel (the
+ * instantiation of a kernel template for a run-time period), one nav_*_ok per argument rule, and nav_record_launch_ok /
+ * nav_rollout_launch_ok for the blocks of rules that the six record entry points and the four period-taking rollout entry
+ * points share.  Each label kind on records still has a static and a timed kernel of its own: one body per kind on a
+ * two-form world description measured slower.
  *
  * Integer work only but for the shaping term (three float32 operations, each rounded once: fp contract off) and the two
  * quotient sums of the path summary (float64, combined in a fixed order), no atomics: the results do not depend on scheduling.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
+#include <utility>
 
 #include "launch.h"
 #include "minigrid_nav.h"
@@ -797,24 +805,30 @@ template <int P> __global__ __launch_bounds__(NAV_THREADS) void mg_nav_timed_fie
     }
 }
 
-using nav_timed_kernel_t = decltype(&mg_nav_timed_field_kernel<1>);
-template <int... Ps> constexpr nav_timed_kernel_t nav_timed_kernel_of[] = {mg_nav_timed_field_kernel<Ps + 1>...};
-constexpr const nav_timed_kernel_t *nav_timed_kernels =                    // [P - 1]
-    nav_timed_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
-static_assert(NAV_MAX_PERIOD == 16, "one instantiation per period");
+// kernel(std::integral_constant<int, P>) -> the instantiation of a kernel template for period P: the one of a run-time period
+template <typename F, int... Ps> auto nav_period_kernel(int period, F kernel, std::integer_sequence<int, Ps...>)
+{
+    const decltype(kernel(std::integral_constant<int, 1>{})) of[] = {kernel(std::integral_constant<int, Ps + 1>{})...};
+    return of[period - 1];
+}
+template <typename F> auto nav_period_kernel(int period, F kernel)
+{
+    return nav_period_kernel(period, kernel, std::make_integer_sequence<int, NAV_MAX_PERIOD>{});
+}
 
 // ------------------------------------------------------------------ timed move sets of records with goals of their own
 // mg_nav_goal_kernel over (cell, phase): the same staging, heads and stores; a flooding half wavefront owns an image of
-// P * cells distances in dynamic LDS, and `flooders` (8, 4, 2 or 1: nav_timed_goal_flooders) of the 8 halves flood at a time.
+// P * cells distances in dynamic LDS, and `flooders` of the 8 halves flood at a time: 8, 4, 2 or 1, as many as fit 64 KiB next
+// to the `fixed` bytes of the kernel that asks (nav_timed_goal_flooders; the shaping and the look-ahead staging are larger).
 // The phase is no part of a run's key: one flood serves the records of every phase.
-inline int nav_timed_goal_flooders(int HW, int P)
+inline int nav_timed_goal_flooders(size_t fixed, int HW, int P)   // fixed: the kernel's static LDS and what aligning it may cost
 {
-    const size_t fixed = sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + 64;    // static LDS and what aligning it may cost
     int f = NAV_GOAL_HALVES;
-    while (f > 1 && fixed + (size_t)f * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)64 * 1024) f >>= 1;
+    while (f > 1 && fixed + nav_timed_bytes(f, HW, P) > (size_t)64 * 1024) f >>= 1;
     return f;
 }
-static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + 64 + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
+constexpr size_t NAV_TIMED_GOAL_LDS = sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + 64;   // of the move sets: staging and phase bytes
+static_assert(NAV_TIMED_GOAL_LDS + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
               "one image of the longest period and the largest world fits next to the staging");
 
 // The flood loop of a timed goal kernel, written once (as nav_goal_floods is for the static ones): one head per flooding
@@ -953,11 +967,6 @@ template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_time
     __syncthreads();
     nav_goal_store(st, g, M, moves, acting_dist);
 }
-
-using nav_timed_goal_kernel_t = decltype(&mg_nav_timed_goal_kernel<1>);
-template <int... Ps> constexpr nav_timed_goal_kernel_t nav_timed_goal_kernel_of[] = {mg_nav_timed_goal_kernel<Ps + 1>...};
-constexpr const nav_timed_goal_kernel_t *nav_timed_goal_kernels =          // [P - 1]
-    nav_timed_goal_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
 // ------------------------------------------------------------------ potential-based reward shaping from the fields
 // The three float operations of minigrid_nav.h ("Reward shaping"), each rounded once: nothing here may fuse.
@@ -1138,13 +1147,6 @@ __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_goal_shape_kernel(
 // its own: MG_NAV_TIMED_GOAL_SHAPE_LDS is what the images share 64 KiB with (static LDS and what aligning it may cost).
 static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + sizeof(nav_goal_shape_stage_t) + 64 == MG_NAV_TIMED_GOAL_SHAPE_LDS,
               "the header states the byte count of the formula");
-inline int nav_timed_goal_shape_flooders(int HW, int P)
-{
-    int f = NAV_GOAL_HALVES;
-    while (f > 1 && (size_t)MG_NAV_TIMED_GOAL_SHAPE_LDS + (size_t)f * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)64 * 1024)
-        f >>= 1;
-    return f;
-}
 static_assert(MG_NAV_TIMED_GOAL_SHAPE_LDS + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
               "one image of the longest period and the largest world fits next to the shaping staging");
 
@@ -1183,12 +1185,6 @@ template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_time
     nav_out_store(mask, M, sm, sh.mask, NAV_GOAL_THREADS);
 }
 
-using nav_timed_goal_shape_kernel_t = decltype(&mg_nav_timed_goal_shape_kernel<1>);
-template <int... Ps> constexpr nav_timed_goal_shape_kernel_t nav_timed_goal_shape_kernel_of[] = {
-    mg_nav_timed_goal_shape_kernel<Ps + 1>...};
-constexpr const nav_timed_goal_shape_kernel_t *nav_timed_goal_shape_kernels =   // [P - 1]
-    nav_timed_goal_shape_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
-
 // ------------------------------------------------------------------ timed look-ahead labels of records with goals of their own
 // mg_nav_goal_ahead_kernel over (cell, phase): the timed goal kernel's keys, heads and floods (nav_timed_goal_floods), the
 // look-ahead kernel's label, staging and stores.  The label walks the half wavefront's P images, `cells` apart, from the
@@ -1196,13 +1192,6 @@ constexpr const nav_timed_goal_shape_kernel_t *nav_timed_goal_shape_kernels =   
 // MG_NAV_TIMED_GOAL_AHEAD_LDS is what the images share 64 KiB with (static LDS and what aligning it may cost).
 static_assert(sizeof(nav_goal_stage_t) + NAV_GOAL_SLOTS + sizeof(nav_goal_ahead_stage_t) + 64 == MG_NAV_TIMED_GOAL_AHEAD_LDS,
               "the header states the byte count of the formula");
-inline int nav_timed_goal_ahead_flooders(int HW, int P)
-{
-    int f = NAV_GOAL_HALVES;
-    while (f > 1 && (size_t)MG_NAV_TIMED_GOAL_AHEAD_LDS + (size_t)f * P * nav_timed_cells(HW) * sizeof(uint16_t) > (size_t)64 * 1024)
-        f >>= 1;
-    return f;
-}
 static_assert(MG_NAV_TIMED_GOAL_AHEAD_LDS + NAV_MAX_PERIOD * NAV_CELLS * sizeof(uint16_t) <= 64 * 1024,
               "one image of the longest period and the largest world fits next to the look-ahead staging");
 
@@ -1238,12 +1227,6 @@ template <int P> __global__ __launch_bounds__(NAV_GOAL_THREADS) void mg_nav_time
     nav_out_store(ahead, M, sa, sh.ahead, NAV_GOAL_THREADS);
     nav_out_store(acting_dist, M, sd, st.dist, NAV_GOAL_THREADS);
 }
-
-using nav_timed_goal_ahead_kernel_t = decltype(&mg_nav_timed_goal_ahead_kernel<1>);
-template <int... Ps> constexpr nav_timed_goal_ahead_kernel_t nav_timed_goal_ahead_kernel_of[] = {
-    mg_nav_timed_goal_ahead_kernel<Ps + 1>...};
-constexpr const nav_timed_goal_ahead_kernel_t *nav_timed_goal_ahead_kernels =   // [P - 1]
-    nav_timed_goal_ahead_kernel_of<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;
 
 // ------------------------------------------------------------------ path efficiency per episode
 // The scan of minigrid_nav.h ("Path efficiency"): ppo_episode_scan's shape, a lane per env over coalesced rows [t][n].  The
@@ -1462,6 +1445,32 @@ bool nav_clock_ok(const int32_t *age, const float *init_pos, bool required)
     return (required ? age && init_pos : !age || init_pos) && nav_aligned(age, 4) && nav_aligned(init_pos, 4);
 }
 
+// A record launch: the world (flags against the mask the entry point admits), the schedule where the launch is timed, the
+// records, the rollout's position arrays (pos_after = pos where there is one) and the clock -- required where timed.
+bool nav_record_launch_ok(const uint8_t *type, int n_envs, int W, int H, uint32_t pass_types, int flags, int allowed, bool timed,
+                          const uint32_t *blocked, int64_t blocked_env_stride, int period, const int32_t *rec_t,
+                          const int32_t *rec_n, const float *rec_goal, int64_t n_records, const float *pos,
+                          const float *pos_after, const int32_t *age, const float *init_pos, int T)
+{
+    return nav_world_ok(type, n_envs, W, H, pass_types, flags, allowed) &&
+           (!timed || nav_schedule_ok(blocked, blocked_env_stride, period, H)) &&
+           nav_records_ok(rec_t, rec_n, rec_goal, n_records) && nav_rollout_ok(pos, T) && nav_rollout_ok(pos_after, T) &&
+           nav_clock_ok(age, init_pos, timed);
+}
+// A rollout launch on fields of a period: the fields, the period, the position arrays (pos_after = pos where there is one),
+// the clock and the element count.
+bool nav_rollout_launch_ok(const uint16_t *dist, int64_t dist_pitch, int period, int n_envs, int W, int H, const float *pos,
+                           const float *pos_after, const int32_t *age, const float *init_pos, bool clock_required, int T)
+{
+    return nav_field_ok(dist, dist_pitch, n_envs, W, H, true) && nav_period_ok(period) && nav_rollout_ok(pos, T) &&
+           nav_rollout_ok(pos_after, T) && nav_clock_ok(age, init_pos, clock_required) && nav_count_ok((int64_t)T * n_envs);
+}
+// the mg_nav_timed_goal*_floods queries: the launch's own count next to its `fixed` bytes
+int nav_floods_query(size_t fixed, int W, int H, int period)
+{
+    return nav_sides_ok(W, H) && nav_period_ok(period) ? nav_timed_goal_flooders(fixed, W * H, period) : TW_E_ARG;
+}
+
 bool nav_moves_out_ok(const uint8_t *moves, const uint16_t *acting_dist) { return moves && nav_aligned(acting_dist, 2); }
 bool nav_ahead_out_ok(int steps, const uint64_t *ahead, const uint16_t *acting_dist)
 {
@@ -1545,9 +1554,9 @@ extern "C" int mg_nav_goal_moves(const uint8_t *type, const uint8_t *state, int 
                                  const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                                  const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream)
 {
-    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
-        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
-        !nav_clock_ok(age, init_pos, false) || !nav_moves_out_ok(moves, acting_dist))
+    if (!nav_record_launch_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN, false, nullptr, 0, 1, rec_t,
+                              rec_n, rec_goal, n_records, pos, pos, age, init_pos, T) ||
+        !nav_moves_out_ok(moves, acting_dist))
         return TW_E_ARG;
     if (n_records == 0) return TW_OK;
     hipLaunchKernelGGL(mg_nav_goal_kernel, nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS), 0,
@@ -1569,8 +1578,8 @@ extern "C" int mg_nav_timed_field(const uint8_t *type, const uint8_t *state, int
         !nav_agents_ok(goal_x, goal_y, goal_stride, agent_x, agent_y, agent_stride, agent_dist || agent_action || agent_clock))
         return TW_E_ARG;
     const int HW = width * height, envs = nav_timed_envs(HW, period);
-    hipLaunchKernelGGL(nav_timed_kernels[period - 1], dim3((n_envs + envs - 1) / envs), dim3(32 * envs),
-                       nav_timed_bytes(envs, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
+    hipLaunchKernelGGL(nav_period_kernel(period, [](auto p) { return &mg_nav_timed_field_kernel<decltype(p)::value>; }),
+                       dim3((n_envs + envs - 1) / envs), dim3(32 * envs), nav_timed_bytes(envs, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
                        pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, goal_x, goal_y, goal_stride,
                        agent_x, agent_y, agent_clock, agent_stride, dist, nav_pitch(dist_pitch, width, height), agent_dist,
                        agent_action, error);
@@ -1582,8 +1591,8 @@ extern "C" int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int 
                                   uint16_t *acting_dist, void *stream)
 {
     const int64_t M = (int64_t)T * n_envs;
-    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) || !nav_rollout_ok(pos, T) ||
-        !nav_clock_ok(age, init_pos, true) || !nav_moves_out_ok(moves, acting_dist) || !nav_count_ok(M))
+    if (!nav_rollout_launch_ok(dist, dist_pitch, period, n_envs, width, height, pos, pos, age, init_pos, true, T) ||
+        !nav_moves_out_ok(moves, acting_dist))
         return TW_E_ARG;
     if (M == 0) return TW_OK;
     hipLaunchKernelGGL(mg_nav_moves_kernel<true>, nav_grid(M, NAV_MOVES_ELEMS), dim3(NAV_MOVES_THREADS), 0,
@@ -1594,8 +1603,7 @@ extern "C" int mg_nav_timed_moves(const uint16_t *dist, int64_t dist_pitch, int 
 
 extern "C" int mg_nav_timed_goal_floods(int width, int height, int period)
 {
-    if (!nav_sides_ok(width, height) || !nav_period_ok(period)) return TW_E_ARG;
-    return nav_timed_goal_flooders(width * height, period);
+    return nav_floods_query(NAV_TIMED_GOAL_LDS, width, height, period);
 }
 
 extern "C" int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
@@ -1604,14 +1612,13 @@ extern "C" int mg_nav_timed_goal_moves(const uint8_t *type, const uint8_t *state
                                        const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                                        const float *init_pos, int T, uint8_t *moves, uint16_t *acting_dist, void *stream)
 {
-    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
-        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
-        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
-        !nav_clock_ok(age, init_pos, true) || !nav_moves_out_ok(moves, acting_dist))
+    if (!nav_record_launch_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN, true, blocked,
+                              blocked_env_stride, period, rec_t, rec_n, rec_goal, n_records, pos, pos, age, init_pos, T) ||
+        !nav_moves_out_ok(moves, acting_dist))
         return TW_E_ARG;
     if (n_records == 0) return TW_OK;
-    const int HW = width * height, flooders = nav_timed_goal_flooders(HW, period);
-    hipLaunchKernelGGL(nav_timed_goal_kernels[period - 1], nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
+    const int HW = width * height, flooders = nav_timed_goal_flooders(NAV_TIMED_GOAL_LDS, HW, period);
+    hipLaunchKernelGGL(nav_period_kernel(period, [](auto p) { return &mg_nav_timed_goal_kernel<decltype(p)::value>; }), nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
                        nav_timed_bytes(flooders, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
                        pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
                        n_records, nav_f2(pos), age, init_pos, T, moves, acting_dist, flooders);
@@ -1624,10 +1631,10 @@ extern "C" int mg_nav_shape(const uint16_t *dist, int64_t dist_pitch, int period
                             float *reward_out, float *shaping, uint8_t *mask, void *stream)
 {
     const int64_t M = (int64_t)T * n_envs;
-    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) ||
-        !nav_rollout_ok(pos_before, T) || !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, period > 1) ||
+    if (!nav_rollout_launch_ok(dist, dist_pitch, period, n_envs, width, height, pos_before, pos_after, age, init_pos,
+                               period > 1, T) ||
         !nav_flags_ok(flags, MG_NAV_SHAPE_ZERO_TERMINAL) ||     // no MG_NAV_DOORS_OPEN: the doors are the field's business
-        !nav_shaping_ok(reward, done, flags, scale, gamma, reward_out, shaping, mask) || !nav_count_ok(M))
+        !nav_shaping_ok(reward, done, flags, scale, gamma, reward_out, shaping, mask))
         return TW_E_ARG;
     if (M == 0) return TW_OK;
     hipLaunchKernelGGL(period > 1 ? mg_nav_shape_kernel<true> : mg_nav_shape_kernel<false>, nav_grid(M, NAV_MOVES_ELEMS),
@@ -1644,9 +1651,8 @@ extern "C" int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int 
                                  const float *init_pos, int T, float scale, float gamma, float *reward_out, float *shaping,
                                  uint8_t *mask, void *stream)
 {
-    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL) ||
-        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos_before, T) ||
-        !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, false) ||
+    if (!nav_record_launch_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL,
+                              false, nullptr, 0, 1, rec_t, rec_n, rec_goal, n_records, pos_before, pos_after, age, init_pos, T) ||
         !nav_shaping_ok(rec_reward, rec_done, flags, scale, gamma, reward_out, shaping, mask))
         return TW_E_ARG;
     if (n_records == 0) return TW_OK;
@@ -1659,8 +1665,7 @@ extern "C" int mg_nav_goal_shape(const uint8_t *type, const uint8_t *state, int 
 
 extern "C" int mg_nav_timed_goal_shape_floods(int width, int height, int period)
 {
-    if (!nav_sides_ok(width, height) || !nav_period_ok(period)) return TW_E_ARG;
-    return nav_timed_goal_shape_flooders(width * height, period);
+    return nav_floods_query(MG_NAV_TIMED_GOAL_SHAPE_LDS, width, height, period);
 }
 
 extern "C" int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
@@ -1671,15 +1676,14 @@ extern "C" int mg_nav_timed_goal_shape(const uint8_t *type, const uint8_t *state
                                        const int32_t *age, const float *init_pos, int T, float scale, float gamma,
                                        float *reward_out, float *shaping, uint8_t *mask, void *stream)
 {
-    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL) ||
-        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
-        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos_before, T) ||
-        !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, true) ||
+    if (!nav_record_launch_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN | MG_NAV_SHAPE_ZERO_TERMINAL,
+                              true, blocked, blocked_env_stride, period, rec_t, rec_n, rec_goal, n_records, pos_before,
+                              pos_after, age, init_pos, T) ||
         !nav_shaping_ok(rec_reward, rec_done, flags, scale, gamma, reward_out, shaping, mask))
         return TW_E_ARG;
     if (n_records == 0) return TW_OK;
-    const int HW = width * height, flooders = nav_timed_goal_shape_flooders(HW, period);
-    hipLaunchKernelGGL(nav_timed_goal_shape_kernels[period - 1], nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
+    const int HW = width * height, flooders = nav_timed_goal_flooders(MG_NAV_TIMED_GOAL_SHAPE_LDS, HW, period);
+    hipLaunchKernelGGL(nav_period_kernel(period, [](auto p) { return &mg_nav_timed_goal_shape_kernel<decltype(p)::value>; }), nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
                        nav_timed_bytes(flooders, HW, period), (hipStream_t)stream, type, state, n_envs, width, height,
                        pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
                        nav_ends(rec_done, flags), rec_reward, n_records, nav_f2(pos_before), nav_f2(pos_after), age,
@@ -1692,8 +1696,8 @@ extern "C" int mg_nav_ahead(const uint16_t *dist, int64_t dist_pitch, int period
                             uint16_t *acting_dist, void *stream)
 {
     const int64_t M = (int64_t)T * n_envs;
-    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) || !nav_rollout_ok(pos, T) ||
-        !nav_clock_ok(age, init_pos, period > 1) || !nav_ahead_out_ok(steps, ahead, acting_dist) || !nav_count_ok(M))
+    if (!nav_rollout_launch_ok(dist, dist_pitch, period, n_envs, width, height, pos, pos, age, init_pos, period > 1, T) ||
+        !nav_ahead_out_ok(steps, ahead, acting_dist))
         return TW_E_ARG;
     if (M == 0) return TW_OK;
     hipLaunchKernelGGL(period > 1 ? mg_nav_ahead_kernel<true> : mg_nav_ahead_kernel<false>, nav_grid(M, NAV_MOVES_ELEMS),
@@ -1709,9 +1713,9 @@ extern "C" int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int 
                                  const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist,
                                  void *stream)
 {
-    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
-        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
-        !nav_clock_ok(age, init_pos, false) || !nav_ahead_out_ok(steps, ahead, acting_dist))
+    if (!nav_record_launch_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN, false, nullptr, 0, 1, rec_t,
+                              rec_n, rec_goal, n_records, pos, pos, age, init_pos, T) ||
+        !nav_ahead_out_ok(steps, ahead, acting_dist))
         return TW_E_ARG;
     if (n_records == 0) return TW_OK;
     hipLaunchKernelGGL(mg_nav_goal_ahead_kernel, nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS), 0,
@@ -1723,8 +1727,7 @@ extern "C" int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int 
 
 extern "C" int mg_nav_timed_goal_ahead_floods(int width, int height, int period)
 {
-    if (!nav_sides_ok(width, height) || !nav_period_ok(period)) return TW_E_ARG;
-    return nav_timed_goal_ahead_flooders(width * height, period);
+    return nav_floods_query(MG_NAV_TIMED_GOAL_AHEAD_LDS, width, height, period);
 }
 
 extern "C" int mg_nav_timed_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
@@ -1732,20 +1735,19 @@ extern "C" int mg_nav_timed_goal_ahead(const uint8_t *type, const uint8_t *state
                                        int64_t blocked_env_stride, int period, const int32_t *rec_t, const int32_t *rec_n,
                                        const float *rec_goal, int64_t n_records, const float *pos, const int32_t *age,
                                        const float *init_pos, int T, int steps, uint64_t *ahead, uint16_t *acting_dist,
-                                       void *launch_stream)
+                                       void *stream)
 {
-    if (!nav_world_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN) ||
-        !nav_schedule_ok(blocked, blocked_env_stride, period, height) ||
-        !nav_records_ok(rec_t, rec_n, rec_goal, n_records) || !nav_rollout_ok(pos, T) ||
-        !nav_clock_ok(age, init_pos, true) || !nav_ahead_out_ok(steps, ahead, acting_dist))
+    if (!nav_record_launch_ok(type, n_envs, width, height, pass_types, flags, MG_NAV_DOORS_OPEN, true, blocked,
+                              blocked_env_stride, period, rec_t, rec_n, rec_goal, n_records, pos, pos, age, init_pos, T) ||
+        !nav_ahead_out_ok(steps, ahead, acting_dist))
         return TW_E_ARG;
     if (n_records == 0) return TW_OK;
-    const int HW = width * height, flooders = nav_timed_goal_ahead_flooders(HW, period);
-    hipLaunchKernelGGL(nav_timed_goal_ahead_kernels[period - 1], nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS),
-                       nav_timed_bytes(flooders, HW, period), (hipStream_t)launch_stream, type, state, n_envs, width,
-                       height, pass_types, flags & MG_NAV_DOORS_OPEN, blocked, blocked_env_stride, rec_t, rec_n, rec_goal,
-                       n_records, nav_f2(pos), age, init_pos, T, steps, reinterpret_cast<unsigned long long *>(ahead),
-                       acting_dist, flooders);
+    const int HW = width * height, flooders = nav_timed_goal_flooders(MG_NAV_TIMED_GOAL_AHEAD_LDS, HW, period);
+    hipLaunchKernelGGL(nav_period_kernel(period, [](auto p) { return &mg_nav_timed_goal_ahead_kernel<decltype(p)::value>; }),
+                       nav_grid(n_records, NAV_GOAL_ELEMS), dim3(NAV_GOAL_THREADS), nav_timed_bytes(flooders, HW, period),
+                       (hipStream_t)stream, type, state, n_envs, width, height, pass_types, flags & MG_NAV_DOORS_OPEN, blocked,
+                       blocked_env_stride, rec_t, rec_n, rec_goal, n_records, nav_f2(pos), age, init_pos, T, steps,
+                       reinterpret_cast<unsigned long long *>(ahead), acting_dist, flooders);
     return tw_launched(__func__);
 }
 
@@ -1756,10 +1758,10 @@ extern "C" int mg_nav_path_scan(const uint16_t *dist, int64_t dist_pitch, int pe
                                 uint16_t *ep_best, int32_t *ep_off, int32_t *ep_steps, void *stream)
 {
     const int64_t M = (int64_t)T * n_envs;
-    if (!nav_field_ok(dist, dist_pitch, n_envs, width, height, true) || !nav_period_ok(period) ||
-        !nav_rollout_ok(pos_before, T) || !nav_rollout_ok(pos_after, T) || !nav_clock_ok(age, init_pos, period > 1) ||
+    if (!nav_rollout_launch_ok(dist, dist_pitch, period, n_envs, width, height, pos_before, pos_after, age, init_pos,
+                               period > 1, T) ||
         !nav_flags_given(terminated, truncated) || !nav_path_arrays_ok(carry_start, carry_best, carry_off, carry_steps, true) ||
-        !nav_path_arrays_ok(ep_start, ep_best, ep_off, ep_steps, false) || !nav_count_ok(M))
+        !nav_path_arrays_ok(ep_start, ep_best, ep_off, ep_steps, false))
         return TW_E_ARG;
     if (M == 0) return TW_OK;
     hipLaunchKernelGGL(period > 1 ? mg_nav_path_scan_kernel<true> : mg_nav_path_scan_kernel<false>,

@@ -431,28 +431,33 @@ class TwoarmyEngine:
             self._schedules[key] = nav.twoarmy_schedule(avoid_risk, blocks=self.variant == 6, device=device)
         return self._schedules[key]
 
+    def _her_args(self, her, pass_types=None, timed=False, avoid_risk=False):
+        """What the *_goal_* methods hand minigrid_nav -> (nav, (type plane, t, n, goal), keywords): the engine's own plane
+        and the records' columns; pass_types (None: PASS_DEFAULT), or for the timed ones PASS_BALL on top and the cached
+        schedule as `blocked`."""
+        from . import minigrid_nav as nav
+        ty = self._views()[0]
+        kw = {"pass_types": nav.PASS_DEFAULT if pass_types is None else pass_types}
+        if timed:
+            kw = {"pass_types": nav.PASS_DEFAULT | nav.PASS_BALL, "blocked": self._schedule(avoid_risk, ty.device)}
+        return nav, (ty, her["t"], her["n"], her["goal"]), kw
+
     def goal_moves(self, her, pos, age=None, init_pos=None, pass_types=None, out=None, dist_out=None):
         """Optimal-move sets of hindsight records under their own goals in the engine's worlds as they stand
         (minigrid_nav.goal_moves, one launch, read from the engine's own planes) -> (moves uint8[R], acting_dist
         uint16[R]).  her: the records of ppo_ops.her_relabel (its "t", "n" and "goal"); pos float32[T, N, 2] BEFORE each
         step, age int32[T, N] and init_pos float32[2] as minigrid_nav.optimal_moves takes them; pass_types as in
         distance_field."""
-        from . import minigrid_nav as nav
-        ty = self._views()[0]
-        return nav.goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17,
-                              nav.PASS_DEFAULT if pass_types is None else pass_types, age=age, init_pos=init_pos, out=out,
-                              dist_out=dist_out)
+        nav, rec, kw = self._her_args(her, pass_types)
+        return nav.goal_moves(*rec, pos, 17, 17, age=age, init_pos=init_pos, out=out, dist_out=dist_out, **kw)
 
     def goal_ahead(self, her, pos, age=None, init_pos=None, steps=3, pass_types=None, out=None, dist_out=None):
         """Look-ahead labels of hindsight records under their own goals in the engine's worlds as they stand
         (minigrid_nav.goal_ahead, one launch, read from the engine's own planes) -> (labels int64[R], acting_dist
         uint16[R]): where a shortest path to the record's goal stands `steps` steps after the record's acting state.
         her, pos, age, init_pos and pass_types as goal_moves takes them."""
-        from . import minigrid_nav as nav
-        ty = self._views()[0]
-        return nav.goal_ahead(ty, her["t"], her["n"], her["goal"], pos, 17, 17, steps=steps,
-                              pass_types=nav.PASS_DEFAULT if pass_types is None else pass_types, age=age,
-                              init_pos=init_pos, out=out, dist_out=dist_out)
+        nav, rec, kw = self._her_args(her, pass_types)
+        return nav.goal_ahead(*rec, pos, 17, 17, steps=steps, age=age, init_pos=init_pos, out=out, dist_out=dist_out, **kw)
 
     def goal_shape(self, her, pos_before, pos_after, age=None, init_pos=None, pass_types=None, scale=1.0, gamma=0.99,
                    zero_terminal=False, out=None, shaping_out=None, mask_out=None):
@@ -461,12 +466,10 @@ class TwoarmyEngine:
         mask uint8[R]).  her: the records of ppo_ops.her_relabel (its "t", "n", "goal", "reward" and "done"); pos_before /
         pos_after float32[T, N, 2], age int32[T, N] and init_pos float32[2] as minigrid_nav.shape takes them; pass_types
         as in distance_field; out=her["reward"] shapes the records in place."""
-        from . import minigrid_nav as nav
-        ty = self._views()[0]
-        return nav.goal_shape(ty, her["t"], her["n"], her["goal"], pos_before, pos_after, 17, 17, reward=her["reward"],
-                              done=her["done"], pass_types=nav.PASS_DEFAULT if pass_types is None else pass_types, age=age,
+        nav, rec, kw = self._her_args(her, pass_types)
+        return nav.goal_shape(*rec, pos_before, pos_after, 17, 17, reward=her["reward"], done=her["done"], age=age,
                               init_pos=init_pos, scale=scale, gamma=gamma, zero_terminal=zero_terminal, out=out,
-                              shaping_out=shaping_out, mask_out=mask_out)
+                              shaping_out=shaping_out, mask_out=mask_out, **kw)
 
     def timed_goal_moves(self, her, pos, age, init_pos, avoid_risk=False, out=None, dist_out=None):
         """goal_moves over (cell, phase): the optimal-move sets of hindsight records under their own goals with the
@@ -481,10 +484,8 @@ class TwoarmyEngine:
         acts before the blocks have dropped, towards a goal it reached before they dropped, do not see them; every other
         record's path leaves the corner and meets the blocks in place.  v4: the caveat of timed_field() holds unchanged
         (blocks as they stand, patrols not scheduled)."""
-        from . import minigrid_nav as nav
-        ty = self._views()[0]
-        return nav.timed_goal_moves(ty, her["t"], her["n"], her["goal"], pos, 17, 17, self._schedule(avoid_risk, ty.device),
-                                    age, init_pos, nav.PASS_DEFAULT | nav.PASS_BALL, out=out, dist_out=dist_out)
+        nav, rec, kw = self._her_args(her, timed=True, avoid_risk=avoid_risk)
+        return nav.timed_goal_moves(*rec, pos, 17, 17, age=age, init_pos=init_pos, out=out, dist_out=dist_out, **kw)
 
     def timed_goal_ahead(self, her, pos, age, init_pos, steps=3, avoid_risk=False, out=None, dist_out=None):
         """goal_ahead over (cell, phase): the look-ahead labels of hindsight records under their own goals with the
@@ -495,11 +496,9 @@ class TwoarmyEngine:
         (avoid_risk as there), the plane's own balls passable (PASS_BALL), v6's blocks planned as present from the reset
         on, v4's caveat unchanged -- so a record's label is the one minigrid_nav.ahead reads from timed_field()'s fields
         for the rollout."""
-        from . import minigrid_nav as nav
-        ty = self._views()[0]
-        return nav.timed_goal_ahead(ty, her["t"], her["n"], her["goal"], pos, 17, 17, self._schedule(avoid_risk, ty.device),
-                                    age, init_pos, steps=steps, pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, out=out,
-                                    dist_out=dist_out)
+        nav, rec, kw = self._her_args(her, timed=True, avoid_risk=avoid_risk)
+        return nav.timed_goal_ahead(*rec, pos, 17, 17, age=age, init_pos=init_pos, steps=steps, out=out, dist_out=dist_out,
+                                    **kw)
 
     def timed_goal_shape(self, her, pos_before, pos_after, age, init_pos, avoid_risk=False, scale=1.0, gamma=0.99,
                          zero_terminal=False, out=None, shaping_out=None, mask_out=None):
@@ -511,12 +510,10 @@ class TwoarmyEngine:
         them -- the schedule timed_field() caches (avoid_risk as there), the plane's own balls passable (PASS_BALL), v6's
         blocks planned as present from the reset on, v4's caveat unchanged -- so a record's potential is the one
         shape() reads from timed_field()'s fields for the rollout."""
-        from . import minigrid_nav as nav
-        ty = self._views()[0]
-        return nav.timed_goal_shape(ty, her["t"], her["n"], her["goal"], pos_before, pos_after, 17, 17,
-                                    self._schedule(avoid_risk, ty.device), age, init_pos, reward=her["reward"],
-                                    done=her["done"], pass_types=nav.PASS_DEFAULT | nav.PASS_BALL, scale=scale, gamma=gamma,
-                                    zero_terminal=zero_terminal, out=out, shaping_out=shaping_out, mask_out=mask_out)
+        nav, rec, kw = self._her_args(her, timed=True, avoid_risk=avoid_risk)
+        return nav.timed_goal_shape(*rec, pos_before, pos_after, 17, 17, age=age, init_pos=init_pos, reward=her["reward"],
+                                    done=her["done"], scale=scale, gamma=gamma, zero_terminal=zero_terminal, out=out,
+                                    shaping_out=shaping_out, mask_out=mask_out, **kw)
 
     def time_rollout(self, T, out, actions=None, autoreset=True, iters=10):
         """Mean kernel time (ms) of one tw_rollout launch, HIP events on the current stream."""

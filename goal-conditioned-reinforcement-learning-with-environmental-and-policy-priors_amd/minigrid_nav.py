@@ -64,10 +64,11 @@ def _clock(age, init_pos, T, N, dev, required=False):
         assert age.shape == (T, N) and age.device == dev and init_pos.shape == (2,) and init_pos.device == dev
 
 
-def _moves_outputs(shape, dev, out, dist_out):
-    """(out, dist_out) of a moves launch: None = a new tensor, dist_out False = no distances (None is returned)."""
+def _moves_outputs(shape, dev, dtype, out, dist_out):
+    """(out, dist_out) of a launch that labels with `dtype` (move sets uint8, look-ahead labels AHEAD_DTYPE): None = a new
+    tensor, dist_out False = no distances (None is returned)."""
     if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        out = torch.empty(shape, dtype=dtype, device=dev)
     assert out.shape == shape and out.device == dev
     if dist_out is None:
         dist_out = torch.empty(shape, dtype=DIST_DTYPE, device=dev)
@@ -85,6 +86,82 @@ def _timed_rows(dist, W, H):
     dpitch = dist.stride(1) if P > 1 else (dist.stride(0) if N > 1 else W * H)
     assert dpitch >= W * H and (N == 1 or dist.stride(0) == P * dpitch), "expected rows of one pitch, P per env"
     return ctypes.c_void_p(dist.data_ptr()), int(dpitch), N, P
+
+
+def _field_rows(field, W, H):
+    """(pointer, pitch in elements, N, P) of a static field uint16[N, H*W] or a timed one uint16[N, P, H*W]."""
+    if field.dim() == 3:
+        return _timed_rows(field, W, H)
+    dp, dpitch, N, row = rows(field, DIST_DTYPE)
+    assert row == W * H
+    return dp, dpitch, N, 1
+
+
+def _launch(name, dev, count, outs, args):
+    """lib.<name>(*args()) over `count` elements or records -> outs.  count = 0: empty tensors have no address to hand over,
+    and there is nothing to launch, so args() is not even formed."""
+    if count:
+        call(name, dev, *args())
+    return outs
+
+
+def _record_args(type_plane, state, width, height, pass_types, flags, blocked, rec_t, rec_n, rec_goal, pos, age, init_pos):
+    """What every record call marshals: the planes, the schedule (blocked None: the static map, the clock optional; else the
+    age is the clock and required), the records, one or two position tensors `pos` and the clock.
+    -> (head, tail, (N, W, H, R, T, P, dev)): head() = the C arguments up to rec_goal, tail() = those from the record count
+    to T; a call is head(), what the kind adds of a record, tail(), then scalars and outputs."""
+    N, W, H, dev = _planes(type_plane, state, width, height)
+    sched, P = (), 1
+    if blocked is not None:
+        sched = _schedule(blocked, N, H, dev)
+        P = sched[2]
+    R = _records(rec_t, rec_n, rec_goal, dev)
+    T = _positions(N, dev, *pos)
+    _clock(age, init_pos, T, N, dev, required=blocked is not None)
+
+    def head():
+        return (ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types), flags, *sched,
+                ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32))
+
+    def tail():
+        return (R, *(ptr(q) for q in pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T)
+    return head, tail, (N, W, H, R, T, P, dev)
+
+
+def _record_moves(name, blocked, type_plane, rec_t, rec_n, rec_goal, pos, width, height, pass_types, age, init_pos, state,
+                  doors_open, out, dist_out):
+    """goal_moves / timed_goal_moves."""
+    head, tail, (N, W, H, R, T, P, dev) = _record_args(type_plane, state, width, height, pass_types,
+                                                       DOORS_OPEN if doors_open else 0, blocked, rec_t, rec_n, rec_goal,
+                                                       (pos,), age, init_pos)
+    out, dist_out = _moves_outputs((R,), dev, torch.uint8, out, dist_out)
+    return _launch(name, dev, R, (out, dist_out),
+                   lambda: (*head(), *tail(), ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE)))
+
+
+def _record_ahead(name, blocked, type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps, pass_types, age, init_pos,
+                  state, doors_open, out, dist_out):
+    """goal_ahead / timed_goal_ahead."""
+    head, tail, (N, W, H, R, T, P, dev) = _record_args(type_plane, state, width, height, pass_types,
+                                                       DOORS_OPEN if doors_open else 0, blocked, rec_t, rec_n, rec_goal,
+                                                       (pos,), age, init_pos)
+    out, dist_out = _moves_outputs((R,), dev, AHEAD_DTYPE, out, dist_out)
+    return _launch(name, dev, R, (out, dist_out),
+                   lambda: (*head(), *tail(), int(steps), ptr(out, AHEAD_DTYPE), ptr(dist_out, DIST_DTYPE)))
+
+
+def _record_shape(name, blocked, type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width, height, reward, done,
+                  pass_types, age, init_pos, state, doors_open, scale, gamma, zero_terminal, out, shaping_out, mask_out):
+    """goal_shape / timed_goal_shape."""
+    flags = (DOORS_OPEN if doors_open else 0) | (SHAPE_ZERO_TERMINAL if zero_terminal else 0)
+    head, tail, (N, W, H, R, T, P, dev) = _record_args(type_plane, state, width, height, pass_types, flags, blocked, rec_t,
+                                                       rec_n, rec_goal, (pos_before, pos_after), age, init_pos)
+    assert not zero_terminal or done is not None, "zero_terminal needs done"
+    assert done is None or (done.shape == (R,) and done.device == dev)
+    outs = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)
+    return _launch(name, dev, R, outs,
+                   lambda: (*head(), ptr(done, torch.uint8), ptr(reward, torch.float32), *tail(), float(scale), float(gamma),
+                            ptr(outs[0], torch.float32), ptr(outs[1], torch.float32), ptr(outs[2], torch.uint8)))
 
 
 def distance_field(type_plane, state_plane, width, height, pass_types=PASS_DEFAULT, goal=None, agent=None, out=None,
@@ -161,7 +238,7 @@ def optimal_moves(dist, pos, width, height, age=None, init_pos=None, out=None, d
     dev = dist.device
     T = _positions(N, dev, pos)
     _clock(age, init_pos, T, N, dev)
-    out, dist_out = _moves_outputs((T, N), dev, out, dist_out)
+    out, dist_out = _moves_outputs((T, N), dev, torch.uint8, out, dist_out)
     call("mg_nav_optimal_moves", dev, dp, dpitch, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
          ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
     return out, dist_out
@@ -176,18 +253,8 @@ def goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, pass_type
     gives in the field of the record's env flooded from the record's goal cell; 0 / UNREACHABLE for a record whose t,
     n, goal or acting position names nothing.  out / dist_out: tensors to write into; dist_out=False: no distances
     (None is returned for them).  One launch (none for R = 0), no host synchronisation."""
-    N, W, H, dev = _planes(type_plane, state, width, height)
-    R = _records(rec_t, rec_n, rec_goal, dev)
-    T = _positions(N, dev, pos)
-    _clock(age, init_pos, T, N, dev)
-    out, dist_out = _moves_outputs((R,), dev, out, dist_out)
-    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, dist_out
-    call("mg_nav_goal_moves", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
-         DOORS_OPEN if doors_open else 0, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32),
-         R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, ptr(out, torch.uint8),
-         ptr(dist_out, DIST_DTYPE))
-    return out, dist_out
+    return _record_moves("mg_nav_goal_moves", None, type_plane, rec_t, rec_n, rec_goal, pos, width, height, pass_types, age,
+                         init_pos, state, doors_open, out, dist_out)
 
 
 def _schedule(blocked, N, H, dev):
@@ -249,12 +316,10 @@ def timed_moves(dist, pos, width, height, age, init_pos, out=None, dist_out=None
     dev = dist.device
     T = _positions(N, dev, pos)
     _clock(age, init_pos, T, N, dev, required=True)
-    out, dist_out = _moves_outputs((T, N), dev, out, dist_out)
-    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, dist_out
-    call("mg_nav_timed_moves", dev, dp, dpitch, P, N, W, H, ptr(pos), ptr(age, torch.int32),
-         ptr(init_pos, torch.float32), T, ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
-    return out, dist_out
+    out, dist_out = _moves_outputs((T, N), dev, torch.uint8, out, dist_out)
+    return _launch("mg_nav_timed_moves", dev, T, (out, dist_out),
+                   lambda: (dp, dpitch, P, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
+                            ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE)))
 
 
 def timed_goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blocked, age, init_pos,
@@ -268,19 +333,8 @@ def timed_goal_moves(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blo
     the goal, or waiting is optimal; 0 / UNREACHABLE for a record whose t, n, goal or acting position names nothing,
     whose goal cell is free at no phase or whose state has no path.  out / dist_out as in goal_moves.  One launch (none
     for R = 0), no field in memory, no host synchronisation."""
-    N, W, H, dev = _planes(type_plane, state, width, height)
-    bp, bstride, P = _schedule(blocked, N, H, dev)
-    R = _records(rec_t, rec_n, rec_goal, dev)
-    T = _positions(N, dev, pos)
-    _clock(age, init_pos, T, N, dev, required=True)
-    out, dist_out = _moves_outputs((R,), dev, out, dist_out)
-    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, dist_out
-    call("mg_nav_timed_goal_moves", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
-         DOORS_OPEN if doors_open else 0, bp, bstride, P, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32),
-         ptr(rec_goal, torch.float32), R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
-         ptr(out, torch.uint8), ptr(dist_out, DIST_DTYPE))
-    return out, dist_out
+    return _record_moves("mg_nav_timed_goal_moves", blocked, type_plane, rec_t, rec_n, rec_goal, pos, width, height,
+                         pass_types, age, init_pos, state, doors_open, out, dist_out)
 
 
 def timed_goal_floods(width, height, period):
@@ -317,26 +371,19 @@ def shape(dist, pos_before, pos_after, width, height, reward=None, age=None, ini
     F = 0 and the reward passes through bit for bit.  out / shaping_out / mask_out: tensors to write into (out=reward
     shapes in place), False: not wanted (None is returned for it); out needs a reward.  One launch (none for T = 0)."""
     W, H = int(width), int(height)
-    if dist.dim() == 3:
-        dp, dpitch, N, P = _timed_rows(dist, W, H)
-    else:
-        dp, dpitch, N, row = rows(dist, DIST_DTYPE)
-        P = 1
-        assert row == W * H
+    dp, dpitch, N, P = _field_rows(dist, W, H)
     dev = dist.device
     T = _positions(N, dev, pos_before, pos_after)
     _clock(age, init_pos, T, N, dev)
     assert age is not None or P == 1, "the age is the clock: age and init_pos are required with a timed field"
     assert not zero_terminal or done is not None, "zero_terminal needs done"
     assert done is None or (done.shape == (T, N) and done.device == dev)
-    out, shaping_out, mask_out = _shape_outputs((T, N), dev, reward, out, shaping_out, mask_out)
-    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, shaping_out, mask_out
-    call("mg_nav_shape", dev, dp, int(dpitch), P, N, W, H, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
-         ptr(init_pos, torch.float32), ptr(done, torch.uint8), ptr(reward, torch.float32), T, float(scale), float(gamma),
-         SHAPE_ZERO_TERMINAL if zero_terminal else 0, ptr(out, torch.float32), ptr(shaping_out, torch.float32),
-         ptr(mask_out, torch.uint8))
-    return out, shaping_out, mask_out
+    outs = _shape_outputs((T, N), dev, reward, out, shaping_out, mask_out)
+    return _launch("mg_nav_shape", dev, T, outs,
+                   lambda: (dp, int(dpitch), P, N, W, H, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
+                            ptr(init_pos, torch.float32), ptr(done, torch.uint8), ptr(reward, torch.float32), T, float(scale),
+                            float(gamma), SHAPE_ZERO_TERMINAL if zero_terminal else 0, ptr(outs[0], torch.float32),
+                            ptr(outs[1], torch.float32), ptr(outs[2], torch.uint8)))
 
 
 def goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width, height, reward=None, done=None,
@@ -349,22 +396,9 @@ def goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width,
     gives in the field of the record's env flooded from the record's goal cell; mask 0 (F = 0, the reward passed through)
     for a record whose t, n, goal or either position names nothing or has no path.  out / shaping_out / mask_out as in
     shape.  One launch (none for R = 0), no field in memory, no host synchronisation."""
-    N, W, H, dev = _planes(type_plane, state, width, height)
-    R = _records(rec_t, rec_n, rec_goal, dev)
-    T = _positions(N, dev, pos_before, pos_after)
-    _clock(age, init_pos, T, N, dev)
-    assert not zero_terminal or done is not None, "zero_terminal needs done"
-    assert done is None or (done.shape == (R,) and done.device == dev)
-    out, shaping_out, mask_out = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)
-    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, shaping_out, mask_out
-    flags = (DOORS_OPEN if doors_open else 0) | (SHAPE_ZERO_TERMINAL if zero_terminal else 0)
-    call("mg_nav_goal_shape", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types), flags,
-         ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32), ptr(done, torch.uint8),
-         ptr(reward, torch.float32), R, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
-         ptr(init_pos, torch.float32), T, float(scale), float(gamma), ptr(out, torch.float32),
-         ptr(shaping_out, torch.float32), ptr(mask_out, torch.uint8))
-    return out, shaping_out, mask_out
+    return _record_shape("mg_nav_goal_shape", None, type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width, height,
+                         reward, done, pass_types, age, init_pos, state, doors_open, scale, gamma, zero_terminal, out,
+                         shaping_out, mask_out)
 
 
 def timed_goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width, height, blocked, age, init_pos,
@@ -379,23 +413,9 @@ def timed_goal_shape(type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, 
     through) for a record whose t, n, goal or either position names nothing, whose goal cell is free at no phase, or
     whose acting or after state is not free at its phase or has no path.  One launch (none for R = 0), no field in memory,
     no host synchronisation."""
-    N, W, H, dev = _planes(type_plane, state, width, height)
-    bp, bstride, P = _schedule(blocked, N, H, dev)
-    R = _records(rec_t, rec_n, rec_goal, dev)
-    T = _positions(N, dev, pos_before, pos_after)
-    _clock(age, init_pos, T, N, dev, required=True)
-    assert not zero_terminal or done is not None, "zero_terminal needs done"
-    assert done is None or (done.shape == (R,) and done.device == dev)
-    out, shaping_out, mask_out = _shape_outputs((R,), dev, reward, out, shaping_out, mask_out)
-    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, shaping_out, mask_out
-    flags = (DOORS_OPEN if doors_open else 0) | (SHAPE_ZERO_TERMINAL if zero_terminal else 0)
-    call("mg_nav_timed_goal_shape", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
-         flags, bp, bstride, P, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32),
-         ptr(done, torch.uint8), ptr(reward, torch.float32), R, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
-         ptr(init_pos, torch.float32), T, float(scale), float(gamma), ptr(out, torch.float32),
-         ptr(shaping_out, torch.float32), ptr(mask_out, torch.uint8))
-    return out, shaping_out, mask_out
+    return _record_shape("mg_nav_timed_goal_shape", blocked, type_plane, rec_t, rec_n, rec_goal, pos_before, pos_after, width,
+                         height, reward, done, pass_types, age, init_pos, state, doors_open, scale, gamma, zero_terminal, out,
+                         shaping_out, mask_out)
 
 
 def timed_goal_shape_floods(width, height, period):
@@ -409,19 +429,6 @@ AHEAD_MAX_STEPS = 3
 AHEAD_DTYPE = torch.int64             # a uint64 label; bits 49..63 are 0, so the sign bit never is set
 
 
-def _ahead_outputs(shape, dev, out, dist_out):
-    """(out, dist_out) of a look-ahead launch, as _moves_outputs makes them, the labels int64."""
-    if out is None:
-        out = torch.empty(shape, dtype=AHEAD_DTYPE, device=dev)
-    assert out.shape == shape and out.device == dev
-    if dist_out is None:
-        dist_out = torch.empty(shape, dtype=DIST_DTYPE, device=dev)
-    elif dist_out is False:
-        dist_out = None
-    assert dist_out is None or (dist_out.shape == shape and dist_out.device == dev)
-    return out, dist_out
-
-
 def ahead(field, pos, width, height, steps=3, age=None, init_pos=None, out=None, dist_out=None):
     """Where a shortest path leads in `steps` (1..3) steps from every acting state of a rollout (mg_nav_ahead,
     include/minigrid_nav.h, "Look-ahead").  field uint16[N, H*W] as distance_field returns it or uint16[N, P, H*W] as
@@ -431,22 +438,15 @@ def ahead(field, pos, width, height, steps=3, age=None, init_pos=None, out=None,
     path stands at displacement (dy, dx) after `steps` steps (at the goal it stays); 0 on an unreachable state or outside
     the world.  out / dist_out as in optimal_moves.  One launch (none for T = 0)."""
     W, H = int(width), int(height)
-    if field.dim() == 3:
-        dp, dpitch, N, P = _timed_rows(field, W, H)
-    else:
-        dp, dpitch, N, row = rows(field, DIST_DTYPE)
-        P = 1
-        assert row == W * H
+    dp, dpitch, N, P = _field_rows(field, W, H)
     dev = field.device
     T = _positions(N, dev, pos)
     _clock(age, init_pos, T, N, dev)
     assert age is not None or P == 1, "the age is the clock: age and init_pos are required with a timed field"
-    out, dist_out = _ahead_outputs((T, N), dev, out, dist_out)
-    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, dist_out
-    call("mg_nav_ahead", dev, dp, int(dpitch), P, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
-         int(steps), ptr(out, AHEAD_DTYPE), ptr(dist_out, DIST_DTYPE))
-    return out, dist_out
+    out, dist_out = _moves_outputs((T, N), dev, AHEAD_DTYPE, out, dist_out)
+    return _launch("mg_nav_ahead", dev, T, (out, dist_out),
+                   lambda: (dp, int(dpitch), P, N, W, H, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T,
+                            int(steps), ptr(out, AHEAD_DTYPE), ptr(dist_out, DIST_DTYPE)))
 
 
 def goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps=3, pass_types=PASS_DEFAULT, age=None,
@@ -456,18 +456,8 @@ def goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps=3, 
     ahead gives in the field of the record's env flooded from the record's goal cell; 0 / UNREACHABLE for a record whose
     t, n, goal or acting position names nothing.  out / dist_out as in goal_moves.  One launch (none for R = 0), no field
     in memory, no host synchronisation."""
-    N, W, H, dev = _planes(type_plane, state, width, height)
-    R = _records(rec_t, rec_n, rec_goal, dev)
-    T = _positions(N, dev, pos)
-    _clock(age, init_pos, T, N, dev)
-    out, dist_out = _ahead_outputs((R,), dev, out, dist_out)
-    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, dist_out
-    call("mg_nav_goal_ahead", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
-         DOORS_OPEN if doors_open else 0, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32), ptr(rec_goal, torch.float32),
-         R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, int(steps), ptr(out, AHEAD_DTYPE),
-         ptr(dist_out, DIST_DTYPE))
-    return out, dist_out
+    return _record_ahead("mg_nav_goal_ahead", None, type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps, pass_types,
+                         age, init_pos, state, doors_open, out, dist_out)
 
 
 def timed_goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blocked, age, init_pos, steps=3,
@@ -479,19 +469,8 @@ def timed_goal_ahead(type_plane, rec_t, rec_n, rec_goal, pos, width, height, blo
     blockers make it; 0 / UNREACHABLE for a record whose t, n, goal or acting position names nothing, whose goal cell is
     free at no phase or whose state has no path.  out / dist_out as in goal_moves.  One launch (none for R = 0), no field
     in memory, no host synchronisation."""
-    N, W, H, dev = _planes(type_plane, state, width, height)
-    bp, bstride, P = _schedule(blocked, N, H, dev)
-    R = _records(rec_t, rec_n, rec_goal, dev)
-    T = _positions(N, dev, pos)
-    _clock(age, init_pos, T, N, dev, required=True)
-    out, dist_out = _ahead_outputs((R,), dev, out, dist_out)
-    if R == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return out, dist_out
-    call("mg_nav_timed_goal_ahead", dev, ptr(type_plane, torch.uint8), ptr(state, torch.uint8), N, W, H, int(pass_types),
-         DOORS_OPEN if doors_open else 0, bp, bstride, P, ptr(rec_t, torch.int32), ptr(rec_n, torch.int32),
-         ptr(rec_goal, torch.float32), R, ptr(pos), ptr(age, torch.int32), ptr(init_pos, torch.float32), T, int(steps),
-         ptr(out, AHEAD_DTYPE), ptr(dist_out, DIST_DTYPE))
-    return out, dist_out
+    return _record_ahead("mg_nav_timed_goal_ahead", blocked, type_plane, rec_t, rec_n, rec_goal, pos, width, height, steps,
+                         pass_types, age, init_pos, state, doors_open, out, dist_out)
 
 
 def timed_goal_ahead_floods(width, height, period):
@@ -540,15 +519,6 @@ def _u16_zeros(shape, dev):
     return torch.zeros(shape, dtype=torch.int16, device=dev).view(DIST_DTYPE)
 
 
-def _field_rows(field, W, H):
-    """(pointer, pitch in elements, N, P) of a static field uint16[N, H*W] or a timed one uint16[N, P, H*W]."""
-    if field.dim() == 3:
-        return _timed_rows(field, W, H)
-    dp, dpitch, N, row = rows(field, DIST_DTYPE)
-    assert row == W * H
-    return dp, dpitch, N, 1
-
-
 def path_scan(field, pos_before, pos_after, width, height, terminated, truncated, carry, age=None, init_pos=None, out=None):
     """Path efficiency per episode, one step after the other (mg_nav_path_scan, include/minigrid_nav.h, "Path
     efficiency").  field uint16[N, H*W] as distance_field returns it or uint16[N, P, H*W] as timed_field does (rows may be
@@ -574,12 +544,10 @@ def path_scan(field, pos_before, pos_after, width, height, terminated, truncated
         assert o is None or (o.shape == (T, N) and o.device == dev and o.dtype == dt)
         outs.append(o)
     assert any(o is not None for o in outs), "no output wanted"
-    if T == 0:                            # empty tensors have no address to hand over, and there is nothing to launch
-        return tuple(outs)
-    call("mg_nav_path_scan", dev, dp, int(dpitch), P, N, W, H, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
-         ptr(init_pos, torch.float32), ptr(terminated, torch.uint8), ptr(truncated, torch.uint8), T,
-         *(ptr(c) for c in carry), *(ptr(o) for o in outs))
-    return tuple(outs)
+    return _launch("mg_nav_path_scan", dev, T, tuple(outs),
+                   lambda: (dp, int(dpitch), P, N, W, H, ptr(pos_before), ptr(pos_after), ptr(age, torch.int32),
+                            ptr(init_pos, torch.float32), ptr(terminated, torch.uint8), ptr(truncated, torch.uint8), T,
+                            *(ptr(c) for c in carry), *(ptr(o) for o in outs)))
 
 
 def path_summary_workspace(T, N):

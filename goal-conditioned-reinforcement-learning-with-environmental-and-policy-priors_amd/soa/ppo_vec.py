@@ -99,7 +99,9 @@ class VecPPOTrainer:
         self.visits = None                    # VisitTracker, made by the first account_visits()
         self.nav_field = self.goal_dist = None  # made by the first account_distance()
         self._nav_field_at = -1               # env_steps when nav_field was last computed: one field per rollout
-        self.paths = self.path_field = None   # PathTracker and its timed field, made by the first account_paths()
+        self.timed_field = None               # uint16[N, 6, 289], made by the first _timed_field(): one for every feature
+        self._timed_field_at = -1             # env_steps when timed_field was last computed
+        self.paths = None                     # PathTracker, made by the first account_paths()
         self.prior = None                     # shortest-path prior: {"coef", "decay", "updates"}, made by enable_prior()
         self.expert_moves = self.expert_dist = self.act_probs = None   # made by enable_prior() / label_expert()
         self.her_moves = self.her_dist = None # labels of the hindsight records (enable_prior(hindsight=True)) ...
@@ -550,6 +552,19 @@ class VecPPOTrainer:
             self._nav_field_at = self.env_steps
         return self.nav_field
 
+    def _timed_field(self, reuse):
+        """`timed_field` <- TwoarmyEngine.timed_field's six phases per env (the row-8 balls on their schedule, the engine's
+        planes as they stand), one buffer and one launch per rollout for every feature that reads it; reuse: keep the one
+        already computed for this rollout -- a pure function of the planes and the cached schedule, neither of which
+        changes between collect() and carry_over()."""
+        from .. import minigrid_nav as nav
+        if self.timed_field is None:
+            self.timed_field = torch.empty((self.N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
+        if not (reuse and self._timed_field_at == self.env_steps):
+            self.engine.timed_field(agent=False, out=self.timed_field)
+            self._timed_field_at = self.env_steps
+        return self.timed_field
+
     def distance_stats(self):
         """{"end_mean", "end_min": over the done steps of the last accounted rollout, "mean": over all its steps,
         "cut_off": steps whose cell is unreachable in the field (left out of the three)}; None where nothing counts.
@@ -581,13 +596,7 @@ class VecPPOTrainer:
             self.paths = nav.PathTracker(self.N, self.device, 17, 17, period=nav.TWOARMY_PERIOD if timed else 1)
         if timed != (self.paths.period > 1):
             raise RuntimeError("account_paths(timed=%s) after account_paths(timed=%s): one tracker, one field" % (timed, not timed))
-        if timed:
-            if self.path_field is None:
-                self.path_field = torch.empty((self.N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
-            self.engine.timed_field(agent=False, out=self.path_field)
-            field = self.path_field
-        else:
-            field = self._static_field(reuse=True)
+        field = self._timed_field(reuse=True) if timed else self._static_field(reuse=True)
         self.paths.account(field, self.pos[3:3 + T], self.pos[4:4 + T], self.term, self.trunc, self.age[:-1], self.init_pos)
 
     def path_stats(self):
@@ -618,7 +627,6 @@ class VecPPOTrainer:
             raise ValueError("the shortest-path prior needs the plain PPO agent's act_batch")
         self.prior = {"coef": float(coef), "decay": float(decay), "updates": 0, "hindsight": bool(hindsight),
                       "timed": bool(timed), "hindsight_timed": bool(hindsight_timed)}
-        self.timed_field = None               # uint16[N, 6, 289], made by the first label_expert() with timed=True
         self.her_moves = self.her_dist = self._her_moves_of = None
         self.act_probs = torch.zeros((self.T, self.N, 5), dtype=torch.float32, device=self.device)
         self._moves_at = -1
@@ -649,10 +657,7 @@ class VecPPOTrainer:
             self.expert_moves = torch.empty((T, N), dtype=torch.uint8, device=self.device)
             self.expert_dist = torch.empty((T, N), dtype=nav.DIST_DTYPE, device=self.device)
         if timed:                             # the same two launches: a field of six phases, labels by the age as clock
-            if self.timed_field is None:
-                self.timed_field = torch.empty((N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
-            self.engine.timed_field(agent=False, out=self.timed_field)
-            nav.timed_moves(self.timed_field, self.pos[3:3 + T], 17, 17, self.age[:-1], self.init_pos,
+            nav.timed_moves(self._timed_field(reuse=True), self.pos[3:3 + T], 17, 17, self.age[:-1], self.init_pos,
                             out=self.expert_moves, dist_out=self.expert_dist)
         else:
             self._static_field(reuse=True)
@@ -726,7 +731,6 @@ class VecPPOTrainer:
             self.reward_train = torch.zeros_like(self.reward)
         self.shape_f = torch.zeros((self.T, self.N), dtype=torch.float32, device=self.device)
         self.shape_mask = torch.zeros((self.T, self.N), dtype=torch.uint8, device=self.device)
-        self.shape_field = None               # uint16[N, 6, 289], made by the first shape_potential() with timed=True
         self.her_shape_f = self.her_shape_mask = self._her_shape_of = None
         self._shaped_at = -1
         return self.shaping
@@ -757,13 +761,7 @@ class VecPPOTrainer:
         before, after = self.pos[3:3 + T], self.pos[4:4 + T]
         zero_terminal = bool(self.agent.use_done_mask)
         done = (self.term | self.trunc).contiguous() if zero_terminal else None
-        if sh["timed"]:
-            if self.shape_field is None:
-                self.shape_field = torch.empty((self.N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
-            self.engine.timed_field(agent=False, out=self.shape_field)
-            field = self.shape_field
-        else:
-            field = self._static_field(reuse=True)
+        field = self._timed_field(reuse=True) if sh["timed"] else self._static_field(reuse=True)
         nav.shape(field, before, after, 17, 17, reward=self.reward_train, age=self.age[:-1], init_pos=self.init_pos,
                   done=done, scale=sh["scale"], gamma=self.agent.gamma, zero_terminal=zero_terminal, out=self.reward_train,
                   shaping_out=self.shape_f, mask_out=self.shape_mask)

@@ -190,7 +190,7 @@ class VecSoATrainer(VecPPOTrainer):
         self.orient_prior = {"coef": coef, "decay": decay, "updates": 0, "steps": steps, "timed": bool(timed),
                              "hindsight": bool(hindsight), "every_state": bool(every_state) and coef > 0.0,
                              "hindsight_timed": bool(hindsight_timed)}
-        self.expert_ahead = self.ahead_dist = self.ahead_field = None
+        self.expert_ahead = self.ahead_dist = None
         self.her_ahead = self.her_ahead_dist = self._her_ahead_of = None
         self._her_sample_rec = None
         self._ahead_at = -1
@@ -221,10 +221,7 @@ class VecSoATrainer(VecPPOTrainer):
             self.expert_ahead = torch.empty((T, N), dtype=nav.AHEAD_DTYPE, device=self.device)
             self.ahead_dist = torch.empty((T, N), dtype=nav.DIST_DTYPE, device=self.device)
         if op["timed"]:
-            if self.ahead_field is None:
-                self.ahead_field = torch.empty((N, nav.TWOARMY_PERIOD, 289), dtype=nav.DIST_DTYPE, device=self.device)
-            self.engine.timed_field(agent=False, out=self.ahead_field)
-            field = self.ahead_field
+            field = self._timed_field(reuse=True)
         else:
             field = self._static_field(reuse=True)
         nav.ahead(field, self.pos[3:3 + T], 17, 17, steps=op["steps"], age=self.age[:-1], init_pos=self.init_pos,

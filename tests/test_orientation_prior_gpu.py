@@ -74,6 +74,11 @@ def test_labels_and_statistics_against_the_reference(timed):
             from twoarmy_amd import minigrid_nav as nav
             blocked = nav.twoarmy_schedule(blocks=True).numpy().view(np.uint32)
             dist = timed_nav_ref.fields(ty, None, 17, 17, blocked, 6, PASS)[0]
+            # the trainer's one timed field: label_ahead() reads the buffer every timed feature shares
+            fields = [v for v in vars(tr).values()
+                      if torch.is_tensor(v) and v.dtype == torch.uint16 and tuple(v.shape) == (N, 6, 289)]
+            assert len(fields) == 1 and fields[0] is tr.timed_field and tr._timed_field_at == tr.env_steps
+            assert np.array_equal(tr.timed_field.cpu().numpy().view(np.uint16), dist)
         else:
             dist = nav_ref.fields(ty, None, 17, 17, PASS)[0]
         want = ahead_ref.ahead(dist, pos, 17, 17, 3, age, init)

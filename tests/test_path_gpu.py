@@ -342,8 +342,8 @@ def test_trainer_accounts_paths_across_rollouts(timed):
         tr.collect()
         assert tr.paths is None or u == 1
         tr.account_paths(timed=timed)
-        field = host(tr.path_field if timed else tr.nav_field)
-        assert field.shape == ((N, 6, 289) if timed else (N, 289)) and (tr.path_field is None) == (not timed)
+        field = host(tr.timed_field if timed else tr.nav_field)
+        assert field.shape == ((N, 6, 289) if timed else (N, 289)) and (tr.timed_field is None) == (not timed)
         ty = eng.get_state()[0].reshape(N, 289)                           # the field is the map as the rollout left it
         if timed:
             sched = nav().twoarmy_schedule(blocks=True).numpy().astype(np.int64)
@@ -371,6 +371,56 @@ def test_trainer_accounts_paths_across_rollouts(timed):
         tr.account_paths(timed=not timed)
     assert seen >= 2 * N
     eng.close()
+
+
+def test_one_timed_field_serves_the_prior_the_shaping_and_the_paths(monkeypatch):
+    """enable_prior(timed=True), enable_shaping(timed=True) and account_paths(timed=True) on one trainer: after one rollout
+    every consumer's outputs are bit for bit those of a trainer with that feature alone (same seed, same uniforms), the
+    trainer holds exactly one uint16[N, 6, 289] buffer, and the front end's launches show one mg_nav_timed_field for the
+    rollout."""
+    N, T = 8, 16
+    names = []
+    real = nav().call
+    monkeypatch.setattr(nav(), "call", lambda name, *args: (names.append(name), real(name, *args))[1])
+    uni = torch.rand(T, N, generator=torch.Generator().manual_seed(40)).to(DEV)
+
+    def run(prior, shaping, paths):
+        tr, eng = _trainer(N, T, max_steps=11)
+        if prior:
+            tr.enable_prior(0.5, timed=True)
+        if shaping:
+            tr.enable_shaping(0.05, hindsight=False, timed=True)
+        del names[:]
+        tr.collect(uniforms=uni)
+        tr.shape_rewards()
+        if prior:
+            tr.label_expert()
+        if shaping:
+            tr.shape_potential()
+        if paths:
+            tr.account_paths(timed=True)
+        torch.cuda.synchronize()
+        eng.close()
+        return tr, names.count("mg_nav_timed_field")
+
+    (both, n_all), (prior, n_p), (shaped, n_s), (paths, n_a) = run(1, 1, 1), run(1, 0, 0), run(0, 1, 0), run(0, 0, 1)
+    assert (n_all, n_p, n_s, n_a) == (1, 1, 1, 1)
+    for other in (prior, shaped, paths):
+        for k in ("pos", "age", "reward", "term", "trunc"):
+            assert np.array_equal(host(getattr(both, k)), host(getattr(other, k))), k
+    for k in ("expert_moves", "expert_dist"):
+        assert np.array_equal(host(getattr(both, k)), host(getattr(prior, k))), k
+    for k in ("shape_f", "shape_mask", "reward_train"):
+        assert np.array_equal(host(getattr(both, k)).view(np.uint8), host(getattr(shaped, k)).view(np.uint8)), k
+    assert host(both.shape_mask).any() and host(both.expert_moves).any()
+    assert np.array_equal(host(both.paths.summary).view(np.uint64), host(paths.paths.summary).view(np.uint64))
+    assert all(np.array_equal(host(a), host(b)) for a, b in zip(both.paths.steps, paths.paths.steps))
+    assert host(both.paths.summary)[0] > 0
+    fields = [v for v in vars(both).values()
+              if torch.is_tensor(v) and v.dtype == torch.uint16 and tuple(v.shape) == (N, 6, 289)]
+    assert len(fields) == 1 and fields[0] is both.timed_field
+    for other in (prior, shaped, paths):
+        assert np.array_equal(host(both.timed_field), host(other.timed_field))
 
 
 def test_an_env_driven_by_the_timed_expert_reaches_spl_one():
@@ -420,8 +470,8 @@ def test_train_ppo_path_stats_appends_fields_and_leaves_the_update_alone(capsys,
     strip = lambda ln: re.sub(r"rollout \S+ \(\S+ env-steps/s/rank\) update \S+ ", "", ln)              # noqa: E731
     assert strip(lines[1]).startswith(strip(lines[0])) and strip(lines[2]).startswith(strip(lines[0]))
     plain, static, timed = runs
-    assert plain.paths is None and plain.path_field is None and plain.nav_field is None            # no launch, no tensor
-    assert static.paths.period == 1 and static.path_field is None and timed.paths.period == 6
+    assert plain.paths is None and plain.timed_field is None and plain.nav_field is None            # no launch, no tensor
+    assert static.paths.period == 1 and static.timed_field is None and timed.paths.period == 6
     for other in (static, timed):                                         # the update itself: every parameter bit for bit
         for net in ("actor", "critic"):
             for p, q in zip(getattr(plain.agent, net).parameters(), getattr(other.agent, net).parameters()):
