@@ -1036,6 +1036,9 @@ __global__ __launch_bounds__(256) void ppo_lstm_cell_kernel(const float4 *__rest
 // ------------------------------------------------------------------ host: argument rules, grids, dispatch
 template <typename... P> bool all_set(const P *...p) { return (... && (p != nullptr)); }
 template <typename... P> bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15u) == 0; }     // NULL counts as aligned
+// every pointer on the alignment of its own element type (float / int32: 4 bytes, double / int64: 8); NULL counts as aligned
+template <typename... P> bool aligned_natural(const P *...p) { return (... && ((uintptr_t)p % alignof(P) == 0)); }
+bool ep_count_ok(int64_t M) { return M < ((int64_t)1 << 40); }      // T * N of the episode entries: a thread's run stays an int
 int blocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
 int blocks_capped(int64_t n, int per, int cap) { return (int)((n + per - 1) / per < cap ? (n + per - 1) / per : cap); }
 int ep_summary_blocks(int64_t M) { return blocks_capped(M, EP_BLOCK_ELEMS, EP_MAX_BLOCKS); }
@@ -1198,14 +1201,16 @@ int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int3
 
 int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
                      double *carry_return, int32_t *carry_length, double *ep_return, int32_t *ep_length, void *stream) {
-    if (!all_set(reward, terminated, truncated, carry_return, carry_length) || T <= 0 || N <= 0) return TW_E_ARG;
+    if (!all_set(reward, terminated, truncated, carry_return, carry_length) || T <= 0 || N <= 0 ||
+        !ep_count_ok((int64_t)T * N) || !aligned_natural(reward, carry_return, carry_length, ep_return, ep_length))
+        return TW_E_ARG;
     hipLaunchKernelGGL(ppo_episode_scan_kernel, dim3(blocks(N, 64)), dim3(64), 0, (hipStream_t)stream, reward, terminated,
                        truncated, T, N, carry_return, carry_length, ep_return, ep_length);
     return tw_launched(__func__);
 }
 
 int ppo_episode_summary_workspace(int T, int N) {
-    if (T <= 0 || N <= 0) return TW_E_ARG;
+    if (T <= 0 || N <= 0 || !ep_count_ok((int64_t)T * N)) return TW_E_ARG;
     return ep_summary_blocks((int64_t)T * N) * EP_NV;
 }
 
@@ -1214,10 +1219,10 @@ int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const
                         double keep, double gain, double *score, double *summary, int64_t *action_hist,
                         int64_t *reward_hist, double *workspace, void *stream) {
     if (!all_set(ep_return, ep_length, terminated, truncated, reward, summary, reward_hist, workspace) || T <= 0 || N <= 0 ||
-        !ppo_actions_ok(A))
+        !ppo_actions_ok(A) || !ep_count_ok((int64_t)T * N) ||
+        !aligned_natural(ep_return, ep_length, reward, action, score, summary, action_hist, reward_hist, workspace))
         return TW_E_ARG;
     const int64_t M = (int64_t)T * N;
-    if (M > ((int64_t)1 << 40)) return TW_E_ARG;                              // per-thread run length stays an int
     const int nblocks = ep_summary_blocks(M);
     const int64_t per_block = (M + nblocks - 1) / nblocks;
     const int per_thread = blocks(per_block, 256);

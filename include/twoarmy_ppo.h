@@ -126,8 +126,13 @@ int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int3
  * a done step ep_return / ep_length are the return and length of the episode that ends there, wherever it began.
  * The additions are float64, one per step, in step order: the result does not depend on how a rollout is cut into
  * launches (T = 128 once and 128 launches of T = 1 give the same bits).
+ * After a done step the scan restarts from exactly +0.0 and 0: a NaN or inf reward never leaves its episode or its env.
+ * Only the first T * N elements of ep_return / ep_length and the N elements of the carries are written.
  *   reward float[T][N]; terminated, truncated uint8[T][N]; carry_return double[N] in/out; carry_length int32[N] in/out;
- *   ep_return double[T][N] | NULL; ep_length int32[T][N] | NULL */
+ *   ep_return double[T][N] | NULL; ep_length int32[T][N] | NULL
+ * Alignment: reward 4 bytes; carry_length, ep_length 4 bytes; carry_return, ep_return 8 bytes (NULL counts as aligned).
+ * TW_E_ARG, and nothing is launched: NULL reward, terminated, truncated, carry_return or carry_length; T <= 0 or N <= 0;
+ * T * N >= 2^40; a pointer off the alignment above. */
 int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
                      double *carry_return, int32_t *carry_length, double *ep_return, int32_t *ep_length, void *stream);
 
@@ -142,7 +147,23 @@ int ppo_episode_scan(const float *reward, const uint8_t *terminated, const uint8
  * Deterministic: a grid fixed by (T, N), per-block partial results in `workspace`
  * (ppo_episode_summary_workspace(T, N) doubles), one ordered final pass.  Counts, min and max are exact; the sums
  * and the fold are evaluated as a tree in row-major order, so they agree with a sequential evaluation up to rounding.
- *   ep_return double[T][N], ep_length int32[T][N] (ppo_episode_scan's outputs); action int32[T][N] | NULL */
+ * The grid, with M = T * N: nblocks = min(ceil(M / 2048), 256) workgroups of 256 threads; workgroup b takes the
+ * per_block = ceil(M / nblocks) elements from b * per_block on, thread i of it the per_thread = ceil(per_block / 256)
+ * elements from b * per_block + i * per_thread on, both cut at the end of the block's share and at M (a run may be empty).
+ * The tree: a thread folds its run in order; the 64 lanes of a wavefront are combined as a binary tree (6 levels), the 4
+ * wavefronts of a workgroup one after the other; the final pass gives each of 64 lanes per_lane = ceil(nblocks / 64)
+ * consecutive partials, folded one after the other, and combines the lanes by the same 6-level tree.  The workspace
+ * holds ppo_episode_summary_workspace(T, N) = 24 * nblocks doubles, every one written before it is read: it needs no
+ * initialisation.  ep_return / ep_length are read at done steps only.
+ * An action outside [0, A) is counted in no bin, and action_hist[k] for k >= A is not written.  A non-finite return leaves
+ * episodes, successes, truncated, length_sum, max_length and both histograms as they would be without it; min and max ignore
+ * a NaN (fmin / fmax); return_sum and score take the non-finite value.
+ *   ep_return double[T][N], ep_length int32[T][N] (ppo_episode_scan's outputs); action int32[T][N] | NULL
+ * Alignment: reward 4 bytes; ep_length, action 4 bytes; ep_return, score, summary, workspace 8 bytes; action_hist,
+ * reward_hist 8 bytes (NULL counts as aligned).
+ * TW_E_ARG, and nothing is launched: NULL ep_return, ep_length, terminated, truncated, reward, summary, reward_hist or
+ * workspace; T <= 0 or N <= 0; T * N >= 2^40; an A outside {2, 3, 4, 5, 7}; a pointer off the alignment above.
+ * ppo_episode_summary_workspace: host only; TW_E_ARG for T <= 0, N <= 0 or T * N >= 2^40. */
 int ppo_episode_summary(const double *ep_return, const int32_t *ep_length, const uint8_t *terminated,
                         const uint8_t *truncated, const float *reward, const int32_t *action, int A, int T, int N,
                         double keep, double gain, double *score, double *summary, int64_t *action_hist,

@@ -53,28 +53,25 @@ def path_scan(dist, pos_before, pos_after, W, H, terminated, truncated, carry, a
 
 def path_summary(ep_start, ep_best, ep_off, ep_steps, terminated, truncated):
     """mg_nav_path_summary -> float64[10] in the order of SUMMARY, the done steps folded in row-major order."""
-    T, N = np.asarray(terminated).shape
     v = np.zeros(10, np.float64)
     v[9] = np.inf
-    for t in range(T):
-        for n in range(N):
-            if not (terminated[t, n] or truncated[t, n]):
-                continue
-            s, b, o, k = int(ep_start[t, n]), int(ep_best[t, n]), int(ep_off[t, n]), int(ep_steps[t, n])
-            v[0] += 1
-            v[1] += 1 if terminated[t, n] else 0
-            v[7] += o
-            v[8] += k
-            if s == UNREACHABLE:
-                continue
-            v[2] += 1
-            if terminated[t, n]:
-                v[3] += np.float64(s) / np.float64(max(k, s))
-            v[4] += s
-            v[5] += b
-            if s >= 1:
-                v[6] += np.float64(s - b) / np.float64(s)
-            v[9] = min(v[9], b)
+    ts, ns = np.nonzero((np.asarray(terminated) != 0) | (np.asarray(truncated) != 0))      # row-major order
+    for t, n in zip(ts.tolist(), ns.tolist()):
+        s, b, o, k = int(ep_start[t, n]), int(ep_best[t, n]), int(ep_off[t, n]), int(ep_steps[t, n])
+        v[0] += 1
+        v[1] += 1 if terminated[t, n] else 0
+        v[7] += o
+        v[8] += k
+        if s == UNREACHABLE:
+            continue
+        v[2] += 1
+        if terminated[t, n]:
+            v[3] += np.float64(s) / np.float64(max(k, s))
+        v[4] += s
+        v[5] += b
+        if s >= 1:
+            v[6] += np.float64(s - b) / np.float64(s)
+        v[9] = min(v[9], b)
     return v
 
 

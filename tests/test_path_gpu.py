@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import episode_cases as EC
 import nav_ref
 import path_ref
 import timed_nav_ref as tref
@@ -228,6 +229,46 @@ def test_summary_of_a_rollout_without_a_done_step():
     assert not got[:9].any() and got[9] == np.inf
     tr = nav().PathTracker(N, DEV, 5, 4)
     assert tr.read()["episodes"] == 0 and tr.read()["best_min"] == np.inf and tr.read()["spl"] is None
+
+
+_SWEEP = {}
+
+
+def sweep_case(M):
+    """Flat scan outputs for M elements, made directly (no scan): done steps at a low random density and at both ends of
+    every workgroup's share and of the whole range (the grid rule ppo_episode_summary documents, tests/episode_cases.py);
+    some unrated episodes, best <= start.  The restatement's summary is computed once per M."""
+    if M not in _SWEEP:
+        rng = np.random.default_rng(900 + M)
+        done = rng.random(M) < min(0.05, 1200.0 / M)
+        done[EC.boundaries(M)] = True
+        term = (done & (rng.random(M) < 0.6)).astype(np.uint8)
+        trunc = (done & ((term == 0) | (rng.random(M) < 0.2))).astype(np.uint8)
+        start = rng.integers(0, 40, M).astype(np.uint16)
+        start[rng.random(M) < 0.05] = U
+        best = np.where(start == U, U, rng.integers(0, 40, M) % (start.astype(np.int64) + 1)).astype(np.uint16)
+        outs = (start, best, rng.integers(0, 50, M).astype(np.int32), rng.integers(1, 51, M).astype(np.int32))
+        want = path_ref.path_summary(*(o.reshape(1, M) for o in outs), term.reshape(1, M), trunc.reshape(1, M))
+        _SWEEP[M] = (outs, term, trunc, want)
+    return _SWEEP[M]
+
+
+@pytest.mark.parametrize("M", EC.PATH_SWEEP_M)
+def test_summary_at_every_grid_boundary(M):
+    """1 -> 2 workgroups, 64 -> 65 partials, the 256-workgroup cap and the first thread run longer than 8 elements, each
+    as [1][M] and [M][1], the workspace of exactly the queried size and filled with NaN."""
+    outs, term, trunc, want = sweep_case(M)
+    g = EC.grid(M)
+    assert want[0] >= 2 * g["nblocks"] - 1 and want[0] > want[2] > want[1] > 0 and want[3] > 0 and want[6] > 0
+    for T, N in ((1, M), (M, 1)):
+        words = nav().path_summary_workspace(T, N)
+        assert words == 10 * g["nblocks"]
+        sbox, wbox = Boxed(10, torch.float64, 1), Boxed(words, torch.float64, 1)
+        wbox.view.fill_(float("nan"))
+        got = nav().path_summary(*(dev(o).view(T, N) for o in outs), dev(term).view(T, N), dev(trunc).view(T, N),
+                                 summary=sbox.view, workspace=wbox.view)
+        check_summary(host(got), want)
+        assert sbox.borders_intact() and wbox.borders_intact() and not np.isnan(host(wbox.view)).any()
 
 
 # ------------------------------------------------------------------------------------------------ the tracker
