@@ -90,6 +90,9 @@ _SIGS.update({
     "ppo_adv_norm": (C.c_int, [_vp, _i64, _f, _vp, _vp]),
     "ppo_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "ppo_loss_fwd_bwd_masked": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "ppo_loss_fwd_bwd_stats": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp]),
+    "ppo_loss_stats_workspace": (C.c_int, [_i]),
     "ppo_prior_loss_fwd_bwd": (C.c_int, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "ppo_gather_stack": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "mg_gen_obs": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),

@@ -354,16 +354,44 @@ __global__ __launch_bounds__(256) void ppo_normalise_kernel(float *__restrict__ 
 }
 
 // ------------------------------------------------------------------ fused PPO losses, forward + backward
-template <int A>
+// The update diagnostics of ppo_loss_fwd_bwd_stats (twoarmy_ppo.h): LS_NV per-row accumulators, every one a sum but
+// LS_MAX.  A row that is padding holds the identity (+0.0 everywhere: |ratio - 1| is never negative), and adding the
+// identity changes no bit of a partial, so neither the padding nor the number of workgroups reaches `stats`.
+constexpr int LS_NV = 12, LS_MAX = 5, LS_CALLS = 12;
+
+__device__ __forceinline__ void ls_combine(double (&v)[LS_NV], const double (&w)[LS_NV]) {
+#pragma unroll
+    for (int k = 0; k < LS_NV; ++k) v[k] = k == LS_MAX ? fmax(v[k], w[k]) : v[k] + w[k];
+}
+
+// The 64 lanes of a wavefront as a binary tree in lane order (the shape of ep_wave_reduce); lane 0 ends with all 64.
+__device__ __forceinline__ void ls_wave_reduce(double (&v)[LS_NV]) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        double w[LS_NV];
+#pragma unroll
+        for (int k = 0; k < LS_NV; ++k) w[k] = __shfl_down(v[k], s, 64);
+        ls_combine(v, w);
+    }
+}
+
+// STATS = false is ppo_loss_fwd_bwd[_masked]'s kernel: `sws` is not read and every statement under `if constexpr (STATS)`
+// is gone, so its bits and its registers are those it had before the diagnostics came.
+template <int A, bool STATS>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(const float *__restrict__ probs, const int32_t *__restrict__ action,
                                                        const float *__restrict__ old_logp, const float *__restrict__ adv,
                                                        const float *__restrict__ value, const float *__restrict__ target_v,
                                                        int B, int n_valid, float clip, float ent_coef,
                                                        float *__restrict__ grad_probs, float *__restrict__ grad_value,
-                                                       float *__restrict__ ws) {
+                                                       float *__restrict__ ws, double *__restrict__ sws) {
     __shared__ float lds[2 * 256];
     const int b = blockIdx.x * 256 + threadIdx.x;
     float la = 0.f, lv = 0.f;
+    [[maybe_unused]] double st[LS_NV];
+    if constexpr (STATS) {
+#pragma unroll
+        for (int k = 0; k < LS_NV; ++k) st[k] = 0.0;
+    }
     if (b >= n_valid && b < B) {                      // padding rows of a fixed-shape minibatch: no loss, no gradient
 #pragma unroll
         for (int k = 0; k < A; ++k) grad_probs[(size_t)b * A + k] = 0.f;
@@ -386,7 +414,8 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float *__restrict__
         float la_logp = 0.f;
 #pragma unroll
         for (int k = 0; k < A; ++k) if (k == a) la_logp = l[k];
-        const float ratio = expf(la_logp - old_logp[b]);
+        const float lr = la_logp - old_logp[b];
+        const float ratio = expf(lr);
         const float ad = adv[b];
         const float lo = 1.0f - clip, hi = 1.0f + clip;
         const float s1 = ratio * ad;
@@ -415,18 +444,89 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(const float *__restrict__
         const float ab = fabsf(d);
         lv = ab < 1.0f ? 0.5f * d * d : ab - 0.5f;
         grad_value[b] = (ab < 1.0f ? d : (d > 0.f ? 1.f : -1.f)) * invB;
+        if constexpr (STATS) {                        // the row's diagnostics, from the float32 values above (twoarmy_ppo.h)
+            bool in_a = false;
+            float top = q[0];
+#pragma unroll
+            for (int k = 0; k < A; ++k) {
+                if (k == a) in_a = inside[k];
+                top = fmaxf(top, q[k]);
+            }
+            const double t = (double)target_v[b], e = (double)(target_v[b] - value[b]);
+            const double dev = (double)ratio - 1.0;
+            st[0] = 1.0;
+            st[1] = (double)H;
+            st[2] = (double)lr;
+            st[3] = dev - (double)lr;                 // (r - 1) - log r in double: nothing is lost near r = 1
+            st[4] = (ratio < lo || ratio > hi) ? 1.0 : 0.0;
+            st[LS_MAX] = fabs(dev);
+            st[6] = t;
+            st[7] = t * t;
+            st[8] = e;
+            st[9] = e * e;
+            st[10] = in_a ? 0.0 : 1.0;
+            st[11] = (double)top;
+        }
     }
     float sums[2] = {la, lv};
     block_sum(sums, lds);
     if (threadIdx.x == 0) { ws[2 * blockIdx.x] = sums[0]; ws[2 * blockIdx.x + 1] = sums[1]; }
+    if constexpr (STATS) {                            // lanes in order, then the four wavefronts in order
+        __shared__ double sh[4][LS_NV];
+        ls_wave_reduce(st);
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < LS_NV; ++k) sh[wave][k] = st[k];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 4; ++w) {
+                double o[LS_NV];
+#pragma unroll
+                for (int k = 0; k < LS_NV; ++k) o[k] = sh[w][k];
+                ls_combine(st, o);
+            }
+#pragma unroll
+            for (int k = 0; k < LS_NV; ++k) sws[(size_t)blockIdx.x * LS_NV + k] = st[k];
+        }
+    }
+}
+
+__device__ __forceinline__ void loss_means(const float *__restrict__ ws, int nblocks, int B, float *__restrict__ losses) {
+    float a = 0.f, v = 0.f;
+    for (int k = 0; k < nblocks; ++k) { a += ws[2 * k]; v += ws[2 * k + 1]; }           // fixed order
+    losses[0] = a / (float)B;
+    losses[1] = v / (float)B;
 }
 
 __global__ void ppo_loss_finalize_kernel(const float *__restrict__ ws, int nblocks, int B, float *__restrict__ losses) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        float a = 0.f, v = 0.f;
-        for (int k = 0; k < nblocks; ++k) { a += ws[2 * k]; v += ws[2 * k + 1]; }       // fixed order
-        losses[0] = a / (float)B;
-        losses[1] = v / (float)B;
+    if (threadIdx.x == 0 && blockIdx.x == 0) loss_means(ws, nblocks, B, losses);
+}
+
+// The final pass of ppo_loss_fwd_bwd_stats, one wavefront: the losses as above, and stats += the partials.  Lane l folds
+// the partials l, l + 64, l + 128, ... one after the other from the identity, the lanes are combined in lane order: which
+// partials meet at which node depends on their index alone, never on nblocks, so the all-identity partials of padding
+// workgroups leave every bit as it is.  The identity is +0.0, hence no sum that reaches stats is -0.0.
+__global__ __launch_bounds__(64) void ppo_loss_stats_finalize_kernel(const float *__restrict__ ws,
+                                                                    const double *__restrict__ sws, int nblocks, int B,
+                                                                    float *__restrict__ losses, double *__restrict__ stats) {
+    const int lane = threadIdx.x;
+    if (lane == 0) loss_means(ws, nblocks, B, losses);
+    double v[LS_NV];
+#pragma unroll
+    for (int k = 0; k < LS_NV; ++k) v[k] = 0.0;
+    for (int blk = lane; blk < nblocks; blk += 64) {
+        double o[LS_NV];
+#pragma unroll
+        for (int k = 0; k < LS_NV; ++k) o[k] = sws[(size_t)blk * LS_NV + k];
+        ls_combine(v, o);
+    }
+    ls_wave_reduce(v);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < LS_NV; ++k) stats[k] = k == LS_MAX ? fmax(stats[k], v[k]) : stats[k] + v[k];
+        stats[LS_CALLS] += 1.0;
     }
 }
 
@@ -1132,9 +1232,28 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
         return TW_E_ARG;
     const int nblocks = blocks(B, 256);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ppo_loss_kernel<5>, dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
-                       target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace);
+    hipLaunchKernelGGL((ppo_loss_kernel<5, false>), dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
+                       target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace, (double *)nullptr);
     hipLaunchKernelGGL(ppo_loss_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, nblocks, n_valid, losses);
+    return tw_launched(__func__);
+}
+
+int ppo_loss_stats_workspace(int B) { return B > 0 ? blocks(B, 256) * LS_NV : TW_E_ARG; }
+
+int ppo_loss_fwd_bwd_stats(const float *probs, const int32_t *action, const float *old_logp, const float *adv,
+                           const float *value, const float *target_v, int B, int n_valid, int A, float clip,
+                           float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
+                           double *stats, double *stats_workspace, void *launch_stream) {
+    if (!all_set(probs, action, old_logp, adv, value, target_v, losses, grad_probs, grad_value, workspace, stats,
+                 stats_workspace) || B <= 0 || A != 5 || n_valid <= 0 || n_valid > B ||       // the masked entry's rules
+        !aligned_natural(stats, stats_workspace))
+        return TW_E_ARG;
+    const int nblocks = blocks(B, 256);
+    hipStream_t st = (hipStream_t)launch_stream;
+    hipLaunchKernelGGL((ppo_loss_kernel<5, true>), dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
+                       target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace, stats_workspace);
+    hipLaunchKernelGGL(ppo_loss_stats_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, stats_workspace, nblocks,
+                       n_valid, losses, stats);
     return tw_launched(__func__);
 }
 

@@ -157,6 +157,18 @@ def broadcast_parameters(modules, src=0):
                 t.data.copy_(buf)
 
 
+def sum_over_ranks(values, device=None):
+    """The element-wise sum over all ranks of a few Python numbers, as floats: one float64 all-reduce (on the CPU unless
+    the backend is nccl, like global_adv_norm_).  Every rank gets the same result, so a decision taken from it -- the KL
+    stop of VecPPOTrainer.update -- is the same on every rank.  Without a process group, or with one rank: the values."""
+    values = [float(v) for v in values]
+    if not (dist.is_initialized() and dist.get_world_size() > 1):
+        return values
+    t = torch.tensor(values, dtype=torch.float64, device="cpu" if dist.get_backend() != "nccl" else device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.tolist()
+
+
 def global_adv_norm_(adv, eps=1e-8):
     """adv <- (adv - mean) / (std + eps) with mean / unbiased std over the samples of ALL ranks (the reference's
     commented normalisation, PPO.py:115, applied to the whole sharded batch): one all-reduce of (count, sum, sum of

@@ -65,10 +65,29 @@ class _AttachGrad(torch.autograd.Function):
         return (grad * g).view(ctx.xshape), None, None
 
 
-def ppo_losses(probs, value, action, old_logp, adv, target_v, clip=0.1, ent_coef=0.01, n_valid=None):
+UPDATE_STATS_WORDS = 16
+# stats[i] of ppo_loss_fwd_bwd_stats (include/twoarmy_ppo.h); 13..15 are reserved
+UPDATE_STATS = dict(rows=0, entropy_sum=1, logr_sum=2, k3_sum=3, clipped=4, ratio_dev_max=5, t_sum=6, t_sq_sum=7, e_sum=8,
+                    e_sq_sum=9, saturated=10, top_mass_sum=11, calls=12)
+_stats_workspaces = {}
+
+
+def _stats_workspace(device, B):
+    """The partial sums of ppo_loss_fwd_bwd_stats for B rows on `device`, made once per (device, B) and kept: written
+    before it is read by every call, so calls that share it must be ordered on one stream (an update's are)."""
+    k = (torch.device(device), int(B))
+    if k not in _stats_workspaces:
+        _stats_workspaces[k] = torch.empty(_query("ppo_loss_stats_workspace", int(B)), dtype=torch.float64, device=device)
+    return _stats_workspaces[k]
+
+
+def ppo_losses(probs, value, action, old_logp, adv, target_v, clip=0.1, ent_coef=0.01, n_valid=None, stats=None):
     """(action_loss, value_loss) of the reference (PPO.py:124-133).  One fused forward+backward launch;
     the two losses are separate autograd nodes so `action_loss.backward(); value_loss.backward()` works
-    exactly like in the reference.  n_valid < B: rows n_valid.. are padding of a fixed-shape minibatch."""
+    exactly like in the reference.  n_valid < B: rows n_valid.. are padding of a fixed-shape minibatch.
+    stats: a float64[16] device tensor (or a row of a larger one) that the call ADDS this minibatch's diagnostics to
+    (ppo_loss_fwd_bwd_stats, include/twoarmy_ppo.h; read with update_stats_read); the losses and gradients are the same
+    bits.  None: ppo_loss_fwd_bwd_masked, nothing else launched."""
     B, A = probs.shape
     n_valid = B if n_valid is None else int(n_valid)
     with torch.no_grad():
@@ -78,10 +97,39 @@ def ppo_losses(probs, value, action, old_logp, adv, target_v, clip=0.1, ent_coef
         gp = torch.empty_like(probs_c)
         gv = torch.empty_like(value_c)
         ws = torch.empty(2 * ((B + 255) // 256), dtype=torch.float32, device=probs.device)
-        _call("ppo_loss_fwd_bwd_masked", probs, _p(probs_c, torch.float32), _p(action.contiguous(), torch.int32),
-              _p(old_logp.contiguous().view(-1)), _p(adv.contiguous().view(-1)), _p(value_c),
-              _p(target_v.contiguous().view(-1)), B, n_valid, A, float(clip), float(ent_coef), _p(losses), _p(gp), _p(gv), _p(ws))
+        args = [_p(probs_c, torch.float32), _p(action.contiguous(), torch.int32), _p(old_logp.contiguous().view(-1)),
+                _p(adv.contiguous().view(-1)), _p(value_c), _p(target_v.contiguous().view(-1)), B, n_valid, A, float(clip),
+                float(ent_coef), _p(losses), _p(gp), _p(gv), _p(ws)]
+        if stats is None:
+            _call("ppo_loss_fwd_bwd_masked", probs, *args)
+        else:
+            assert stats.shape == (UPDATE_STATS_WORDS,) and stats.device == probs.device
+            _call("ppo_loss_fwd_bwd_stats", probs, *args, _p(stats, torch.float64),
+                  _p(_stats_workspace(probs.device, B), torch.float64))
     return _AttachGrad.apply(probs, losses[0], gp), _AttachGrad.apply(value, losses[1], gv)
+
+
+def update_stats_read(stats):
+    """The accumulators of ppo_losses(..., stats=) as numbers: float64[..., 16] on any device -> a dict of Python floats
+    (one row) or numpy arrays over the leading dimensions.  rows, calls: counts.  entropy, top_mass (mean of max_k q):
+    means over the rows.  approx_kl = k3_sum / rows, the non-negative estimator mean((r - 1) - log r);
+    approx_kl_k1 = -logr_sum / rows.  clip_frac: the share of rows outside the clip range; saturated_frac: of rows whose
+    acted action sits on the Categorical's clamp.  ratio_dev_max = max |r - 1|.  explained_variance = 1 - Var(e) / Var(t),
+    e = target - value, population variances from the raw moments (include/twoarmy_ppo.h on their precision).  Where
+    rows == 0 every mean is NaN; where Var(t) == 0 explained_variance is NaN.  This is the one host read."""
+    import numpy as np
+    s = stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    assert s.dtype == np.float64 and s.shape[-1] == UPDATE_STATS_WORDS
+    g = {k: s[..., i] for k, i in UPDATE_STATS.items()}
+    n = np.where(g["rows"] > 0, g["rows"], np.nan)                       # NaN rows: every mean below is NaN
+    with np.errstate(all="ignore"):                                      # NaN in, NaN out: nothing to warn about
+        var_t = np.maximum(g["t_sq_sum"] / n - (g["t_sum"] / n) ** 2, 0.0)
+        var_e = np.maximum(g["e_sq_sum"] / n - (g["e_sum"] / n) ** 2, 0.0)
+        out = dict(rows=g["rows"], calls=g["calls"], entropy=g["entropy_sum"] / n, approx_kl=g["k3_sum"] / n,
+                   approx_kl_k1=-g["logr_sum"] / n, clip_frac=g["clipped"] / n, ratio_dev_max=g["ratio_dev_max"],
+                   explained_variance=1.0 - var_e / np.where(var_t > 0, var_t, np.nan),
+                   saturated_frac=g["saturated"] / n, top_mass=g["top_mass_sum"] / n)
+    return {k: float(v) if s.ndim == 1 else np.array(v) for k, v in out.items()}
 
 
 def prior_loss(probs, moves, coef, n_valid=None):

@@ -51,6 +51,11 @@ def _make_writer(log_dir):
 
 
 class PPO:
+    # float64[16] device tensor that every minibatch_step_x adds its update diagnostics to (ppo_ops.ppo_losses(stats=)),
+    # e.g. a row of VecPPOTrainer.enable_update_stats()'s tensor; None: the plain loss launch.  A class attribute, so
+    # every agent that goes through minibatch_step_x has it.
+    stats_row = None
+
     def __init__(self, log_root=None, use_tensorboard=False):
         self.traindate = datetime.now().strftime("%Y_%m_%d_%H_%M_%S")
         root = Path(log_root or os.environ.get("TWOARMY_LOG_ROOT", "./runs"))
@@ -177,7 +182,8 @@ class PPO:
         probs = self.actor_probs(x0, p0, g)
         value = self.critic_value(x0, p0, g)
         action_loss, value_loss = ppo_ops.ppo_losses(probs, value, a, old_logp, adv, target_v,
-                                                     clip=self.clip_param, ent_coef=self.entropy_coef, n_valid=n_valid)
+                                                     clip=self.clip_param, ent_coef=self.entropy_coef, n_valid=n_valid,
+                                                     stats=self.stats_row)
         actor_loss, prior_loss = action_loss, None
         if prior is not None:
             prior_loss, _ = ppo_ops.prior_loss(probs, prior[0], prior[1], n_valid=n_valid)

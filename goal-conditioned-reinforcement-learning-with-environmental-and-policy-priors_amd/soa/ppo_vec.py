@@ -39,6 +39,13 @@ def padded_permutation(perm, n_steps, minibatch):
     return perm
 
 
+def kl_stop(k3_sum, rows, target_kl):
+    """The KL early stop of VecPPOTrainer.update: after an epoch whose accumulators (ppo_ops.UPDATE_STATS) are k3_sum and
+    rows, skip the remaining epochs iff approx_kl = k3_sum / rows EXCEEDS target_kl (a value equal to it goes on).  No
+    rows: nothing was measured, go on."""
+    return rows > 0 and k3_sum / rows > target_kl
+
+
 class VecPPOTrainer:
     def __init__(self, agent, engine, rollout_steps=128, minibatch=4096, value_chunk=16384, frame_codes=False):
         """frame_codes=True stores the rollout's frames as uint8 codes (TW_F_MATRIX_CODE; 304 B instead of 1168 B
@@ -111,6 +118,7 @@ class VecPPOTrainer:
         self.shaping = None                   # potential-based shaping: {"scale", "hindsight", "timed", "hindsight_timed"}, made by enable_shaping()
         self._relabel_at = -1                 # env_steps when relabel() last ran: shape_potential() comes after it
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
+        self.update_diag = None               # update diagnostics: {"stats", "target_kl", "epochs_run"}, made by enable_update_stats()
         self.env_steps = 0
         self.episodes_done = 0
         self.return_sum = 0.0
@@ -403,7 +411,16 @@ class VecPPOTrainer:
         synced = ag.grad_sync is not None and torch.distributed.is_initialized()
         if synced:
             n_steps = agree_on_steps(n_steps, self.device)
+        diag = self.update_diag
+        if diag is not None:                                          # one row per epoch, cleared with one fill
+            if diag["stats"].shape[0] != ag.K_epochs:
+                diag["stats"] = torch.zeros((ag.K_epochs, ppo_ops.UPDATE_STATS_WORDS), dtype=torch.float64, device=self.device)
+            else:
+                diag["stats"].zero_()
+            diag["epochs_run"] = 0
         for ep in range(ag.K_epochs):
+            if diag is not None:
+                ag.stats_row = diag["stats"][ep]
             perm = (torch.randperm(total) if permutations is None else torch.as_tensor(permutations[ep])).to(self.device)
             if synced:
                 perm = padded_permutation(perm, n_steps, self.minibatch)
@@ -427,6 +444,17 @@ class VecPPOTrainer:
                                                  prior=(smp_moves[idx], prior_coef))
                 done_steps += 1
             assert done_steps == n_steps or not synced, (done_steps, n_steps)
+            if diag is not None:
+                diag["epochs_run"] = ep + 1
+                if diag["target_kl"] is not None:                     # the one two-element host read per epoch
+                    k3, rows = diag["stats"][ep, [ppo_ops.UPDATE_STATS["k3_sum"], ppo_ops.UPDATE_STATS["rows"]]].tolist()
+                    if synced:                                        # every rank stops at the same epoch
+                        from .. import dist as twdist
+                        k3, rows = twdist.sum_over_ranks([k3, rows], self.device)
+                    if kl_stop(k3, rows, diag["target_kl"]):
+                        break
+        if diag is not None:
+            ag.stats_row = None
         if ag.use_lr_decay:
             ag.scheduler_actor.step(); ag.scheduler_critic.step()
         if self.time_phases:
@@ -797,7 +825,42 @@ class VecPPOTrainer:
         return {"mean": v[1] / n if n else None, "unshaped": 1.0 - n / total,
                 "her_mean": v[3] / hn if hn else None, "her_unshaped": 1.0 - hn / htotal if htotal else None}
 
+    # ------------------------------------------------------------------ update diagnostics
+    def enable_update_stats(self, target_kl=None):
+        """Keep the diagnostics of every update() on the device: one float64[16] row per epoch (float64[K_epochs, 16],
+        cleared with one fill at the start of update()), which the loss launch of every minibatch of that epoch adds to
+        (agent.stats_row -> ppo_ops.ppo_losses(stats=), ppo_loss_fwd_bwd_stats in include/twoarmy_ppo.h): entropy, the
+        approximate KL between the acting and the updated policy, the share of clipped samples, how much of the targets'
+        variance the critic explains.  Losses, gradients and parameters are the same bits as without it.
+        target_kl: after an epoch whose approx_kl exceeds it, the remaining epochs of that update are skipped (kl_stop);
+        their rows stay zero and the LR schedulers step once per update as before.  This costs ONE two-element host read
+        per epoch (a synchronisation; without target_kl update() adds none).  With a process group of several ranks k3_sum
+        and rows are summed over the ranks first (dist.sum_over_ranks, one more small all-reduce per epoch), so every rank
+        stops at the same epoch and takes part in the same gradient all-reduces."""
+        if target_kl is not None and not (math.isfinite(float(target_kl)) and float(target_kl) >= 0.0):
+            raise ValueError("enable_update_stats(): target_kl must be a finite number >= 0 or None, got %r" % (target_kl,))
+        self.update_diag = {"stats": torch.zeros((self.agent.K_epochs, ppo_ops.UPDATE_STATS_WORDS), dtype=torch.float64,
+                                                 device=self.device),
+                            "target_kl": None if target_kl is None else float(target_kl), "epochs_run": 0}
+        return self.update_diag
+
+    def update_stats(self):
+        """ppo_ops.update_stats_read() of the last update(): {"per_epoch": its dict of arrays over the K_epochs rows (rows
+        of skipped epochs are zero, their means NaN), "epochs_run", and the values of the last epoch that ran under the
+        plain key names (rows, calls, entropy, approx_kl, approx_kl_k1, clip_frac, ratio_dev_max, explained_variance,
+        saturated_frac, top_mass)}.  One device-to-host copy."""
+        if self.update_diag is None or self.update_diag["epochs_run"] == 0:
+            raise RuntimeError("update_stats() before enable_update_stats() and update()")
+        per = ppo_ops.update_stats_read(self.update_diag["stats"])
+        n = self.update_diag["epochs_run"]
+        out = {k: float(v[n - 1]) for k, v in per.items()}
+        out.update(per_epoch=per, epochs_run=n)
+        return out
+
     def stats(self):
         done = (self.term | self.trunc) != 0
-        return {"env_steps": self.env_steps, "episodes": int(done.sum()), "successes": int(self.term.sum()),
-                "mean_reward": float(self.reward.mean())}
+        out = {"env_steps": self.env_steps, "episodes": int(done.sum()), "successes": int(self.term.sum()),
+               "mean_reward": float(self.reward.mean())}
+        if self.update_diag is not None and self.update_diag["epochs_run"]:
+            out.update({k: v for k, v in self.update_stats().items() if k != "per_epoch"})
+        return out

@@ -38,6 +38,10 @@ labels from the time-expanded field, --orient_prior_hindsight labels the hindsig
 --orient_prior_hindsight) labels them by the time-expanded search (minigrid_nav.timed_goal_ahead in its place, so that with
 --orient_prior_timed both kinds of sample wait for the balls), --orient_prior_every_state adds every rollout step that is no
 success sample as a prior-only row; all off by default.
+--update_stats accumulates the update's diagnostics inside its loss kernel (ppo_ops.ppo_losses(stats=): no launch more
+per minibatch, one host read per update) and appends `ent`, `kl`, `clipfrac`, `ev` (of the last epoch that ran) and
+`epochs` to the log line; --target_kl X (implies it) skips the remaining epochs of an update once an epoch's `kl` exceeds X
+(one two-element host read per epoch); both off by default.
 """
 import argparse
 import math
@@ -47,6 +51,14 @@ import time
 
 import numpy as np
 import torch
+
+
+class _TargetKL(argparse.Action):
+    """--target_kl X: the value, and --update_stats with it (the stop reads the update's KL estimate)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.target_kl = values
+        namespace.update_stats = True
 
 
 def build_parser():
@@ -193,7 +205,21 @@ def build_parser():
                    help="self-orientation agent: label every rollout with the look-ahead and append `orient agree` (share of "
                         "the labelled steps whose drawn orientation sample lies in the label) to the log line, without "
                         "training on it; implied by --orient_prior_coef")
+    p.add_argument("--update_stats", action="store_true",
+                   help="accumulate the diagnostics of every update inside its loss kernel (one row per epoch, read once per "
+                        "update): appends `ent` (policy entropy), `kl` (approximate KL between the acting and the updated "
+                        "policy), `clipfrac` (share of samples outside the clip range), `ev` (explained variance of the "
+                        "critic), all of the last epoch that ran, and `epochs` to the log line; off by default")
+    p.add_argument("--target_kl", type=float, default=None, metavar="X", action=_TargetKL,
+                   help="KL early stop: skip the remaining epochs of an update after an epoch whose `kl` exceeds X (one small "
+                        "host read per epoch; summed over the ranks first); implies --update_stats; off by default")
     return p
+
+
+def update_fields(us):
+    """Tail of the log line with --update_stats (VecPPOTrainer.update_stats())."""
+    return " ent %.4f kl %.6f clipfrac %.4f ev %.4f epochs %d" % (us["entropy"], us["approx_kl"], us["clip_frac"],
+                                                                 us["explained_variance"], us["epochs_run"])
 
 
 def orient_fields(os_, hindsight=False):
@@ -312,6 +338,8 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--shaping_hindsight_timed shapes the hindsight records: not with --shaping_no_hindsight")
     if args.path_stats_timed and not args.path_stats:
         raise SystemExit("--path_stats_timed needs --path_stats")
+    if args.target_kl is not None and not (math.isfinite(args.target_kl) and args.target_kl >= 0.0):
+        raise SystemExit("--target_kl must be a finite number >= 0")
     use_orient = args.orient_prior_coef != 0.0 or args.orient_agreement
     if not (math.isfinite(args.orient_prior_coef) and args.orient_prior_coef >= 0.0):
         raise SystemExit("--orient_prior_coef must be a finite number >= 0")
@@ -393,6 +421,8 @@ def main(argv=None, predictor=False, soa=False):
                                          timed=args.orient_prior_timed, hindsight=args.orient_prior_hindsight,
                                          every_state=args.orient_prior_every_state,
                                          hindsight_timed=args.orient_prior_hindsight_timed)
+    if args.update_stats:
+        trainer.enable_update_stats(args.target_kl)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
@@ -458,6 +488,12 @@ def main(argv=None, predictor=False, soa=False):
             tail += orient_fields(ots, args.orient_prior_hindsight)
         if args.path_stats:                                     # behind every other field
             tail += path_fields(trainer.path_stats())
+        if args.update_stats:                                   # behind every other field
+            us = trainer.update_stats()
+            tail += update_fields(us)
+            for tag, key in (("diag/entropy", "entropy"), ("diag/approx_kl", "approx_kl"), ("diag/clip_frac", "clip_frac"),
+                             ("diag/explained_variance", "explained_variance"), ("diag/epochs_run", "epochs_run")):
+                agent.writer.add_scalar(tag, us[key], u)
         if args.track_buffer_file and rank == 0:
             dump_track(trainer, args.track_buffer_file, u, args.dump_envs)
         trainer.carry_over()

@@ -71,6 +71,49 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
                             float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
                             void *stream);
 
+/* ppo_loss_fwd_bwd_masked plus the diagnostics of the update, accumulated on the device: losses, grad_probs and grad_value
+ * are bit for bit what ppo_loss_fwd_bwd_masked writes for the same arguments (one row routine, two instantiations), and
+ * `stats` double[16], in/out, gets ADDED what the rows b < n_valid contribute.  All-zero = nothing accumulated, so one fill
+ * clears it.  With the row's float32 values as the loss computes them -- q = p / sum(p), l = log(clamp(q, eps, 1 - eps)),
+ * H = -sum q l, lr = l[a] - old_logp[b] (the float32 difference that feeds expf), ratio = expf(lr), lo = 1 - clip,
+ * hi = 1 + clip -- a row adds:
+ *    0 rows            1
+ *    1 entropy_sum     (double)H
+ *    2 logr_sum        (double)lr                                   -logr_sum / rows = the k1 estimate of KL(old || new)
+ *    3 k3_sum          ((double)ratio - 1.0) - (double)lr           the non-negative estimator (r - 1) - log r, evaluated in
+ *                                                                   double from the two float32 values: exact near r = 1
+ *    4 clipped         1 where ratio < lo or ratio > hi             the loss's own float compares
+ *    5 ratio_dev_max   stats[5] = fmax(stats[5], |(double)ratio - 1|)          a maximum, not a sum
+ *    6 t_sum           (double)target_v
+ *    7 t_sq_sum        (double)target_v squared in double
+ *    8 e_sum           e = target_v - value as ONE float32 subtraction, then (double)e
+ *    9 e_sq_sum        (double)e squared in double
+ *   10 saturated       1 where q[a] of the acted action lies outside [eps, 1 - eps]: the clamp is active there and the
+ *                      row sends no policy gradient
+ *   11 top_mass_sum    (double)max_k q[k]
+ *   12 calls           1 per call
+ *   13..15 reserved    never read or written
+ * t_sq_sum and e_sq_sum are RAW second moments: a variance taken from them and the sums loses digits where |mean| is far
+ * larger than the standard deviation.  Twoarmy's targets are of order 1.
+ * Deterministic, no floating-point atomics: per-workgroup partials (12 doubles each: the 64 lanes of a wavefront as a
+ * binary tree in lane order, then the four wavefronts in order) go into `stats_workspace`,
+ * ppo_loss_stats_workspace(B) = 12 * ceil(B / 256) doubles, every one written before it is read (no initialisation needed);
+ * the final pass, one wavefront, gives lane l the partials l, l + 64, ... folded in that order and combines the lanes by the
+ * same tree.  Two calls from equal `stats` on equal inputs give equal bits.  Rows n_valid .. B-1 add exactly nothing (+0.0
+ * and 0), and which partials meet where does not depend on the number of workgroups: a padded call and the unpadded call on
+ * the first n_valid rows leave equal bits in all of `stats`.  Cutting one batch into several calls changes the sums by double
+ * rounding only; counts and the maximum do not change.
+ * Two launches, both on `launch_stream` (a hipStream_t as void*, like `stream` elsewhere), nothing allocated or read back
+ * between them: the call may be captured into a graph and replayed.
+ * TW_E_ARG, and nothing is launched: the rules of ppo_loss_fwd_bwd_masked (every pointer set, B > 0, A == 5,
+ * 0 < n_valid <= B), NULL stats or stats_workspace, either of the two off 8-byte alignment.
+ * ppo_loss_stats_workspace: host only; TW_E_ARG for B <= 0. */
+int ppo_loss_fwd_bwd_stats(const float *probs, const int32_t *action, const float *old_logp, const float *adv,
+                           const float *value, const float *target_v, int B, int n_valid, int A, float clip,
+                           float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
+                           double *stats, double *stats_workspace, void *launch_stream);
+int ppo_loss_stats_workspace(int B);
+
 /* Shortest-path prior: a set-valued imitation term on the actor, forward + backward for one minibatch.  No reference
  * counterpart; the labels are the optimal-move sets of mg_nav_optimal_moves (minigrid_nav.h).
  *   probs float[B][A] (A as for ppo_sample); moves uint8[B]: a mask over POLICY indices, bit a set iff action a is optimal

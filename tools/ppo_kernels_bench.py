@@ -52,6 +52,10 @@ act = torch.randint(0, A, (B,), generator=g, dtype=torch.int32).to(dev)
 olp, ad, tg = (torch.randn(B, 1, generator=g).to(dev) for _ in range(3))
 report("ppo_loss_fwd_bwd (minibatch 32768)", B * (A * 4 + 4 + 4 + 4 + 4 + 4 + A * 4 + 4),
        timed(lambda: ppo_ops.ppo_losses(pb, val, act, olp, ad, tg, clip=0.1, ent_coef=0.01)), "launch-bound at this size")
+loss_stats = torch.zeros(ppo_ops.UPDATE_STATS_WORDS, dtype=torch.float64, device=dev)
+report("ppo_loss_fwd_bwd_stats (minibatch 32768)", B * (A * 4 + 4 + 4 + 4 + 4 + 4 + A * 4 + 4) + 2 * (B // 256) * 12 * 8,
+       timed(lambda: ppo_ops.ppo_losses(pb, val, act, olp, ad, tg, clip=0.1, ent_coef=0.01, stats=loss_stats)),
+       "the row above plus the update diagnostics; same two launches")
 
 frames = torch.randn(T + 4, N, 292, generator=g).to(dev)[..., :289]
 codes = torch.randint(0, 4, (T + 4, N, 304), generator=g, dtype=torch.uint8).to(dev)[..., :289]
