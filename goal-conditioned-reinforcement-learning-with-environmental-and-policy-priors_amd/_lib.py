@@ -87,6 +87,9 @@ _SIGS.update({
     "ppo_sample": (C.c_int, [_vp, _i, _i, _vp, _u64, _u64, _vp, _vp, _vp]),
     "ppo_sample_dev": (C.c_int, [_vp, _i, _i, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "ppo_gae": (C.c_int, [_vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ppo_run_ends": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ppo_gae_runs": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ppo_gae_runs_workspace": (C.c_int, [_i64]),
     "ppo_adv_norm": (C.c_int, [_vp, _i64, _f, _vp, _vp]),
     "ppo_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "ppo_loss_fwd_bwd_masked": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),

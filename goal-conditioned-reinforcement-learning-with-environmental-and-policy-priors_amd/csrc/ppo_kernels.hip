@@ -319,6 +319,146 @@ __global__ __launch_bounds__(256) void ppo_gae_kernel(const float *__restrict__ 
     }
 }
 
+// ------------------------------------------------------------------ GAE along a flat record array, cut at run ends
+// The records of ppo_her_relabel come as runs; A_j = d_j + c_j * A_{j+1} with c_j = 0 at a run end is again a suffix
+// composition of affine maps, now along ONE array of H records, so it is scanned as a tree over workgroups instead of
+// by one wavefront per column: a workgroup owns GR_BLOCK = 2048 consecutive records, each of its 4 wavefronts
+// GR_CHUNKS = 8 chunks of 64 (coalesced: lane = record inside the chunk), scanned by gae_suffix_scan and folded from
+// the last chunk to the first.  Level 0 are the records, level l + 1 the composites of the workgroups of level l:
+//   reduce  level l -> the composite (c, d) of every workgroup, written to level l + 1      (while a level has > 2048 maps)
+//   apply   the top level from x = 0, then every level below it with x of workgroup b + 1 (level l + 1, already applied)
+//           as the value that enters workgroup b from behind
+// H <= 2048: one launch; H <= 2048^2: three.  Every combine keeps the c != 0 guard, so a map with c = 0 hands its d on
+// exactly and nothing behind it is looked at.
+constexpr int GR_CHUNKS = 8;
+constexpr int GR_WAVE = 64 * GR_CHUNKS;
+constexpr int GR_BLOCK = 4 * GR_WAVE;
+constexpr int GR_MAX_LEVELS = 4;                    // 2048^4 > 2^40 records
+
+// The shuffle step of ppo_gae_kernel as a function (that kernel keeps its own loop: its code is pinned, section 6.26 of
+// DESIGN.md): on entry lane l holds the map x -> d + c * x of its element, on exit the composite of the elements l .. 63.
+__device__ __forceinline__ void gae_suffix_scan(float &c, float &d, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float d2 = __shfl_down(d, off), c2 = __shfl_down(c, off);
+        if (lane + off < 64 && c != 0.f) { d = fmaf(c, d2, d); c = c * c2; }     // c == 0 ends the segment, as there
+    }
+}
+
+// first o behind: the map of (c, d) followed by (C, D), kept in (C, D)
+__device__ __forceinline__ void gr_compose(float c, float d, float &C, float &D) {
+    if (c != 0.f) { D = fmaf(c, D, d); C = c * C; }
+    else { D = d; C = 0.f; }
+}
+__device__ __forceinline__ float gr_eval(float c, float d, float x) { return c != 0.f ? fmaf(c, x, d) : d; }
+
+struct gr_records {                                 // level 0: the maps come from the records, the scan goes to adv / ret
+    const float *reward, *value, *next_value;
+    const uint8_t *done, *run_end;
+    float gamma, lambda;
+    int use_done_mask;
+    float *adv, *target, *ret;
+    __device__ __forceinline__ void load(int64_t i, int64_t n, bool write, float &c, float &d) const {
+        c = 1.f; d = 0.f;                           // identity behind the last record
+        if (i < n) {
+            const float cut = (use_done_mask && done[i]) ? 0.f : 1.f;
+            const float tv = reward[i] + (gamma * next_value[i]) * cut;      // ppo_gae_kernel's rounding sequence
+            if (write && target) target[i] = tv;
+            d = tv - value[i];
+            c = (run_end[i] || i == n - 1) ? 0.f : gamma * lambda * cut;
+        }
+    }
+    __device__ __forceinline__ void store(int64_t i, float a) const {
+        if (adv) adv[i] = a;
+        if (ret) ret[i] = a + value[i];
+    }
+};
+struct gr_composites {                              // level >= 1: (c[i], d[i]) in the workspace; x replaces d in place
+    const float *c;
+    float *d;
+    __device__ __forceinline__ void load(int64_t i, int64_t n, bool, float &cc, float &dd) const {
+        cc = 1.f; dd = 0.f;
+        if (i < n) { cc = c[i]; dd = d[i]; }
+    }
+    __device__ __forceinline__ void store(int64_t i, float x) const { d[i] = x; }
+};
+
+template <typename Src>
+__global__ __launch_bounds__(256) void ppo_gae_runs_reduce_kernel(Src src, int64_t n, float *__restrict__ out_c,
+                                                                  float *__restrict__ out_d) {
+    __shared__ float wc[4], wd[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t base = (int64_t)blockIdx.x * GR_BLOCK + wave * GR_WAVE;
+    float C = 1.f, D = 0.f;                         // composite of the chunks behind the current one
+#pragma unroll
+    for (int q = GR_CHUNKS - 1; q >= 0; --q) {
+        float c, d;
+        src.load(base + q * 64 + lane, n, false, c, d);
+        gae_suffix_scan(c, d, lane);
+        gr_compose(__shfl(c, 0), __shfl(d, 0), C, D);
+    }
+    if (lane == 0) { wc[wave] = C; wd[wave] = D; }
+    __syncthreads();
+    if (tid == 0) {
+        C = wc[3]; D = wd[3];                       // the four wavefronts, last to first
+        for (int w = 2; w >= 0; --w) gr_compose(wc[w], wd[w], C, D);
+        out_c[blockIdx.x] = C; out_d[blockIdx.x] = D;
+    }
+}
+
+template <typename Src>
+__global__ __launch_bounds__(256) void ppo_gae_runs_apply_kernel(Src src, int64_t n, const float *__restrict__ carry_x,
+                                                                 int64_t n_carry) {
+    __shared__ float wc[4], wd[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t base = (int64_t)blockIdx.x * GR_BLOCK + wave * GR_WAVE;
+    float cs[GR_CHUNKS], ds[GR_CHUNKS];             // suffix composites inside each chunk, kept for the second walk
+    float C = 1.f, D = 0.f;
+#pragma unroll
+    for (int q = GR_CHUNKS - 1; q >= 0; --q) {
+        src.load(base + q * 64 + lane, n, true, cs[q], ds[q]);
+        gae_suffix_scan(cs[q], ds[q], lane);
+        gr_compose(__shfl(cs[q], 0), __shfl(ds[q], 0), C, D);
+    }
+    if (lane == 0) { wc[wave] = C; wd[wave] = D; }
+    __syncthreads();
+    // what enters this wavefront from behind: the next workgroup's value pushed through the wavefronts in between
+    const int64_t nb = (int64_t)blockIdx.x + 1;
+    float x = (carry_x && nb < n_carry) ? carry_x[nb] : 0.f;
+    for (int w = 3; w > wave; --w) x = gr_eval(wc[w], wd[w], x);
+#pragma unroll
+    for (int q = GR_CHUNKS - 1; q >= 0; --q) {
+        const float a = gr_eval(cs[q], ds[q], x);
+        const int64_t i = base + q * 64 + lane;
+        if (i < n) src.store(i, a);
+        x = __shfl(a, 0);
+    }
+}
+
+// link_j of the header, four records per thread; the out-of-pattern count as one integer atomic per wavefront
+__global__ __launch_bounds__(256) void ppo_run_ends_kernel(const int32_t *__restrict__ t, const int32_t *__restrict__ n,
+                                                           const float *__restrict__ goal, const uint8_t *__restrict__ done,
+                                                           int64_t H, uint8_t *__restrict__ run_end,
+                                                           int32_t *__restrict__ broken) {
+    int count = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t j = ((int64_t)blockIdx.x * 4 + k) * 256 + threadIdx.x;
+        bool brk = false;
+        if (j < H) {
+            const bool dn = done[j] != 0;
+            bool link = false;
+            if (!dn && j + 1 < H)                   // nothing at index H is read
+                link = n[j + 1] == n[j] && (int64_t)t[j + 1] == (int64_t)t[j] + 1 && goal[2 * j + 2] == goal[2 * j] &&
+                       goal[2 * j + 3] == goal[2 * j + 1];
+            run_end[j] = link ? 0 : 1;
+            brk = !dn && !link;
+        }
+        count += __popcll(__ballot(brk));
+    }
+    if (broken && (threadIdx.x & 63) == 0 && count) atomicAdd(broken, count);
+}
+
 // ------------------------------------------------------------------ advantage normalisation
 __global__ __launch_bounds__(256) void ppo_moments_kernel(const float *__restrict__ x, int64_t n, double *__restrict__ ws) {
     __shared__ double lds[2 * 256];
@@ -1139,6 +1279,15 @@ template <typename... P> bool aligned16(const P *...p) { return ((... | (uintptr
 // every pointer on the alignment of its own element type (float / int32: 4 bytes, double / int64: 8); NULL counts as aligned
 template <typename... P> bool aligned_natural(const P *...p) { return (... && ((uintptr_t)p % alignof(P) == 0)); }
 bool ep_count_ok(int64_t M) { return M < ((int64_t)1 << 40); }      // T * N of the episode entries: a thread's run stays an int
+bool gr_count_ok(int64_t H) { return H > 0 && H < ((int64_t)1 << 40); }    // the record entries: grids and workspace stay ints
+// Levels of the scan tree of ppo_gae_runs: n[0] = H records, n[l + 1] = ceil(n[l] / GR_BLOCK) composites for as long as
+// level l has more maps than one workgroup takes.  Returns the number of levels (>= 1).
+int gr_levels(int64_t H, int64_t (&n)[GR_MAX_LEVELS]) {
+    int levels = 1;
+    n[0] = H;
+    while (n[levels - 1] > GR_BLOCK) { n[levels] = (n[levels - 1] + GR_BLOCK - 1) / GR_BLOCK; ++levels; }
+    return levels;
+}
 int blocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
 int blocks_capped(int64_t n, int per, int cap) { return (int)((n + per - 1) / per < cap ? (n + per - 1) / per : cap); }
 int ep_summary_blocks(int64_t M) { return blocks_capped(M, EP_BLOCK_ELEMS, EP_MAX_BLOCKS); }
@@ -1203,6 +1352,58 @@ int ppo_gae(const float *reward, const float *value, const float *next_value, co
     };
     if (N >= 16384) launch(int_c<64>{});
     else launch(int_c<16>{});
+    return tw_launched(__func__);
+}
+
+int ppo_run_ends(const int32_t *t, const int32_t *n, const float *goal, const uint8_t *done, int64_t H, uint8_t *run_end,
+                 int32_t *broken, void *launch_stream) {
+    if (!all_set(t, n, goal, done, run_end) || !gr_count_ok(H)) return TW_E_ARG;
+    hipLaunchKernelGGL(ppo_run_ends_kernel, dim3(blocks(H, 1024)), dim3(256), 0, (hipStream_t)launch_stream, t, n, goal,
+                       done, H, run_end, broken);
+    return tw_launched(__func__);
+}
+
+int ppo_gae_runs_workspace(int64_t H) {
+    if (!gr_count_ok(H)) return TW_E_ARG;
+    int64_t n[GR_MAX_LEVELS];
+    const int levels = gr_levels(H, n);
+    int64_t floats = 0;
+    for (int l = 1; l < levels; ++l) floats += 2 * n[l];
+    return (int)(floats > 2 ? floats : 2);
+}
+
+int ppo_gae_runs(const float *reward, const float *value, const float *next_value, const uint8_t *done,
+                 const uint8_t *run_end, float gamma, float lambda, int use_done_mask, int64_t H, float *adv, float *target,
+                 float *ret, float *workspace, void *launch_stream) {
+    if (!all_set(reward, value, next_value, run_end, workspace) || !gr_count_ok(H) || (use_done_mask && !done))
+        return TW_E_ARG;
+    hipStream_t st = (hipStream_t)launch_stream;
+    int64_t n[GR_MAX_LEVELS];
+    const int levels = gr_levels(H, n);
+    float *lc[GR_MAX_LEVELS] = {}, *ld[GR_MAX_LEVELS] = {};      // level l >= 1: c[n_l] then d[n_l]
+    for (int l = 1; l < levels; ++l) {
+        lc[l] = l == 1 ? workspace : ld[l - 1] + n[l - 1];
+        ld[l] = lc[l] + n[l];
+    }
+    const gr_records rec{reward, value, next_value, done, run_end, gamma, lambda, use_done_mask, adv, target, ret};
+    for (int l = 0; l + 1 < levels; ++l) {                       // up: the composites of every level but the top
+        if (l == 0)
+            hipLaunchKernelGGL(ppo_gae_runs_reduce_kernel<gr_records>, dim3((unsigned)n[1]), dim3(256), 0, st, rec, H, lc[1],
+                               ld[1]);
+        else
+            hipLaunchKernelGGL(ppo_gae_runs_reduce_kernel<gr_composites>, dim3((unsigned)n[l + 1]), dim3(256), 0, st,
+                               gr_composites{lc[l], ld[l]}, n[l], lc[l + 1], ld[l + 1]);
+    }
+    for (int l = levels - 1; l >= 0; --l) {                      // down: the top from x = 0, the rest from the level above
+        const float *carry = l + 1 < levels ? ld[l + 1] : nullptr;
+        const int64_t n_carry = l + 1 < levels ? n[l + 1] : 0;
+        const dim3 grid((unsigned)blocks(n[l], GR_BLOCK));
+        if (l == 0)
+            hipLaunchKernelGGL(ppo_gae_runs_apply_kernel<gr_records>, grid, dim3(256), 0, st, rec, H, carry, n_carry);
+        else
+            hipLaunchKernelGGL(ppo_gae_runs_apply_kernel<gr_composites>, grid, dim3(256), 0, st, gr_composites{lc[l], ld[l]},
+                               n[l], carry, n_carry);
+    }
     return tw_launched(__func__);
 }
 

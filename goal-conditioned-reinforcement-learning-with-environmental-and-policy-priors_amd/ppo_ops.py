@@ -44,6 +44,35 @@ def gae(reward, value, next_value, done=None, gamma=0.99, lam=0.0, use_done_mask
     return adv, target, ret
 
 
+def run_ends(t, n, goal, done, broken=None):
+    """Where the runs of a flat record array end (ppo_run_ends, include/twoarmy_ppo.h) -> uint8[H]: 1 unless the record
+    behind continues the run (not done, same env, next step, same goal).  t, n int32[H], goal f32[H,2], done u8[H], e.g.
+    the records of her_relabel.  broken: an int32[1] device tensor that gets ADDED the number of records that are not
+    done and still end a run (out of pattern)."""
+    H = t.numel()
+    assert n.shape == (H,) and goal.shape == (H, 2) and done.shape == (H,) and (broken is None or broken.shape == (1,))
+    run_end = torch.empty(H, dtype=torch.uint8, device=t.device)
+    _call("ppo_run_ends", t, _p(t, torch.int32), _p(n, torch.int32), _p(goal, torch.float32), _p(done, torch.uint8), H,
+          _p(run_end), _p(broken, torch.int32))
+    return run_end
+
+
+def gae_runs(reward, value, next_value, done, run_end, gamma, lam, use_done_mask, want_ret=True):
+    """gae() along a flat record array, cut at the run ends instead of scanned per column (ppo_gae_runs,
+    include/twoarmy_ppo.h) -> (adv, target, ret), each [H].  done may be None without the done mask."""
+    H = reward.numel()
+    assert reward.shape == (H,) and value.shape == (H,) and next_value.shape == (H,) and run_end.shape == (H,)
+    assert done is None or done.shape == (H,)
+    adv = torch.empty_like(reward)
+    target = torch.empty_like(reward)
+    ret = torch.empty_like(reward) if want_ret else None
+    ws = torch.empty(_query("ppo_gae_runs_workspace", H), dtype=torch.float32, device=reward.device)
+    _call("ppo_gae_runs", reward, _p(reward, torch.float32), _p(value, torch.float32), _p(next_value, torch.float32),
+          _p(done, torch.uint8), _p(run_end, torch.uint8), gamma, lam, int(bool(use_done_mask)), H, _p(adv), _p(target),
+          _p(ret), _p(ws))
+    return adv, target, ret
+
+
 def adv_norm_(adv, eps=1e-8):
     ws = torch.empty(4096, dtype=torch.float64, device=adv.device)
     _call("ppo_adv_norm", adv, _p(adv, torch.float32), adv.numel(), eps, _p(ws))

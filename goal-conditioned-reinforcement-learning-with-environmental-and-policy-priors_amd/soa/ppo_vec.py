@@ -97,6 +97,8 @@ class VecPPOTrainer:
         agent.to(d)
         self.her = None                       # relabelled index records of the current rollout (relabel())
         self.her_out_of_pattern = 0           # records of the last update whose V(s') could not be taken from a neighbour
+        self.her_gae = False                  # GAE(lambda) along the relabelled runs instead of their one-step targets
+        self.her_targets = None               # her_gae: {"value", "next_value", "run_end"} of the last compute_targets()
         # hindsight relabelling looks back over every rollout an episode ending now may have started in:
         # ceil((max_steps - 1) / T) earlier ones; each entry is (pos, term, trunc, reward, age0) of one rollout
         self.max_steps = int(getattr(engine, "max_steps", 50))
@@ -325,11 +327,49 @@ class VecPPOTrainer:
         ok_next = torch.zeros_like(done)
         ok_next[:-1] = (n[1:] == n[:-1]) & (t[1:] == t[:-1] + 1) & (g[1:] == g[:-1]).all(-1)
         need = torch.nonzero(done | ~ok_next).view(-1)          # run ends, plus anything out of pattern (incl. the last row)
+        hnv = self._next_values_from_neighbours(h, hgoal, hv, need)
+        self.her_out_of_pattern = int((~done & ~ok_next).sum())
+        return hnv
+
+    def _next_values_from_neighbours(self, h, hgoal, hv, need):
+        """V(s') of every record: V(s) of the record behind it, except at the indices `need`, whose after-states are
+        evaluated."""
         hnv = torch.full_like(hv, float("nan"))                  # a row nobody fills would poison the loss visibly
         hnv[:-1] = hv[1:]
         hnv[need] = self._values_one(h["t"][need], h["n"][need], hgoal[need], True)
-        self.her_out_of_pattern = int((~done & ~ok_next).sum())
         return hnv
+
+    def _her_targets_one_step(self, h, hgoal):
+        """The default: the reference's one-step target with the relabelled goal and reward (PPO.py:112-114)."""
+        assert self.agent.gae_lambda == 0.0 and not self.agent.use_done_mask, "HER records use the TD(0) targets"
+        if self.reuse_next_values:
+            # a relabelled prefix is a run of consecutive steps of one episode under ONE goal that ends with its
+            # done record (ppo_her_relabel's emission order), so V(s'_j) of a record that is not done is V(s) of the
+            # record behind it; only the prefix ends are evaluated on their after-states
+            hv = self._values_one(h["t"], h["n"], hgoal, False)
+            hnv = self._her_next_values(h, hgoal, hv)
+        else:
+            hv, hnv = self._values(h["t"], h["n"], hgoal)
+        H = hv.numel()
+        hadv, htarget, _ = ppo_ops.gae(h["reward"].view(1, H), hv.view(1, H), hnv.view(1, H), None,
+                                       gamma=self.agent.gamma, lam=0.0, use_done_mask=False)
+        return hadv.view(-1), htarget.view(-1)
+
+    def _her_targets_gae(self, h, hgoal):
+        """her_gae: GAE(lambda) over the relabelled records, scanned along each run and cut at its end (ppo_run_ends +
+        ppo_gae_runs) -> (adv, critic target).  A record that breaks the run pattern is a run of its own: its after-state
+        is evaluated and its advantage is its one-step delta.  The done mask follows the agent as for the rollout rows;
+        without it a run's last record keeps its bootstrap like every done record of the reference (PPO.py:113)."""
+        ag = self.agent
+        hv = self._values_one(h["t"], h["n"], hgoal, False)
+        broken = torch.zeros(1, dtype=torch.int32, device=self.device)
+        run_end = ppo_ops.run_ends(h["t"], h["n"], h["goal"], h["done"], broken)
+        hnv = self._next_values_from_neighbours(h, hgoal, hv, torch.nonzero(run_end).view(-1))
+        self.her_out_of_pattern = int(broken)
+        self.her_targets = dict(value=hv, next_value=hnv, run_end=run_end)
+        hadv, htarget, hret = ppo_ops.gae_runs(h["reward"], hv, hnv, h["done"], run_end, ag.gamma, ag.gae_lambda,
+                                               ag.use_done_mask)
+        return hadv, htarget if ag.gae_lambda == 0.0 else hret
 
     @torch.no_grad()
     def compute_targets(self):
@@ -345,23 +385,14 @@ class VecPPOTrainer:
         critic_target = target if self.agent.gae_lambda == 0.0 else ret
         adv, critic_target = adv.view(-1), critic_target.view(-1)
         if self.her is not None and self.her["t"].numel():
-            # relabelled records: the reference's one-step target with the relabelled goal and reward (PPO.py:112-114)
-            assert self.agent.gae_lambda == 0.0 and not self.agent.use_done_mask, "HER records use the TD(0) targets"
-            h = self.her
+            h = self.her                                          # relabelled records, with their own goals and rewards
             hgoal = self.sample_goal(h["t"], h["n"], h["goal"], h["done"])
-            if self.reuse_next_values:
-                # a relabelled prefix is a run of consecutive steps of one episode under ONE goal that ends with its
-                # done record (ppo_her_relabel's emission order), so V(s'_j) of a record that is not done is V(s) of the
-                # record behind it; only the prefix ends are evaluated on their after-states
-                hv = self._values_one(h["t"], h["n"], hgoal, False)
-                hnv = self._her_next_values(h, hgoal, hv)
+            if self.her_gae:
+                hadv, htarget = self._her_targets_gae(h, hgoal)
             else:
-                hv, hnv = self._values(h["t"], h["n"], hgoal)
-            H = hv.numel()
-            hadv, htarget, _ = ppo_ops.gae(h["reward"].view(1, H), hv.view(1, H), hnv.view(1, H), None,
-                                           gamma=self.agent.gamma, lam=0.0, use_done_mask=False)
-            adv = torch.cat([adv, hadv.view(-1)])
-            critic_target = torch.cat([critic_target, htarget.view(-1)])
+                hadv, htarget = self._her_targets_one_step(h, hgoal)
+            adv = torch.cat([adv, hadv])
+            critic_target = torch.cat([critic_target, htarget])
         if self.agent.normalize_adv:
             if self.agent.grad_sync is not None and torch.distributed.is_initialized() and \
                     torch.distributed.get_world_size() > 1:

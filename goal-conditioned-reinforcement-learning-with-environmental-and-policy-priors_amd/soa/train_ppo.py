@@ -42,6 +42,9 @@ success sample as a prior-only row; all off by default.
 per minibatch, one host read per update) and appends `ent`, `kl`, `clipfrac`, `ev` (of the last epoch that ran) and
 `epochs` to the log line; --target_kl X (implies it) skips the remaining epochs of an update once an epoch's `kl` exceeds X
 (one two-element host read per epoch); both off by default.
+--her_gae (plain PPO agent) keeps the hindsight records when --gae_lambda > 0: their advantages are GAE(lambda) scanned
+along each relabelled run on the device (ppo_ops.run_ends + gae_runs, two calls per update) instead of the one-step
+targets that --gae_lambda 0 uses; without it --gae_lambda > 0 trains on the rollout alone; off by default.
 """
 import argparse
 import math
@@ -103,6 +106,10 @@ def build_parser():
     p.add_argument("--k_epochs_orientation", type=int, default=50, help="SoA: epochs of the orientation head per update")
     p.add_argument("--gae_lambda", type=float, default=0.0)
     p.add_argument("--normalize_adv", action="store_true")
+    p.add_argument("--her_gae", action="store_true",
+                   help="with --gae_lambda > 0: relabel as with --gae_lambda 0 and give the hindsight records GAE(lambda) "
+                        "advantages, scanned along each relabelled run and cut at its end on the device; plain PPO agent "
+                        "only; off by default (then --gae_lambda > 0 switches relabelling off)")
     p.add_argument("--score", default="rollout", choices=["rollout", "episode"],
                    help="what drives the HER switch and the logged score: rollout = one EMA step per rollout with the "
                         "rollout's reward sum over its finished episodes; episode = the reference's fold, one step per "
@@ -214,6 +221,12 @@ def build_parser():
                    help="KL early stop: skip the remaining epochs of an update after an epoch whose `kl` exceeds X (one small "
                         "host read per epoch; summed over the ranks first); implies --update_stats; off by default")
     return p
+
+
+def relabel_wanted(her, gae_lambda, her_gae):
+    """Whether this update relabels: the HER switch is on, and the records have targets -- the one-step ones at
+    lambda = 0, GAE along their runs with --her_gae."""
+    return bool(her) and (gae_lambda == 0.0 or bool(her_gae))
 
 
 def update_fields(us):
@@ -351,6 +364,8 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--orient_prior_hindsight_timed needs --orient_prior_hindsight")
     if not 1 <= args.orient_prior_steps <= 3:
         raise SystemExit("--orient_prior_steps must be 1, 2 or 3")
+    if args.her_gae and (predictor or soa):
+        raise SystemExit("--her_gae: plain PPO agent only")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -423,6 +438,7 @@ def main(argv=None, predictor=False, soa=False):
                                          hindsight_timed=args.orient_prior_hindsight_timed)
     if args.update_stats:
         trainer.enable_update_stats(args.target_kl)
+    trainer.her_gae = args.her_gae
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
@@ -431,10 +447,11 @@ def main(argv=None, predictor=False, soa=False):
         if args.bonus != "none" or use_shaping:
             trainer.shape_rewards()
         her = trainer.her_switch(her, score)                  # train_ppo.py:128-131 of the reference
-        if her and agent.gae_lambda == 0.0:
+        relabel = relabel_wanted(her, agent.gae_lambda, args.her_gae)
+        if relabel:
             trainer.relabel()
         if use_shaping:                                       # behind relabel(): the records copy the unshaped reward_train
-            trainer.shape_potential(expect_her=her and agent.gae_lambda == 0.0)
+            trainer.shape_potential(expect_her=relabel)
         trainer.account_episodes()
         if args.visit_dir:
             trainer.account_visits(trainer.her)

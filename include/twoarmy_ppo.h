@@ -50,6 +50,45 @@ int ppo_gae(const float *reward, const float *value, const float *next_value, co
             float gamma, float lambda, int use_done_mask, int T, int N, float *adv, float *target, float *ret,
             void *stream);
 
+/* GAE(lambda) for the hindsight records of ppo_her_relabel, which form no [T][N] tile: a flat array of H records that
+ * come as RUNS of consecutive steps of one env under one goal, each run ending with its own done record.
+ *
+ * ppo_run_ends: where the runs end, one launch.  For j < H - 1
+ *   link_j = done_j == 0 && n_{j+1} == n_j && t_{j+1} == t_j + 1 && goal_{j+1}[0] == goal_j[0] && goal_{j+1}[1] == goal_j[1]
+ * (float compares: a NaN never links, -0.0 links with +0.0), link_{H-1} = 0 and nothing at index H is read;
+ * run_end_j = !link_j.  `broken` int32[1] | NULL, in/out, gets ADDED the number of j with done_j == 0 && !link_j: the
+ * records that break the run pattern (external `choices`, a permuted array).  An integer atomic per wavefront: exact.
+ *   t, n int32[H]; goal float[H][2]; done uint8[H]; run_end uint8[H]
+ * TW_E_ARG, and nothing is launched: NULL t, n, goal, done or run_end; H <= 0 or H >= 2^40.
+ *
+ * ppo_gae_runs: ppo_gae's formula and rounding sequence along the array, cut at the run ends:
+ *   cut_j = (use_done_mask && done_j) ? 0 : 1;   tv_j = r_j + (gamma * nv_j) * cut_j;   delta_j = tv_j - v_j
+ *   c_j = (run_end_j || j == H - 1) ? 0 : gamma * lambda * cut_j;   A_j = c_j != 0 ? fma(c_j, A_{j+1}, delta_j) : delta_j
+ *   adv = A, target = tv, ret = A + v   (each nullable)
+ * The run ends cut the scan, not the done flags: without the done mask (the reference, PPO.py:113) a done record keeps
+ * its bootstrap gamma * nv, and a record that breaks the pattern is a run of its own with A = delta.  Where c_j = 0,
+ * A_j is delta_j exactly: a non-finite delta never leaves its run.  With lambda = 0, or every run_end set, adv, target
+ * and ret are bit for bit what ppo_gae gives on the same arrays as [1][H].
+ * Runs may have any length and start anywhere.  The scan is a tree, not a walk: a workgroup takes 2048 consecutive
+ * records, its four wavefronts 8 chunks of 64 each (6 shuffle steps over affine maps, as ppo_gae, then a fold over the
+ * chunks and the wavefronts), and writes its composite map to `workspace`; the composites are scanned the same way
+ * (2048 per workgroup, a level more for every factor of 2048 in H), and an apply pass per level hands every workgroup
+ * the value that enters it from behind.  Launches: 1 for H <= 2048, 3 up to 2048^2, 5 up to 2048^3, 7 beyond; the
+ * serial depth is 8 chunks + 4 wavefronts per level, whatever H.  Every combine keeps the c != 0 guard.
+ * `workspace`: ppo_gae_runs_workspace(H) floats = 2 * (n_1 + n_2 + ...) with n_0 = H, n_{l+1} = ceil(n_l / 2048) for as
+ * long as n_l > 2048, at least 2; every entry is written before it is read (no initialisation needed).  All launches go
+ * to `launch_stream` (a hipStream_t as void*, like `stream` elsewhere), nothing is allocated or read back between them:
+ * the call may be captured into a graph and replayed.  Deterministic: two calls on equal inputs give equal bits.
+ *   reward, value, next_value float[H]; done uint8[H] (nullable when !use_done_mask); run_end uint8[H]
+ * TW_E_ARG, and nothing is launched: NULL reward, value, next_value, run_end or workspace; use_done_mask with a NULL
+ * done; H <= 0 or H >= 2^40.  ppo_gae_runs_workspace: host only; TW_E_ARG for H <= 0 or H >= 2^40. */
+int ppo_run_ends(const int32_t *t, const int32_t *n, const float *goal, const uint8_t *done, int64_t H,
+                 uint8_t *run_end, int32_t *broken, void *launch_stream);
+int ppo_gae_runs(const float *reward, const float *value, const float *next_value, const uint8_t *done,
+                 const uint8_t *run_end, float gamma, float lambda, int use_done_mask, int64_t H,
+                 float *adv, float *target, float *ret, float *workspace, void *launch_stream);
+int ppo_gae_runs_workspace(int64_t H);
+
 /* adv <- (adv - mean) / (std + eps), std unbiased (torch.Tensor.std default).  workspace: >= 4096 doubles. */
 int ppo_adv_norm(float *adv, int64_t n, float eps, double *workspace, void *stream);
 

@@ -43,6 +43,20 @@ report("ppo_gae lambda=0 (reference targets)", T * N * (3 * 4 + 3 * 4),
        timed(lambda: ppo_ops.gae(r, v, nv, None, gamma=0.99, lam=0.0, use_done_mask=False)))
 report("ppo_gae lambda=0.95 + done mask", T * N * (3 * 4 + 1 + 3 * 4),
        timed(lambda: ppo_ops.gae(r, v, nv, done, gamma=0.99, lam=0.95, use_done_mask=True)))
+# hindsight records: H = 2^21 in runs of 1..64 (what ppo_her_relabel emits), against the one-step call on [1][H] they use
+# without her_gae.  Floor: 3 floats + 2 bytes read, 3 floats written per record; the scan reads its inputs twice (40 B).
+H = 1 << 21
+hr, hv, hnv = (torch.randn(H, generator=g).to(dev) for _ in range(3))
+run_end = torch.zeros(H, dtype=torch.uint8)
+run_end[torch.cumsum(torch.randint(1, 65, (H,), generator=g), 0).clamp_(max=H) - 1] = 1
+run_end = run_end.to(dev)
+rt = torch.arange(H, dtype=torch.int32, device=dev)
+rn, rgoal = torch.zeros(H, dtype=torch.int32, device=dev), torch.zeros((H, 2), device=dev)
+report("ppo_gae [1][H] lambda=0 (records today)", H * (3 * 4 + 3 * 4),
+       timed(lambda: ppo_ops.gae(hr.view(1, H), hv.view(1, H), hnv.view(1, H), None, gamma=0.99, lam=0.0)))
+report("ppo_gae_runs lambda=0.95 + done mask", H * (3 * 4 + 2 + 3 * 4),
+       timed(lambda: ppo_ops.gae_runs(hr, hv, hnv, run_end, run_end, 0.99, 0.95, True)), "3 launches, inputs read twice")
+report("ppo_run_ends", H * (4 + 4 + 8 + 1 + 1), timed(lambda: ppo_ops.run_ends(rt, rn, rgoal, run_end)))
 adv = torch.randn(T * N, generator=g).to(dev)
 report("ppo_adv_norm (2 passes)", T * N * (4 + 4 + 4), timed(lambda: ppo_ops.adv_norm_(adv)))
 
