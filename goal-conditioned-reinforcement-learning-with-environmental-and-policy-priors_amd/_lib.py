@@ -77,8 +77,8 @@ _SIGS = {
     "tw_alloc_outputs": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(TwOutputs)]),
     "tw_free_outputs": (C.c_int, [C.POINTER(TwOutputs)]),
     "tw_abi_sizeof_outputs": (C.c_int, []),
-    "tw_time_rollout": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp,
-                                  C.POINTER(C.c_float)]),
+    "tw_time_rollout": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
+                                  C.POINTER(C.c_float), _vp]),
 }
 
 _f, _i, _u64, _i64 = C.c_float, C.c_int, C.c_uint64, C.c_int64

@@ -1356,9 +1356,9 @@ int ppo_gae(const float *reward, const float *value, const float *next_value, co
 }
 
 int ppo_run_ends(const int32_t *t, const int32_t *n, const float *goal, const uint8_t *done, int64_t H, uint8_t *run_end,
-                 int32_t *broken, void *launch_stream) {
+                 int32_t *broken, void *stream) {
     if (!all_set(t, n, goal, done, run_end) || !gr_count_ok(H)) return TW_E_ARG;
-    hipLaunchKernelGGL(ppo_run_ends_kernel, dim3(blocks(H, 1024)), dim3(256), 0, (hipStream_t)launch_stream, t, n, goal,
+    hipLaunchKernelGGL(ppo_run_ends_kernel, dim3(blocks(H, 1024)), dim3(256), 0, (hipStream_t)stream, t, n, goal,
                        done, H, run_end, broken);
     return tw_launched(__func__);
 }
@@ -1374,10 +1374,10 @@ int ppo_gae_runs_workspace(int64_t H) {
 
 int ppo_gae_runs(const float *reward, const float *value, const float *next_value, const uint8_t *done,
                  const uint8_t *run_end, float gamma, float lambda, int use_done_mask, int64_t H, float *adv, float *target,
-                 float *ret, float *workspace, void *launch_stream) {
+                 float *ret, float *workspace, void *stream) {
     if (!all_set(reward, value, next_value, run_end, workspace) || !gr_count_ok(H) || (use_done_mask && !done))
         return TW_E_ARG;
-    hipStream_t st = (hipStream_t)launch_stream;
+    hipStream_t st = (hipStream_t)stream;
     int64_t n[GR_MAX_LEVELS];
     const int levels = gr_levels(H, n);
     float *lc[GR_MAX_LEVELS] = {}, *ld[GR_MAX_LEVELS] = {};      // level l >= 1: c[n_l] then d[n_l]
@@ -1444,13 +1444,13 @@ int ppo_loss_stats_workspace(int B) { return B > 0 ? blocks(B, 256) * LS_NV : TW
 int ppo_loss_fwd_bwd_stats(const float *probs, const int32_t *action, const float *old_logp, const float *adv,
                            const float *value, const float *target_v, int B, int n_valid, int A, float clip,
                            float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
-                           double *stats, double *stats_workspace, void *launch_stream) {
+                           double *stats, double *stats_workspace, void *stream) {
     if (!all_set(probs, action, old_logp, adv, value, target_v, losses, grad_probs, grad_value, workspace, stats,
                  stats_workspace) || B <= 0 || A != 5 || n_valid <= 0 || n_valid > B ||       // the masked entry's rules
         !aligned_natural(stats, stats_workspace))
         return TW_E_ARG;
     const int nblocks = blocks(B, 256);
-    hipStream_t st = (hipStream_t)launch_stream;
+    hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((ppo_loss_kernel<5, true>), dim3(nblocks), dim3(256), 0, st, probs, action, old_logp, adv, value,
                        target_v, B, n_valid, clip, ent_coef, grad_probs, grad_value, workspace, stats_workspace);
     hipLaunchKernelGGL(ppo_loss_stats_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, stats_workspace, nblocks,

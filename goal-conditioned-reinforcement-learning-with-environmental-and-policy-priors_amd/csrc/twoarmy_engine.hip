@@ -2109,7 +2109,7 @@ const char *tw_build_id(void) { return TW_BUILD_ID; }
 
 int tw_time_rollout(tw_engine *e, int T, const int32_t *actions, uint8_t *obs, int obs_pitch, float *state_matrix,
                     int mat_pitch, float *pos, float *reward, uint8_t *terminated, uint8_t *truncated, int flags,
-                    int iters, void *stream, float *ms_per_launch) {
+                    int iters, float *ms_per_launch, void *stream) {
     if (!e || T <= 0 || iters <= 0 || !ms_per_launch) return TW_E_ARG;
     DeviceGuard g(e->device);
     hipStream_t st = (hipStream_t)stream;

@@ -521,7 +521,7 @@ class TwoarmyEngine:
         flags = (TW_F_AUTORESET if autoreset else 0) | TW_F_POLICY_IDX
         outs, flags = self._out_args((T, self.num_envs), out, flags)
         _lib.check(_lib.lib().tw_time_rollout(self._h, T, ptr(actions, torch.int32), *outs, flags, iters,
-                                              stream(self.device), C.byref(ms)), "tw_time_rollout")
+                                              C.byref(ms), stream(self.device)), "tw_time_rollout")
         return ms.value
 
     # ------------------------------------------------------------------ state

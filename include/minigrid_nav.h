@@ -446,14 +446,13 @@ int mg_nav_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int
  * mg_nav_goal_ahead's; (c) at steps = 1 the label is the image of mg_nav_timed_goal_moves' move set (invariant (a) of the
  * look-ahead block), with the same acting_dist; (d) ahead[b] != 0 iff acting_dist[b] != MG_NAV_UNREACHABLE.
  * n_records == 0 returns 0 and launches nothing.
- * launch_stream is the `stream` of every other entry, spelt apart because its two stream checks live with its own GPU tests.
  * TW_E_ARG: the cases of mg_nav_timed_goal_moves with ahead for moves; steps outside 1..MG_NAV_AHEAD_MAX_STEPS; ahead not
  * 8-byte aligned. */
 int mg_nav_timed_goal_ahead(const uint8_t *type, const uint8_t *state, int n_envs, int width, int height,
                             uint32_t pass_types, int flags, const uint32_t *blocked, int64_t blocked_env_stride,
                             int period, const int32_t *rec_t, const int32_t *rec_n, const float *rec_goal,
                             int64_t n_records, const float *pos, const int32_t *age, const float *init_pos, int T,
-                            int steps, uint64_t *ahead, uint16_t *acting_dist, void *launch_stream);
+                            int steps, uint64_t *ahead, uint16_t *acting_dist, void *stream);
 
 /* Host only, no launch: how many floods a workgroup of mg_nav_timed_goal_ahead runs at a time at this size and period: by the
  * formula of mg_nav_timed_goal_shape_floods with MG_NAV_TIMED_GOAL_AHEAD_LDS, the workgroup's staging in bytes -- the move

@@ -216,7 +216,7 @@ int tw_abi_sizeof_outputs(void);      /* sizeof(tw_outputs) of the built library
 int tw_time_rollout(tw_engine *e, int T, const int32_t *actions, uint8_t *obs, int obs_pitch,
                     float *state_matrix, int mat_pitch, float *pos, float *reward, uint8_t *terminated,
                     uint8_t *truncated, int flags,
-                    int iters, void *stream, float *ms_per_launch);
+                    int iters, float *ms_per_launch, void *stream);
 
 #ifdef __cplusplus
 }

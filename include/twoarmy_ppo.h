@@ -77,16 +77,16 @@ int ppo_gae(const float *reward, const float *value, const float *next_value, co
  * serial depth is 8 chunks + 4 wavefronts per level, whatever H.  Every combine keeps the c != 0 guard.
  * `workspace`: ppo_gae_runs_workspace(H) floats = 2 * (n_1 + n_2 + ...) with n_0 = H, n_{l+1} = ceil(n_l / 2048) for as
  * long as n_l > 2048, at least 2; every entry is written before it is read (no initialisation needed).  All launches go
- * to `launch_stream` (a hipStream_t as void*, like `stream` elsewhere), nothing is allocated or read back between them:
- * the call may be captured into a graph and replayed.  Deterministic: two calls on equal inputs give equal bits.
+ * to `stream`, nothing is allocated or read back between them: the call may be captured into a graph and replayed.
+ * Deterministic: two calls on equal inputs give equal bits.
  *   reward, value, next_value float[H]; done uint8[H] (nullable when !use_done_mask); run_end uint8[H]
  * TW_E_ARG, and nothing is launched: NULL reward, value, next_value, run_end or workspace; use_done_mask with a NULL
  * done; H <= 0 or H >= 2^40.  ppo_gae_runs_workspace: host only; TW_E_ARG for H <= 0 or H >= 2^40. */
 int ppo_run_ends(const int32_t *t, const int32_t *n, const float *goal, const uint8_t *done, int64_t H,
-                 uint8_t *run_end, int32_t *broken, void *launch_stream);
+                 uint8_t *run_end, int32_t *broken, void *stream);
 int ppo_gae_runs(const float *reward, const float *value, const float *next_value, const uint8_t *done,
                  const uint8_t *run_end, float gamma, float lambda, int use_done_mask, int64_t H,
-                 float *adv, float *target, float *ret, float *workspace, void *launch_stream);
+                 float *adv, float *target, float *ret, float *workspace, void *stream);
 int ppo_gae_runs_workspace(int64_t H);
 
 /* adv <- (adv - mean) / (std + eps), std unbiased (torch.Tensor.std default).  workspace: >= 4096 doubles. */
@@ -142,15 +142,15 @@ int ppo_loss_fwd_bwd_masked(const float *probs, const int32_t *action, const flo
  * and 0), and which partials meet where does not depend on the number of workgroups: a padded call and the unpadded call on
  * the first n_valid rows leave equal bits in all of `stats`.  Cutting one batch into several calls changes the sums by double
  * rounding only; counts and the maximum do not change.
- * Two launches, both on `launch_stream` (a hipStream_t as void*, like `stream` elsewhere), nothing allocated or read back
- * between them: the call may be captured into a graph and replayed.
+ * Two launches, both on `stream`, nothing allocated or read back between them: the call may be captured into a graph and
+ * replayed.
  * TW_E_ARG, and nothing is launched: the rules of ppo_loss_fwd_bwd_masked (every pointer set, B > 0, A == 5,
  * 0 < n_valid <= B), NULL stats or stats_workspace, either of the two off 8-byte alignment.
  * ppo_loss_stats_workspace: host only; TW_E_ARG for B <= 0. */
 int ppo_loss_fwd_bwd_stats(const float *probs, const int32_t *action, const float *old_logp, const float *adv,
                            const float *value, const float *target_v, int B, int n_valid, int A, float clip,
                            float ent_coef, float *losses, float *grad_probs, float *grad_value, float *workspace,
-                           double *stats, double *stats_workspace, void *launch_stream);
+                           double *stats, double *stats_workspace, void *stream);
 int ppo_loss_stats_workspace(int B);
 
 /* Shortest-path prior: a set-valued imitation term on the actor, forward + backward for one minibatch.  No reference

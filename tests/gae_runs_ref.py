@@ -1,9 +1,11 @@
 """float64 statement of ppo_gae_runs and a numpy restatement of ppo_run_ends (include/twoarmy_ppo.h), shared by
-test_gae_runs_cpu.py and test_gae_runs_gpu.py.  A plain module like update_stats_ref.py; it mirrors _gae64 of
+test_gae_runs_cpu.py, test_gae_runs_gpu.py and the two cases of test_streams_gpu.py, with the record generator and the
+rounding bound of the scan they use.  A plain module like update_stats_ref.py; it mirrors _gae64 of
 test_ppo_kernels_edges_gpu.py, along a flat record array cut at the run ends instead of along the columns of a tile."""
 import numpy as np
 
 EPS32 = 2.0 ** -23
+CHUNK, BLOCK = 64, 2048                          # records per shuffle scan / per workgroup (GR_BLOCK)
 
 
 def run_ends(t, n, goal, done):
@@ -93,3 +95,50 @@ def dones(run_end, seed, mid_run=0.02):
     the done mask cuts at and reference mode scans through)."""
     rs = np.random.RandomState(2000 + seed)
     return (run_end | (rs.rand(len(run_end)) < mid_run)).astype(np.uint8)
+
+
+def _records(H, seed):
+    """Records in ppo_her_relabel's shape: runs of 1..64 consecutive steps of one env under one goal, each ending done."""
+    rs = np.random.RandomState(seed)
+    end = pattern("her", H, seed)
+    run = np.concatenate([[0], np.cumsum(end)[:-1]]).astype(np.int64)          # run index of every record
+    start = np.concatenate([[0], np.nonzero(end)[0] + 1])[run]
+    t = (rs.randint(0, 50, run.max() + 1)[run] + np.arange(H) - start).astype(np.int32)
+    n = rs.randint(0, 64, run.max() + 1)[run].astype(np.int32)
+    goal = rs.randint(0, 17, (run.max() + 1, 2))[run].astype(np.float32)
+    done = end.copy()
+    done[H - 1] = rs.randint(0, 2)                                 # the array may stop in mid-run
+    return t, n, goal, done
+
+
+def _levels(H):
+    levels, n = 1, H
+    while n > BLOCK:
+        n, levels = -(-n // BLOCK), levels + 1
+    return levels
+
+
+def _k(L, H):
+    """k of |adv - adv64| <= k * EPS32 * S_j, counted in roundings of 2^-24 = EPS32 / 2 (each relative to a partial
+    magnitude <= S_j) along the longest path of one term delta_k, k >= j, into A_j; L_j terms enter A_j.
+
+    Every term: 3 roundings of delta (gamma * nv, + r, - v).  Its coefficient is a product of k - j <= L_j - 1 factors c,
+    joined pairwise by the shuffle scan, the folds and the carries: at most L_j - 2 multiplications (any order of
+    evaluation, a serial one too, rounds a product of m factors m - 1 times).
+
+    L_j <= 64: the terms lie in the chunk of j and the next one.  The partial sum a term sits in is rounded by the <= 6
+    fmas of the shuffle scan of its own chunk, by the fma that takes the value into the chunk (gr_eval), and, if it comes
+    from the next chunk, by the fma of gr_eval in the chunk of j: <= 8.  The run ends inside that next chunk, so its
+    composite has c = 0, and whatever lies between the two chunks -- a wavefront's fold, a workgroup's composite, the
+    levels above -- hands (0, d) on through the c == 0 branches without arithmetic.  3 + 62 + 8 = 73, one more for the
+    second-order terms of (1 + 2^-24)^73: k = 74 / 2 = 37, whatever H and wherever the run lies.
+
+    Longer runs: the sum a term sits in is rounded, per level of the tree it visits, by <= 6 shuffle fmas + 8 chunk folds
+    + 4 wavefront folds on the way up and <= 3 wavefronts + 8 chunks + 1 on the way down: 31.  A run inside one
+    workgroup visits level 0 only; a run that crosses a workgroup carry visits at most every level H has.  So
+    2 k = 3 + (L_j - 1) + 31 * levels visited + 1.  The run length enters because the coefficient of the farthest term is
+    a product of L_j - 1 factors; a run that crosses w carries has L_j <= 2048 (w + 1)."""
+    j = np.arange(len(L))
+    crosses = (j // BLOCK) != ((j + L - 1) // BLOCK)
+    visited = np.where(crosses, _levels(H), 1)
+    return np.where(L <= CHUNK, 37.0, (L + 3 + 31 * visited) / 2.0)

@@ -121,7 +121,7 @@ def test_ctypes_table_and_header_agree_on_the_new_entry_points():
         assert len(params) == arity == len(_lib._SIGS[name][1]), name
         assert name in _lib.exported_symbols()
         if arity > 1:
-            assert params[-1] == "void *launch_stream", name      # not `stream`: see tests/test_streams_gpu.py
+            assert params[-1] == "void *stream", name             # the spelling tests/test_streams_gpu.py lists entries by
 
 
 def test_parser_accepts_her_gae_and_it_is_off_by_default():

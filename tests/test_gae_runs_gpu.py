@@ -1,8 +1,9 @@
 """ppo_run_ends and ppo_gae_runs (csrc/ppo_kernels.hip): the run ends bit for bit against the numpy restatement, the scan
-against the float64 statement of gae_runs_ref.py within a rounding bound derived below, its bit-exact special cases
-against ppo_gae, isolation of non-finite values, every argument rule, the two stream checks of stream_util.py for both
-entry points, and the trainer's her_gae path.  The sizes are the smallest that reach every edge: one record, a chunk of
-64 less / exactly / plus one, a workgroup's 4 wavefronts (256, 257), 1 000, and 70 001 (35 workgroups: three launches)."""
+against the float64 statement of gae_runs_ref.py within the rounding bound derived there, its bit-exact special cases
+against ppo_gae, isolation of non-finite values, every argument rule, and the trainer's her_gae path.  The two stream
+checks of both entry points are cases of the table in test_streams_gpu.py.  The sizes are the smallest that reach
+every edge: one record, a chunk of 64 less / exactly / plus one, a workgroup's 4 wavefronts (256, 257), 1 000, and
+70 001 (35 workgroups: three launches)."""
 import ctypes as C
 
 import numpy as np
@@ -10,13 +11,12 @@ import pytest
 import torch
 
 import gae_runs_ref as gr
+from gae_runs_ref import BLOCK, _k, _records
 from ppo_util import DEV, accepted, dev as _dev, lib as _lib, lib_module as _libmod, ops as _ops, ptr as _P
-from stream_util import (Case, check_against_ref, check_same, expected_sequence, host, run_captured, run_default, run_side,
-                         same_bits)
+from stream_util import host, same_bits
 
 pytestmark = pytest.mark.gpu
 EPS32 = gr.EPS32
-CHUNK, BLOCK = 64, 2048                          # records per shuffle scan / per workgroup (GR_BLOCK)
 PARAMS = [(0.99, 0.0), (0.99, 0.95), (1.0, 1.0)]
 SIZES = [1, 63, 64, 65, 256, 257, 1000, 70001]
 
@@ -30,20 +30,6 @@ def _at_end(a):
     t.copy_(torch.from_numpy(a))
     assert t.data_ptr() + a.nbytes == buf.data_ptr() + buf.numel()
     return t
-
-
-def _records(H, seed):
-    """Records in ppo_her_relabel's shape: runs of 1..64 consecutive steps of one env under one goal, each ending done."""
-    rs = np.random.RandomState(seed)
-    end = gr.pattern("her", H, seed)
-    run = np.concatenate([[0], np.cumsum(end)[:-1]]).astype(np.int64)          # run index of every record
-    start = np.concatenate([[0], np.nonzero(end)[0] + 1])[run]
-    t = (rs.randint(0, 50, run.max() + 1)[run] + np.arange(H) - start).astype(np.int32)
-    n = rs.randint(0, 64, run.max() + 1)[run].astype(np.int32)
-    goal = rs.randint(0, 17, (run.max() + 1, 2))[run].astype(np.float32)
-    done = end.copy()
-    done[H - 1] = rs.randint(0, 2)                                 # the array may stop in mid-run
-    return t, n, goal, done
 
 
 def _run_ends(t, n, goal, done, broken=None):
@@ -115,39 +101,6 @@ def test_run_ends_rejections_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------------ ppo_gae_runs
-def _levels(H):
-    levels, n = 1, H
-    while n > BLOCK:
-        n, levels = -(-n // BLOCK), levels + 1
-    return levels
-
-
-def _k(L, H):
-    """k of |adv - adv64| <= k * EPS32 * S_j, counted in roundings of 2^-24 = EPS32 / 2 (each relative to a partial
-    magnitude <= S_j) along the longest path of one term delta_k, k >= j, into A_j; L_j terms enter A_j.
-
-    Every term: 3 roundings of delta (gamma * nv, + r, - v).  Its coefficient is a product of k - j <= L_j - 1 factors c,
-    joined pairwise by the shuffle scan, the folds and the carries: at most L_j - 2 multiplications (any order of
-    evaluation, a serial one too, rounds a product of m factors m - 1 times).
-
-    L_j <= 64: the terms lie in the chunk of j and the next one.  The partial sum a term sits in is rounded by the <= 6
-    fmas of the shuffle scan of its own chunk, by the fma that takes the value into the chunk (gr_eval), and, if it comes
-    from the next chunk, by the fma of gr_eval in the chunk of j: <= 8.  The run ends inside that next chunk, so its
-    composite has c = 0, and whatever lies between the two chunks -- a wavefront's fold, a workgroup's composite, the
-    levels above -- hands (0, d) on through the c == 0 branches without arithmetic.  3 + 62 + 8 = 73, one more for the
-    second-order terms of (1 + 2^-24)^73: k = 74 / 2 = 37, whatever H and wherever the run lies.
-
-    Longer runs: the sum a term sits in is rounded, per level of the tree it visits, by <= 6 shuffle fmas + 8 chunk folds
-    + 4 wavefront folds on the way up and <= 3 wavefronts + 8 chunks + 1 on the way down: 31.  A run inside one
-    workgroup visits level 0 only; a run that crosses a workgroup carry visits at most every level H has.  So
-    2 k = 3 + (L_j - 1) + 31 * levels visited + 1.  The run length enters because the coefficient of the farthest term is
-    a product of L_j - 1 factors; a run that crosses w carries has L_j <= 2048 (w + 1)."""
-    j = np.arange(len(L))
-    crosses = (j // BLOCK) != ((j + L - 1) // BLOCK)
-    visited = np.where(crosses, _levels(H), 1)
-    return np.where(L <= CHUNK, 37.0, (L + 3 + 31 * visited) / 2.0)
-
-
 def _gae_runs(r, v, nv, done, end, gamma, lam, mask, want_ret=True):
     out = _ops().gae_runs(_dev(r), _dev(v), _dev(nv), None if done is None else _dev(done), _dev(end), gamma, lam, mask,
                           want_ret=want_ret)
@@ -253,71 +206,6 @@ def test_gae_runs_rejections_launch_nothing():
         2, 2, 4, 70, 4096, 2 * 2049 + 2 * 2]
     with pytest.raises(_libmod().TwoarmyLibraryError):             # the front end raises what the C call returns
         _ops().gae_runs(r, v, nv, None, end, 0.99, 0.95, True)
-
-
-# ------------------------------------------------------------------------------------------------ streams and capture
-H_STREAM = 5000                                                    # three workgroups: reduce, carry pass, apply
-
-
-def _runs_case():
-    def make(seed):
-        t, n, goal, done = _records(H_STREAM, 50 + seed)
-        return dict(t=_dev(t), n=_dev(n), goal=_dev(goal), done=_dev(done),
-                    broken=torch.zeros(1, dtype=torch.int32, device=DEV))
-
-    def call(b, o, ctx):
-        return dict(run_end=_ops().run_ends(b["t"], b["n"], b["goal"], b["done"], b["broken"]), broken=b["broken"])
-
-    def ref(h):
-        end, broken = gr.run_ends(h["t"], h["n"], h["goal"], h["done"])
-        return dict(run_end=end, broken=h["broken"] + np.int32(broken))
-
-    return Case("run_ends", "ppo", ["ppo_run_ends"], make, call, ref=ref, state=("broken",))
-
-
-def _gae_runs_case():
-    def make(seed):
-        r, v, nv = gr.inputs(H_STREAM, 60 + seed)
-        end = gr.pattern("her", H_STREAM, 60 + seed)
-        return dict(reward=_dev(r), value=_dev(v), next_value=_dev(nv), done=_dev(gr.dones(end, seed)), run_end=_dev(end))
-
-    def call(b, o, ctx):
-        adv, target, ret = _ops().gae_runs(b["reward"], b["value"], b["next_value"], b["done"], b["run_end"], 0.99, 0.95, True)
-        return dict(adv=adv, target=target, ret=ret)
-
-    def ref(h):
-        a64, _, r64, S, L = gr.gae_runs64(h["reward"], h["value"], h["next_value"], h["done"], h["run_end"], 0.99, 0.95, True)
-        bound = _k(L, H_STREAM) * EPS32 * S
-        return dict(adv=a64, ret=r64, target=gr.one_step32(h["reward"], h["value"], h["next_value"], h["done"], 0.99, True)[0],
-                    _atol=dict(adv=bound, ret=bound + EPS32 * (S + np.abs(h["value"]))))
-
-    return Case("gae_runs", "ppo", ["ppo_gae_runs"], make, call, ref=ref)
-
-
-STREAM_CASES = [_runs_case, _gae_runs_case]
-
-
-@pytest.mark.parametrize("make_case", STREAM_CASES)
-def test_eager_on_a_side_stream_behind_a_delay(make_case):
-    case = make_case()
-    want = run_default(case, 1)
-    got, still_running = run_side(case, 1)
-    assert still_running, "the delay ended before the host had enqueued the launch: the run proves nothing"
-    check_same(case, got, want, "side stream")
-    check_against_ref(case, got, case.ref({k: host(v) for k, v in case.make(1).items()}), "side stream")
-    decoy = run_default(case, 0)
-    assert not any(np.array_equal(got[k], decoy[k]) for k in got if got[k].size > 1)   # the decoy has other arrays everywhere
-
-
-@pytest.mark.parametrize("make_case", STREAM_CASES)
-def test_captured_and_replayed_with_changed_inputs(make_case):
-    case = make_case()
-    eager, cpu = expected_sequence(case)
-    got = run_captured(case)
-    for i, g in enumerate(got, 1):
-        check_same(case, g, eager[i], "replay %d" % i)
-        check_against_ref(case, g, cpu[i], "replay %d" % i)
-    assert not any(np.array_equal(got[0][k], got[1][k]) for k in got[0] if got[0][k].size > 1)
 
 
 # ------------------------------------------------------------------------------------------------ trainer

@@ -16,26 +16,46 @@ def _declared():
     return syms
 
 
-def _prototypes():
-    """{name: (return type, [parameter types])} of every prototype in include/*.h, each type as the header spells it
-    with `const` and the parameter's name dropped and every pointer reduced to "*".  The headers are plain C with one
-    declarator per parameter."""
-    protos = {}
+def _declarations():
+    """(return type, name, [parameter declarations]) of every prototype in include/*.h, as the header spells them.  The
+    headers are plain C with one declarator per parameter."""
     for fn in sorted(os.listdir(os.path.join(ROOT, "include"))):
         txt = open(os.path.join(ROOT, "include", fn)).read()
         txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
         txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
         for ret, name, params in re.findall(r"([A-Za-z_][\w \*\n]*?)\b((?:tw|ppo|mg)_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
-            assert name not in protos, "%s is declared twice" % name
-            params = [] if params.strip() == "void" else params.split(",")
+            yield ret, name, [] if params.strip() == "void" else params.split(",")
 
-            def kind(decl, named):
-                if "*" in decl:
-                    return "char *" if re.sub(r"\bconst\b", "", decl).split() == ["char", "*"] else "*"
-                words = [w for w in decl.split() if w != "const"]
-                return " ".join(words[:-1] if named else words)
-            protos[name] = (kind(ret, False), [kind(p, True) for p in params])
+
+def _prototypes():
+    """{name: (return type, [parameter types])} of every prototype in include/*.h, each type as the header spells it
+    with `const` and the parameter's name dropped and every pointer reduced to "*"."""
+    def kind(decl, named):
+        if "*" in decl:
+            return "char *" if re.sub(r"\bconst\b", "", decl).split() == ["char", "*"] else "*"
+        words = [w for w in decl.split() if w != "const"]
+        return " ".join(words[:-1] if named else words)
+    protos = {}
+    for ret, name, params in _declarations():
+        assert name not in protos, "%s is declared twice" % name
+        protos[name] = (kind(ret, False), [kind(p, True) for p in params])
     return protos
+
+
+def test_a_stream_parameter_is_spelled_stream_and_comes_last():
+    """Every `void *` parameter whose name contains "stream" is named exactly `stream` and is its prototype's last one:
+    tests/test_streams_gpu.py lists the entry points that take a stream by that spelling, and a prototype that spells it
+    otherwise escapes its completeness test."""
+    found, bad = 0, []
+    for _, name, params in _declarations():
+        for i, p in enumerate(params):
+            m = re.fullmatch(r"\s*void\s*\*\s*(\w*stream\w*)\s*", p)
+            if m:
+                found += 1
+                if m.group(1) != "stream" or i != len(params) - 1:
+                    bad.append("%s: parameter %d of %d is `%s`" % (name, i + 1, len(params), p.strip()))
+    assert not bad, "\n".join(bad)
+    assert found >= 60, "only %d prototypes with a stream were found: the parser has lost them" % found
 
 
 def test_ctypes_signatures_mirror_the_headers():

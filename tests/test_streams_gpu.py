@@ -15,12 +15,16 @@ import torch
 
 import bonus_ref
 import episode_ref
+import gae_runs_ref as gr
 import nav_ref
 import obs_ref
 import path_ref
 import render_ref
 import replay_ref
+import timed_goal_ahead_ref as taref
+import update_stats_ref as ur
 import visit_ref
+from nav_util import u16_full
 from stream_util import (DEV, ENQUEUE_MS, Case, check_against_ref, check_same, dev, expected_sequence, hip_error, host,
                          rng, run_captured, run_default, run_side, same_bits)
 
@@ -47,6 +51,11 @@ def M():
 
 def pick(d, *keys):
     return {k: d[k] for k in keys}
+
+
+def unchanged(x, y, keys):
+    """The names among `keys` whose arrays are equal in the results x and y: what a case's `also` expects to be empty."""
+    return [k for k in keys if np.array_equal(x[k], y[k])]
 
 
 def probs(r, B, A):
@@ -256,6 +265,84 @@ for _F in (4, 8):
 CASES.append(Case("conv1_up4_bias_relu_infer", "ppo", ["ppo_conv1_up4_bias_relu_c"], _conv1_make(4),
                   lambda b, o, ctx: dict(y=ops().conv1_up4_bias_relu_infer(b["frames"], b["w"], b["bias"])),
                   note="default-stream run only"))
+
+B_STATS, NV_STATS = 600, 257
+
+
+def _stats_case():
+    """stream_util's protocol on the front end: every seed draws its own minibatch (seed 0 is the decoy); `stats` is state
+    the call updates in place, carried across the warm-up and the replays."""
+    def make(seed):
+        p, a, old, adv, value, target = ur.inputs(B_STATS, 8100 + seed)
+        return dict(up(dict(probs=p, action=a, old_logp=old, adv=adv, value=value, target_v=target)),
+                    stats=torch.zeros(16, dtype=torch.float64, device=DEV))
+
+    def call(b, o, ctx):
+        p, v = b["probs"].detach().requires_grad_(), b["value"].detach().requires_grad_()
+        al, vl = ops().ppo_losses(p, v, b["action"], b["old_logp"], b["adv"], b["target_v"], clip=ur.CLIP, ent_coef=ur.ENT,
+                                  n_valid=NV_STATS, stats=b["stats"])
+        return dict(action_loss=al.detach(), value_loss=vl.detach(), grad_probs=al.grad_fn.saved_tensors[0],
+                    grad_value=vl.grad_fn.saved_tensors[0], stats=b["stats"])
+
+    def ref(h):
+        x = (h["probs"], h["action"], h["old_logp"], h["adv"], h["value"], h["target_v"])
+        want, R = ur.accumulate(h["stats"], x[0], x[1], x[2], x[4], x[5], ur.CLIP, NV_STATS)
+        return dict(stats=want, _atol=dict(stats=ur._bounds(x, R, NV_STATS)))
+
+    def also(part, x, y):
+        if part == "A":                                        # the decoy has another answer everywhere
+            assert not unchanged(x, y, x) and x["stats"][12] == 1
+            return
+        # the row is carried: the eager warm-up is call 1, so the two replays added exactly two calls and two batches of rows
+        assert [x["stats"][12], y["stats"][12]] == [2, 3] and [x["stats"][0], y["stats"][0]] == [2 * NV_STATS, 3 * NV_STATS]
+        assert not unchanged(x, y, ["grad_probs"])
+
+    return Case("ppo_losses(stats=)", "ppo", ["ppo_loss_fwd_bwd_stats"], make, call, ref=ref, state=("stats",), also=also)
+
+
+H_RUNS = 5000                                                      # three workgroups: reduce, carry pass, apply
+
+
+def _arrays_differ(part, x, y):
+    """Both parts: every output with more than one element differs, from the decoy's and between the replays."""
+    assert not unchanged(x, y, [k for k in x if x[k].size > 1])
+
+
+def _runs_case():
+    def make(seed):
+        t, n, goal, done = gr._records(H_RUNS, 50 + seed)
+        return dict(up(dict(t=t, n=n, goal=goal, done=done)), broken=torch.zeros(1, dtype=torch.int32, device=DEV))
+
+    def call(b, o, ctx):
+        return dict(run_end=ops().run_ends(b["t"], b["n"], b["goal"], b["done"], b["broken"]), broken=b["broken"])
+
+    def ref(h):
+        end, broken = gr.run_ends(h["t"], h["n"], h["goal"], h["done"])
+        return dict(run_end=end, broken=h["broken"] + np.int32(broken))
+
+    return Case("run_ends", "ppo", ["ppo_run_ends"], make, call, ref=ref, state=("broken",), also=_arrays_differ)
+
+
+def _gae_runs_case():
+    def make(seed):
+        r, v, nv = gr.inputs(H_RUNS, 60 + seed)
+        end = gr.pattern("her", H_RUNS, 60 + seed)
+        return up(dict(reward=r, value=v, next_value=nv, done=gr.dones(end, seed), run_end=end))
+
+    def call(b, o, ctx):
+        adv, target, ret = ops().gae_runs(b["reward"], b["value"], b["next_value"], b["done"], b["run_end"], 0.99, 0.95, True)
+        return dict(adv=adv, target=target, ret=ret)
+
+    def ref(h):
+        a64, _, r64, S, L = gr.gae_runs64(h["reward"], h["value"], h["next_value"], h["done"], h["run_end"], 0.99, 0.95, True)
+        bound = gr._k(L, H_RUNS) * gr.EPS32 * S
+        return dict(adv=a64, ret=r64, target=gr.one_step32(h["reward"], h["value"], h["next_value"], h["done"], 0.99, True)[0],
+                    _atol=dict(adv=bound, ret=bound + gr.EPS32 * (S + np.abs(h["value"]))))
+
+    return Case("gae_runs", "ppo", ["ppo_gae_runs"], make, call, ref=ref, also=_arrays_differ)
+
+
+CASES += [_stats_case(), _runs_case(), _gae_runs_case()]
 
 # --------------------------------------------------------------------------------------------------------- replay
 
@@ -604,6 +691,53 @@ _nav_case("path_summary", ["mg_nav_path_summary"], ("dist", "pos_b", "pos_a", "t
           extra=_psum_extra, outs=lambda: dict(summary=torch.empty(10, dtype=torch.float64, device=DEV),
                                                workspace=torch.empty(nav().path_summary_workspace(TS, N), dtype=torch.float64, device=DEV)))
 
+
+def _timed_goal_ahead_case():
+    """The 17 x 17 world under stream_util's protocol: every seed draws its own records, rollout and clocks (seed 0 is the
+    decoy), so a launch on the wrong stream, or a replay that kept the captured inputs, reads another answer."""
+    R = 1100
+    sets = {}
+
+    def world_of(seed):
+        if seed not in sets:
+            base = taref.twoarmy()
+            rng = np.random.default_rng(900 + seed)
+            c = dict(base, memo={})
+            free = np.stack([np.asarray(base["ty"][n] != 2).reshape(17, 17) for n in range(base["N"])])
+            c["pos"] = taref._walk(rng, free, 17, 17, base["T"], base["N"], [(5 + 2 * n, 9 + (n + seed) % 2) for n in range(base["N"])])
+            c["age"] = taref._clocks(rng, base["T"], base["N"], base["P"])
+            c["rec"] = taref._records_of_runs(rng, c, R, 40)
+            sets[seed] = c
+        return sets[seed]
+
+    def make(seed):
+        c = world_of(seed)
+        b = dict(ty=c["ty"], sched=c["sched"].view(np.int32), pos=c["pos"], age=c["age"], init=c["init"], rt=c["rec"]["t"],
+                 rn=c["rec"]["n"], rgoal=c["rec"]["goal"])
+        return up({k: np.array(v) for k, v in b.items()})      # copies: the shared world is read-only (nav_util.dev)
+
+    def call(b, o, ctx):
+        nav().timed_goal_ahead(b["ty"], b["rt"], b["rn"], b["rgoal"], b["pos"], 17, 17, b["sched"], b["age"], b["init"],
+                               pass_types=taref.STATIC, out=o["labels"], dist_out=o["dist"])
+        return dict(labels=o["labels"], dist=o["dist"])
+
+    def ref(h):
+        c = dict(taref.twoarmy(), memo={}, pos=h["pos"], age=h["age"], init=h["init"])
+        lab, ad = taref.timed_goal_ahead(c, h["rt"], h["rn"], h["rgoal"], 3)
+        return dict(labels=lab.view(np.int64), dist=ad)
+
+    def also(part, x, y):
+        if part == "A":                                        # the decoy has another answer
+            assert len(unchanged(x, y, x)) < len(x)
+        else:
+            assert not unchanged(x, y, ["labels"])
+
+    return Case("timed_goal_ahead 17x17 N=4 P=6", "navigation", ["mg_nav_timed_goal_ahead"], make, call, ref=ref, also=also,
+                outs=lambda: dict(labels=torch.empty(R, dtype=torch.int64, device=DEV), dist=u16_full(R)))
+
+
+CASES.append(_timed_goal_ahead_case())
+
 # -------------------------------------------------------------------------------------------- observation wrappers
 
 
@@ -849,6 +983,8 @@ def test_eager_on_a_side_stream(case):
     if case.ref is not None:
         h = {k: host(v) for k, v in case.make(1).items()}
         check_against_ref(case, got, case.ref(h), "side stream")
+    if case.also is not None:
+        case.also("A", got, run_default(case, 0))
     assert hip_error() == 0
 
 
@@ -871,6 +1007,8 @@ def test_captured_and_replayed(case):
         check_same(case, g, eager[i], "replay %d" % i)
         if cpu and case.ref_in_b:
             check_against_ref(case, g, cpu[i], "replay %d" % i)
+    if case.also is not None:
+        case.also("B", *got)
     assert hip_error() == 0
 
 
@@ -959,7 +1097,8 @@ def stream_functions():
 
 def test_every_stream_function_has_a_case():
     want = stream_functions()
-    assert len(want) >= 56 and "tw_rollout" in want and "mg_obs_onehot" in want
+    print("%d prototypes take a stream" % len(want))
+    assert len(want) >= 60 and "tw_rollout" in want and "mg_obs_onehot" in want and "ppo_gae_runs" in want
     part_a = {f for c in CASES for f in c.fns}
     part_b = {f for c in CASES for f in c.fns if c.exempt_b is None or c.exempt_b.startswith("own test")} | \
         {f for f in want if f in EXEMPT}

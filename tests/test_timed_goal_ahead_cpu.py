@@ -148,11 +148,11 @@ def test_the_flood_count_is_the_headers_formula():
 
 
 # ------------------------------------------------------------------------------------------------ header and ABI
-def test_header_signatures_and_the_streams_name():
+def test_header_signatures_and_parameter_names():
     import twoarmy_amd
     txt = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
     want = {"mg_nav_timed_goal_ahead": "type state n_envs width height pass_types flags blocked blocked_env_stride period rec_t "
-                                       "rec_n rec_goal n_records pos age init_pos T steps ahead acting_dist launch_stream",
+                                       "rec_n rec_goal n_records pos age init_pos T steps ahead acting_dist stream",
             "mg_nav_timed_goal_ahead_floods": "width height period"}
     for name, names in want.items():
         args = [a.strip() for a in re.search(r"\b%s\s*\((.*?)\);" % name, txt, re.S).group(1).split(",")]

@@ -2,7 +2,7 @@
 goal in a world whose blockers move, bit for bit against timed_goal_ahead_ref.py (a queue BFS over (cell, phase) per record's
 env and goal, then ahead_ref's frontier loop) on the worlds test_timed_goal_ahead_cpu.py vets, and against the kernels it must
 agree with; through the torch front end, TwoarmyEngine and VecSoATrainer.  The entry's two stream checks (a side stream
-behind a delay, capture and replay) are here as well, by the protocol of stream_util.py."""
+behind a delay, capture and replay) are a case of the table in test_streams_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -10,8 +10,7 @@ import torch
 import timed_goal_ahead_ref as taref
 import timed_nav_ref as tref
 from nav_util import Boxed, dev, host, u16_full
-from stream_util import (Case, check_against_ref, check_same, expected_sequence, hip_error, run_captured, run_default,
-                         run_side)
+from stream_util import hip_error
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -179,66 +178,6 @@ def test_one_step_is_the_image_of_the_timed_move_set(name):
     image = sum(((m >> np.uint64(k)) & np.uint64(1)) << np.uint64(b) for k, b in enumerate((LEFT, RIGHT, UP, DOWN, SAME)))
     got = run(c, rec, 1)
     assert np.array_equal(got[0], image) and np.array_equal(got[1], h16(ad)) and (m & np.uint64(0x10)).any()
-
-
-# ------------------------------------------------------------------------------------------------ streams and capture
-def _stream_case():
-    """The 17 x 17 world under stream_util's protocol: every seed draws its own records, rollout and clocks (seed 0 is the
-    decoy), so a launch on the wrong stream, or a replay that kept the captured inputs, reads another answer."""
-    base = taref.twoarmy()
-    R = 1100
-    sets = {}
-
-    def world_of(seed):
-        if seed not in sets:
-            rng = np.random.default_rng(900 + seed)
-            c = dict(base, memo={})
-            free = np.stack([np.asarray(base["ty"][n] != 2).reshape(17, 17) for n in range(base["N"])])
-            c["pos"] = taref._walk(rng, free, 17, 17, base["T"], base["N"], [(5 + 2 * n, 9 + (n + seed) % 2) for n in range(base["N"])])
-            c["age"] = taref._clocks(rng, base["T"], base["N"], base["P"])
-            c["rec"] = taref._records_of_runs(rng, c, R, 40)
-            sets[seed] = c
-        return sets[seed]
-
-    def make(seed):
-        c = world_of(seed)
-        return dict(ty=dev(c["ty"]), sched=dev(c["sched"].view(np.int32)), pos=dev(c["pos"]), age=dev(c["age"]),
-                    init=dev(c["init"]), rt=dev(c["rec"]["t"]), rn=dev(c["rec"]["n"]), rgoal=dev(c["rec"]["goal"]))
-
-    def outs():
-        return dict(labels=torch.empty(R, dtype=torch.int64, device=DEV), dist=u16_full(R))
-
-    def call(b, o, ctx):
-        nav().timed_goal_ahead(b["ty"], b["rt"], b["rn"], b["rgoal"], b["pos"], 17, 17, b["sched"], b["age"], b["init"],
-                               pass_types=base["pass_types"], out=o["labels"], dist_out=o["dist"])
-        return dict(labels=o["labels"], dist=o["dist"])
-
-    def ref(h):
-        c = dict(base, memo={}, pos=h["pos"], age=h["age"], init=h["init"])
-        lab, ad = taref.timed_goal_ahead(c, h["rt"], h["rn"], h["rgoal"], 3)
-        return dict(labels=lab.view(np.int64), dist=ad)
-
-    return Case("timed_goal_ahead 17x17 N=4 P=6", "navigation", ["mg_nav_timed_goal_ahead"], make, call, outs=outs, ref=ref)
-
-
-def test_eager_on_a_side_stream_behind_a_delay():
-    case = _stream_case()
-    want = run_default(case, 1)
-    got, still_running = run_side(case, 1)
-    assert still_running, "the delay ended before the host had enqueued the launch: the run proves nothing"
-    check_same(case, got, want, "side stream")
-    check_against_ref(case, got, case.ref({k: host(v) for k, v in case.make(1).items()}), "side stream")
-    assert not all(np.array_equal(got[k], run_default(case, 0)[k]) for k in got)          # the decoy has another answer
-
-
-def test_captured_and_replayed_with_changed_inputs():
-    case = _stream_case()
-    eager, cpu = expected_sequence(case)
-    got = run_captured(case)
-    for i, g in enumerate(got, 1):
-        check_same(case, g, eager[i], "replay %d" % i)
-        check_against_ref(case, g, cpu[i], "replay %d" % i)
-    assert not np.array_equal(got[0]["labels"], got[1]["labels"])
 
 
 # ------------------------------------------------------------------------------------------------ engine and trainer

@@ -1,7 +1,7 @@
 """ppo_loss_fwd_bwd_stats (csrc/ppo_kernels.hip): the loss outputs bit for bit against ppo_loss_fwd_bwd_masked, the
 accumulators against the float64 statement of update_stats_ref.py within float32 rounding bounds derived next to them,
-accumulation, padding, determinism, every argument rule, the two stream checks of stream_util.py, and the trainer's
-wiring with the KL stop.  The shapes are the smallest that reach every edge: one row, one workgroup less and more than
+accumulation, padding, determinism, every argument rule, and the trainer's wiring with the KL stop.  The entry's two
+stream checks are a case of the table in test_streams_gpu.py.  The shapes are the smallest that reach every edge: one row, one workgroup less and more than
 full, padding across workgroups, and 66 workgroups (more partials than the final pass has lanes)."""
 import numpy as np
 import pytest
@@ -9,8 +9,7 @@ import torch
 
 import update_stats_ref as ur
 from ppo_util import DEV, accepted, dev as _dev, lib as _lib, lib_module as _libmod, ops as _ops, ptr as _P
-from stream_util import (Case, check_against_ref, check_same, expected_sequence, host, run_captured, run_default, run_side,
-                         same_bits)
+from stream_util import host, same_bits
 
 pytestmark = pytest.mark.gpu
 EPS32 = ur.EPS32
@@ -62,29 +61,6 @@ def test_loss_outputs_equal_the_masked_entry_bit_for_bit(B, n_valid):
 
 
 # ------------------------------------------------------------------------------------------------ the accumulators
-def _bounds(x, R, n_valid):
-    """Absolute bounds of the 16 entries after ONE call from zero, from the float64 rows R: the per-row float32 bounds
-    that test_losses_vs_float64_autograd derives, summed over the rows, plus 2^-40 of the summed magnitudes for the
-    double accumulation (a 64-lane tree, four wavefronts, a fold over the workgroups: far fewer than 2^12 roundings of
-    2^-53 each).  Counts, calls and the reserved entries: 0."""
-    old = x[2][:n_valid].astype(np.float64)
-    acc = 2.0 ** -40
-    # logp and ratio: q (A + 1 roundings), logf, expf of a difference of magnitude <= |logp| + |old|
-    rel = 8 * EPS32 * (1 + np.abs(R["logp"]) + np.abs(old))
-    b = np.zeros(ur.WORDS)
-    b[1] = (8 * EPS32 * (np.abs(R["l"]) + 2).sum(1)).sum() + acc * np.abs(R["H"]).sum()
-    b[2] = rel.sum() + acc * np.abs(R["lr"]).sum()                 # lr: the absolute error of a logarithm of the ratio
-    b[3] = (rel * (R["ratio"] + 1)).sum() + acc * (np.abs(R["ratio"] - 1) + np.abs(R["lr"])).sum()
-    j = int(np.argmax(R["dev"]))
-    b[5] = rel[j] * R["ratio"][j]                                  # the reference's maximising row
-    b[6] = acc * np.abs(R["t"]).sum()                              # float32 -> double and its square are exact
-    b[7] = acc * (R["t"] ** 2).sum()
-    b[8] = (2.0 ** -24 * np.abs(R["e"])).sum() + acc * np.abs(R["e"]).sum()       # e: one float32 subtraction
-    b[9] = (2.0 ** -23 * R["e"] ** 2).sum() + acc * (R["e"] ** 2).sum()
-    b[11] = (6 * EPS32 * R["top"]).sum() + acc * R["top"].sum()    # max q: A + 1 roundings of one quotient
-    return b
-
-
 @pytest.mark.parametrize("B,n_valid", SHAPES + [BIG])
 def test_accumulators_vs_float64_reference(B, n_valid):
     x = _x(B)
@@ -92,7 +68,7 @@ def test_accumulators_vs_float64_reference(B, n_valid):
     _stats_call(x, n_valid, stats)
     got = host(stats)
     want, R = ur.accumulate(np.zeros(ur.WORDS), x[0], x[1], x[2], x[4], x[5], CLIP, n_valid)
-    bound = _bounds(x, R, n_valid)
+    bound = ur._bounds(x, R, n_valid)
     err = np.abs(got - want)
     print("B %d n_valid %d: err / bound %s" % (B, n_valid, " ".join(
         "%d:%.3g" % (i, err[i] / bound[i]) for i in range(13) if bound[i] > 0)))
@@ -205,57 +181,6 @@ def test_front_end_accumulates_into_a_row_of_a_larger_tensor_and_caches_its_work
     want = ur.read(ur.accumulate(np.zeros(16), x[0], x[1], x[2], x[4], x[5], CLIP, 257)[0])
     for k in ("entropy", "approx_kl", "clip_frac", "explained_variance", "saturated_frac", "top_mass"):
         assert np.isnan(d[k][0]) and abs(d[k][1] - want[k]) <= 1e-5 * max(1.0, abs(want[k])), k
-
-
-# ------------------------------------------------------------------------------------------------ streams and capture
-B_STREAM, NV_STREAM = 600, 257
-
-
-def _stream_case():
-    """stream_util's protocol on the front end: every seed draws its own minibatch (seed 0 is the decoy); `stats` is state
-    the call updates in place, carried across the warm-up and the replays."""
-    def make(seed):
-        p, a, old, adv, value, target = ur.inputs(B_STREAM, 8100 + seed)
-        return dict(probs=_dev(p), action=_dev(a), old_logp=_dev(old), adv=_dev(adv), value=_dev(value), target_v=_dev(target),
-                    stats=torch.zeros(16, dtype=torch.float64, device=DEV))
-
-    def call(b, o, ctx):
-        p, v = b["probs"].detach().requires_grad_(), b["value"].detach().requires_grad_()
-        al, vl = _ops().ppo_losses(p, v, b["action"], b["old_logp"], b["adv"], b["target_v"], clip=CLIP, ent_coef=ENT,
-                                   n_valid=NV_STREAM, stats=b["stats"])
-        return dict(action_loss=al.detach(), value_loss=vl.detach(), grad_probs=al.grad_fn.saved_tensors[0],
-                    grad_value=vl.grad_fn.saved_tensors[0], stats=b["stats"])
-
-    def ref(h):
-        x = (h["probs"], h["action"], h["old_logp"], h["adv"], h["value"], h["target_v"])
-        want, R = ur.accumulate(h["stats"], x[0], x[1], x[2], x[4], x[5], CLIP, NV_STREAM)
-        return dict(stats=want, _atol=dict(stats=_bounds(x, R, NV_STREAM)))
-
-    return Case("ppo_losses(stats=)", "ppo", ["ppo_loss_fwd_bwd_stats"], make, call, ref=ref, state=("stats",))
-
-
-def test_eager_on_a_side_stream_behind_a_delay():
-    case = _stream_case()
-    want = run_default(case, 1)
-    got, still_running = run_side(case, 1)
-    assert still_running, "the delay ended before the host had enqueued the launch: the run proves nothing"
-    check_same(case, got, want, "side stream")
-    check_against_ref(case, got, case.ref({k: host(v) for k, v in case.make(1).items()}), "side stream")
-    decoy = run_default(case, 0)
-    assert not any(np.array_equal(got[k], decoy[k]) for k in got)                  # the decoy has another answer everywhere
-    assert got["stats"][12] == 1
-
-
-def test_captured_and_replayed_with_changed_inputs():
-    case = _stream_case()
-    eager, cpu = expected_sequence(case)
-    got = run_captured(case)
-    for i, g in enumerate(got, 1):
-        check_same(case, g, eager[i], "replay %d" % i)
-        check_against_ref(case, g, cpu[i], "replay %d" % i)
-    # the row is carried: the eager warm-up is call 1, so the two replays added exactly two calls and two batches of rows
-    assert [g["stats"][12] for g in got] == [2, 3] and [g["stats"][0] for g in got] == [2 * NV_STREAM, 3 * NV_STREAM]
-    assert not np.array_equal(got[0]["grad_probs"], got[1]["grad_probs"])
 
 
 # ------------------------------------------------------------------------------------------------ trainer

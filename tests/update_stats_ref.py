@@ -1,7 +1,8 @@
 """The update diagnostics of ppo_loss_fwd_bwd_stats (include/twoarmy_ppo.h) stated in float64 numpy on float32 inputs: the
 torch formulation of `_losses64` in test_ppo_kernels_edges_gpu.py (Categorical(probs = p) with the float32 clamp eps,
 ratio = exp(logp - old)) extended by the thirteen accumulators, and an input generator in the style of that file's
-`_loss_inputs` whose margins make the three counts a matter of the reference alone.  A plain module like ppo_util.py."""
+`_loss_inputs` whose margins make the three counts a matter of the reference alone, and the float32 rounding bounds of the accumulators
+(test_update_stats_gpu.py and the case of test_streams_gpu.py).  A plain module like ppo_util.py."""
 import numpy as np
 
 EPS32 = float(np.finfo(np.float32).eps)          # 2^-23: the clamp of the kernel's (float32) Categorical
@@ -105,3 +106,26 @@ def inputs(B, seed, A=5, clip=CLIP):
     srt = np.sort(R["q"], 1)
     assert (srt[:, -1] - srt[:, -2] > TIE_MARGIN).all()
     return p, a, old, adv, value, target
+
+
+def _bounds(x, R, n_valid):
+    """Absolute bounds of the 16 entries after ONE call from zero, from the float64 rows R: the per-row float32 bounds
+    that test_losses_vs_float64_autograd derives, summed over the rows, plus 2^-40 of the summed magnitudes for the
+    double accumulation (a 64-lane tree, four wavefronts, a fold over the workgroups: far fewer than 2^12 roundings of
+    2^-53 each).  Counts, calls and the reserved entries: 0."""
+    old = x[2][:n_valid].astype(np.float64)
+    acc = 2.0 ** -40
+    # logp and ratio: q (A + 1 roundings), logf, expf of a difference of magnitude <= |logp| + |old|
+    rel = 8 * EPS32 * (1 + np.abs(R["logp"]) + np.abs(old))
+    b = np.zeros(WORDS)
+    b[1] = (8 * EPS32 * (np.abs(R["l"]) + 2).sum(1)).sum() + acc * np.abs(R["H"]).sum()
+    b[2] = rel.sum() + acc * np.abs(R["lr"]).sum()                 # lr: the absolute error of a logarithm of the ratio
+    b[3] = (rel * (R["ratio"] + 1)).sum() + acc * (np.abs(R["ratio"] - 1) + np.abs(R["lr"])).sum()
+    j = int(np.argmax(R["dev"]))
+    b[5] = rel[j] * R["ratio"][j]                                  # the reference's maximising row
+    b[6] = acc * np.abs(R["t"]).sum()                              # float32 -> double and its square are exact
+    b[7] = acc * (R["t"] ** 2).sum()
+    b[8] = (2.0 ** -24 * np.abs(R["e"])).sum() + acc * np.abs(R["e"]).sum()       # e: one float32 subtraction
+    b[9] = (2.0 ** -23 * R["e"] ** 2).sum() + acc * (R["e"] ** 2).sum()
+    b[11] = (6 * EPS32 * R["top"]).sum() + acc * R["top"].sum()    # max q: A + 1 roundings of one quotient
+    return b
