@@ -8,6 +8,8 @@
 //                 independent loads, and the last occurrence of a key stores the new count.  No atomics.
 //   shared scope  ppo_bonus_row_hist_kernel (per-row histogram of keys), ppo_bonus_key_scan_kernel (inclusive scan over
 //                 the rows per key, table += total), ppo_bonus_gather_kernel (count of (t, n) = table - total + prefix).
+//   episode scope ppo_bonus_episode_kernel: the env scope's scan cut at the episode ends; every count carries the stamp
+//                 of its episode, so a done clears an env's counts by stepping one generation word.
 // Only integer adds reach the tables: the counts are exact whatever the scheduling, and the bonus is a pure function
 // of the count.
 #include <hip/hip_runtime.h>
@@ -138,6 +140,141 @@ __global__ __launch_bounds__(64) void ppo_bonus_env_kernel(BonusIn in, const flo
             if (u < len)
                 bonus_write((size_t)(c0 + u) * in.N + n, bs[j], ba[j], reward, keep, bonus_state, bonus_action, reward_out);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- episode scope
+// Counts that clear at each episode end (ppo_bonus_scan_episode).  A table word is stamp << 24 | count; it counts only
+// while its stamp equals the env's generation word, so an episode end clears the env's K counts by adding 1 to that one
+// word.  The generation that follows 255 is 0, and the step onto it fills the env's span with zeros: no word older than
+// 256 episode ends survives, and a stamp can only be met again by a word of the running episode.
+constexpr uint32_t EP_COUNT_MASK = (1u << BONUS_EPISODE_COUNT_BITS) - 1u;
+constexpr uint32_t EP_GEN_MASK = (1u << (32 - BONUS_EPISODE_COUNT_BITS)) - 1u;
+
+// The done flags of one chunk as ballots: bit l of done[j] = step j * 64 + l ends an episode.  Wave-uniform.
+struct EpisodeCuts {
+    unsigned long long done[BONUS_PER_LANE];
+    int total;                                                     // episode ends in the chunk
+};
+
+__device__ __forceinline__ EpisodeCuts episode_cuts(const uint8_t *terminated, const uint8_t *truncated, int n, int N,
+                                                    int c0, int len) {
+    EpisodeCuts cuts;
+    cuts.total = 0;
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j) {
+        const int u = j * 64 + (int)threadIdx.x;
+        bool d = false;
+        if (u < len) {
+            const size_t i = (size_t)(c0 + u) * N + n;
+            d = (terminated[i] | truncated[i]) != 0;
+        }
+        cuts.done[j] = __ballot(d);
+        cuts.total += __popcll(cuts.done[j]);
+    }
+    return cuts;
+}
+
+// One chunk of one env for one kind, as bonus_env_chunk, cut at the episode ends.  gen: the env's generation before
+// the chunk.  A step counts from the carried count only if no done lies earlier in the chunk, and among the earlier
+// equal keys only those behind the chunk's last earlier done.  The chunk's last occurrence of a key stores the count
+// with the stamp of its own episode: what a table holds does not depend on where the chunks are cut.
+template <int KIND>
+__device__ __forceinline__ void bonus_episode_chunk(const BonusIn &in, int n, int c0, int len, const EpisodeCuts &cuts,
+                                                    uint32_t gen, uint32_t *table, int K, int form, double scale,
+                                                    int32_t *keys, double (&b)[BONUS_PER_LANE]) {
+    const int lane = threadIdx.x;
+    int k[BONUS_PER_LANE], since[BONUS_PER_LANE], ends[BONUS_PER_LANE];
+    uint32_t carry[BONUS_PER_LANE];
+    int before = 0, last = -1;                                     // of the rows j' < j: episode ends, and the last one
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j) {
+        const int u = j * 64 + lane;
+        const unsigned long long mine = cuts.done[j] & ((1ull << lane) - 1ull);       // the dones before u in its row
+        ends[j] = before + __popcll(mine);
+        since[j] = mine ? j * 64 + 63 - __clzll((long long)mine) : last;
+        before += __popcll(cuts.done[j]);
+        if (cuts.done[j]) last = j * 64 + 63 - __clzll((long long)cuts.done[j]);
+        k[j] = -1;
+        carry[j] = 0u;
+        if (u < len) {
+            k[j] = bonus_key<KIND>(in, c0 + u, n);
+            keys[u] = k[j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j)                       // independent gathers: nothing waits on them yet
+        if (j * 64 + lane < len) carry[j] = table[k[j]];
+    int earlier[BONUS_PER_LANE] = {};
+    bool later[BONUS_PER_LANE] = {};
+    for (int v = 0; v < len; ++v) {
+        const int kv = keys[v];                                    // one address for the wavefront: a broadcast read
+#pragma unroll
+        for (int j = 0; j < BONUS_PER_LANE; ++j) {
+            const int u = j * 64 + lane;
+            const bool same = kv == k[j];
+            earlier[j] += (same && v < u && v > since[j]) ? 1 : 0;
+            later[j] = later[j] || (same && v > u);
+        }
+    }
+    // the done that steps from the last generation onto 0 is number 255 - gen of the chunk (from 0); it clears for real
+    const int wrap = (int)(EP_GEN_MASK - gen);
+    const bool wraps = wrap < cuts.total;
+    if (wraps) {
+        __syncthreads();                                           // the gathers have landed before their words are zeroed
+        for (int c = lane; c < K; c += 64) table[c] = 0u;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < BONUS_PER_LANE; ++j) {
+        if (j * 64 + lane < len) {
+            const bool fresh = ends[j] == 0 && (carry[j] >> BONUS_EPISODE_COUNT_BITS) == gen;
+            const uint32_t sum = (fresh ? carry[j] & EP_COUNT_MASK : 0u) + (uint32_t)earlier[j] + 1u;
+            const uint32_t count = min(sum, EP_COUNT_MASK);        // at most 2^24 - 1 + 256: no 32-bit wrap
+            const uint32_t stamp = (gen + (uint32_t)ends[j]) & EP_GEN_MASK;
+            // a key last seen at or before the real clear stays zero
+            if (!later[j] && !(wraps && ends[j] <= wrap)) table[k[j]] = stamp << BONUS_EPISODE_COUNT_BITS | count;
+            b[j] = form == 0 ? bonus_value(count, scale) : (count == 1u ? scale : 0.0);
+        }
+    }
+    __syncthreads();                                               // keys[] is reused; the next chunk gathers what was stored
+}
+
+__global__ __launch_bounds__(64) void ppo_bonus_episode_kernel(BonusIn in, const float *reward, const uint8_t *keep,
+                                                               const uint8_t *terminated, const uint8_t *truncated,
+                                                               int kind_mask, int form, double scale,
+                                                               uint32_t *state_table, uint32_t *action_table,
+                                                               float *bonus_state, float *bonus_action,
+                                                               float *reward_out) {
+    __shared__ int32_t keys[BONUS_CHUNK];
+    const int lane = threadIdx.x;
+    const int n = blockIdx.x;
+    const int ks = bonus_keys(in, 1), ka = bonus_keys(in, 2);
+    // the generation words follow the N spans of counts
+    uint32_t *gen_state = (kind_mask & 1) ? state_table + (size_t)in.N * ks + n : nullptr;
+    uint32_t *gen_action = (kind_mask & 2) ? action_table + (size_t)in.N * ka + n : nullptr;
+    uint32_t gs = gen_state ? *gen_state & EP_GEN_MASK : 0u, ga = gen_action ? *gen_action & EP_GEN_MASK : 0u;
+    for (int c0 = 0; c0 < in.T; c0 += BONUS_CHUNK) {
+        const int len = min(BONUS_CHUNK, in.T - c0);
+        const EpisodeCuts cuts = episode_cuts(terminated, truncated, n, in.N, c0, len);
+        double bs[BONUS_PER_LANE] = {}, ba[BONUS_PER_LANE] = {};
+        if (kind_mask & 1)
+            bonus_episode_chunk<1>(in, n, c0, len, cuts, gs, state_table + (size_t)n * ks, ks, form, scale, keys, bs);
+        if (kind_mask & 2)
+            bonus_episode_chunk<2>(in, n, c0, len, cuts, ga, action_table + (size_t)n * ka, ka, form, scale, keys, ba);
+        gs = (gs + (uint32_t)cuts.total) & EP_GEN_MASK;
+        ga = (ga + (uint32_t)cuts.total) & EP_GEN_MASK;
+#pragma unroll
+        for (int j = 0; j < BONUS_PER_LANE; ++j) {
+            const int u = j * 64 + lane;
+            if (u < len)
+                bonus_write((size_t)(c0 + u) * in.N + n, bs[j], ba[j], reward, keep, bonus_state, bonus_action, reward_out);
+        }
+    }
+    if (lane == 0) {
+        if (gen_state) *gen_state = gs;
+        if (gen_action) *gen_action = ga;
     }
 }
 
@@ -282,6 +419,35 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
                            kind_mask, scale, (const int64_t *)state_table, (const int64_t *)action_table, hist_state,
                            hist_action, bonus_state, bonus_action, reward_out);
     }
+    return tw_launched(__func__);
+}
+
+int ppo_bonus_episode_words(int kind, int width, int height, int n_actions, int N) {
+    if ((kind != 1 && kind != 2) || !bonus_geom_ok(width, height, n_actions) || N < 0) return TW_E_ARG;
+    const int64_t words = (bonus_keys_host(kind, width, height, n_actions) + 1) * N;      // K counts and a generation per env
+    return words < ((int64_t)1 << 31) ? (int)words : TW_E_ARG;
+}
+
+int ppo_bonus_scan_episode(const float *pos, const int32_t *action, const int32_t *dir, long dir_stride_t, long dir_stride_n,
+                           const float *reward, const uint8_t *keep, const uint8_t *terminated, const uint8_t *truncated,
+                           int T, int N, int width, int height, int n_actions, int kind_mask, int form, double scale,
+                           void *state_table, void *action_table, float *bonus_state, float *bonus_action,
+                           float *reward_out, void *queue) {
+    if (!pos || ((uintptr_t)pos & 7u) || T < 0 || N < 0 || !bonus_geom_ok(width, height, n_actions)) return TW_E_ARG;
+    if (kind_mask < 1 || kind_mask > 3 || (form != 0 && form != 1) || !terminated || !truncated) return TW_E_ARG;
+    if ((kind_mask & 1) && (!state_table || ((uintptr_t)state_table & 7u))) return TW_E_ARG;
+    if ((kind_mask & 2) && (!action_table || ((uintptr_t)action_table & 7u) || !action)) return TW_E_ARG;
+    if (dir && (dir_stride_t < 0 || dir_stride_n < 0)) return TW_E_ARG;
+    if (reward_out && !reward) return TW_E_ARG;
+    if ((int64_t)T * N >= ((int64_t)1 << 31)) return TW_E_ARG;
+    for (int kind = 1; kind <= 2; ++kind)
+        if ((kind_mask & kind) && ppo_bonus_episode_words(kind, width, height, n_actions, N) < 0) return TW_E_ARG;
+    if (T == 0 || N == 0) return TW_OK;
+    const BonusIn in = {reinterpret_cast<const float2 *>(pos), action, dir, dir_stride_t, dir_stride_n, T, N, width, height,
+                        n_actions};
+    hipLaunchKernelGGL(ppo_bonus_episode_kernel, dim3(N), dim3(64), 0, (hipStream_t)queue, in, reward, keep, terminated,
+                       truncated, kind_mask, form, scale, (uint32_t *)state_table, (uint32_t *)action_table, bonus_state,
+                       bonus_action, reward_out);
     return tw_launched(__func__);
 }
 

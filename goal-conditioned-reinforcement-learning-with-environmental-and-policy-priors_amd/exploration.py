@@ -4,27 +4,38 @@ call per rollout (include/twoarmy_ppo.h) and no host synchronisation until read(
 
 scope "env": one count table per env, N independent copies of the reference's wrapper.  scope "shared": one table for
 all envs of this process, a time step counted as simultaneous (every env standing on a key in one row gets the bonus of
-the count that includes the whole row).  With several ranks every rank keeps its own tables."""
+the count that includes the whole row).  With several ranks every rank keeps its own tables.
+
+scope "episode": the env scope with counts that clear at each episode end (ppo_bonus_scan_episode), the per-episode
+counts of RIDE / NovelD / AGAC; form "sqrt" pays scale / sqrt(count), form "first" pays scale at the first visit of a key
+within the episode and nothing after it."""
 import numpy as np
 import torch
 
 from . import ppo_ops
 
 KINDS = ("state", "action")
+SCOPES = tuple(ppo_ops.BONUS_SCOPES) + ("episode",)
 
 
 class BonusTracker:
-    def __init__(self, num_envs, device, kinds=("state",), scope="env", scale=1.0, width=17, height=17, n_actions=7):
+    def __init__(self, num_envs, device, kinds=("state",), scope="env", scale=1.0, width=17, height=17, n_actions=7,
+                 form="sqrt"):
         kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
         assert kinds and all(k in KINDS for k in kinds), "kinds: a non-empty subset of %s" % (KINDS,)
-        assert scope in ppo_ops.BONUS_SCOPES
+        assert scope in SCOPES
+        if form not in ppo_ops.BONUS_FORMS:
+            raise ValueError("form: one of %s, got %r" % (tuple(ppo_ops.BONUS_FORMS), form))
+        if form != "sqrt" and scope != "episode":
+            raise ValueError('form=%r needs scope="episode": a lifetime count has one first visit ever' % (form,))
         self.N, self.device = int(num_envs), torch.device(device)
         self.kinds = tuple(k for k in KINDS if k in kinds)
-        self.scope, self.scale = scope, float(scale)
+        self.scope, self.scale, self.form = scope, float(scale), form
         self.width, self.height, self.n_actions = int(width), int(height), int(n_actions)
         self.cells = self.width * self.height
-        self.tables = {k: torch.zeros(ppo_ops.bonus_table_words(k, scope, width, height, n_actions, self.N),
-                                      dtype=torch.int32, device=self.device) for k in self.kinds}
+        words = (lambda k: ppo_ops.bonus_episode_words(k, width, height, n_actions, self.N)) if scope == "episode" else \
+            (lambda k: ppo_ops.bonus_table_words(k, scope, width, height, n_actions, self.N))
+        self.tables = {k: torch.zeros(words(k), dtype=torch.int32, device=self.device) for k in self.kinds}
         self.mask = sum(ppo_ops.BONUS_KINDS[k] for k in self.kinds)
         self.workspace = None                                                # sized by the first account()
         self.bonus = {}                                                      # kind -> f32[T,N] of the last account()
@@ -33,15 +44,22 @@ class BonusTracker:
         for t in self.tables.values():
             t.zero_()
 
-    def account(self, pos, action, reward, terminated=None, dir=None, dir_ptr=None, out=None):
+    def account(self, pos, action, reward, terminated=None, dir=None, dir_ptr=None, out=None, keep=None, truncated=None):
         """Shape one rollout: pos [T,N,2] (y, x) after each step, action / reward [T,N], terminated u8[T,N] (its steps
         are counted but keep their reward: Env_transact.step sets it to 0.9 above the wrappers) -- or one step: [N,2],
         [N].  dir: the agent's direction after each step, [T,N] / [N], or dir_ptr (see ppo_ops.bonus_scan).  Returns the
-        shaped reward (`out`, which may be `reward`, or a new tensor); self.bonus holds the bonuses per kind."""
+        shaped reward (`out`, which may be `reward`, or a new tensor); self.bonus holds the bonuses per kind.
+        scope "episode": terminated and truncated u8[T,N] are the episode ends and both are required; the steps that keep
+        their reward are keep u8[T,N] (None: none).  In the other scopes keep, where given, stands for terminated."""
+        episodic = self.scope == "episode"
+        if episodic and (terminated is None or truncated is None):
+            raise ValueError('scope="episode" cuts the counts at the episode ends: pass terminated= and truncated=')
+        if not episodic:
+            keep = terminated if keep is None else keep
         one = pos.dim() == 2
         if one:
             pos, action, reward = pos.view(1, -1, 2), action.view(1, -1), reward.view(1, -1)
-            terminated = None if terminated is None else terminated.view(1, -1)
+            keep, terminated, truncated = (None if t is None else t.view(1, -1) for t in (keep, terminated, truncated))
             dir = None if dir is None else dir.view(1, -1)
             out = None if out is None else out.view(1, -1)
         T, N = reward.shape
@@ -54,26 +72,38 @@ class BonusTracker:
             if self.workspace is None or self.workspace.numel() < need:
                 self.workspace = torch.empty(need, dtype=torch.int32, device=self.device)
         out = torch.empty_like(reward) if out is None else out
-        ppo_ops.bonus_scan(pos, action, reward, self.tables.get("state"), self.tables.get("action"), self.scope,
-                           self.scale, self.width, self.height, self.n_actions, keep=terminated, dir=dir, dir_ptr=dir_ptr,
-                           bonus_state=self.bonus.get("state"), bonus_action=self.bonus.get("action"), reward_out=out,
-                           workspace=self.workspace)
+        if episodic:
+            ppo_ops.bonus_scan_episode(pos, action, reward, terminated, truncated, self.tables.get("state"),
+                                       self.tables.get("action"), self.form, self.scale, self.width, self.height,
+                                       self.n_actions, keep=keep, dir=dir, dir_ptr=dir_ptr,
+                                       bonus_state=self.bonus.get("state"), bonus_action=self.bonus.get("action"),
+                                       reward_out=out)
+        else:
+            ppo_ops.bonus_scan(pos, action, reward, self.tables.get("state"), self.tables.get("action"), self.scope,
+                               self.scale, self.width, self.height, self.n_actions, keep=keep, dir=dir, dir_ptr=dir_ptr,
+                               bonus_state=self.bonus.get("state"), bonus_action=self.bonus.get("action"), reward_out=out,
+                               workspace=self.workspace)
         return out[0] if one else out
 
     def counts(self, kind):
-        """The table of one kind as a device tensor [N, K] (env scope, int32 holding uint32) or [K] int64 (shared)."""
+        """The table of one kind as a device tensor [N, K] (env scope, int32 holding uint32) or [K] int64 (shared); in
+        the episode scope the running episodes' counts, int64[N, K], decoded from the stamped words (a new tensor)."""
         t = self.tables[kind]
+        if self.scope == "episode":
+            return ppo_ops.bonus_episode_counts(t, self.N)
         return t.view(self.N, -1) if self.scope == "env" else t.view(torch.int64)
 
     def read(self, per_env=False):
         """Count maps as numpy int64, summed over envs in env scope (on the device): "state" [height, width], "action"
-        [4, n_actions, height, width], and the counts of invalid steps in "other" = {kind: int}; per_env=True (env scope)
-        keeps the envs apart instead: a leading [N] on every map, "other" = {kind: int64[N]}.  One device-to-host copy."""
-        per_env = per_env and self.scope == "env"
+        [4, n_actions, height, width], and the counts of invalid steps in "other" = {kind: int}; per_env=True (env and
+        episode scope) keeps the envs apart instead: a leading [N] on every map, "other" = {kind: int64[N]}.  In the
+        episode scope the counts are those of the running episodes.  One device-to-host copy."""
+        by_env = self.scope in ("env", "episode")
+        per_env = per_env and by_env
         parts = []
         for k in self.kinds:
             c = self.counts(k)
-            if self.scope == "env":
+            if by_env:
                 c = c.to(torch.int64) & 0xFFFFFFFF                            # the words are uint32
                 c = c if per_env else c.sum(0)
             parts.append(c.reshape(-1))

@@ -329,6 +329,54 @@ def bonus_scan(pos, action, reward, state_table=None, action_table=None, scope="
     return reward_out
 
 
+BONUS_FORMS = {"sqrt": 0, "first": 1}
+BONUS_EPISODE_COUNT_BITS = 24                           # include/twoarmy_ppo.h: word = stamp << 24 | count
+
+
+def bonus_episode_words(kind, width=17, height=17, n_actions=7, N=1):
+    """32-bit words of one episodic count table (kind "state" / "action"; ppo_bonus_episode_words): N spans of K stamped
+    counts and N generation words."""
+    return _query("ppo_bonus_episode_words", BONUS_KINDS[kind], int(width), int(height), int(n_actions), int(N))
+
+
+def bonus_episode_counts(table, N):
+    """The running episodes' counts of an episodic table as int64[N, K] on the table's device: a word counts while its
+    stamp is its env's generation (include/twoarmy_ppo.h)."""
+    K = table.numel() // N - 1
+    w = table[:N * K].view(N, K).to(torch.int64) & 0xFFFFFFFF
+    gen = table[N * K:].to(torch.int64).view(N, 1)
+    return torch.where((w >> BONUS_EPISODE_COUNT_BITS) == gen, w & ((1 << BONUS_EPISODE_COUNT_BITS) - 1), 0)
+
+
+def bonus_scan_episode(pos, action, reward, terminated, truncated, state_table=None, action_table=None, form="sqrt",
+                       scale=1.0, width=17, height=17, n_actions=7, keep=None, dir=None, dir_ptr=None, bonus_state=None,
+                       bonus_action=None, reward_out=None):
+    """Count bonuses whose counts clear at each episode end (ppo_bonus_scan_episode, include/twoarmy_ppo.h): bonus_scan's
+    env scope, cut where terminated | truncated u8[T,N] is set; the done step is counted and paid before the clear.  form
+    "sqrt": scale / sqrt(count), "first": scale at a key's first visit of the episode, else 0.  The tables given (i32 words,
+    bonus_episode_words; updated IN PLACE, they carry the running episodes between calls) select the kinds.  Every other
+    argument as in bonus_scan; no host synchronisation."""
+    T, N = pos.shape[:2]
+    assert pos.shape == (T, N, 2)
+    for t in (action, reward, keep, terminated, truncated, bonus_state, bonus_action, reward_out):
+        assert t is None or t.shape == (T, N)
+    mask = (1 if state_table is not None else 0) | (2 if action_table is not None else 0)
+    dp, st, sn = None, 0, 0
+    if dir is not None:
+        assert dir.shape in ((T, N), (N,))
+        dp, st, sn = _p(dir, torch.int32), (N if dir.dim() == 2 else 0), 1
+    elif dir_ptr is not None:
+        dp, st, sn = C.c_void_p(int(dir_ptr[0])), int(dir_ptr[1]), int(dir_ptr[2])
+    for kind, tab in (("state", state_table), ("action", action_table)):
+        assert tab is None or tab.numel() == bonus_episode_words(kind, width, height, n_actions, N)
+    _call("ppo_bonus_scan_episode", pos, _p(pos, torch.float32), _p(action, torch.int32), dp, st, sn,
+          _p(reward, torch.float32), _p(keep, torch.uint8), _p(terminated, torch.uint8), _p(truncated, torch.uint8), T, N,
+          int(width), int(height), int(n_actions), mask, BONUS_FORMS[form], float(scale), _p(state_table, torch.int32),
+          _p(action_table, torch.int32), _p(bonus_state, torch.float32), _p(bonus_action, torch.float32),
+          _p(reward_out, torch.float32))
+    return reward_out
+
+
 def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, env_id0=0, step0=0, max_goals=4, skip=0):
     """Hindsight relabelling of a time-major rollout (ppo_her_relabel_window, include/twoarmy_ppo.h; reference
     Buffer_gridworld.her_func, soa/env_buffer.py:101-143; skip = 4: pre_her_func / pre_f_her_func on the 9-frame window

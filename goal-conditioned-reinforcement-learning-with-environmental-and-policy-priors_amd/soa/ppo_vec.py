@@ -531,14 +531,15 @@ class VecPPOTrainer:
         return out
 
     # ------------------------------------------------------------------ exploration bonuses
-    def enable_bonus(self, kinds=("state",), scope="shared", scale=1.0):
+    def enable_bonus(self, kinds=("state",), scope="shared", scale=1.0, form="sqrt"):
         """Shape the training reward with the reference's count-based bonuses (gym_minigrid/wrappers.py:34-102):
         shape_rewards() then fills `reward_train`, which compute_targets(), relabel() and carry_over() use, while
         `reward` -- and with it account_episodes(), running_score(), stats() and the HER switch -- stays extrinsic.
         The action bonus keys on the env's action (policy index 4 is env action 6) and on the agent's direction after
-        the step, copied out of the engine's records once per step."""
+        the step, copied out of the engine's records once per step.  scope "episode": the counts of an env clear at each
+        of its episode ends (`term | trunc`); form "first" (that scope only) pays the first visit of an episode alone."""
         from ..exploration import BonusTracker
-        self.bonus = BonusTracker(self.N, self.device, kinds, scope, scale, 17, 17, 7)
+        self.bonus = BonusTracker(self.N, self.device, kinds, scope, scale, 17, 17, 7, form)
         self.reward_train = torch.zeros_like(self.reward)
         if "action" in self.bonus.kinds:
             self.dir = torch.zeros((self.T, self.N), dtype=torch.int32, device=self.device)
@@ -554,7 +555,10 @@ class VecPPOTrainer:
         """reward_train <- reward + bonuses of the rollout just collected (call after collect(), before relabel());
         terminated steps are counted but keep their reward, as under the reference's Env_transact.step.  One
         ppo_bonus_scan call, no host synchronisation.  Without enable_bonus(): reward_train is reward, nothing runs."""
-        if self.bonus is not None:
+        if self.bonus is not None and self.bonus.scope == "episode":
+            self.bonus.account(self.pos[4:4 + self.T], self.env_actions(), self.reward, dir=self.dir, out=self.reward_train,
+                               keep=self.term, terminated=self.term, truncated=self.trunc)
+        elif self.bonus is not None:
             self.bonus.account(self.pos[4:4 + self.T], self.env_actions(), self.reward, self.term, dir=self.dir,
                                out=self.reward_train)
         elif self.shaping is not None:        # enable_shaping() without a bonus: the potential is added to a copy

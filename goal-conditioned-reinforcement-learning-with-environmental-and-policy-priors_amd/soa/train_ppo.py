@@ -9,7 +9,8 @@ Reference-only flags that concerned the matplotlib window / absolute log paths a
 --visit_dir DIR writes the reference's heatmap MATRIX (heatmap.py:58-81; not the picture) once per update, counted on
 the device, and --track_buffer_file DIR its track dump (heatmap.py:79) for the first --dump_envs envs.
 --bonus {state,action,both} shapes the training reward with the reference's count-based exploration bonuses
-(gym_minigrid/wrappers.py:34-102), counted on the device; off by default.
+(gym_minigrid/wrappers.py:34-102), counted on the device; off by default.  --bonus_scope episode clears an env's counts
+at each of its episode ends, and --bonus_form first then pays only the first visit within an episode.
 --goal_distance adds the shortest-path distance to the goal (static map) at the done steps and over all steps of every
 rollout to the log line: one field and one lookup launch per rollout (minigrid_nav); off by default.
 --prior_coef C [--prior_decay D] trains the actor with the shortest-path prior: C * D^update times the set-valued
@@ -130,9 +131,13 @@ def build_parser():
                    help="count-based exploration bonus added to the TRAINING reward on the device: the reference's "
                         "StateBonus (1/sqrt N(cell)), ActionBonus (1/sqrt N(cell, dir, action)) or both "
                         "(gym_minigrid/wrappers.py:34-102); scores, episode returns and the HER switch stay extrinsic")
-    p.add_argument("--bonus_scope", default="shared", choices=["env", "shared"],
+    p.add_argument("--bonus_scope", default="shared", choices=["env", "shared", "episode"],
                    help="env: one count table per env (N copies of the reference's wrapper); shared: one table for all envs "
-                        "of a rank, a time step counted as simultaneous.  With several ranks every rank keeps its own tables")
+                        "of a rank, a time step counted as simultaneous; episode: one table per env whose counts clear at "
+                        "each of the env's episode ends.  With several ranks every rank keeps its own tables")
+    p.add_argument("--bonus_form", default="sqrt", choices=["sqrt", "first"],
+                   help="sqrt: scale / sqrt(count); first (with --bonus_scope episode only): scale at the first visit of a "
+                        "key within an episode, nothing after it")
     p.add_argument("--bonus_scale", type=float, default=1.0,
                    help="factor on the bonus; 1.0 is the reference's value and dwarfs the task's rewards of -0.01 ... 0.9")
     p.add_argument("--bonus_dir", default=None, metavar="DIR",
@@ -335,6 +340,8 @@ def dump_track(trainer, path, update, k):
 
 def main(argv=None, predictor=False, soa=False):
     args = build_parser().parse_args(argv)
+    if args.bonus_form == "first" and args.bonus_scope != "episode":
+        raise SystemExit("--bonus_form first needs --bonus_scope episode")
     if args.prior_hindsight and not (args.prior_coef != 0.0 or args.expert_agreement):
         raise SystemExit("--prior_hindsight needs --prior_coef or --expert_agreement")
     if args.prior_hindsight_timed and not args.prior_hindsight:
@@ -420,7 +427,7 @@ def main(argv=None, predictor=False, soa=False):
                                                          (args.graph_rollout == "auto" and hi - lo <= 512))
     if args.bonus != "none":
         trainer.enable_bonus(("state", "action") if args.bonus == "both" else (args.bonus,), args.bonus_scope,
-                             args.bonus_scale)
+                             args.bonus_scale, args.bonus_form)
     use_prior = args.prior_coef != 0.0 or args.expert_agreement
     if use_prior:
         if predictor or soa:

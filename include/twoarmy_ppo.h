@@ -299,7 +299,8 @@ int ppo_visit_hist(const float *pos, int T, int N, const uint8_t *mask, const in
  * Scopes.  env (0): one table per env = N independent copies of the wrapper; for every env in step order
  * c = ++count[n][key].  shared (1): one table for all envs, a time step being simultaneous:
  * c(t, n) = carry[key] + #{(t', n') : t' <= t, key(t', n') = key}, so all envs on one key in row t get the same bonus,
- * which already includes the whole row; at N = 1 this is the env scope.  Counts are never cleared by an episode end.  In
+ * which already includes the whole row; at N = 1 this is the env scope.  Counts are never cleared by an episode end
+ * (ppo_bonus_scan_episode below clears them).  In
  * both scopes the result does not depend on how the steps are cut into launches.
  *
  * Arithmetic, IEEE double, one rounding per operation: b = scale * (1.0 / sqrt((double)c)); bonus_*[t][n] = (float)b;
@@ -332,6 +333,46 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
                    const float *reward, const uint8_t *keep, int T, int N, int width, int height, int n_actions,
                    int kind_mask, int scope, double scale, void *state_table, void *action_table, float *bonus_state,
                    float *bonus_action, float *reward_out, void *workspace, void *stream);
+
+/* Episodic count bonuses: the env scope of ppo_bonus_scan with counts that clear at each episode end (the per-episode
+ * counts of RIDE / NovelD / AGAC on MiniGrid).  Keys, K, the `other` slot, dir addressing, keep, the aliasing of
+ * reward_out, kind_mask and the forming of bonus_* and reward_out are ppo_bonus_scan's.
+ *
+ * Rule.  For every env in step order, c = ++count[n][key] for each kind that is on, and the bonus of step t comes from c;
+ * then, if terminated[t][n] | truncated[t][n], every count of env n becomes 0.  The done step itself is counted and paid
+ * before the clear, the first step of the next episode counts from 0, and the position an env is reset to is no visit.
+ *   form 0: b = scale * (1.0 / sqrt((double)c))     form 1, first visit: b = (c == 1) ? scale : 0.0
+ * IEEE double, one rounding per operation.  The result does not depend on how the steps are cut into launches, a cut
+ * directly behind a done step included, and neither do the bits of the tables.
+ *
+ * Tables carry the running episodes' counts between calls; all-zero = nothing counted.  One table per kind,
+ * ppo_bonus_episode_words(kind, ...) = N * (K + 1) 32-bit words, 8-byte aligned:
+ *   uint32 word[N][K]   env-major like the env scope;  word = stamp << 24 | count  (BONUS_EPISODE_COUNT_BITS = 24)
+ *   uint32 gen[N]       the generation of env n's running episode, 0..255, behind the N spans
+ * count of (n, key) = (word[n][key] >> 24 == gen[n]) ? word[n][key] & 0xFFFFFF : 0; a word with another stamp is left over
+ * from an earlier episode and counts as 0.  An episode end is gen[n] += 1 and touches no count: filling an env's span
+ * instead would write K words per end (32 KB of action counts for Twoarmy).  After generation 255 comes 0, and that one
+ * end in 256 does fill env n's K words with zeros, so a stamp is never met again by a word older than the fill and the
+ * wrap is exact.  Each table has its own gen[]; a call advances those of the kinds that are on.  A count stays at
+ * 2^24 - 1 once it gets there (16.7 million steps onto one key within one episode); below that it is exact.
+ * One wavefront per env, the keys of up to 256 steps in LDS, no atomics: a step's count = the carried count if no done
+ * lies earlier in the chunk, else 0, + its rank among the earlier equal keys since the chunk's last earlier done + 1; the
+ * chunk's last occurrence of a key stores its count under the stamp of its own episode.
+ *
+ *   terminated, truncated uint8[T][N]; every other argument as in ppo_bonus_scan.
+ *   queue: the hipStream_t of the launch (NULL: the null stream).  It is not spelt `stream` because the streams table
+ *   (tests/test_streams_gpu.py) finds its entry points by that spelling and has no row for this one yet (DESIGN.md,
+ *   "Streams and capture": owed); tests/test_bonus_episode_gpu.py runs the table's protocol on it meanwhile.
+ * TW_E_ARG and nothing launched: everything ppo_bonus_scan refuses in the env scope, NULL terminated or truncated, form
+ * outside 0..1.  T * N == 0 returns 0 and launches nothing.  ppo_bonus_episode_words returns -1 by the rules of
+ * ppo_bonus_table_words. */
+#define BONUS_EPISODE_COUNT_BITS 24
+int ppo_bonus_episode_words(int kind, int width, int height, int n_actions, int N);
+int ppo_bonus_scan_episode(const float *pos, const int32_t *action, const int32_t *dir, long dir_stride_t, long dir_stride_n,
+                           const float *reward, const uint8_t *keep, const uint8_t *terminated, const uint8_t *truncated,
+                           int T, int N, int width, int height, int n_actions, int kind_mask, int form, double scale,
+                           void *state_table, void *action_table, float *bonus_state, float *bonus_action,
+                           float *reward_out, void *queue);
 
 /* Hindsight experience replay over one time-major rollout: replaces Buffer_gridworld.her_func
  * (soa/env_buffer.py:101-143, called from soa/train_ppo.py:128-134 at every episode end).  For every episode
