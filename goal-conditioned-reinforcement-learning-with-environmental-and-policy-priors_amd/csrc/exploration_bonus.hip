@@ -3,12 +3,12 @@
 // The reference's gym_minigrid/wrappers.py:34-102 keep a dict of visit counts and add 1/sqrt(count) to the reward:
 // StateBonus keyed by agent_pos, ActionBonus by (agent_pos, agent_dir, action).  The bonus of a step depends on how often
 // its key was seen BEFORE it, so the work is an ordered count, not a histogram:
-//   env scope     ppo_bonus_env_kernel: one wavefront per env; a chunk of steps has its keys in LDS, every step's rank
+//   env scope     ppo_bonus_env_kernel<false>: one wavefront per env; a chunk of steps has its keys in LDS, every step's rank
 //                 among the earlier equal keys of the chunk is counted there, the carried counts are gathered with
 //                 independent loads, and the last occurrence of a key stores the new count.  No atomics.
 //   shared scope  ppo_bonus_row_hist_kernel (per-row histogram of keys), ppo_bonus_key_scan_kernel (inclusive scan over
 //                 the rows per key, table += total), ppo_bonus_gather_kernel (count of (t, n) = table - total + prefix).
-//   episode scope ppo_bonus_episode_kernel: the env scope's scan cut at the episode ends; every count carries the stamp
+//   episode scope ppo_bonus_env_kernel<true>: the env scope's scan cut at the episode ends; every count carries the stamp
 //                 of its episode, so a done clears an env's counts by stepping one generation word.
 // Only integer adds reach the tables: the counts are exact whatever the scheduling, and the bonus is a pure function
 // of the count.
@@ -76,78 +76,12 @@ __device__ __forceinline__ void bonus_write(size_t i, double bs, double ba, cons
     }
 }
 
-// ---------------------------------------------------------------------------------------------------- env scope
-// One chunk of one env for one kind.  Lane l owns the steps u = j * 64 + l of the chunk.  b[j] receives the bonus.
-template <int KIND>
-__device__ __forceinline__ void bonus_env_chunk(const BonusIn &in, int n, int c0, int len, uint32_t *table, double scale,
-                                                int32_t *keys, double (&b)[BONUS_PER_LANE]) {
-    const int lane = threadIdx.x;
-    int k[BONUS_PER_LANE];
-    uint32_t carry[BONUS_PER_LANE];
-#pragma unroll
-    for (int j = 0; j < BONUS_PER_LANE; ++j) {
-        const int u = j * 64 + lane;
-        k[j] = -1;
-        carry[j] = 0u;
-        if (u < len) {
-            k[j] = bonus_key<KIND>(in, c0 + u, n);
-            keys[u] = k[j];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < BONUS_PER_LANE; ++j)                       // independent gathers: nothing waits on them yet
-        if (j * 64 + lane < len) carry[j] = table[k[j]];
-    int earlier[BONUS_PER_LANE] = {};
-    bool later[BONUS_PER_LANE] = {};
-    for (int v = 0; v < len; ++v) {
-        const int kv = keys[v];                                    // one address for the wavefront: a broadcast read
-#pragma unroll
-        for (int j = 0; j < BONUS_PER_LANE; ++j) {
-            const int u = j * 64 + lane;
-            const bool same = kv == k[j];
-            earlier[j] += (same && v < u) ? 1 : 0;
-            later[j] = later[j] || (same && v > u);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < BONUS_PER_LANE; ++j) {
-        if (j * 64 + lane < len) {
-            const uint32_t count = carry[j] + (uint32_t)earlier[j] + 1u;
-            if (!later[j]) table[k[j]] = count;                    // the chunk's last occurrence of the key
-            b[j] = bonus_value(count, scale);
-        }
-    }
-    __syncthreads();                                               // keys[] is reused; the next chunk gathers what was stored
-}
-
-__global__ __launch_bounds__(64) void ppo_bonus_env_kernel(BonusIn in, const float *reward, const uint8_t *keep,
-                                                           int kind_mask, double scale, uint32_t *state_table,
-                                                           uint32_t *action_table, float *bonus_state,
-                                                           float *bonus_action, float *reward_out) {
-    __shared__ int32_t keys[BONUS_CHUNK];
-    const int lane = threadIdx.x;
-    const int n = blockIdx.x;
-    const size_t ks = (size_t)bonus_keys(in, 1), ka = (size_t)bonus_keys(in, 2);
-    for (int c0 = 0; c0 < in.T; c0 += BONUS_CHUNK) {
-        const int len = min(BONUS_CHUNK, in.T - c0);
-        double bs[BONUS_PER_LANE] = {}, ba[BONUS_PER_LANE] = {};
-        if (kind_mask & 1) bonus_env_chunk<1>(in, n, c0, len, state_table + (size_t)n * ks, scale, keys, bs);
-        if (kind_mask & 2) bonus_env_chunk<2>(in, n, c0, len, action_table + (size_t)n * ka, scale, keys, ba);
-#pragma unroll
-        for (int j = 0; j < BONUS_PER_LANE; ++j) {
-            const int u = j * 64 + lane;
-            if (u < len)
-                bonus_write((size_t)(c0 + u) * in.N + n, bs[j], ba[j], reward, keep, bonus_state, bonus_action, reward_out);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------- episode scope
-// Counts that clear at each episode end (ppo_bonus_scan_episode).  A table word is stamp << 24 | count; it counts only
-// while its stamp equals the env's generation word, so an episode end clears the env's K counts by adding 1 to that one
-// word.  The generation that follows 255 is 0, and the step onto it fills the env's span with zeros: no word older than
-// 256 episode ends survives, and a stamp can only be met again by a word of the running episode.
+// -------------------------------------------------------------------------------------- env scope and episode scope
+// One scan, bonus_chunk, in two instantiations: EPISODIC = false is the env scope, whose table word is the lifetime count;
+// EPISODIC = true cuts it at the episode ends (ppo_bonus_scan_episode).  There a table word is stamp << 24 | count; it
+// counts only while its stamp equals the env's generation word, so an episode end clears the env's K counts by adding 1
+// to that one word.  The generation that follows 255 is 0, and the step onto it fills the env's span with zeros: no word
+// older than 256 episode ends survives, and a stamp can only be met again by a word of the running episode.
 constexpr uint32_t EP_COUNT_MASK = (1u << BONUS_EPISODE_COUNT_BITS) - 1u;
 constexpr uint32_t EP_GEN_MASK = (1u << (32 - BONUS_EPISODE_COUNT_BITS)) - 1u;
 
@@ -175,14 +109,16 @@ __device__ __forceinline__ EpisodeCuts episode_cuts(const uint8_t *terminated, c
     return cuts;
 }
 
-// One chunk of one env for one kind, as bonus_env_chunk, cut at the episode ends.  gen: the env's generation before
-// the chunk.  A step counts from the carried count only if no done lies earlier in the chunk, and among the earlier
-// equal keys only those behind the chunk's last earlier done.  The chunk's last occurrence of a key stores the count
-// with the stamp of its own episode: what a table holds does not depend on where the chunks are cut.
-template <int KIND>
-__device__ __forceinline__ void bonus_episode_chunk(const BonusIn &in, int n, int c0, int len, const EpisodeCuts &cuts,
-                                                    uint32_t gen, uint32_t *table, int K, int form, double scale,
-                                                    int32_t *keys, double (&b)[BONUS_PER_LANE]) {
+// One chunk of one env for one kind.  Lane l owns the steps u = j * 64 + l of the chunk.  b[j] receives the bonus.
+// Every step's rank among the earlier equal keys of the chunk is added to the carried count, and the chunk's last
+// occurrence of a key stores the new count.  EPISODIC (cuts, gen = the env's generation before the chunk, K and form are
+// read in no other case): a step counts from the carried count only if no done lies earlier in the chunk, and among the
+// earlier equal keys only those behind the chunk's last earlier done.  The count is stored with the stamp of its own
+// episode: what a table holds does not depend on where the chunks are cut.
+template <int KIND, bool EPISODIC>
+__device__ __forceinline__ void bonus_chunk(const BonusIn &in, int n, int c0, int len, const EpisodeCuts &cuts, uint32_t gen,
+                                            uint32_t *table, int K, int form, double scale, int32_t *keys,
+                                            double (&b)[BONUS_PER_LANE]) {
     const int lane = threadIdx.x;
     int k[BONUS_PER_LANE], since[BONUS_PER_LANE], ends[BONUS_PER_LANE];
     uint32_t carry[BONUS_PER_LANE];
@@ -190,11 +126,13 @@ __device__ __forceinline__ void bonus_episode_chunk(const BonusIn &in, int n, in
 #pragma unroll
     for (int j = 0; j < BONUS_PER_LANE; ++j) {
         const int u = j * 64 + lane;
-        const unsigned long long mine = cuts.done[j] & ((1ull << lane) - 1ull);       // the dones before u in its row
-        ends[j] = before + __popcll(mine);
-        since[j] = mine ? j * 64 + 63 - __clzll((long long)mine) : last;
-        before += __popcll(cuts.done[j]);
-        if (cuts.done[j]) last = j * 64 + 63 - __clzll((long long)cuts.done[j]);
+        if constexpr (EPISODIC) {
+            const unsigned long long mine = cuts.done[j] & ((1ull << lane) - 1ull);   // the dones before u in its row
+            ends[j] = before + __popcll(mine);
+            since[j] = mine ? j * 64 + 63 - __clzll((long long)mine) : last;
+            before += __popcll(cuts.done[j]);
+            if (cuts.done[j]) last = j * 64 + 63 - __clzll((long long)cuts.done[j]);
+        }
         k[j] = -1;
         carry[j] = 0u;
         if (u < len) {
@@ -214,57 +152,87 @@ __device__ __forceinline__ void bonus_episode_chunk(const BonusIn &in, int n, in
         for (int j = 0; j < BONUS_PER_LANE; ++j) {
             const int u = j * 64 + lane;
             const bool same = kv == k[j];
-            earlier[j] += (same && v < u && v > since[j]) ? 1 : 0;
+            bool counted = same && v < u;
+            if constexpr (EPISODIC) counted = counted && v > since[j];
+            earlier[j] += counted ? 1 : 0;
             later[j] = later[j] || (same && v > u);
         }
     }
-    // the done that steps from the last generation onto 0 is number 255 - gen of the chunk (from 0); it clears for real
-    const int wrap = (int)(EP_GEN_MASK - gen);
-    const bool wraps = wrap < cuts.total;
-    if (wraps) {
-        __syncthreads();                                           // the gathers have landed before their words are zeroed
-        for (int c = lane; c < K; c += 64) table[c] = 0u;
-        __syncthreads();
+    int wrap = 0;
+    bool wraps = false;
+    if constexpr (EPISODIC) {
+        // the done that steps from the last generation onto 0 is number 255 - gen of the chunk (from 0); it clears for real
+        wrap = (int)(EP_GEN_MASK - gen);
+        wraps = wrap < cuts.total;
+        if (wraps) {
+            __syncthreads();                                       // the gathers have landed before their words are zeroed
+            for (int c = lane; c < K; c += 64) table[c] = 0u;
+            __syncthreads();
+        }
     }
 #pragma unroll
     for (int j = 0; j < BONUS_PER_LANE; ++j) {
         if (j * 64 + lane < len) {
-            const bool fresh = ends[j] == 0 && (carry[j] >> BONUS_EPISODE_COUNT_BITS) == gen;
-            const uint32_t sum = (fresh ? carry[j] & EP_COUNT_MASK : 0u) + (uint32_t)earlier[j] + 1u;
-            const uint32_t count = min(sum, EP_COUNT_MASK);        // at most 2^24 - 1 + 256: no 32-bit wrap
-            const uint32_t stamp = (gen + (uint32_t)ends[j]) & EP_GEN_MASK;
-            // a key last seen at or before the real clear stays zero
-            if (!later[j] && !(wraps && ends[j] <= wrap)) table[k[j]] = stamp << BONUS_EPISODE_COUNT_BITS | count;
-            b[j] = form == 0 ? bonus_value(count, scale) : (count == 1u ? scale : 0.0);
+            if constexpr (EPISODIC) {
+                const bool fresh = ends[j] == 0 && (carry[j] >> BONUS_EPISODE_COUNT_BITS) == gen;
+                const uint32_t sum = (fresh ? carry[j] & EP_COUNT_MASK : 0u) + (uint32_t)earlier[j] + 1u;
+                const uint32_t count = min(sum, EP_COUNT_MASK);    // at most 2^24 - 1 + 256: no 32-bit wrap
+                const uint32_t stamp = (gen + (uint32_t)ends[j]) & EP_GEN_MASK;
+                // a key last seen at or before the real clear stays zero
+                if (!later[j] && !(wraps && ends[j] <= wrap)) table[k[j]] = stamp << BONUS_EPISODE_COUNT_BITS | count;
+                b[j] = form == 0 ? bonus_value(count, scale) : (count == 1u ? scale : 0.0);
+            } else {
+                const uint32_t count = carry[j] + (uint32_t)earlier[j] + 1u;
+                if (!later[j]) table[k[j]] = count;                // the chunk's last occurrence of the key
+                b[j] = bonus_value(count, scale);
+            }
         }
     }
     __syncthreads();                                               // keys[] is reused; the next chunk gathers what was stored
 }
 
-__global__ __launch_bounds__(64) void ppo_bonus_episode_kernel(BonusIn in, const float *reward, const uint8_t *keep,
-                                                               const uint8_t *terminated, const uint8_t *truncated,
-                                                               int kind_mask, int form, double scale,
-                                                               uint32_t *state_table, uint32_t *action_table,
-                                                               float *bonus_state, float *bonus_action,
-                                                               float *reward_out) {
+// The episode ends, an argument of the episodic kernel only: the env scope's has nothing there to read, and the empty
+// array keeps it at no bytes, so that kernel's argument block and code are what they were without it.
+template <bool EPISODIC>
+struct EpisodeFlags {
+    char none[0];
+};
+template <>
+struct EpisodeFlags<true> {
+    const uint8_t *terminated, *truncated;
+};
+
+// One wavefront per env.  EPISODIC: the kernel also owns the env's generation words, which follow the N spans of counts.
+template <bool EPISODIC>
+__global__ __launch_bounds__(64) void ppo_bonus_env_kernel(BonusIn in, const float *reward, const uint8_t *keep,
+                                                           EpisodeFlags<EPISODIC> flags, int kind_mask, int form,
+                                                           double scale, uint32_t *state_table, uint32_t *action_table,
+                                                           float *bonus_state, float *bonus_action, float *reward_out) {
     __shared__ int32_t keys[BONUS_CHUNK];
     const int lane = threadIdx.x;
     const int n = blockIdx.x;
     const int ks = bonus_keys(in, 1), ka = bonus_keys(in, 2);
-    // the generation words follow the N spans of counts
-    uint32_t *gen_state = (kind_mask & 1) ? state_table + (size_t)in.N * ks + n : nullptr;
-    uint32_t *gen_action = (kind_mask & 2) ? action_table + (size_t)in.N * ka + n : nullptr;
-    uint32_t gs = gen_state ? *gen_state & EP_GEN_MASK : 0u, ga = gen_action ? *gen_action & EP_GEN_MASK : 0u;
+    uint32_t *gen_state = nullptr, *gen_action = nullptr;
+    uint32_t gs = 0u, ga = 0u;
+    if constexpr (EPISODIC) {
+        if (kind_mask & 1) gen_state = state_table + (size_t)in.N * ks + n;
+        if (kind_mask & 2) gen_action = action_table + (size_t)in.N * ka + n;
+        gs = gen_state ? *gen_state & EP_GEN_MASK : 0u;
+        ga = gen_action ? *gen_action & EP_GEN_MASK : 0u;
+    }
     for (int c0 = 0; c0 < in.T; c0 += BONUS_CHUNK) {
         const int len = min(BONUS_CHUNK, in.T - c0);
-        const EpisodeCuts cuts = episode_cuts(terminated, truncated, n, in.N, c0, len);
+        EpisodeCuts cuts = {};
+        if constexpr (EPISODIC) cuts = episode_cuts(flags.terminated, flags.truncated, n, in.N, c0, len);
         double bs[BONUS_PER_LANE] = {}, ba[BONUS_PER_LANE] = {};
         if (kind_mask & 1)
-            bonus_episode_chunk<1>(in, n, c0, len, cuts, gs, state_table + (size_t)n * ks, ks, form, scale, keys, bs);
+            bonus_chunk<1, EPISODIC>(in, n, c0, len, cuts, gs, state_table + (size_t)n * ks, ks, form, scale, keys, bs);
         if (kind_mask & 2)
-            bonus_episode_chunk<2>(in, n, c0, len, cuts, ga, action_table + (size_t)n * ka, ka, form, scale, keys, ba);
-        gs = (gs + (uint32_t)cuts.total) & EP_GEN_MASK;
-        ga = (ga + (uint32_t)cuts.total) & EP_GEN_MASK;
+            bonus_chunk<2, EPISODIC>(in, n, c0, len, cuts, ga, action_table + (size_t)n * ka, ka, form, scale, keys, ba);
+        if constexpr (EPISODIC) {
+            gs = (gs + (uint32_t)cuts.total) & EP_GEN_MASK;
+            ga = (ga + (uint32_t)cuts.total) & EP_GEN_MASK;
+        }
 #pragma unroll
         for (int j = 0; j < BONUS_PER_LANE; ++j) {
             const int u = j * 64 + lane;
@@ -272,9 +240,11 @@ __global__ __launch_bounds__(64) void ppo_bonus_episode_kernel(BonusIn in, const
                 bonus_write((size_t)(c0 + u) * in.N + n, bs[j], ba[j], reward, keep, bonus_state, bonus_action, reward_out);
         }
     }
-    if (lane == 0) {
-        if (gen_state) *gen_state = gs;
-        if (gen_action) *gen_action = ga;
+    if constexpr (EPISODIC) {
+        if (lane == 0) {
+            if (gen_state) *gen_state = gs;
+            if (gen_action) *gen_action = ga;
+        }
     }
 }
 
@@ -353,16 +323,43 @@ bool bonus_geom_ok(int width, int height, int n_actions) {
     return visit_grid_ok(width, height) && n_actions >= 1 && n_actions <= BONUS_MAX_ACTIONS;
 }
 
+// Words of one table that holds (K + extra) * times words for the K keys of `kind`; TW_E_ARG where there is no such
+// table or it has 2^31 words or more.
+int bonus_words(int kind, int width, int height, int n_actions, int extra, int64_t times) {
+    if ((kind != 1 && kind != 2) || !bonus_geom_ok(width, height, n_actions) || times < 0) return TW_E_ARG;
+    const int64_t words = (bonus_keys_host(kind, width, height, n_actions) + extra) * times;
+    return words < ((int64_t)1 << 31) ? (int)words : TW_E_ARG;
+}
+
+BonusIn bonus_in(const float *pos, const int32_t *action, const int32_t *dir, long dir_stride_t, long dir_stride_n, int T,
+                 int N, int width, int height, int n_actions) {
+    return {reinterpret_cast<const float2 *>(pos), action, dir, dir_stride_t, dir_stride_n, T, N, width, height, n_actions};
+}
+
+// What both scan entries refuse.  words(kind): the entry's own table-size query, asked for the kinds in the mask.
+template <typename Words>
+bool bonus_scan_ok(const BonusIn &in, const float *reward, int kind_mask, const void *state_table, const void *action_table,
+                   const float *reward_out, Words words) {
+    if (!in.pos || ((uintptr_t)in.pos & 7u) || in.T < 0 || in.N < 0 || !bonus_geom_ok(in.width, in.height, in.n_actions))
+        return false;
+    if (kind_mask < 1 || kind_mask > 3) return false;
+    if ((kind_mask & 1) && (!state_table || ((uintptr_t)state_table & 7u))) return false;
+    if ((kind_mask & 2) && (!action_table || ((uintptr_t)action_table & 7u) || !in.action)) return false;
+    if (in.dir && (in.dir_stride_t < 0 || in.dir_stride_n < 0)) return false;
+    if (reward_out && !reward) return false;
+    if ((int64_t)in.T * in.N >= ((int64_t)1 << 31)) return false;         // a row histogram's 32-bit prefix cannot wrap
+    for (int kind = 1; kind <= 2; ++kind)
+        if ((kind_mask & kind) && words(kind) < 0) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
 
 int ppo_bonus_table_words(int kind, int scope, int width, int height, int n_actions, int N) {
-    if ((kind != 1 && kind != 2) || (scope != 0 && scope != 1) || !bonus_geom_ok(width, height, n_actions) || N < 0)
-        return TW_E_ARG;
-    const int64_t K = bonus_keys_host(kind, width, height, n_actions);
-    const int64_t words = scope == 0 ? K * N : 2 * K;
-    return words < ((int64_t)1 << 31) ? (int)words : TW_E_ARG;
+    if ((scope != 0 && scope != 1) || N < 0) return TW_E_ARG;
+    return bonus_words(kind, width, height, n_actions, 0, scope == 0 ? N : 2);        // a span per env, or one of int64
 }
 
 int64_t ppo_bonus_workspace_bytes(int kind_mask, int scope, int T, int width, int height, int n_actions) {
@@ -379,23 +376,16 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
                    const float *reward, const uint8_t *keep, int T, int N, int width, int height, int n_actions,
                    int kind_mask, int scope, double scale, void *state_table, void *action_table, float *bonus_state,
                    float *bonus_action, float *reward_out, void *workspace, void *stream) {
-    if (!pos || ((uintptr_t)pos & 7u) || T < 0 || N < 0 || !bonus_geom_ok(width, height, n_actions)) return TW_E_ARG;
-    if (kind_mask < 1 || kind_mask > 3 || (scope != 0 && scope != 1)) return TW_E_ARG;
-    if ((kind_mask & 1) && (!state_table || ((uintptr_t)state_table & 7u))) return TW_E_ARG;
-    if ((kind_mask & 2) && (!action_table || ((uintptr_t)action_table & 7u) || !action)) return TW_E_ARG;
-    if (dir && (dir_stride_t < 0 || dir_stride_n < 0)) return TW_E_ARG;
-    if (reward_out && !reward) return TW_E_ARG;
-    if ((int64_t)T * N >= ((int64_t)1 << 31)) return TW_E_ARG;            // a row histogram's 32-bit prefix cannot wrap
-    for (int kind = 1; kind <= 2; ++kind)
-        if ((kind_mask & kind) && ppo_bonus_table_words(kind, scope, width, height, n_actions, N) < 0) return TW_E_ARG;
-    if (scope == 1 && (!workspace || ((uintptr_t)workspace & 3u))) return TW_E_ARG;
+    const BonusIn in = bonus_in(pos, action, dir, dir_stride_t, dir_stride_n, T, N, width, height, n_actions);
+    const auto words = [&](int kind) { return ppo_bonus_table_words(kind, scope, width, height, n_actions, N); };
+    if (!bonus_scan_ok(in, reward, kind_mask, state_table, action_table, reward_out, words)) return TW_E_ARG;
+    if ((scope != 0 && scope != 1) || (scope == 1 && (!workspace || ((uintptr_t)workspace & 3u)))) return TW_E_ARG;
     if (T == 0 || N == 0) return TW_OK;
     const hipStream_t s = (hipStream_t)stream;
-    const BonusIn in = {reinterpret_cast<const float2 *>(pos), action, dir, dir_stride_t, dir_stride_n, T, N, width, height,
-                        n_actions};
     if (scope == 0) {
-        hipLaunchKernelGGL(ppo_bonus_env_kernel, dim3(N), dim3(64), 0, s, in, reward, keep, kind_mask, scale,
-                           (uint32_t *)state_table, (uint32_t *)action_table, bonus_state, bonus_action, reward_out);
+        hipLaunchKernelGGL(ppo_bonus_env_kernel<false>, dim3(N), dim3(64), 0, s, in, reward, keep, EpisodeFlags<false>{},
+                           kind_mask, 0, scale, (uint32_t *)state_table, (uint32_t *)action_table, bonus_state, bonus_action,
+                           reward_out);
         return tw_launched(__func__);
     }
     const int Ks = (int)bonus_keys_host(1, width, height, n_actions), Ka = (int)bonus_keys_host(2, width, height, n_actions);
@@ -423,31 +413,22 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
 }
 
 int ppo_bonus_episode_words(int kind, int width, int height, int n_actions, int N) {
-    if ((kind != 1 && kind != 2) || !bonus_geom_ok(width, height, n_actions) || N < 0) return TW_E_ARG;
-    const int64_t words = (bonus_keys_host(kind, width, height, n_actions) + 1) * N;      // K counts and a generation per env
-    return words < ((int64_t)1 << 31) ? (int)words : TW_E_ARG;
+    return bonus_words(kind, width, height, n_actions, 1, N);                              // K counts and a generation per env
 }
 
 int ppo_bonus_scan_episode(const float *pos, const int32_t *action, const int32_t *dir, long dir_stride_t, long dir_stride_n,
                            const float *reward, const uint8_t *keep, const uint8_t *terminated, const uint8_t *truncated,
                            int T, int N, int width, int height, int n_actions, int kind_mask, int form, double scale,
                            void *state_table, void *action_table, float *bonus_state, float *bonus_action,
-                           float *reward_out, void *queue) {
-    if (!pos || ((uintptr_t)pos & 7u) || T < 0 || N < 0 || !bonus_geom_ok(width, height, n_actions)) return TW_E_ARG;
-    if (kind_mask < 1 || kind_mask > 3 || (form != 0 && form != 1) || !terminated || !truncated) return TW_E_ARG;
-    if ((kind_mask & 1) && (!state_table || ((uintptr_t)state_table & 7u))) return TW_E_ARG;
-    if ((kind_mask & 2) && (!action_table || ((uintptr_t)action_table & 7u) || !action)) return TW_E_ARG;
-    if (dir && (dir_stride_t < 0 || dir_stride_n < 0)) return TW_E_ARG;
-    if (reward_out && !reward) return TW_E_ARG;
-    if ((int64_t)T * N >= ((int64_t)1 << 31)) return TW_E_ARG;
-    for (int kind = 1; kind <= 2; ++kind)
-        if ((kind_mask & kind) && ppo_bonus_episode_words(kind, width, height, n_actions, N) < 0) return TW_E_ARG;
+                           float *reward_out, void *stream) {
+    const BonusIn in = bonus_in(pos, action, dir, dir_stride_t, dir_stride_n, T, N, width, height, n_actions);
+    const auto words = [&](int kind) { return ppo_bonus_episode_words(kind, width, height, n_actions, N); };
+    if (!bonus_scan_ok(in, reward, kind_mask, state_table, action_table, reward_out, words)) return TW_E_ARG;
+    if ((form != 0 && form != 1) || !terminated || !truncated) return TW_E_ARG;
     if (T == 0 || N == 0) return TW_OK;
-    const BonusIn in = {reinterpret_cast<const float2 *>(pos), action, dir, dir_stride_t, dir_stride_n, T, N, width, height,
-                        n_actions};
-    hipLaunchKernelGGL(ppo_bonus_episode_kernel, dim3(N), dim3(64), 0, (hipStream_t)queue, in, reward, keep, terminated,
-                       truncated, kind_mask, form, scale, (uint32_t *)state_table, (uint32_t *)action_table, bonus_state,
-                       bonus_action, reward_out);
+    hipLaunchKernelGGL(ppo_bonus_env_kernel<true>, dim3(N), dim3(64), 0, (hipStream_t)stream, in, reward, keep,
+                       EpisodeFlags<true>{terminated, truncated}, kind_mask, form, scale, (uint32_t *)state_table,
+                       (uint32_t *)action_table, bonus_state, bonus_action, reward_out);
     return tw_launched(__func__);
 }
 

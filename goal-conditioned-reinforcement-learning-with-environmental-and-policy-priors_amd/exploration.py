@@ -33,9 +33,9 @@ class BonusTracker:
         self.scope, self.scale, self.form = scope, float(scale), form
         self.width, self.height, self.n_actions = int(width), int(height), int(n_actions)
         self.cells = self.width * self.height
-        words = (lambda k: ppo_ops.bonus_episode_words(k, width, height, n_actions, self.N)) if scope == "episode" else \
-            (lambda k: ppo_ops.bonus_table_words(k, scope, width, height, n_actions, self.N))
-        self.tables = {k: torch.zeros(words(k), dtype=torch.int32, device=self.device) for k in self.kinds}
+        words = (ppo_ops.bonus_episode_words,) if scope == "episode" else (ppo_ops.bonus_table_words, scope)
+        self.tables = {k: torch.zeros(words[0](k, *words[1:], width, height, n_actions, self.N), dtype=torch.int32,
+                                      device=self.device) for k in self.kinds}
         self.mask = sum(ppo_ops.BONUS_KINDS[k] for k in self.kinds)
         self.workspace = None                                                # sized by the first account()
         self.bonus = {}                                                      # kind -> f32[T,N] of the last account()
@@ -72,17 +72,13 @@ class BonusTracker:
             if self.workspace is None or self.workspace.numel() < need:
                 self.workspace = torch.empty(need, dtype=torch.int32, device=self.device)
         out = torch.empty_like(reward) if out is None else out
+        common = dict(state_table=self.tables.get("state"), action_table=self.tables.get("action"), scale=self.scale,
+                      width=self.width, height=self.height, n_actions=self.n_actions, keep=keep, dir=dir, dir_ptr=dir_ptr,
+                      bonus_state=self.bonus.get("state"), bonus_action=self.bonus.get("action"), reward_out=out)
         if episodic:
-            ppo_ops.bonus_scan_episode(pos, action, reward, terminated, truncated, self.tables.get("state"),
-                                       self.tables.get("action"), self.form, self.scale, self.width, self.height,
-                                       self.n_actions, keep=keep, dir=dir, dir_ptr=dir_ptr,
-                                       bonus_state=self.bonus.get("state"), bonus_action=self.bonus.get("action"),
-                                       reward_out=out)
+            ppo_ops.bonus_scan_episode(pos, action, reward, terminated, truncated, form=self.form, **common)
         else:
-            ppo_ops.bonus_scan(pos, action, reward, self.tables.get("state"), self.tables.get("action"), self.scope,
-                               self.scale, self.width, self.height, self.n_actions, keep=keep, dir=dir, dir_ptr=dir_ptr,
-                               bonus_state=self.bonus.get("state"), bonus_action=self.bonus.get("action"), reward_out=out,
-                               workspace=self.workspace)
+            ppo_ops.bonus_scan(pos, action, reward, scope=self.scope, workspace=self.workspace, **common)
         return out[0] if one else out
 
     def counts(self, kind):

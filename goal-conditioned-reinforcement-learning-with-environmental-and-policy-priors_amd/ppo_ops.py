@@ -295,6 +295,25 @@ def bonus_workspace_bytes(kind_mask, scope, T, width=17, height=17, n_actions=7)
                   int(n_actions))
 
 
+def _bonus_args(pos, per_step, tables, dir, dir_ptr, words):
+    """What the two bonus scans share -> (T, N, kind mask, (dir pointer, stride_t, stride_n)): pos is [T,N,2], every
+    tensor of per_step [T,N] or None, and the (state, action) tables given have words(kind, N) words."""
+    T, N = pos.shape[:2]
+    assert pos.shape == (T, N, 2)
+    for t in per_step:
+        assert t is None or t.shape == (T, N)
+    mask = (1 if tables[0] is not None else 0) | (2 if tables[1] is not None else 0)
+    dp, st, sn = None, 0, 0
+    if dir is not None:
+        assert dir.shape in ((T, N), (N,))
+        dp, st, sn = _p(dir, torch.int32), (N if dir.dim() == 2 else 0), 1
+    elif dir_ptr is not None:
+        dp, st, sn = C.c_void_p(int(dir_ptr[0])), int(dir_ptr[1]), int(dir_ptr[2])
+    for kind, tab in zip(("state", "action"), tables):
+        assert tab is None or tab.numel() == words(kind, N)
+    return T, N, mask, (dp, st, sn)
+
+
 def bonus_scan(pos, action, reward, state_table=None, action_table=None, scope="env", scale=1.0, width=17, height=17,
                n_actions=7, keep=None, dir=None, dir_ptr=None, bonus_state=None, bonus_action=None, reward_out=None,
                workspace=None):
@@ -304,25 +323,15 @@ def bonus_scan(pos, action, reward, state_table=None, action_table=None, scope="
     (one direction per env), or dir_ptr = (address, stride_t, stride_n) of directions that live elsewhere on the device
     (the engine's records); neither: direction 0.  keep u8[T,N]: steps whose reward passes through unshaped.  Writes the
     outputs given (bonus_state / bonus_action / reward_out f32[T,N]; reward_out may be reward); no host synchronisation."""
-    T, N = pos.shape[:2]
-    assert pos.shape == (T, N, 2)
-    for t in (action, reward, keep, bonus_state, bonus_action, reward_out):
-        assert t is None or t.shape == (T, N)
-    mask = (1 if state_table is not None else 0) | (2 if action_table is not None else 0)
-    dp, st, sn = None, 0, 0
-    if dir is not None:
-        assert dir.shape in ((T, N), (N,))
-        dp, st, sn = _p(dir, torch.int32), (N if dir.dim() == 2 else 0), 1
-    elif dir_ptr is not None:
-        dp, st, sn = C.c_void_p(int(dir_ptr[0])), int(dir_ptr[1]), int(dir_ptr[2])
+    T, N, mask, dirs = _bonus_args(pos, (action, reward, keep, bonus_state, bonus_action, reward_out),
+                                   (state_table, action_table), dir, dir_ptr,
+                                   lambda kind, N: bonus_table_words(kind, scope, width, height, n_actions, N))
     if BONUS_SCOPES[scope] == 1:
         need = bonus_workspace_bytes(mask, scope, T, width, height, n_actions)
         if workspace is None:
             workspace = torch.empty(max(1, need // 4), dtype=torch.int32, device=pos.device)
         assert workspace.numel() * 4 >= need
-    for kind, tab in (("state", state_table), ("action", action_table)):
-        assert tab is None or tab.numel() == bonus_table_words(kind, scope, width, height, n_actions, N)
-    _call("ppo_bonus_scan", pos, _p(pos, torch.float32), _p(action, torch.int32), dp, st, sn, _p(reward, torch.float32),
+    _call("ppo_bonus_scan", pos, _p(pos, torch.float32), _p(action, torch.int32), *dirs, _p(reward, torch.float32),
           _p(keep, torch.uint8), T, N, int(width), int(height), int(n_actions), mask, BONUS_SCOPES[scope], float(scale),
           _p(state_table, torch.int32), _p(action_table, torch.int32), _p(bonus_state, torch.float32),
           _p(bonus_action, torch.float32), _p(reward_out, torch.float32), _p(workspace, torch.int32))
@@ -356,20 +365,10 @@ def bonus_scan_episode(pos, action, reward, terminated, truncated, state_table=N
     "sqrt": scale / sqrt(count), "first": scale at a key's first visit of the episode, else 0.  The tables given (i32 words,
     bonus_episode_words; updated IN PLACE, they carry the running episodes between calls) select the kinds.  Every other
     argument as in bonus_scan; no host synchronisation."""
-    T, N = pos.shape[:2]
-    assert pos.shape == (T, N, 2)
-    for t in (action, reward, keep, terminated, truncated, bonus_state, bonus_action, reward_out):
-        assert t is None or t.shape == (T, N)
-    mask = (1 if state_table is not None else 0) | (2 if action_table is not None else 0)
-    dp, st, sn = None, 0, 0
-    if dir is not None:
-        assert dir.shape in ((T, N), (N,))
-        dp, st, sn = _p(dir, torch.int32), (N if dir.dim() == 2 else 0), 1
-    elif dir_ptr is not None:
-        dp, st, sn = C.c_void_p(int(dir_ptr[0])), int(dir_ptr[1]), int(dir_ptr[2])
-    for kind, tab in (("state", state_table), ("action", action_table)):
-        assert tab is None or tab.numel() == bonus_episode_words(kind, width, height, n_actions, N)
-    _call("ppo_bonus_scan_episode", pos, _p(pos, torch.float32), _p(action, torch.int32), dp, st, sn,
+    T, N, mask, dirs = _bonus_args(pos, (action, reward, keep, terminated, truncated, bonus_state, bonus_action, reward_out),
+                                   (state_table, action_table), dir, dir_ptr,
+                                   lambda kind, N: bonus_episode_words(kind, width, height, n_actions, N))
+    _call("ppo_bonus_scan_episode", pos, _p(pos, torch.float32), _p(action, torch.int32), *dirs,
           _p(reward, torch.float32), _p(keep, torch.uint8), _p(terminated, torch.uint8), _p(truncated, torch.uint8), T, N,
           int(width), int(height), int(n_actions), mask, BONUS_FORMS[form], float(scale), _p(state_table, torch.int32),
           _p(action_table, torch.int32), _p(bonus_state, torch.float32), _p(bonus_action, torch.float32),

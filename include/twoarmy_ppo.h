@@ -359,10 +359,7 @@ int ppo_bonus_scan(const float *pos, const int32_t *action, const int32_t *dir, 
  * lies earlier in the chunk, else 0, + its rank among the earlier equal keys since the chunk's last earlier done + 1; the
  * chunk's last occurrence of a key stores its count under the stamp of its own episode.
  *
- *   terminated, truncated uint8[T][N]; every other argument as in ppo_bonus_scan.
- *   queue: the hipStream_t of the launch (NULL: the null stream).  It is not spelt `stream` because the streams table
- *   (tests/test_streams_gpu.py) finds its entry points by that spelling and has no row for this one yet (DESIGN.md,
- *   "Streams and capture": owed); tests/test_bonus_episode_gpu.py runs the table's protocol on it meanwhile.
+ *   terminated, truncated uint8[T][N]; every other argument, `stream` included, as in ppo_bonus_scan.
  * TW_E_ARG and nothing launched: everything ppo_bonus_scan refuses in the env scope, NULL terminated or truncated, form
  * outside 0..1.  T * N == 0 returns 0 and launches nothing.  ppo_bonus_episode_words returns -1 by the rules of
  * ppo_bonus_table_words. */
@@ -372,7 +369,7 @@ int ppo_bonus_scan_episode(const float *pos, const int32_t *action, const int32_
                            const float *reward, const uint8_t *keep, const uint8_t *terminated, const uint8_t *truncated,
                            int T, int N, int width, int height, int n_actions, int kind_mask, int form, double scale,
                            void *state_table, void *action_table, float *bonus_state, float *bonus_action,
-                           float *reward_out, void *queue);
+                           float *reward_out, void *stream);
 
 /* Hindsight experience replay over one time-major rollout: replaces Buffer_gridworld.her_func
  * (soa/env_buffer.py:101-143, called from soa/train_ppo.py:128-134 at every episode end).  For every episode

@@ -21,16 +21,18 @@ class Case:
     atol)} of the existing test of that op, exact where absent; ref may also return "_atol": {name: bound} where that test's
     bound depends on the data.  ref_in_b=False: part B compares with the eager sequence only.  setup(seed) -> ctx: host-side objects a run needs
     (an engine), made before the protocol starts.  blocks_host: the call returns only when its work is done.
+    read(name, array) -> array: how a result or a state input is read before it meets the CPU restatement, where its
+    words hold more than the restatement defines (None: as it is).
     also(part, x, y): what this case asserts beyond the protocol, called after the generic checks of each part, None:
     nothing.  Part "A": x = the side-stream results, y = the default-stream results of the decoy (seed 0), which the case
     expects to differ.  Part "B": x, y = the results of replay 1 and replay 2."""
 
     def __init__(self, name, family, fns, make, call, outs=None, ref=None, state=(), tol=None, setup=None, note=None,
-                 exempt_b=None, blocks_host=False, ref_in_b=True, also=None):
+                 exempt_b=None, blocks_host=False, ref_in_b=True, also=None, read=None):
         self.name, self.family, self.fns, self.make, self.call = name, family, tuple(fns), make, call
         self.outs, self.ref, self.state, self.tol = outs or (lambda: {}), ref, tuple(state), tol or {}
         self.setup, self.exempt_b, self.blocks_host = setup or (lambda seed: None), exempt_b, blocks_host
-        self.ref_in_b, self.also = ref_in_b, also
+        self.ref_in_b, self.also, self.read = ref_in_b, also, read or (lambda name, array: array)
         self.note = note if note is not None else ("CPU restatement + default-stream run" if ref else
                                                    "default-stream run only")
         assert ref is not None or "only" in self.note
@@ -184,7 +186,7 @@ def check_against_ref(case, got, want, where):
     for k, w in want.items():
         if k == "_atol":
             continue
-        g, w = got[k], np.asarray(w)
+        g, w = case.read(k, got[k]), np.asarray(w)
         assert g.shape == w.shape, (case.name, where, k, g.shape, w.shape)
         if k in bounds:
             assert (np.abs(g.astype(np.float64) - w.astype(np.float64)) <= bounds[k]).all(), (case.name, where, k, g, w)

@@ -1,8 +1,8 @@
 """ppo_bonus_scan_episode (csrc/exploration_bonus.hip) bit for bit against tests/bonus_episode_ref.py: outputs, and the
 tables read by the layout the header documents (stamped words, a generation per env); raw table bits where two runs of
-the kernel are compared.  Then every front end: BonusTracker(scope="episode"), VecPPOTrainer.enable_bonus on a real
-engine, train_ppo --bonus_scope episode, and the streams protocol of tests/stream_util.py, which the streams table owes
-this entry (its last parameter is spelt `queue`, include/twoarmy_ppo.h)."""
+the kernel are compared, and bonus_scan's env scope where no episode ends.  Then every front end:
+BonusTracker(scope="episode"), VecPPOTrainer.enable_bonus on a real engine, train_ppo --bonus_scope episode.  Side streams
+and graph capture: the entry's row in tests/test_streams_gpu.py."""
 import ctypes as C
 import functools
 import os
@@ -15,7 +15,6 @@ import pytest
 import torch
 
 import bonus_episode_ref as er
-import stream_util as su
 from test_bonus_cpu import random_walk
 
 pytestmark = pytest.mark.gpu
@@ -381,7 +380,7 @@ def test_bad_arguments_are_refused_and_change_nothing():
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())                 # noqa: E731
     good = dict(pos=p(pos), action=p(act), dir=None, st=0, sn=0, reward=p(rew), keep=None, term=p(flag), trunc=p(flag), T=T,
                 N=N, w=17, h=17, na=7, mask=3, form=0, scale=1.0, stab=p(st), atab=p(at), bs=p(bs), ba=None, ro=p(rew),
-                queue=None)
+                stream=None)
     call = lambda **kw: lib.ppo_bonus_scan_episode(*{**good, **kw}.values())      # noqa: E731
     bad = [dict(pos=None), dict(pos=C.c_void_p(pos.data_ptr() + 4)), dict(stab=None), dict(atab=None), dict(action=None),
            dict(mask=0), dict(mask=4), dict(w=0), dict(h=33), dict(na=0), dict(na=9), dict(T=-1), dict(N=-1),
@@ -402,76 +401,28 @@ def test_bad_arguments_are_refused_and_change_nothing():
     assert _lib.lib().tw_last_hip_error() == 0 and (bs != -7).all() and st.any() and at.any()
 
 
-# ------------------------------------------------------------------------------------------------ 5. streams
-ST, SN = 40, 70
-
-
-def _stream_case():
+# ------------------------------------------------------------------------------------------------ 5. the env scope
+@pytest.mark.parametrize("T,N", [(1, 1), (257, 3), (513, 65)])      # one step, a chunk boundary, two chunks and 65 envs
+@pytest.mark.parametrize("mask", (1, 2, 3))
+def test_without_an_episode_end_it_is_the_env_scope(T, N, mask):
+    """No step flagged done, form "sqrt", fresh tables: bonus_scan(scope="env") bit for bit in every output, its counts
+    in the decoded tables, and every generation word 0."""
     from twoarmy_amd import ppo_ops
-
-    def make(seed):
-        pos, action, dirs, reward, term, trunc = walk(ST, SN, 50 + seed)
-        keep = (su.rng(seed).random((ST, SN)) < 0.3).astype(np.uint8)
-        b = dict(pos=dev(pos, torch.float32), action=dev(action, torch.int32), dirs=dev(dirs, torch.int32),
-                 reward=dev(reward, torch.float32), term=dev(term, torch.uint8), trunc=dev(trunc, torch.uint8),
-                 keep=dev(keep, torch.uint8))
-        for k in KINDS[3]:
-            b["table_" + k] = torch.zeros(ppo_ops.bonus_episode_words(k, N=SN), dtype=torch.int32, device=DEV)
-        return b
-
-    def outs():
-        return {k: torch.empty((ST, SN), device=DEV) for k in ("bonus_state", "bonus_action", "reward_out")}
-
-    def call(b, o, ctx):
-        ppo_ops.bonus_scan_episode(b["pos"], b["action"], b["reward"], b["term"], b["trunc"], b["table_state"],
-                                   b["table_action"], scale=0.5, keep=b["keep"], dir=b["dirs"], bonus_state=o["bonus_state"],
-                                   bonus_action=o["bonus_action"], reward_out=o["reward_out"])
-        return dict(o, table_state=b["table_state"], table_action=b["table_action"])
-
-    return su.Case("bonus_scan_episode", "bonuses", ["ppo_bonus_scan_episode"], make, call, outs=outs,
-                   state=("table_state", "table_action"),
-                   note="default-stream run only: the restatement is compared by this file on the tables as decoded")
-
-
-def _against_ref(ref, h, got, where):
-    """One call's results against the restatement `ref`, which carries the counts from call to call."""
-    want = ref.scan(h["pos"], h["action"], h["reward"], h["term"], h["trunc"], keep=h["keep"], dirs=h["dirs"])
-    for k in KINDS[3]:
-        assert su.same_bits(got["bonus_" + k], want[k]), (where, k)
-        counts, gen, _ = er.decode(got["table_" + k], SN)
-        assert np.array_equal(counts, ref.table(k)) and list(gen) == ref.gen[k], (where, k)
-    assert su.same_bits(got["reward_out"], want["reward"]), where
-
-
-def test_eager_on_a_side_stream_and_the_control_call_on_the_default_stream():
-    """Part A of the streams table's protocol: staged behind the delay on a side stream, the call must run there too.
-    Then the control: the same staging with the call on the default stream reads the decoy, and that is seen."""
-    case = _stream_case()
-    want = su.run_default(case, 1)
-    got, still_running = su.run_side(case, 1)
-    assert still_running, "the delay ended before the host had enqueued the call (%.3f ms)" % su.ENQUEUE_MS[case.name]
-    su.check_same(case, got, want, "side stream")
-    _against_ref(er.EpisodeBonusRef(SN, KINDS[3], 0.5), su.host_inputs(case.make(1)), got, "side stream")
-    wrong, still_running = su.run_side(case, 1, call_on_default=True)
-    assert still_running
-    assert not all(su.same_bits(wrong[k], want[k]) for k in want), "a call on the wrong stream went unnoticed"
-    assert su.hip_error() == 0
-
-
-def test_captured_and_replayed_twice():
-    """Part B: an eager warm-up, capture, two replays on fresh inputs with the tables carried through all three."""
-    case = _stream_case()
-    eager, _ = su.expected_sequence(case)
-    got = su.run_captured(case)
-    ref = er.EpisodeBonusRef(SN, KINDS[3], 0.5)
-    for i, seed in enumerate(su.SEEDS_B):
-        h = su.host_inputs(case.make(seed))
-        if i == 0:
-            _against_ref(ref, h, eager[0], "warm-up")
-            continue
-        su.check_same(case, got[i - 1], eager[i], "replay %d" % i)
-        _against_ref(ref, h, got[i - 1], "replay %d" % i)
-    assert su.hip_error() == 0
+    pos, action, dirs, reward = walk(T, N, 11, 0.0)[:4]
+    none = np.zeros((T, N), np.uint8)
+    keep = (np.random.RandomState(5).rand(T, N) < 0.3).astype(np.uint8)
+    run = Run(N, mask, "sqrt", 0.5)
+    got = run.scan(pos, action, dirs, reward, none, none, keep=keep)
+    tab = {k: torch.zeros(ppo_ops.bonus_table_words(k, "env", N=N), dtype=torch.int32, device=DEV) for k in KINDS[mask]}
+    out = {k: torch.full((T, N), -7.0, device=DEV) for k in KINDS[mask] + ("reward",)}
+    ppo_ops.bonus_scan(dev(pos, torch.float32), dev(action, torch.int32), dev(reward, torch.float32), tab.get("state"),
+                       tab.get("action"), "env", 0.5, keep=dev(keep, torch.uint8), dir=dev(dirs, torch.int32),
+                       bonus_state=out.get("state"), bonus_action=out.get("action"), reward_out=out["reward"])
+    same(got, {k: t.cpu().numpy() for k, t in out.items()}, mask)
+    for k, words in run.raw().items():
+        counts, gen, _ = er.decode(words, N)
+        assert np.array_equal(counts, (tab[k].cpu().numpy().astype(np.int64) & 0xFFFFFFFF).reshape(N, -1)), k
+        assert counts.sum() == T * N and not gen.any(), k
 
 
 # ------------------------------------------------------------------------------------------------ 6. front ends

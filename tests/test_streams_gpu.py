@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import bonus_episode_ref
 import bonus_ref
 import episode_ref
 import gae_runs_ref as gr
@@ -25,6 +26,7 @@ import timed_goal_ahead_ref as taref
 import update_stats_ref as ur
 import visit_ref
 from nav_util import u16_full
+from test_bonus_episode_gpu import walk as episode_walk
 from stream_util import (DEV, ENQUEUE_MS, Case, check_against_ref, check_same, dev, expected_sequence, hip_error, host,
                          rng, run_captured, run_default, run_side, same_bits)
 
@@ -559,7 +561,56 @@ def _bonus_case(scope):
                 state=("table_state", "table_action"))
 
 
-CASES += [_bonus_case("env"), _bonus_case("shared")]
+BT, BN = 40, 70                      # the episodic scan: column 1 of episode_walk ends an episode at every step
+
+
+def _episode_tables(words):
+    """Stamped words -> what they mean: the running episodes' counts, then the generations."""
+    counts, gen, _ = bonus_episode_ref.decode(words, BN)
+    return np.concatenate([counts.reshape(-1), gen])
+
+
+def _bonus_episode_case():
+    def make(seed):
+        pos, action, dirs, reward, term, trunc = episode_walk(BT, BN, 50 + seed)
+        b = up(dict(pos=pos, action=action.astype(I32), dirs=dirs.astype(I32), reward=reward, term=term, trunc=trunc,
+                    keep=(rng(seed).random((BT, BN)) < 0.3).astype(U8)))
+        for k in ("state", "action"):
+            b["table_" + k] = torch.zeros(ops().bonus_episode_words(k, N=BN), dtype=torch.int32, device=DEV)
+        return b
+
+    def call(b, o, ctx):
+        ops().bonus_scan_episode(b["pos"], b["action"], b["reward"], b["term"], b["trunc"], b["table_state"], b["table_action"],
+                                 scale=0.5, keep=b["keep"], dir=b["dirs"], bonus_state=o["bonus_state"],
+                                 bonus_action=o["bonus_action"], reward_out=o["reward_out"])
+        return dict(o, table_state=b["table_state"], table_action=b["table_action"])
+
+    def ref(h):
+        r = bonus_episode_ref.EpisodeBonusRef(BN, ("state", "action"), 0.5)
+        for k in r.kinds:
+            counts, gen, _ = bonus_episode_ref.decode(h["table_" + k], BN)
+            r.preset(k, counts, gen)
+        w = r.scan(h["pos"], h["action"], h["reward"], h["term"], h["trunc"], keep=h["keep"], dirs=h["dirs"])
+        tabs = {k: np.concatenate([r.table(k).reshape(-1), r.gen[k]]) for k in r.kinds}
+        return dict(bonus_state=w["state"], bonus_action=w["action"], reward_out=w["reward"], table_state=tabs["state"],
+                    table_action=tabs["action"])
+
+    def also(part, x, y):
+        if part == "A":                                        # the decoy has another answer everywhere
+            assert not unchanged(x, y, x)
+            return
+        for k in ("table_state", "table_action"):              # the tables are carried: 40 more episode ends per call
+            gens = [bonus_episode_ref.decode(r[k], BN)[1] for r in (x, y)]
+            assert [g[1] for g in gens] == [2 * BT, 3 * BT] and not gens[1][0]
+
+    return Case("bonus_scan_episode", "bonuses", ["ppo_bonus_scan_episode"], make, call, ref=ref, also=also,
+                outs=lambda: {k: torch.empty((BT, BN), device=DEV) for k in ("bonus_state", "bonus_action", "reward_out")},
+                state=("table_state", "table_action"),
+                read=lambda k, a: _episode_tables(a) if k.startswith("table_") else a)
+
+
+BONUS_EPISODE = _bonus_episode_case()
+CASES += [_bonus_case("env"), _bonus_case("shared"), BONUS_EPISODE]
 
 # ----------------------------------------------------------------------------------------------------- navigation
 R_ = CHUNK + 1
@@ -988,7 +1039,7 @@ def test_eager_on_a_side_stream(case):
     assert hip_error() == 0
 
 
-@pytest.mark.parametrize("case", [GAE, ADV_NORM], ids=repr)
+@pytest.mark.parametrize("case", [GAE, ADV_NORM, BONUS_EPISODE], ids=repr)
 def test_control_call_on_the_default_stream_is_seen(case):
     """The protocol with the mistake it looks for made on purpose: the inputs are staged on the side stream behind the
     delay, the call goes to the default stream and reads the decoy (valid memory: a mis-ordering, not a fault)."""
@@ -1098,7 +1149,7 @@ def stream_functions():
 def test_every_stream_function_has_a_case():
     want = stream_functions()
     print("%d prototypes take a stream" % len(want))
-    assert len(want) >= 60 and "tw_rollout" in want and "mg_obs_onehot" in want and "ppo_gae_runs" in want
+    assert len(want) >= 61 and "tw_rollout" in want and "mg_obs_onehot" in want and "ppo_gae_runs" in want
     part_a = {f for c in CASES for f in c.fns}
     part_b = {f for c in CASES for f in c.fns if c.exempt_b is None or c.exempt_b.startswith("own test")} | \
         {f for f in want if f in EXEMPT}
