@@ -14,6 +14,7 @@
 #include "philox.h"
 #include "twoarmy.h"
 #include "twoarmy_ppo.h"
+#include "visit_cell.h"
 
 namespace {
 
@@ -822,6 +823,27 @@ __global__ __launch_bounds__(256) void ppo_gather_stack_kernel(const FT *__restr
 // One wavefront per env walks its episodes in time order; an episode (<= 64 steps) sits one step per lane.
 constexpr int HER_MAX_LEN = 64;
 
+// np.unique(axis=0) of an episode that sits one record per lane, (py, px) = lane's achieved (y, x), L <= 64 records:
+// first = this lane holds the first occurrence of its (y, x), rank = its place among the first occurrences ordered
+// lexicographically by (y, x) -- the unit of `choices`; returns the mask of first occurrences.  Float compares, so
+// +0.0 and -0.0 are one position.  Window records (skip = 4, env_buffer.py:145-280) only offer the states after steps
+// skip, skip + 1, ...  Every lane of the wavefront must call this.
+__device__ __forceinline__ unsigned long long her_first_visits(float py, float px, int lane, int L, int skip, bool &first,
+                                                               int &rank) {
+    first = lane < L && lane >= skip;
+    for (int j = skip; j < L; ++j) {
+        const float qy = __shfl(py, j), qx = __shfl(px, j);
+        if (j < lane && qy == py && qx == px) first = false;
+    }
+    const unsigned long long fm = __ballot(first);
+    rank = 0;
+    for (int j = 0; j < L; ++j) {
+        const float qy = __shfl(py, j), qx = __shfl(px, j);
+        if (((fm >> j) & 1ull) && (qy < py || (qy == py && qx < px))) ++rank;
+    }
+    return fm;
+}
+
 __global__ __launch_bounds__(64) void ppo_her_kernel(const float *__restrict__ pos, const uint8_t *__restrict__ terminated,
                                                      const uint8_t *__restrict__ truncated,
                                                      const int32_t *__restrict__ age0, const float *__restrict__ reward,
@@ -854,20 +876,9 @@ __global__ __launch_bounds__(64) void ppo_her_kernel(const float *__restrict__ p
             const bool in = lane < L;
             const size_t row = (size_t)(s0 + (in ? lane : 0)) * N + n;
             const float py = pos[row * 2], px = pos[row * 2 + 1];
-            // np.unique(axis=0): first occurrence of every distinct (y, x), ordered lexicographically by (y, x).
-            // Window records (skip = 4, env_buffer.py:145-280) only offer the states after steps skip, skip+1, ...
-            bool first = in && lane >= skip;
-            for (int j = skip; j < L; ++j) {
-                const float qy = __shfl(py, j), qx = __shfl(px, j);
-                if (j < lane && qy == py && qx == px) first = false;
-            }
-            const unsigned long long fm = __ballot(first);
-            const int U = __popcll(fm);
-            int rank = 0;
-            for (int j = 0; j < L; ++j) {
-                const float qy = __shfl(py, j), qx = __shfl(px, j);
-                if (((fm >> j) & 1ull) && (qy < py || (qy == py && qx < px))) ++rank;
-            }
+            bool first;
+            int rank;
+            const int U = __popcll(her_first_visits(py, px, lane, L, skip, first, rank));
             const int k = max_goals < U ? max_goals : U;
             // Fisher-Yates over the U unique entries when no explicit picks are supplied (lane j holds perm[j])
             int perm = lane;
@@ -904,6 +915,90 @@ __global__ __launch_bounds__(64) void ppo_her_kernel(const float *__restrict__ p
         }
     }
     if (lane == 0 && counts) counts[n] = total;
+}
+
+// Which first visits become goals, by rule: the picks ppo_her_kernel reads as `choices`.  The same walk over the same
+// episodes; the candidates are the first visits but the one at record `skip`, which the relabelling never uses
+// (`0 < index`).  The smallest (key, Philox word, rank) comes first; a lane finds its place by counting the candidates
+// that come before it, one broadcast per candidate.  The tallies stay in registers until the env is walked.
+__global__ __launch_bounds__(64) void ppo_her_select_kernel(const float *__restrict__ pos, const uint8_t *__restrict__ terminated,
+                                                            const uint8_t *__restrict__ truncated,
+                                                            const int32_t *__restrict__ age0, int T, int N, int max_goals,
+                                                            int skip, int rule, const uint16_t *__restrict__ key16,
+                                                            const int64_t *__restrict__ table, int width, int height,
+                                                            uint32_t k0, uint32_t k1, uint32_t env_id0, uint32_t step0,
+                                                            int32_t *__restrict__ choices,
+                                                            unsigned long long *__restrict__ stats) {
+    const int n = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (n >= N) return;
+    long long tally = 0;                             // lane j < 6 carries stats[j] of this env
+    long long prefix_sum = 0, key_sum = 0;           // per lane, summed over the lanes at the end
+    int unreachable = 0;
+    int start = age0[n] == 0 ? 0 : -1;               // an episode already running at t = 0 is not relabelled
+    for (int c0 = 0; c0 < T; c0 += 64) {
+        const int tl = c0 + lane;
+        const bool d = tl < T && done_at(terminated, truncated, (size_t)tl * N + n) != 0;
+        unsigned long long dm = __ballot(d);
+        while (dm) {
+            const int t1 = c0 + __builtin_ctzll(dm);
+            dm &= dm - 1;
+            const int s0 = start;
+            start = t1 + 1;
+            if (s0 < 0) continue;
+            const int L = t1 - s0 + 1;
+            if (L > HER_MAX_LEN) continue;
+            const bool in = lane < L;
+            const size_t row = (size_t)(s0 + (in ? lane : 0)) * N + n;
+            const float py = pos[row * 2], px = pos[row * 2 + 1];
+            bool first;
+            int rank;
+            const unsigned long long fm = her_first_visits(py, px, lane, L, skip, first, rank);
+            const bool cand = first && lane != skip;
+            const unsigned long long cm = fm & ~(1ull << skip);
+            const int C = __popcll(cm);
+            long long key = 0;
+            uint32_t word = 0;
+            if (cand) {
+                if (rule == PPO_HER_LATE) key = 63 - lane;
+                else if (rule == PPO_HER_KEY16) key = key16[row];
+                else key = table[visit_cell(py, px, width, height)];
+                uint32_t w1 = step0 + (uint32_t)t1, w2 = (uint32_t)rank, w3 = 0x54574F53u;   // 'TWOS'
+                word = env_id0 + (uint32_t)n;
+                philox4x32_10(k0, k1, word, w1, w2, w3);
+            }
+            const unsigned long long tie = ((unsigned long long)word << 32) | (uint32_t)rank;
+            int place = 0;
+            for (unsigned long long m = cm; m; m &= m - 1) {
+                const int j = __builtin_ctzll(m);
+                const long long qk = __shfl(key, j);
+                const unsigned long long qt = __shfl(tie, j);
+                if (qk < key || (qk == key && qt < tie)) ++place;
+            }
+            const int k = max_goals < C ? max_goals : C;
+            int32_t *out = choices + ((size_t)t1 * N + n) * 4;
+            const bool picked = cand && place < k;
+            if (picked) {
+                out[place] = rank;
+                prefix_sum += lane + 1;
+                if (rule == PPO_HER_KEY16 && key == 0xFFFF) ++unreachable;
+                else if (rule != PPO_HER_LATE) key_sum += key;
+            }
+            if (lane < 4 && lane >= k) out[lane] = -1;
+            tally += lane == 0 ? 1 : lane == 1 ? C : lane == 2 ? k : 0;
+        }
+    }
+    if (!stats) return;
+    long long unreachable_sum = unreachable;
+    for (int off = 32; off > 0; off >>= 1) {
+        prefix_sum += __shfl_xor(prefix_sum, off);
+        key_sum += __shfl_xor(key_sum, off);
+        unreachable_sum += __shfl_xor(unreachable_sum, off);
+    }
+    if (lane == 3) tally = prefix_sum;
+    if (lane == 4) tally = key_sum;
+    if (lane == 5) tally = unreachable_sum;
+    if (lane < 6 && tally != 0) atomicAdd(&stats[lane], (unsigned long long)tally);
 }
 
 __global__ void ppo_age_scan_kernel(const uint8_t *__restrict__ terminated, const uint8_t *__restrict__ truncated,
@@ -1509,6 +1604,23 @@ int ppo_her_relabel(const float *pos, const uint8_t *terminated, const uint8_t *
                     float *out_goal, float *out_reward, uint8_t *out_done, void *stream) {
     return ppo_her_relabel_window(pos, terminated, truncated, age0, reward, choices, seed, env_id0, step0, T, N, max_goals,
                                   0, offsets, counts, out_t, out_n, out_goal, out_reward, out_done, stream);
+}
+
+int ppo_her_select(const float *pos, const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0, int T, int N,
+                   int max_goals, int skip, int rule, const uint16_t *key16, const int64_t *table, int width, int height,
+                   uint64_t seed, uint32_t env_id0, uint32_t step0, int32_t *choices, int64_t *stats, void *stream) {
+    if (!all_set(pos, terminated, truncated, age0, choices) || T < 0 || N <= 0 || !ep_count_ok((int64_t)T * N))
+        return TW_E_ARG;
+    if (max_goals < 1 || max_goals > 4 || skip < 0 || skip >= HER_MAX_LEN) return TW_E_ARG;
+    if (rule != PPO_HER_LATE && rule != PPO_HER_KEY16 && rule != PPO_HER_TABLE) return TW_E_ARG;
+    if (rule == PPO_HER_KEY16 && !key16) return TW_E_ARG;
+    if (rule == PPO_HER_TABLE && (!table || !visit_grid_ok(width, height))) return TW_E_ARG;
+    if ((uintptr_t)pos % 8 || !aligned_natural(choices, key16, table, stats)) return TW_E_ARG;
+    if (T == 0) return TW_OK;
+    hipLaunchKernelGGL(ppo_her_select_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, pos, terminated, truncated, age0, T,
+                       N, max_goals, skip, rule, key16, table, width, height, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       env_id0, step0, choices, reinterpret_cast<unsigned long long *>(stats));
+    return tw_launched(__func__);
 }
 
 int ppo_age_scan(const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0, int T, int N, int32_t *age,

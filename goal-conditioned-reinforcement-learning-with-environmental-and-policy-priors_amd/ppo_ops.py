@@ -404,6 +404,39 @@ def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, 
     return out
 
 
+HER_RULES = {"late": 0, "key16": 1, "table": 2}          # PPO_HER_LATE / _KEY16 / _TABLE of include/twoarmy_ppo.h
+
+
+def her_select(pos, terminated, truncated, age0, rule, key16=None, table=None, width=17, height=17, seed=0, env_id0=0,
+               step0=0, max_goals=4, skip=0, choices=None, stats=None):
+    """Which first visits of every episode become hindsight goals, by rule (ppo_her_select, include/twoarmy_ppo.h): the
+    `choices` i32[T,N,4] that her_relabel takes.  rule "late" (or 0): the latest first visits; "key16" (1): the smallest
+    key16 u16[T,N] (minigrid_nav.lookup's distances: nearest the goal); "table" (2): the smallest
+    table i64[width*height + 1] entry of the candidate's cell (the lifetime visit counts: the rarest cells).  Ties fall by a
+    Philox word of (seed, env_id0 + n, step0 + t1, rank).  Only the rows of handled episodes are written; a `choices` made
+    here starts as -1 everywhere.  stats i64[6] is ADDED {episodes, candidates, picks, records the picks will emit, sum
+    of the picked keys, picks with an unreachable key}; made (zero) here if None.  Returns (choices, stats); no host
+    synchronisation.  An empty rollout (T == 0) returns at once: its tensors have no address to pass, so the entry is
+    not called and none of its argument rules is applied to the other arguments."""
+    T, N = terminated.shape
+    dev = pos.device
+    rule = HER_RULES.get(rule, rule)
+    assert pos.shape == (T, N, 2) and truncated.shape == (T, N) and age0.shape == (N,)
+    assert key16 is None or (key16.shape == (T, N) and key16.element_size() == 2)
+    assert table is None or table.numel() == int(width) * int(height) + 1
+    if choices is None:
+        choices = torch.full((T, N, 4), -1, dtype=torch.int32, device=dev)
+    if stats is None:
+        stats = torch.zeros(6, dtype=torch.int64, device=dev)
+    assert choices.shape == (T, N, 4) and stats.shape == (6,)
+    if T == 0:
+        return choices, stats
+    _call("ppo_her_select", pos, _p(pos, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
+          _p(age0, torch.int32), T, N, int(max_goals), int(skip), int(rule), _p(key16), _p(table, torch.int64), int(width),
+          int(height), int(seed), int(env_id0), int(step0), _p(choices, torch.int32), _p(stats, torch.int64))
+    return choices, stats
+
+
 class _ConvBiasReLU(torch.autograd.Function):
     """relu(conv2d(x, w) + b) on channels-last fp32 tensors: the conv (and its two backward GEMMs) in MIOpen, bias +
     ReLU and ReLU-backward + bias-gradient as ONE pass each (ppo_bias_relu_nhwc / ppo_relu_bwd_bias_grad_nhwc) instead

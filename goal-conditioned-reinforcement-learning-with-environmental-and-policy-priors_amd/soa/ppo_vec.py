@@ -104,6 +104,8 @@ class VecPPOTrainer:
         self.max_steps = int(getattr(engine, "max_steps", 50))
         self._hist = collections.deque(maxlen=max(1, -(-(self.max_steps - 1) // self.T)))
         self.her_seed = int(getattr(engine, "seed", 9981))
+        self.her_select_rule = None           # "late" | "near" | "rare": enable_her_select(); None: the reference's draw
+        self._her_select_stats = None         # int64[6] of the last relabel() that selected (ppo_her_select's stats)
         self.episodes = None                  # EpisodeTracker, made by the first account_episodes()
         self.visits = None                    # VisitTracker, made by the first account_visits()
         self.nav_field = self.goal_dist = None  # made by the first account_distance()
@@ -251,17 +253,23 @@ class VecPPOTrainer:
             raise ValueError("hindsight relabelling handles episodes of up to %d steps (max_steps = %d)"
                              % (HER_MAX_LEN, self.max_steps))
         start = self.env_steps // N - T                       # global step index of this rollout's first step
+        select = self.her_select_rule if choices is None else None
         if not self._hist or choices is not None:
-            self.her = ppo_ops.her_relabel(self.pos[4:4 + T], self.term, self.trunc, self.age[0].contiguous(),
+            pos, age0 = self.pos[4:4 + T], self.age[0].contiguous()
+            if select is not None:
+                choices = self._select_goals(pos, self.term, self.trunc, age0, start, max_goals, skip)
+            self.her = ppo_ops.her_relabel(pos, self.term, self.trunc, age0,
                                            self.reward_train, choices, seed=self.her_seed, env_id0=self.engine.env_id0,
                                            step0=start, max_goals=max_goals, skip=skip)
             return self.her
         hist = list(self._hist)
         back = T * len(hist)
-        h = ppo_ops.her_relabel(torch.cat([x[0] for x in hist] + [self.pos[4:4 + T]]),
-                                torch.cat([x[1] for x in hist] + [self.term]),
-                                torch.cat([x[2] for x in hist] + [self.trunc]), hist[0][4],
-                                torch.cat([x[3] for x in hist] + [self.reward_train]), None,
+        pos = torch.cat([x[0] for x in hist] + [self.pos[4:4 + T]])
+        term, trunc = torch.cat([x[1] for x in hist] + [self.term]), torch.cat([x[2] for x in hist] + [self.trunc])
+        if select is not None:                                # over the same window, so the picks see whole episodes
+            choices = self._select_goals(pos, term, trunc, hist[0][4], start - back, max_goals, skip)
+        h = ppo_ops.her_relabel(pos, term, trunc, hist[0][4],
+                                torch.cat([x[3] for x in hist] + [self.reward_train]), choices,
                                 seed=self.her_seed, env_id0=self.engine.env_id0, step0=start - back, max_goals=max_goals,
                                 skip=skip)
         keep = h["t"] >= back
@@ -269,6 +277,57 @@ class VecPPOTrainer:
                         reward=h["reward"][keep].contiguous(), done=h["done"][keep].contiguous())
         self.her["counts"] = torch.bincount(self.her["n"].long(), minlength=N).int()
         return self.her
+
+    def enable_her_select(self, rule):
+        """Pick the hindsight goals of relabel() by rule instead of the reference's uniform draw (ppo_ops.her_select):
+        "late": the latest first visits of an episode, i.e. the longest prefixes; "near": the first visits nearest the
+        real goal by the shortest-path field of the static map (TwoarmyEngine.distance_field as account_distance() takes
+        it, one lookup over the achieved positions; unreachable cells last); "rare": the first visits in the cells the
+        VisitTracker has counted least over its lifetime (`cumulative`; the tracker is made here if there is none, and
+        something has to feed it: account_visits() once per rollout).  relabel() comes before account_visits(), so "rare"
+        reads the counts as they stand BEFORE the rollout being relabelled is accounted.  Ties fall by a Philox word of
+        her_seed.  None: the reference's draw again.  relabel(choices=...) is never overridden.  "near" takes ONE field,
+        the map as it stands when relabel() runs (the wall drops at this rollout's end, like account_distance()), for
+        every episode of the window: an episode that ended in an earlier rollout, or before a wall dropped, is ranked
+        against the present map, not the one it was played on."""
+        if rule not in (None, "late", "near", "rare"):
+            raise ValueError("enable_her_select(): rule is one of 'late', 'near', 'rare' or None, got %r" % (rule,))
+        self.her_select_rule = rule
+        self._her_select_stats = None
+        if rule == "rare" and self.visits is None:
+            from ..visitation import VisitTracker
+            self.visits = VisitTracker(self.N, self.device, 17, 17)
+
+    def _select_goals(self, pos, term, trunc, age0, step0, max_goals, skip):
+        """`choices` of her_relabel for the arrays relabel() is about to pass it, by the enabled rule; the stats of this
+        selection replace the last ones.  Two launches more at most (field and lookup of "near"), no host
+        synchronisation."""
+        rule, key16, table = self.her_select_rule, None, None
+        if rule == "near":
+            from .. import minigrid_nav as nav
+            key16 = nav.lookup(self._static_field(reuse=True), pos, 17, 17)
+        elif rule == "rare":
+            table = self.visits.cumulative
+        choices, self._her_select_stats = ppo_ops.her_select(
+            pos, term, trunc, age0, {"late": "late", "near": "key16", "rare": "table"}[rule], key16=key16, table=table,
+            seed=self.her_seed, env_id0=self.engine.env_id0, step0=step0, max_goals=max_goals, skip=skip)
+        return choices
+
+    def her_select_stats(self):
+        """What the last relabel() selected under the enabled rule: {"episodes", "candidates", "picks", "mean_prefix":
+        records per pick, "mean_key": the mean key of the picks that have one ("near": the distance, unreachable picks
+        left out; "rare": the visit count; "late": None), "unreachable": picks whose cell the field does not reach};
+        None where nothing was selected.  Counted over the arrays relabel() ran on: with earlier rollouts in the window,
+        their episodes are in it again.  One device-to-host copy."""
+        if self.her_select_rule is None or self._her_select_stats is None:
+            return None
+        episodes, cand, picks, records, keys, unreachable = self._her_select_stats.cpu().tolist()
+        if picks == 0:
+            return None
+        keyed = picks - unreachable
+        mean_key = None if self.her_select_rule == "late" or keyed == 0 else keys / keyed
+        return {"episodes": episodes, "candidates": cand, "picks": picks, "mean_prefix": records / picks,
+                "mean_key": mean_key, "unreachable": unreachable}
 
     def sample_goal(self, t_idx, n_idx, goal2, done):
         """Hook: per-sample goal record carried through targets / update (default: the 2-d goal itself)."""

@@ -46,6 +46,10 @@ per minibatch, one host read per update) and appends `ent`, `kl`, `clipfrac`, `e
 --her_gae (plain PPO agent) keeps the hindsight records when --gae_lambda > 0: their advantages are GAE(lambda) scanned
 along each relabelled run on the device (ppo_ops.run_ends + gae_runs, two calls per update) instead of the one-step
 targets that --gae_lambda 0 uses; without it --gae_lambda > 0 trains on the rollout alone; off by default.
+--her_select {late,near,rare} picks the hindsight goals of every episode by rule on the device (ppo_ops.her_select, one
+launch per rollout, two more for near's field and lookup) instead of the reference's uniform draw: the latest first
+visits, those nearest the real goal on the static map, or those in the cells visited least so far (rare counts the
+visited cells of every rollout, after relabelling); appends `her_sel` to the log line; random, the default, is the draw.
 """
 import argparse
 import math
@@ -111,6 +115,11 @@ def build_parser():
                    help="with --gae_lambda > 0: relabel as with --gae_lambda 0 and give the hindsight records GAE(lambda) "
                         "advantages, scanned along each relabelled run and cut at its end on the device; plain PPO agent "
                         "only; off by default (then --gae_lambda > 0 switches relabelling off)")
+    p.add_argument("--her_select", default="random", choices=["random", "late", "near", "rare"],
+                   help="which first-visited cells of an episode become hindsight goals: random = the reference's uniform "
+                        "draw; late = the latest first visits (the longest prefixes); near = the smallest shortest-path "
+                        "distance to the real goal on the static map; rare = the smallest lifetime visit count, as counted "
+                        "before the rollout being relabelled; ties fall by a Philox word; appends `her_sel` to the log line")
     p.add_argument("--score", default="rollout", choices=["rollout", "episode"],
                    help="what drives the HER switch and the logged score: rollout = one EMA step per rollout with the "
                         "rollout's reward sum over its finished episodes; episode = the reference's fold, one step per "
@@ -238,6 +247,15 @@ def update_fields(us):
     """Tail of the log line with --update_stats (VecPPOTrainer.update_stats())."""
     return " ent %.4f kl %.6f clipfrac %.4f ev %.4f epochs %d" % (us["entropy"], us["approx_kl"], us["clip_frac"],
                                                                  us["explained_variance"], us["epochs_run"])
+
+
+def select_fields(rule, hs):
+    """Tail of the log line with --her_select (VecPPOTrainer.her_select_stats())."""
+    if hs is None:
+        return " her_sel %s -" % rule
+    key = "-" if hs["mean_key"] is None else "%.2f" % hs["mean_key"]
+    return " her_sel %s picks %d prefix %.2f key %s unreachable %d" % (rule, hs["picks"], hs["mean_prefix"], key,
+                                                                      hs["unreachable"])
 
 
 def orient_fields(os_, hindsight=False):
@@ -446,6 +464,9 @@ def main(argv=None, predictor=False, soa=False):
     if args.update_stats:
         trainer.enable_update_stats(args.target_kl)
     trainer.her_gae = args.her_gae
+    use_select = args.her_select != "random"
+    if use_select:
+        trainer.enable_her_select(args.her_select)
     her = str(args.her).lower() not in ("false", "0", "no")
     score = 0.0
     for u in range(args.updates):
@@ -460,7 +481,7 @@ def main(argv=None, predictor=False, soa=False):
         if use_shaping:                                       # behind relabel(): the records copy the unshaped reward_train
             trainer.shape_potential(expect_her=relabel)
         trainer.account_episodes()
-        if args.visit_dir:
+        if args.visit_dir or args.her_select == "rare":       # behind relabel(): rare reads the counts before this rollout
             trainer.account_visits(trainer.her)
         if args.goal_distance:
             trainer.account_distance()
@@ -512,6 +533,8 @@ def main(argv=None, predictor=False, soa=False):
             tail += orient_fields(ots, args.orient_prior_hindsight)
         if args.path_stats:                                     # behind every other field
             tail += path_fields(trainer.path_stats())
+        if use_select:                                          # in front of the update's diagnostics only
+            tail += select_fields(args.her_select, trainer.her_select_stats() if relabel else None)
         if args.update_stats:                                   # behind every other field
             us = trainer.update_stats()
             tail += update_fields(us)

@@ -408,6 +408,46 @@ int ppo_her_relabel_window(const float *pos, const uint8_t *terminated, const ui
                            int T, int N, int max_goals, int skip, const int64_t *offsets, int32_t *counts, int32_t *out_t,
                            int32_t *out_n, float *out_goal, float *out_reward, uint8_t *out_done, void *stream);
 
+/* Which first visits become hindsight goals, by rule instead of the uniform draw: fills the `choices` that
+ * ppo_her_relabel[_window] reads.  Same walk as there: one wavefront per env, one record per lane, and an episode is
+ * handled iff it starts inside the arrays (age0[n] == 0 or the step after a done), ends inside them and has L <= 64
+ * records.
+ *
+ * Candidates: the first visits among the records skip, skip + 1, ... (np.unique(axis=0) over (y, x), +0.0 and -0.0 one
+ * position) EXCEPT the one at record `skip` itself, which the relabelling never uses (`0 < index`); C of them (C = 0 for
+ * L <= skip + 1).  rank = a first visit's place in the lexicographically sorted unique array, the unit of `choices`; idx
+ * = its record index inside the episode; s0, t1 = the episode's first and last row.
+ *
+ * Rules, the smallest key first:
+ *   PPO_HER_LATE   key = 63 - idx                            the latest first visits, the longest prefixes
+ *   PPO_HER_KEY16  key = key16[(s0 + idx) * N + n]           uint16[T][N], e.g. mg_nav_lookup's distances: the goals
+ *                                                            nearest the real goal; 0xFFFF (unreachable) last by value
+ *   PPO_HER_TABLE  key = table[cell(y, x)], signed int64     int64[width * height + 1], e.g. ppo_visit_hist's counts:
+ *                                                            the rarest cells; cell by ppo_visit_scan's rule, a position
+ *                                                            outside the world reads the extra bin width * height
+ * Order: (key, word, rank) ascending, word = Philox4x32-10(key = seed, counter = (env_id0 + n, step0 + t1, rank,
+ * 'TWOS' = 0x54574F53))[0].  Each lane counts the candidates before it; no atomics, no LDS.
+ *
+ * Written: with k' = min(max_goals, C), choices[t1][n][j] = rank of the candidate in place j for j < k', -1 for
+ * k' <= j < 4, for the rows (t1, n) of handled episodes only; every other row of choices int32[T][N][4] is left as it
+ * is, and ppo_her_relabel reads none of them.  The picks of a row are distinct.
+ * stats int64[6] | NULL, each += (64-bit integer atomics: exact, whatever the scheduling): 0 handled episodes,
+ * 1 candidates, 2 picks, 3 sum over the picks of idx + 1 = the records ppo_her_relabel emits from these choices,
+ * 4 sum of the picked keys (LATE: 0; KEY16: the 0xFFFF keys left out), 5 picks with a 0xFFFF key (KEY16 only).
+ *
+ *   pos float[T][N][2] (8-byte aligned), terminated, truncated uint8[T][N], age0 int32[N]; key16, table, width and height
+ *   are read by their rule only.  Positions must be finite, as for ppo_her_relabel.
+ * TW_E_ARG, and nothing is launched or written: NULL pos, terminated, truncated, age0 or choices; T < 0 or N <= 0;
+ * max_goals outside 1..4; skip outside 0..63; a rule other than the three; PPO_HER_KEY16 with a NULL key16; PPO_HER_TABLE
+ * with a NULL table or width or height outside 1..32; T * N >= 2^40; pos off 8-byte alignment, choices off 4, key16 off
+ * 2, table or stats off 8.  T == 0 returns 0 and launches nothing. */
+#define PPO_HER_LATE 0
+#define PPO_HER_KEY16 1
+#define PPO_HER_TABLE 2
+int ppo_her_select(const float *pos, const uint8_t *terminated, const uint8_t *truncated, const int32_t *age0, int T, int N,
+                   int max_goals, int skip, int rule, const uint16_t *key16, const int64_t *table, int width, int height,
+                   uint64_t seed, uint32_t env_id0, uint32_t step0, int32_t *choices, int64_t *stats, void *stream);
+
 /* Epilogues of the conv layers of TINet (all_net.py:141-150: Conv2d + ReLU x 4) on channels-last activations
  * float[n_pixels][C] (n_pixels = B * H * W, C % 4 == 0, C <= 256); the conv GEMMs themselves run in MIOpen.
  *   ppo_bias_relu_nhwc               y <- relu(y + bias[c])  in place: what Conv2d's bias add + nn.ReLU compute, one pass.
