@@ -110,6 +110,94 @@ def test_patterns_are_what_they_say():
     assert np.nonzero(gr.pattern("whole", 1000))[0].tolist() == [999]
 
 
+def test_edge_table_and_boundary_runs_are_what_they_say():
+    assert gr.EDGES == (64, 512, 2048, 131072, 1048576, 4194304) and gr.EDGE_NAMES[131072] == "chunk1"
+    assert gr.boundaries(64) == [] and gr.boundaries(65) == [64] and gr.boundaries(2048 * 2048) == list(gr.EDGES[:5])
+    assert gr.boundaries(2048 * 2048 + 1) == list(gr.EDGES)
+    lengths = np.diff(np.concatenate([[-1], np.nonzero(gr.pattern("her16", 70001))[0]]))
+    assert lengths.min() >= 1 and lengths.max() == 16 and lengths.sum() == 70001
+    H = 64 * 2048 + 1
+    B = gr.boundaries(H)
+    e, placed = gr.boundary_runs(H, B, "ends", True)
+    assert placed == [(b - 4 + 4 * k, min(b - 1 + 4 * k, H - 1)) for b in B for k in (0, 1)]
+    assert all(e[a - 1] and e[b] and not e[a:b].any() for a, b in placed)
+    e, placed = gr.boundary_runs(H, B, "straddle", True)
+    assert placed == [(b - 3, min(b + 2, H - 1)) for b in B] and all(e[a - 1] and e[b] and not e[a:b].any() for a, b in placed)
+    d = gr.boundary_dones(e, B, "straddle", 0)
+    assert all(d[b - 1] and not e[b - 1] for b in B) and (d[e != 0] == 1).all()
+    e, placed = gr.boundary_runs(H, B, "long", False)
+    assert placed == [(40, 87), (384, 639), (1024, 3071), (H - 1 - 2 * 2048, H - 1)]
+    assert all(e[a - 1] and e[b] and not e[a:b].any() for a, b in placed)
+    d = gr.boundary_dones(e, B, "long", 0)
+    assert all(d[b] for b in B) and not e[[64, 512, 2048]].any()
+
+
+def _exact_cases(H):
+    """(family, run_end, done) over the background patterns and every placement of the boundary sweep that fits H."""
+    for family in gr.FAMILIES:
+        short = family != "c1"
+        for kind in ("singletons", "her16", "whole") if short and H <= 16 else ("singletons", "her16") if short else (
+                "singletons", "runs64", "runs64+1", "her", "whole"):
+            end = gr.pattern(kind, H, H)
+            yield family, kind, end, gr.dones(end, H)
+        for variant in gr.variants(family):
+            end, _ = gr.boundary_runs(H, gr.boundaries(H), variant, short, H)
+            yield family, variant, end, gr.boundary_dones(end, gr.boundaries(H), variant, H)
+
+
+def test_exact_reference_equals_the_float64_loop():
+    for H in (1, 65, 2049, 5000):
+        for family, name, end, done in _exact_cases(H):
+            gamma, lam = gr.FAMILIES[family]
+            r, v, nv = gr.exact_inputs(family, H, H)
+            for mask in (False, True):
+                want = gr.gae_runs64(r, v, nv, done, end, gamma, lam, mask)[:3]
+                got = gr.exact_runs(r, v, nv, done, end, gamma, lam, mask)
+                for g, w in zip(got, want):
+                    assert g.dtype == np.float64 and np.array_equal(g, w), (H, family, name, mask)
+                t32, d32 = gr.one_step32(r, v, nv, done, gamma, mask)      # the one-step formula in float32 is exact too
+                assert np.array_equal(t32.astype(np.float64), want[1])
+                assert np.array_equal((got[0].astype(np.float32) + v).astype(np.float64), want[2])
+
+
+def test_exact_inputs_use_all_three_arrays_and_the_mask_changes_delta():
+    H = 5000
+    for family, (gamma, lam) in gr.FAMILIES.items():
+        r, v, nv = gr.exact_inputs(family, H, 1)
+        assert all(len(np.unique(x)) > 5 for x in (r, v, nv))
+        end, _ = gr.boundary_runs(H, gr.boundaries(H), "straddle", family != "c1", 1)
+        done = gr.boundary_dones(end, gr.boundaries(H), "straddle", 1)
+        off, on = (gr.exact_runs(r, v, nv, done, end, gamma, lam, m) for m in (False, True))
+        assert not np.array_equal(off[0], on[0]) and not np.array_equal(off[1], on[1])
+        lone = gr.exact_runs(r, v, nv, done, np.ones(H, np.uint8), gamma, lam, False)
+        assert not np.array_equal(off[0], lone[0])                     # and the runs enter the advantage
+
+
+def test_exactness_assertion_fires_on_inputs_that_are_too_large():
+    import pytest
+    one = np.zeros(4, np.uint8)
+    z = np.zeros(4, np.float32)
+    big = np.full(4, 2.0 ** 23, np.float32)                            # suffix sums up to 2^25
+    with pytest.raises(AssertionError, match="does not fit float32"):
+        gr.exact_runs(big, z, z, one, one, 1.0, 1.0, False)
+    assert gr.exact_runs(big / 4, z, z, one, one, 1.0, 1.0, False)[0].tolist() == [2.0 ** 23, 3 * 2.0 ** 21, 2.0 ** 22, 2.0 ** 21]
+    gr.exact_runs(big, z, z, one, np.ones(4, np.uint8), 1.0, 1.0, False)       # cut into singletons they fit
+    up_down = np.array([2.0 ** 23, 2.0 ** 23, -2.0 ** 23, -2.0 ** 23], np.float32)
+    with pytest.raises(AssertionError, match="does not fit float32"):    # a piece in mid-run, not only the suffix sums
+        gr.exact_runs(up_down, z, z, one, one, 1.0, 1.0, False)
+    for gamma, lam in ((0.5, 1.0), (1.0, 0.5)):
+        e30 = np.zeros(30, np.uint8)
+        d30 = np.full(30, 15, np.float32)
+        with pytest.raises(AssertionError, match="need 34 bits"):        # a run of 30: 29 + 5 bits
+            gr.exact_runs(d30, 0 * d30, 0 * d30, e30, e30, gamma, lam, False)
+        e30[15::16] = 1
+        gr.exact_runs(d30, 0 * d30, 0 * d30, e30, e30, gamma, lam, False)      # runs of 16: 20 bits
+        with pytest.raises(AssertionError, match="need 28 bits"):        # magnitudes < 2^13 in runs of 16
+            gr.exact_runs(d30 * 256, 0 * d30, 0 * d30, e30, e30, gamma, lam, False)
+        with pytest.raises(AssertionError):                            # a delta that is no integer
+            gr.exact_runs(d30 / 2, 0 * d30, 0 * d30, e30, e30, gamma, lam, False)
+
+
 def test_ctypes_table_and_header_agree_on_the_new_entry_points():
     from twoarmy_amd import _lib
     txt = open(os.path.join(ROOT, "include", "twoarmy_ppo.h")).read()

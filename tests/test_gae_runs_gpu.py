@@ -1,9 +1,15 @@
 """ppo_run_ends and ppo_gae_runs (csrc/ppo_kernels.hip): the run ends bit for bit against the numpy restatement, the scan
 against the float64 statement of gae_runs_ref.py within the rounding bound derived there, its bit-exact special cases
-against ppo_gae, isolation of non-finite values, every argument rule, and the trainer's her_gae path.  The two stream
-checks of both entry points are cases of the table in test_streams_gpu.py.  The sizes are the smallest that reach
-every edge: one record, a chunk of 64 less / exactly / plus one, a workgroup's 4 wavefronts (256, 257), 1 000, and
-70 001 (35 workgroups: three launches)."""
+against ppo_gae, the scan tree bit for bit at every structural edge on inputs whose float32 arithmetic is exact,
+isolation of non-finite values at level 0 and through the upper levels, every argument rule, and the trainer's her_gae
+path.  The two stream checks of both entry points are cases of the table in test_streams_gpu.py.  The sizes are the
+smallest that reach every edge.  With float inputs: one record, a chunk of 64 less / exactly / plus one, 256 and 257, a
+wavefront's 512 and a workgroup's 2048 less / exactly / plus one (2049: three launches), 1 000, 4 097, and 70 001 (35
+workgroups).  With exact inputs (the boundary sweep): the same level-0 edges as array ends, 4096 and 4097, and level 1
+and above: 64 * 2048 and one more (the second chunk of level 1), 512 * 2048 + 1 (its second wavefront), 2048^2 (a full
+top level of two), 2048^2 + 1 and + 2049 (three levels, five launches; level 1 holds 2049 and 2050 maps, level 2
+two) and 2048^2 + 512 * 2048 + 1 (513 maps behind the level-2 edge: the reduce of level 1 folds full chunks and two
+wavefronts).  gae_runs_ref.LEVEL_EDGES is the table."""
 import ctypes as C
 
 import numpy as np
@@ -11,14 +17,15 @@ import pytest
 import torch
 
 import gae_runs_ref as gr
-from gae_runs_ref import BLOCK, _k, _records
+from gae_runs_ref import BLOCK, CHUNK, WAVE, _k, _records
+from nav_util import Boxed
 from ppo_util import DEV, accepted, dev as _dev, lib as _lib, lib_module as _libmod, ops as _ops, ptr as _P
 from stream_util import host, same_bits
 
 pytestmark = pytest.mark.gpu
 EPS32 = gr.EPS32
 PARAMS = [(0.99, 0.0), (0.99, 0.95), (1.0, 1.0)]
-SIZES = [1, 63, 64, 65, 256, 257, 1000, 70001]
+SIZES = [1, 63, 64, 65, 256, 257, 511, 512, 513, 1000, 2047, 2048, 2049, 4097, 70001]
 
 
 # ------------------------------------------------------------------------------------------------ ppo_run_ends
@@ -189,6 +196,98 @@ def test_gae_runs_nonfinite_delta_stays_in_its_run(bad):
             assert same_bits(g[other], c[other])
 
 
+# ------------------------------------------------------------------------------------------------ the boundary sweep
+SWEEP = [511, 512, 513, 2047, 2048, 2049, 4096, 4097, CHUNK * BLOCK, CHUNK * BLOCK + 1, WAVE * BLOCK + 1, BLOCK * BLOCK,
+         BLOCK * BLOCK + 1, BLOCK * BLOCK + 2049,
+         BLOCK * BLOCK + WAVE * BLOCK + 1]        # 513 maps behind the level-2 edge: the reduce of level 1 folds 8 full
+#                                                   chunks and 2 wavefronts under the long run that ends on the last record
+
+
+def _boxed_call(dev_in, done, end, gamma, lam, mask, H):
+    """ppo_gae_runs through the C entry: every output and a NaN-filled workspace of exactly the queried size inside
+    0xA5-filled buffers -> (adv, target, ret) on the host; the borders of all four buffers are intact."""
+    outs = [Boxed(H, torch.float32) for _ in range(3)]
+    ws = Boxed(_lib().ppo_gae_runs_workspace(H), torch.float32)
+    ws.view.fill_(np.nan)                                          # written before it is read
+    td, te = _dev(done), _dev(end)
+    args = [_P(x) for x in dev_in] + [_P(td) if mask else None, _P(te), gamma, lam, int(mask), C.c_int64(H)]
+    assert accepted("ppo_gae_runs", args + [_P(o.view) for o in outs] + [_P(ws.view)])
+    got = []
+    for name, box in zip(("adv", "target", "ret", "workspace"), outs + [ws]):
+        b = host(box.buf)
+        assert (b[:box.lo] == 0xA5).all() and (b[box.hi:] == 0xA5).all(), "%s: a border was written" % name
+        got.append(b[box.lo:box.hi].view(np.float32))
+    return got[:3]
+
+
+def _first_difference(got, want, placed):
+    i = int(np.argmax(got.view(np.uint32) != want.view(np.uint32)))
+    run = [p for p in placed if p[0] <= i <= p[1]]
+    return "first at record %d (block %d, wavefront %d, chunk %d, lane %d)%s: got %r, want %r" % (
+        i, i // BLOCK, i % BLOCK // WAVE, i % WAVE // CHUNK, i % CHUNK, " in the placed run %s" % (run[0],) if run else "",
+        got[i], want[i])
+
+
+@pytest.mark.parametrize("H", SWEEP)
+@pytest.mark.parametrize("family", list(gr.FAMILIES))
+def test_gae_runs_boundary_sweep(family, H):
+    """Bit for bit against the exact reference, with a run ending on, beginning on, straddling and (c = 1) reaching far
+    across EVERY edge of the tree below H (gae_runs_ref.boundary_runs), mask off and on with a done record on either side
+    of each edge.  A difference is a finding about the kernels or the level loop of the host entry: the index of the
+    first one names the edge."""
+    gamma, lam = gr.FAMILIES[family]
+    bounds = gr.boundaries(H)
+    r, v, nv = gr.exact_inputs(family, H, H)
+    dev_in = [_dev(x) for x in (r, v, nv)]
+    for variant in gr.variants(family):
+        end, placed = gr.boundary_runs(H, bounds, variant, family != "c1", H)
+        done = gr.boundary_dones(end, bounds, variant, H)
+        for mask in (False, True):
+            a64, _, _ = gr.exact_runs(r, v, nv, done, end, gamma, lam, mask)       # asserts exactness before the launch
+            want_adv = a64.astype(np.float32)
+            want_tgt, _ = gr.one_step32(r, v, nv, done, gamma, mask)
+            adv, tgt, ret = _boxed_call(dev_in, done, end, gamma, lam, mask, H)
+            where = (family, H, variant, "mask" if mask else "no mask")
+            assert same_bits(tgt, want_tgt), (where, "target", _first_difference(tgt, want_tgt, placed))
+            assert same_bits(adv, want_adv), (where, "adv", _first_difference(adv, want_adv, placed))
+            want_ret = want_adv + v                                    # exact here
+            assert same_bits(ret, want_ret), (where, "ret", _first_difference(ret, want_ret, placed))
+
+
+@pytest.mark.parametrize("bad", [np.inf, np.nan])
+def test_gae_runs_nonfinite_delta_stays_in_its_run_through_the_upper_levels(bad):
+    """test_gae_runs_nonfinite_delta_stays_in_its_run one and two levels higher, device against device.  A non-finite
+    delta reaches a map of level >= 1 only through the run that covers a workgroup's first record (that workgroup's
+    composite d is the advantage of its first record).  So the run "just before" an edge B of level 1 / 2 is the one over
+    the first record of the last workgroup before B (map B / 2048 - 1, the last of its chunk / wavefront / workgroup of
+    level 1), the straddling run lies over B itself (map B / 2048, the first behind the edge), and the bad record sits
+    behind the workgroup's first record in both."""
+    H = BLOCK * BLOCK + 2049
+    r, v, nv = gr.inputs(H, 13)
+    end = gr.pattern("her", H, 13)
+    spots = []
+    for B in gr.LEVEL_EDGES[1]:
+        for first in (B - BLOCK - 10, B - 10):                         # 20 records over a workgroup's first record
+            end[first - 1] = end[first + 19] = 1
+            end[first:first + 19] = 0
+            spots.append(first + 13)
+    run = np.concatenate([[0], np.cumsum(end)[:-1]]).astype(np.int64)
+    dirty = r.copy()
+    dirty[spots] = bad
+    hit = np.isin(run, run[spots])
+    assert hit.sum() == 20 * len(spots) == 120
+    first = np.array(spots) - 13
+    done = gr.dones(end, 13, mid_run=0.0)
+    dev_clean, dev_dirty = [_dev(x) for x in (r, v, nv)], [_dev(x) for x in (dirty, v, nv)]
+    for mask in (False, True):
+        clean = _boxed_call(dev_clean, done, end, 0.99, 0.95, mask, H)
+        got = _boxed_call(dev_dirty, done, end, 0.99, 0.95, mask, H)
+        for name, g, c in zip(("adv", "target", "ret"), got, clean):
+            assert np.isfinite(c).all()
+            assert same_bits(g[~hit], c[~hit]), (name, mask, int(np.argmax((g != c) & ~hit)))
+        assert not np.isfinite(got[0][first]).any() and not np.isfinite(got[2][first]).any()
+
+
 def test_gae_runs_rejections_launch_nothing():
     from test_ppo_kernels_edges_gpu import _each_rejected, _fill
     H = 9
@@ -204,6 +303,8 @@ def test_gae_runs_rejections_launch_nothing():
     assert [ws_of(h) for h in (0, -1, 1 << 40)] == [-1, -1, -1]
     assert [ws_of(h) for h in (1, 2048, 2049, 70001, 2048 * 2048, 2048 * 2048 + 1)] == [
         2, 2, 4, 70, 4096, 2 * 2049 + 2 * 2]
+    assert [ws_of(h) for h in (CHUNK * BLOCK + 1, WAVE * BLOCK + 1, BLOCK * BLOCK + 2049)] == [
+        2 * 65, 2 * 513, 2 * 2050 + 2 * 2]
     with pytest.raises(_libmod().TwoarmyLibraryError):             # the front end raises what the C call returns
         _ops().gae_runs(r, v, nv, None, end, 0.99, 0.95, True)
 
