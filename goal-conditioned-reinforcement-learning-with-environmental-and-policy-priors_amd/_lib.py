@@ -170,6 +170,9 @@ _SIGS.update({
     "ppo_bonus_episode_words": (C.c_int, [_i, _i, _i, _i, _i]),
     "ppo_bonus_scan_episode": (C.c_int, [_vp, _vp, _vp, C.c_long, C.c_long, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
                                          C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ppo_reward_norm_workspace": (C.c_int, [_i]),
+    "ppo_reward_norm_update": (C.c_int, [_vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "ppo_reward_norm_apply": (C.c_int, [_vp, _i64, _vp, _f, _vp, _vp]),
     "ppo_bias_relu_nhwc": (C.c_int, [_vp, _vp, _i64, _i, _vp]),
     "ppo_conv1_up4_bias_relu": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ppo_conv1_up4_bias_relu_c": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

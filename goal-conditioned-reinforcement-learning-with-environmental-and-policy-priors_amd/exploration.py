@@ -8,7 +8,10 @@ the count that includes the whole row).  With several ranks every rank keeps its
 
 scope "episode": the env scope with counts that clear at each episode end (ppo_bonus_scan_episode), the per-episode
 counts of RIDE / NovelD / AGAC; form "sqrt" pays scale / sqrt(count), form "first" pays scale at the first visit of a key
-within the episode and nothing after it."""
+within the episode and nothing after it.
+
+RewardNormalizer, below BonusTracker: the answer to what scale such a bonus should have -- the training reward divided by
+the running standard deviation of its discounted return."""
 import numpy as np
 import torch
 
@@ -118,3 +121,51 @@ class BonusTracker:
             other[k] = tab[:, -1].copy() if per_env else int(tab[0, -1])
         out["other"] = other
         return out
+
+
+class RewardNormalizer:
+    """Rewards divided by the running standard deviation of the discounted return (gym's NormalizeReward, the baselines'
+    VecNormalize) for N envs on the device: update() advances the moments by one rollout (ppo_ops.reward_norm_update),
+    apply() scales any reward array by the scale that stands when the launch runs and clamps it to [-clip, clip]
+    (ppo_ops.reward_norm_apply; clip <= 0 or inf: no clamp).  It owns the envs' running returns `ret_carry` f64[N], `stats`
+    f64[4] = (count, mean, M2, scale) and the workspace; no host synchronisation until read().  With several ranks every
+    rank keeps its own statistics."""
+
+    def __init__(self, num_envs, gamma, clip=10.0, device="cuda"):
+        gamma, clip = float(gamma), float(clip)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("gamma must lie in [0, 1], got %r" % (gamma,))
+        if clip != clip:
+            raise ValueError("clip must be a number (<= 0 or inf: no clamp), got %r" % (clip,))
+        self.N, self.gamma, self.clip, self.device = int(num_envs), gamma, clip, torch.device(device)
+        self.ret_carry = torch.zeros(self.N, dtype=torch.float64, device=self.device)
+        self.stats = torch.zeros(4, dtype=torch.float64, device=self.device)
+        self.workspace = torch.empty(ppo_ops.reward_norm_workspace(self.N), dtype=torch.float64, device=self.device)
+
+    def update(self, reward, terminated, truncated):
+        """Count the returns of one rollout: reward f32[T,N], terminated / truncated u8[T,N].  Returns stats."""
+        assert reward.shape[1:] == (self.N,), "normalizer made for %d envs, got %s" % (self.N, tuple(reward.shape))
+        return ppo_ops.reward_norm_update(reward, terminated, truncated, self.gamma, self.ret_carry, self.stats, self.workspace)
+
+    def apply(self, reward, out=None):
+        """reward (f32, any shape) scaled and clamped -> out (reward itself: in place; None: a new tensor)."""
+        return ppo_ops.reward_norm_apply(reward, self.stats, self.clip, out)
+
+    def read(self):
+        return ppo_ops.reward_norm_read(self.stats)
+
+    def reset(self):
+        """Forget everything: nothing seen, every env at an episode's start."""
+        self.stats.zero_()
+        self.ret_carry.zero_()
+
+    def state_dict(self):
+        return {"ret_carry": self.ret_carry.clone(), "stats": self.stats.clone(), "gamma": self.gamma, "clip": self.clip}
+
+    def load_state_dict(self, state):
+        """Continue from a state_dict(): the tensors are copied into this normalizer's own, in place (a captured launch
+        keeps reading them); gamma and clip are taken over."""
+        assert tuple(state["ret_carry"].shape) == (self.N,) and tuple(state["stats"].shape) == (4,)
+        self.ret_carry.copy_(state["ret_carry"])
+        self.stats.copy_(state["stats"])
+        self.gamma, self.clip = float(state["gamma"]), float(state["clip"])

@@ -376,6 +376,54 @@ def bonus_scan_episode(pos, action, reward, terminated, truncated, state_table=N
     return reward_out
 
 
+REWARD_NORM_STATS = dict(count=0, mean=1, m2=2, scale=3)     # stats[i] of ppo_reward_norm_update (include/twoarmy_ppo.h)
+
+
+def reward_norm_workspace(N):
+    return _query("ppo_reward_norm_workspace", int(N))
+
+
+def reward_norm_update(reward, terminated, truncated, gamma, ret_carry, stats, workspace=None):
+    """Advance the running moments of the discounted return by one rollout (ppo_reward_norm_update,
+    include/twoarmy_ppo.h): reward f32[T,N], terminated / truncated u8[T,N]; ret_carry f64[N] (the envs' running returns)
+    and stats f64[4] = (count, mean, M2, scale) are updated IN PLACE, all-zero = nothing seen.  workspace: f64 of
+    reward_norm_workspace(N) elements, made here if None.  Returns stats; two launches, no host synchronisation.  An empty
+    rollout (T == 0) returns at once and changes nothing."""
+    T, N = reward.shape
+    assert terminated.shape == (T, N) and truncated.shape == (T, N) and ret_carry.shape == (N,) and stats.shape == (4,)
+    need = reward_norm_workspace(N)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=reward.device)
+    assert workspace.numel() >= need
+    if T == 0:
+        return stats
+    _call("ppo_reward_norm_update", reward, _p(reward, torch.float32), _p(terminated, torch.uint8), _p(truncated, torch.uint8),
+          T, N, float(gamma), _p(ret_carry, torch.float64), _p(stats, torch.float64), _p(workspace, torch.float64))
+    return stats
+
+
+def reward_norm_apply(reward, stats, clip=0.0, out=None):
+    """reward * (float)stats[3], clamped to [-clip, clip] where clip is positive and finite (ppo_reward_norm_apply):
+    reward f32 of any shape, contiguous; the scale is read from stats f64[4] on the device when the launch runs.  out: a
+    tensor of reward's shape, reward itself for in place, or None for a new one.  Returns out; one launch, no host
+    synchronisation."""
+    assert stats.shape == (4,)
+    out = torch.empty_like(reward) if out is None else out
+    assert out.shape == reward.shape
+    if reward.numel():
+        _call("ppo_reward_norm_apply", reward, _p(reward, torch.float32), reward.numel(), _p(stats, torch.float64),
+              float(clip), _p(out, torch.float32))
+    return out
+
+
+def reward_norm_read(stats):
+    """stats f64[4] as numbers: {"count", "mean", "var" = M2 / count, "std", "scale" = what reward_norm_apply multiplies
+    by}; with nothing seen var and std are 0.0 and scale is 1.0.  One device-to-host copy."""
+    count, mean, m2, scale = stats.detach().cpu().tolist()
+    var = m2 / count if count else 0.0
+    return dict(count=count, mean=mean, var=var, std=var ** 0.5, scale=scale if count else 1.0)
+
+
 def her_relabel(pos, terminated, truncated, age0, reward, choices=None, seed=0, env_id0=0, step0=0, max_goals=4, skip=0):
     """Hindsight relabelling of a time-major rollout (ppo_her_relabel_window, include/twoarmy_ppo.h; reference
     Buffer_gridworld.her_func, soa/env_buffer.py:101-143; skip = 4: pre_her_func / pre_f_her_func on the 9-frame window

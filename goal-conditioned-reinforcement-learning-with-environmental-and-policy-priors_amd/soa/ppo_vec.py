@@ -123,6 +123,7 @@ class VecPPOTrainer:
         self._relabel_at = -1                 # env_steps when relabel() last ran: shape_potential() comes after it
         self.dir = None                       # agent direction after each step [T, N], kept only for the action bonus
         self.update_diag = None               # update diagnostics: {"stats", "target_kl", "epochs_run"}, made by enable_update_stats()
+        self.reward_norm = None               # RewardNormalizer, made by enable_reward_norm()
         self.env_steps = 0
         self.episodes_done = 0
         self.return_sum = 0.0
@@ -439,12 +440,15 @@ class VecPPOTrainer:
         done = (self.term | self.trunc).contiguous()
         goal = self.sample_goal(idx // N, idx % N, self.goal1.expand(total, 2), done.view(-1))
         v, nv = self._values_rollout(goal, done) if self.reuse_next_values else self._values(idx // N, idx % N, goal)
-        adv, target, ret = ppo_ops.gae(self.reward_train, v.view(T, N), nv.view(T, N), done, gamma=self.agent.gamma,
+        reward = self.reward_train if self.reward_norm is None else self.normalize_rewards()
+        adv, target, ret = ppo_ops.gae(reward, v.view(T, N), nv.view(T, N), done, gamma=self.agent.gamma,
                                        lam=self.agent.gae_lambda, use_done_mask=self.agent.use_done_mask)
         critic_target = target if self.agent.gae_lambda == 0.0 else ret
         adv, critic_target = adv.view(-1), critic_target.view(-1)
         if self.her is not None and self.her["t"].numel():
             h = self.her                                          # relabelled records, with their own goals and rewards
+            if self.reward_norm is not None and self._reward_norm_hindsight:
+                h = dict(h, reward=self.reward_norm.apply(h["reward"]))      # a scaled copy: self.her stays raw
             hgoal = self.sample_goal(h["t"], h["n"], h["goal"], h["done"])
             if self.her_gae:
                 hadv, htarget = self._her_targets_gae(h, hgoal)
@@ -918,6 +922,47 @@ class VecPPOTrainer:
         hn, htotal = (int(v[2]), int(self.her_shape_f.numel())) if her else (0, 0)
         return {"mean": v[1] / n if n else None, "unshaped": 1.0 - n / total,
                 "her_mean": v[3] / hn if hn else None, "her_unshaped": 1.0 - hn / htotal if htotal else None}
+
+    # ------------------------------------------------------------------ reward normalisation
+    def enable_reward_norm(self, clip=10.0, hindsight=True):
+        """Divide the training reward by the running standard deviation of its discounted return (RewardNormalizer;
+        include/twoarmy_ppo.h, "Reward normalisation"), gamma being the agent's as it stands now.  compute_targets() then
+        advances the statistics once per rollout from `reward_train` as the bonus and shaping stages left it, and hands
+        ppo_ops.gae a SCALED COPY, `reward_scaled`, clamped to [-clip, clip] (clip <= 0 or inf: no clamp).
+        hindsight=True: the records' rewards, the 0.9 of a record's last step included, enter their targets through a
+        scaled copy as well, by the same statistics.  Nothing else changes: `reward`, `reward_train`, the history window
+        of relabel(), her["reward"], account_episodes(), running_score() and stats() keep raw values, so no reward is
+        scaled twice and relabel() never copies a scaled one.  With several ranks every rank keeps its own statistics."""
+        from ..exploration import RewardNormalizer
+        if not isinstance(hindsight, bool):
+            raise ValueError("enable_reward_norm(): hindsight is a boolean")
+        try:
+            self.reward_norm = RewardNormalizer(self.N, self.agent.gamma, clip, self.device)
+        except ValueError as ex:
+            raise ValueError("enable_reward_norm(): %s" % ex) from None
+        self._reward_norm_hindsight = hindsight
+        self._reward_norm_at = -1             # env_steps when the statistics last advanced: once per rollout
+        self.reward_scaled = torch.zeros_like(self.reward)
+        return self.reward_norm
+
+    @torch.no_grad()
+    def normalize_rewards(self):
+        """`reward_scaled` <- reward_train of the rollout just collected, scaled and clamped; the first call after a
+        collect() counts that rollout's returns first.  Call after shape_rewards() / shape_potential() (compute_targets()
+        does).  Three launches, no host synchronisation."""
+        if self.reward_norm is None:
+            raise RuntimeError("normalize_rewards() before enable_reward_norm()")
+        if self._reward_norm_at != self.env_steps:
+            self.reward_norm.update(self.reward_train, self.term, self.trunc)
+            self._reward_norm_at = self.env_steps
+        return self.reward_norm.apply(self.reward_train, out=self.reward_scaled)
+
+    def reward_norm_stats(self):
+        """RewardNormalizer.read(): {"count", "mean", "var", "std", "scale"} of the returns seen so far.  One
+        device-to-host copy."""
+        if self.reward_norm is None:
+            raise RuntimeError("reward_norm_stats() before enable_reward_norm()")
+        return self.reward_norm.read()
 
     # ------------------------------------------------------------------ update diagnostics
     def enable_update_stats(self, target_kl=None):

@@ -50,6 +50,11 @@ targets that --gae_lambda 0 uses; without it --gae_lambda > 0 trains on the roll
 launch per rollout, two more for near's field and lookup) instead of the reference's uniform draw: the latest first
 visits, those nearest the real goal on the static map, or those in the cells visited least so far (rare counts the
 visited cells of every rollout, after relabelling); appends `her_sel` to the log line; random, the default, is the draw.
+--reward_norm [--reward_norm_clip C] [--reward_norm_no_hindsight] divides the training reward, as --bonus and
+--shaping_scale left it, by the running standard deviation of its discounted return (VecPPOTrainer.enable_reward_norm: the
+statistics advance once per rollout on the device, the targets get a scaled copy clamped to [-C, C], default 10, and the
+hindsight records' rewards one by the same statistics unless --reward_norm_no_hindsight); everything logged stays raw;
+appends `rstd` to the log line; every rank keeps its own statistics; not with the self-orientation agent; off by default.
 """
 import argparse
 import math
@@ -234,6 +239,17 @@ def build_parser():
     p.add_argument("--target_kl", type=float, default=None, metavar="X", action=_TargetKL,
                    help="KL early stop: skip the remaining epochs of an update after an epoch whose `kl` exceeds X (one small "
                         "host read per epoch; summed over the ranks first); implies --update_stats; off by default")
+    p.add_argument("--reward_norm", action="store_true",
+                   help="divide the training reward (bonus and shaping included) by the running standard deviation of its "
+                        "discounted return, kept on the device (gym's NormalizeReward; three launches per update): "
+                        "--bonus_scale and --shaping_scale then are ratios to the task's own return spread; logged rewards, "
+                        "the score and the HER switch stay raw; appends `rstd` (that standard deviation) to the log line; "
+                        "every rank keeps its own statistics; off by default")
+    p.add_argument("--reward_norm_clip", type=float, default=None, metavar="C",
+                   help="with --reward_norm: clamp the scaled reward to [-C, C]; 0 or inf: no clamp; default 10")
+    p.add_argument("--reward_norm_no_hindsight", action="store_true",
+                   help="with --reward_norm: leave the hindsight records' rewards unscaled (by default they are scaled by "
+                        "the same statistics, one launch per update)")
     return p
 
 
@@ -391,6 +407,14 @@ def main(argv=None, predictor=False, soa=False):
         raise SystemExit("--orient_prior_steps must be 1, 2 or 3")
     if args.her_gae and (predictor or soa):
         raise SystemExit("--her_gae: plain PPO agent only")
+    if (args.reward_norm_clip is not None or args.reward_norm_no_hindsight) and not args.reward_norm:
+        raise SystemExit("--reward_norm_clip / --reward_norm_no_hindsight need --reward_norm")
+    if args.reward_norm_clip is not None and not args.reward_norm_clip >= 0.0:
+        raise SystemExit("--reward_norm_clip must be a number >= 0 (0 or inf: no clamp)")
+    if args.reward_norm and soa:
+        raise SystemExit("--reward_norm: not with the self-orientation agent")
+    if args.reward_norm and not 0.0 <= args.gamma <= 1.0:
+        raise SystemExit("--reward_norm needs --gamma in [0, 1]")
     from .. import dist as twdist
     from ..engine import TwoarmyEngine
     from .agent.PPO import PPO
@@ -463,6 +487,9 @@ def main(argv=None, predictor=False, soa=False):
                                          hindsight_timed=args.orient_prior_hindsight_timed)
     if args.update_stats:
         trainer.enable_update_stats(args.target_kl)
+    if args.reward_norm:
+        trainer.enable_reward_norm(10.0 if args.reward_norm_clip is None else args.reward_norm_clip,
+                                   hindsight=not args.reward_norm_no_hindsight)
     trainer.her_gae = args.her_gae
     use_select = args.her_select != "random"
     if use_select:
@@ -533,6 +560,8 @@ def main(argv=None, predictor=False, soa=False):
             tail += orient_fields(ots, args.orient_prior_hindsight)
         if args.path_stats:                                     # behind every other field
             tail += path_fields(trainer.path_stats())
+        if args.reward_norm:                                    # the statistics the update just trained under
+            tail += " rstd %.6f" % trainer.reward_norm_stats()["std"]
         if use_select:                                          # in front of the update's diagnostics only
             tail += select_fields(args.her_select, trainer.her_select_stats() if relabel else None)
         if args.update_stats:                                   # behind every other field

@@ -371,6 +371,56 @@ int ppo_bonus_scan_episode(const float *pos, const int32_t *action, const int32_
                            void *state_table, void *action_table, float *bonus_state, float *bonus_action,
                            float *reward_out, void *stream);
 
+/* Reward normalisation (<package>/csrc/reward_norm.hip): rewards divided by the running standard deviation of the
+ * discounted return, gym's NormalizeReward / the baselines' VecNormalize for N envs at once.  No reference counterpart;
+ * pinned bit for bit against the float64 restatement of the formulas below (tests/reward_norm_ref.py).
+ *
+ * stats double[4], in/out: {count, mean, M2, scale} of every return seen so far; variance = M2 / count.  All-zero = nothing
+ * seen, so one fill clears it.  ret_carry double[N], in/out: the running return of every env, 0 at an episode's start.
+ *
+ * ppo_reward_norm_update, two launches.  All arithmetic is IEEE float64 with ONE rounding per operation; no product is
+ * fused into a sum.
+ * Scan: for every env n, G = ret_carry[n], (k, mean, M2) = (0, 0, 0), and for t = 0 .. T-1 in order
+ *   p = gamma * G;  G = p + (double)reward[t][n]
+ *   k = k + 1;  d = G - mean;  q = d / k;  mean = mean + q;  e = G - mean;  f = d * e;  M2 = M2 + f          (Welford)
+ *   then, where terminated[t][n] | truncated[t][n] is set, G = 0: the done step's return is counted, then cleared (the
+ *   order of gym's wrapper).
+ * ret_carry[n] = G at the end; the env's triple goes to workspace[n], workspace[N + n], workspace[2 N + n].
+ * Fold: the N triples are merged pairwise by Chan's rule, merge(a, b) with a the LEFT operand:
+ *   n = na + nb;  d = mb - ma;  mean = ma + (d * nb) / n;  M2 = (M2a + M2b) + (((d * d) * na) * nb) / n
+ *   nb == 0 returns a's three values, else na == 0 returns b's, bit for bit.
+ * The order is the balanced tree over the env index: the triples are elements 0 .. N-1 of an array padded with empty
+ * triples (0, 0, 0) to P = the next power of two; level l = 0, 1, ... replaces element 2^l * 2j by
+ * merge(element 2^l * 2j, element 2^l * (2j + 1)) for every j, until element 0 holds the rollout's triple.  The lower
+ * index is always the left operand.  One workgroup walks the tree, 64 elements per wavefront and pass (six shuffle
+ * levels), in place in `workspace`: the result depends on N and the data alone.
+ * Then stats[0..2] = merge(a = stats[0..2], b = the rollout's triple) and, of the merged values,
+ *   stats[3] = 1.0 / sqrt(M2 / count + 1e-8)   (a quotient, a sum, a square root, a quotient);  1.0 where count == 0.
+ * The result depends on how the steps are cut into calls only through the order of the merges (every call is one merge
+ * into stats).  A non-finite reward makes the statistics non-finite for good.
+ *   reward float[T][N]; terminated, truncated uint8[T][N]; workspace double[ppo_reward_norm_workspace(N) = 3 N], every
+ *   entry written before it is read.
+ * TW_E_ARG, and nothing is launched: NULL reward, terminated, truncated, ret_carry, stats or workspace; T < 0; N <= 0 or
+ * 3 N >= 2^31; T * N >= 2^40; ret_carry, stats or workspace off 8-byte alignment; gamma outside [0, 1] (a NaN included).
+ * T == 0 returns 0, launches nothing and leaves stats and ret_carry alone.  ppo_reward_norm_workspace: host only;
+ * TW_E_ARG for N <= 0 or 3 N >= 2^31.
+ *
+ * ppo_reward_norm_apply, one launch, for the rollout's [T][N] rewards and for a flat array of hindsight records alike:
+ *   s = stats[0] == 0 ? 1.0f : (float)stats[3];   x = reward[i] * s   (ONE float32 product)
+ *   out[i] = (clip > 0 && clip < +inf) ? fminf(fmaxf(x, -clip), clip) : x
+ * stats is read on the device: no host value enters the launch, and a captured launch scales by the statistics that are
+ * current when it is replayed.  With all-zero stats and no clamp out[i] has the bits of reward[i].  out may alias reward
+ * (wholly; a lane reads exactly the elements it writes).  16 bytes per lane by the aligned row store of row_store.h: any
+ * n and any 4-byte alignment of reward and out; only out[0 .. n) is written.
+ * TW_E_ARG, and nothing is launched: NULL reward, stats or out; n < 0 or n >= 2^40; reward or out off 4-byte alignment,
+ * stats off 8; a NaN clip.  n == 0 returns 0 and launches nothing.
+ * Neither call allocates or reads back: both may be captured into a graph and replayed.  No floating-point atomics: two
+ * calls from equal state on equal inputs give equal bits. */
+int ppo_reward_norm_workspace(int N);
+int ppo_reward_norm_update(const float *reward, const uint8_t *terminated, const uint8_t *truncated, int T, int N,
+                           double gamma, double *ret_carry, double *stats, double *workspace, void *stream);
+int ppo_reward_norm_apply(const float *reward, int64_t n, const double *stats, float clip, float *out, void *stream);
+
 /* Hindsight experience replay over one time-major rollout: replaces Buffer_gridworld.her_func
  * (soa/env_buffer.py:101-143, called from soa/train_ppo.py:128-134 at every episode end).  For every episode
  * [s0, t1] that starts (age0[n] == 0 or the step after a done) and ends (terminated | truncated) inside the
