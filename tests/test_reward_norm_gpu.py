@@ -1,7 +1,10 @@
 """Reward normalisation on the MI355X (csrc/reward_norm.hip; include/twoarmy_ppo.h, "Reward normalisation"):
 ppo_reward_norm_update and ppo_reward_norm_apply bit for bit against tests/reward_norm_ref.py, every argument rule, the
 stream protocol of tests/stream_util.py, and VecPPOTrainer with and without enable_reward_norm() over two rollouts of
-8 envs x 16 steps (episodes of 10 steps, relabelling on).  The stream cases live here; see the note at STREAM_CASES."""
+8 envs x 16 steps (episodes of 10 steps, relabelling on).  The stream cases live here; see the note at STREAM_CASES.
+Beyond rn.SHAPES: the fold at every N at which a wavefront takes another chunk or the walk another pass (rn.FOLD_EDGES),
+the scan at every T around its batches of 8 rows with done steps where the batches meet, and non-finite rewards and
+scales."""
 import functools
 
 import numpy as np
@@ -47,18 +50,35 @@ def reference(T, N, dones, gamma, zero):
 
 def device_chain(T, N, dones, gamma, zero):
     """The same chain on the device, every in/out array between canaries -> [(ret_carry, stats)] on the host."""
-    c0, s0 = start(N, zero)
+    return device_calls(rn.case(T, N, dones), gamma, *start(N, zero))
+
+
+def device_calls(rolls, gamma, c0, s0, nan_workspace=False):
+    """One update per rollout of `rolls` from (c0, s0), every in/out array between canaries -> [(ret_carry, stats)] on the
+    host.  nan_workspace: the workspace holds NaN before the first call, so that an entry read before it is written (the
+    header: "every entry written before it is read") ends in the statistics."""
+    N = c0.size
     cbuf, carry = guarded(N, F64)
     sbuf, stats = guarded(4, F64)
     wbuf, ws = guarded(_ops().reward_norm_workspace(N), F64)
     carry.copy_(_d(c0))
     stats.copy_(_d(s0))
+    if nan_workspace:
+        ws.fill_(float("nan"))
     out = []
-    for r, te, tr in rn.case(T, N, dones):
+    for r, te, tr in rolls:
         assert _ops().reward_norm_update(_d(r), _d(te), _d(tr), gamma, carry, stats, ws) is stats
         out.append((host(carry), host(stats)))
     assert intact(cbuf, N) and intact(sbuf, 4) and intact(wbuf, 3 * N)
     return out
+
+
+def same_bits_or_nan(got, want):
+    """Equal bits where `want` is no NaN, some NaN where it is one: a NaN's sign and payload are not the header's to fix."""
+    got, want = np.asarray(got), np.asarray(want)
+    nan = np.isnan(want)
+    return got.shape == want.shape and got.dtype == want.dtype and bool(np.isnan(got[nan]).all()) \
+        and same_bits(got[~nan], want[~nan])
 
 
 # --------------------------------------------------------------------------------------------------------- update
@@ -74,6 +94,82 @@ def test_update_equals_the_restatement_over_three_calls(T, N):
                     assert same_bits(gc, wc), ("ret_carry", T, N, zero, dones, gamma, i)
                     assert same_bits(gs, ws), ("stats", T, N, zero, dones, gamma, i, gs, ws)
                 assert want[-1][1][0] == start(N, zero)[1][0] + 3 * T * N
+
+
+def fold_chains(N):
+    """(dones, zero) of the chains the sweep runs at N: every start and flag pattern up to FOLD_SMALL, one chain beyond."""
+    return [(d, z) for z in (True, False) for d in ("mixed", "none")] if N <= rn.FOLD_SMALL else [("mixed", True)]
+
+
+@functools.lru_cache(maxsize=None)
+def fold_reference(N, dones, zero):
+    """reference() with the tree taken level-wise (rn.tree_levelwise, equal to rn.tree at these sizes: the CPU file)."""
+    carry, stats = start(N, zero)
+    out = []
+    for r, te, tr in rn.case(rn.FOLD_T, N, dones):
+        carry, stats = rn.update(r, te, tr, 0.99, carry, stats, levelwise=True)
+        out.append((carry, stats))
+    return out
+
+
+def check_chain(got, want, what):
+    for i, ((gc, gs), (wc, ws)) in enumerate(zip(got, want)):
+        assert same_bits(gc, wc), ("ret_carry", what, i)
+        assert same_bits(gs, ws), ("stats", what, i, gs, ws)
+    assert len(got) == len(want) == 3
+
+
+@pytest.mark.parametrize("N", [n for n, _ in rn.FOLD_EDGES])
+def test_fold_boundary_sweep(N):
+    """The fold at every N at which it changes its path (rn.FOLD_EDGES names each edge): a wavefront's second and later
+    chunks, partial and one-element chunks behind full ones, the third and fourth pass.  Three calls, a NaN-filled
+    workspace."""
+    assert _ops().reward_norm_workspace(N) == 3 * N
+    for dones, zero in fold_chains(N):
+        want = fold_reference(N, dones, zero)
+        got = device_calls(rn.case(rn.FOLD_T, N, dones), 0.99, *start(N, zero), nan_workspace=True)
+        check_chain(got, want, (N, dones, zero))
+        assert want[-1][1][0] == got[-1][1][0] == start(N, zero)[1][0] + 3 * rn.FOLD_T * N      # the count is exact
+
+
+@pytest.mark.parametrize("N", rn.SCAN_N)
+@pytest.mark.parametrize("T", rn.SCAN_T)
+def test_scan_batch_boundaries(T, N):
+    """T around the scan's batches of 8 rows: a last batch of 1, 7 and 8 rows behind one and two whole ones, done steps on
+    the last row of a batch and the first of the next (rn.edge_flags), and the longest carried chains (gamma 1, no flags)
+    from a non-zero start."""
+    c0, s0 = start(N, False)
+    assert s0[0] > 0 and c0.any()
+    for kind in rn.SCAN_KINDS:
+        gamma = 0.99 if kind == "edge" else 1.0
+        rolls = rn.scan_case(T, N, kind)
+        want, carry, stats = [], c0, s0
+        for r, te, tr in rolls:
+            carry, stats = rn.update(r, te, tr, gamma, carry, stats)
+            want.append((carry, stats))
+        check_chain(device_calls(rolls, gamma, c0, s0, nan_workspace=True), want, (T, N, kind))
+        assert want[-1][1][0] == s0[0] + 3 * T * N
+
+
+def test_a_non_finite_reward_stays_with_its_env_and_its_episode():
+    """The header: "a non-finite reward makes the statistics non-finite for good".  What else it does: nothing.  The other
+    envs' returns and the count go on, and a done step clears a non-finite return like any other."""
+    rolls = rn.nonfinite_case()
+    zero = np.zeros(rn.NF_N), np.zeros(4)
+    want, (carry, stats) = [], zero
+    with np.errstate(all="ignore"):
+        for r, te, tr in rolls:
+            carry, stats = rn.update(r, te, tr, 0.99, carry, stats)
+            want.append((carry, stats))
+    got = device_calls(rolls, 0.99, *zero, nan_workspace=True)
+    for i, ((gc, gs), (wc, ws)) in enumerate(zip(got, want)):
+        assert same_bits_or_nan(gc, wc), ("ret_carry", i)                     # the infinities too, bit for bit
+        assert np.array_equal(np.isfinite(gc), np.isfinite(wc))
+        assert gs[0] == ws[0] == (i + 1) * rn.NF_T * rn.NF_N                  # the count is exact
+        assert np.isnan(gs[1:]).all() and np.isnan(ws[1:]).all(), (i, gs)     # mean, M2 and scale: NaN, and they stay
+    (c1, _), (c2, _) = got
+    assert np.isnan(c1[5]) and c1[70] == np.inf and np.isfinite(c1[129]) and (~np.isfinite(c1)).sum() == 2
+    assert np.isfinite(c2[5]) and c2[70] == np.inf and (~np.isfinite(c2)).sum() == 1
 
 
 def test_the_cases_hold_what_they_are_meant_to():
@@ -155,6 +251,51 @@ def test_apply_equals_the_restatement_at_every_alignment(n):
     assert not same_bits(rn.apply(r_np, stats_np, CLIP), r_np)
     shaped = _d(r_np.reshape(1, n))                                           # any shape goes in flat
     assert same_bits(host(_ops().reward_norm_apply(shaped, stats, CLIP)), rn.apply(r_np, stats_np, CLIP).reshape(1, n))
+
+
+NAN_SCALE = np.array([10.0, 0.1, 2.5, np.nan])
+ODD_EMPTY = np.array([0.0, 5.0, 9.0, 123.0])       # count 0 and the rest not: only the count says "nothing seen"
+
+
+def applied(r_np, stats_np, clip):
+    """apply into a guarded buffer -> the host copy; the input keeps its bits and the canaries theirs."""
+    n = r_np.size
+    r = _d(r_np)
+    obuf, out = guarded(n, F32)
+    assert _ops().reward_norm_apply(r, _d(stats_np), clip, out) is out
+    assert intact(obuf, n) and same_bits(host(r), r_np)
+    return host(out)
+
+
+def test_apply_on_non_finite_rewards_and_a_non_finite_scale():
+    n = 2049
+    stats_np = reference(5, 65, "mixed", 0.99, True)[-1][1]
+    special, no_nan = rn.special_rewards(n), rn.special_rewards(n, nan=False)
+    for clip in (CLIP, 0.0):
+        want = rn.apply(special, stats_np, clip)
+        assert same_bits_or_nan(applied(special, stats_np, clip), want), clip
+        assert np.isnan(want).sum() == (0 if clip else np.isnan(special).sum())      # the clamp turns a NaN into -clip
+    assert (rn.apply(special, stats_np, CLIP)[np.isnan(special)] == np.float32(-CLIP)).all()
+    tiny = (special != 0) & (np.abs(special) < np.finfo(np.float32).tiny)
+    assert tiny.any() and (rn.apply(special, stats_np, 0.0)[tiny] != 0).all()         # denormals are not flushed
+    plain = rn.rewards(np.random.default_rng(n), 1, n).reshape(-1)
+    got = applied(plain, NAN_SCALE, CLIP)                                             # fminf(fmaxf(NaN, -c), c) = -c
+    assert same_bits(got, rn.apply(plain, NAN_SCALE, CLIP)) and (got == np.float32(-CLIP)).all()
+    got = applied(plain, NAN_SCALE, 0.0)
+    assert same_bits_or_nan(got, rn.apply(plain, NAN_SCALE, 0.0)) and np.isnan(got).all()
+    for clip in (0.0, float("inf")):                                                  # an odd empty: the bits stay
+        assert same_bits(applied(no_nan, ODD_EMPTY, clip), no_nan) and same_bits(rn.apply(no_nan, ODD_EMPTY, clip), no_nan)
+    assert same_bits(applied(no_nan, ODD_EMPTY, CLIP), rn.apply(no_nan, ODD_EMPTY, CLIP))
+
+
+def test_update_from_an_odd_empty_returns_the_rollouts_triple_alone():
+    T, N = 5, 65
+    rolls = rn.case(T, N, "mixed")[:1]
+    c0 = start(N, False)[0]
+    (gc, gs), = device_calls(rolls, 0.99, c0, ODD_EMPTY, nan_workspace=True)
+    (zc, zs), = device_calls(rolls, 0.99, c0, np.zeros(4))
+    wc, ws = rn.update(*rolls[0], 0.99, c0, ODD_EMPTY)
+    assert same_bits(gs, ws) and same_bits(gs, zs) and same_bits(gc, wc) and same_bits(gc, zc) and gs[0] == T * N
 
 
 # ------------------------------------------------------------------------------------------------ argument rules
